@@ -7,9 +7,14 @@ thresholded sparse top-n multiply (K4p / K4).  Workload at N=1: the configuratio
 is quoted on -- 663k-name self-join, 3-grams, ntop=10, min_sim=0.8, fp32 -- on SynthNames-v1
 (the sec__edgar list is not distributable; see string_grouper_amd/synth.py).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
-``--gpus N`` with N > 1 and no rank environment re-executes itself under ``torch.distributed.run`` (N ranks,
+A plain run sets up, warms up, times the K steps and prints the line of the headline figure.  ``--full`` adds what is
+measured beside it (exact_kernel, end_to_end, the side runs at other settings and in the other dtype, cpu_baseline and,
+N > 1, the 5 M-name block); the ``--no-*`` switches leave parts of that out.  ``--dump-outputs DIR`` writes the match
+matrix of the last timed step to DIR/*.npy, so that two builds can be compared output for output on the same input.
+
+``--gpus N`` with N > 1 and no rank environment runs itself under ``torch.distributed.run`` in a child (N ranks,
 one per GPU, RCCL); launched BY torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE.  N > 1 is strong
 scaling of the same workload (string_grouper_amd/distributed.py): every rank vectorises its block of the rows (one
 all-reduce of the df table, one all-gather of the CSR blocks), builds the index, and scores the pairs (i, j <= i) of its
@@ -19,6 +24,7 @@ Prints ONE JSON line (rank 0):
   value / ms_per_step   the hot path, inputs in HBM (the contract's metric)
   roofline              the multiply kernel of the step, live HIP-event time on the library's stream, priced on its
                         own algorithmic bytes
+ --full only:
   exact_kernel          K4 timed live on the same input; results compared bit for bit
   end_to_end            wall-clock of the PUBLIC match_strings() incl. host string preparation, PCIe both ways, the
                         device match list (K6) and the pandas frames, fp32 and fp64, with the split -- this is what
@@ -74,18 +80,28 @@ def parse_args():
                                                               "reference + ~10 s of the multiply), composed and scaled -- "
                                                               "instead of the default, the unmodified reference's "
                                                               "match_strings on ALL rows (~95 s on 4 cores at 663 k)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline figure: exact kernel, match_strings() end to end, side "
+                         "runs, CPU baseline, (N > 1) the 5 M-name block; without it only the timed steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the match matrix of the last timed step to DIR/*.npy (float32 / float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs: one GPU only (the ranks' results stay on the ranks)")
+    return args
 
 
 def respawn_under_torchrun(args) -> None:
-    """``python bench.py --gpus N`` (N > 1) outside a launcher: become ``torch.distributed.run`` with N ranks."""
+    """``python bench.py --gpus N`` (N > 1) outside a launcher: run ``torch.distributed.run`` with N ranks in a child
+    process and exit with its status."""
     import socket
+    import subprocess
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 def main():
@@ -125,6 +141,36 @@ def main():
             raise
         return
     run(args)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, res, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """What the caller of the step receives -- its top-n match matrix as CSR (TopN.to_scipy: rows in score order) -- as
+    DIR/match_indptr.npy, match_indices.npy (float64: exact for these integers) and match_scores.npy (the step's dtype).
+    A matrix larger than `limit` is cut to a fixed sample of rows (seed 0), whose ids DIR/match_rows.npy holds."""
+    C = res.to_scipy()
+    n_rows = C.shape[0]
+    size = lambda rows, nnz: 8 * (rows + 1) + (8 + C.data.itemsize) * nnz    # noqa: E731
+    out = {}
+    if size(n_rows, C.nnz) > limit:
+        order = np.random.default_rng(0).permutation(n_rows)
+        k = max(1, n_rows * limit // size(n_rows, C.nnz))
+        while True:
+            rows = np.sort(order[:k])
+            sample = C[rows]
+            if k == 1 or size(k, sample.nnz) + 8 * k <= limit:      # (+ the row ids themselves)
+                break
+            k = max(1, k * 3 // 4)
+        out["match_rows"] = rows.astype(np.float64)
+        C = sample
+    out["match_indptr"] = C.indptr.astype(np.float64)
+    out["match_indices"] = C.indices.astype(np.float64)
+    out["match_scores"] = C.data
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 _JSON_FD = []      # the descriptor the one JSON line goes to (stdout as it was when the process started)
@@ -278,6 +324,8 @@ def run(args):
     if distributed and dist_mode == "sharded":
         # (the multi-GPU self-join form merges the mirrored pairs after the multiply's own count: count the rank's rows)
         out_nnz = int(ops.topn_tensors(last)[2].sum().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     last.free()
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
@@ -294,7 +342,7 @@ def run(args):
     # metric, and the same step on 5 M names is timed beside it (every rank: its block of the column in HBM, three timed
     # steps bracketed like the main region, max over ranks) -- a nested block of the one JSON line.
     config3 = None
-    if distributed and dist_mode == "sharded" and not args.no_config3 and args.rows < args.config3_rows:
+    if args.full and distributed and dist_mode == "sharded" and not args.no_config3 and args.rows < args.config3_rows:
         last = None
         try:
             n3 = args.config3_rows
@@ -435,7 +483,7 @@ def run(args):
     #  between runs on the shared boxes: the download of the match list -- 22 MB, device to host -- takes 2 ms on most runs and
     #  20 - 30 on some, whatever the destination and the copy engine, and the end-to-end figure then reads 0.045 s instead of
     #  0.022; `match_list_and_download_s` in the split tells which it was: scripts/e2e_variance.sh)
-    if world == 1 and not args.no_end_to_end:
+    if args.full and world == 1 and not args.no_end_to_end:
         # the public API end to end: pandas Series in, match frame out (host preparation, PCIe, K1-K4p, K6, frames)
         import pandas as pd
         import string_grouper_amd as sga
@@ -495,7 +543,7 @@ def run(args):
             result["end_to_end"][dname] = {"seconds": best, "rows_per_s": args.rows / best, "match_rows": n_match, "warm_up_calls": warm,
                                            "split": {k: round(v, 5) for k, v in split.items()}}
 
-    if world == 1 and not args.no_side_runs:
+    if args.full and world == 1 and not args.no_side_runs:
         # the step WITHOUT the collapse of identical rows (every one of the 663 000 rows indexed and multiplied: 16.5 % of
         # SynthNames-v1's names repeat, a property of the generator, not of sec__edgar) ...
         ctx.set_option("SG_COLLAPSE", "0")
@@ -530,7 +578,7 @@ def run(args):
                          "kernel_frac_of_hbm_peak": o_bytes / (kms * 1e-3) / 1e9 / HBM_PEAK_GBPS, "steps": 12,
                          "matches": st_o["out_nnz"]}
 
-    if world == 1 and not args.no_side_runs:
+    if args.full and world == 1 and not args.no_side_runs:
         # ... and at other values of the two parameters the reference leaves to the caller (string_grouper.py:192-193): the whole
         # step again -- every one rebuilds its indexes, the second one of a form included -- on the same list.  Which form of
         # the multiply the library picked is read off its statistics ("Which form runs").
@@ -547,7 +595,7 @@ def run(args):
                                    "rows_handed_to_exact_kernel": st_s["exact_rows"] if st_s["prune_rows"] > 0 else None, "steps": 4})
         result["other_settings"] = other_settings
 
-    if world == 1 and pruned and not args.no_exact_kernel:
+    if args.full and world == 1 and pruned and not args.no_exact_kernel:
         # the exact kernel (K4) on the same input, timed live beside the pruned one: it is what runs when the
         # data is not cosine-like or top_n > 64, and the pruned result must equal it bit for bit
         ctx.set_option("SG_PRUNE", "0")          # (an option of this context, set explicitly -- the environment is not touched)
@@ -580,7 +628,7 @@ def run(args):
                                   "pruned_result_identical": identical,
                                   "note": "stream model (4+s) B per intermediate product + A + out"}
 
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # the reference's CPU path on this box's host cores, in a child process pinned to --cpu-cores CPUs
         # (oracle/baseline.py).  The child gets the full TF-IDF matrix from this process (built by the GPU path,
         # parity-checked by the tests) so that its budget goes into what it measures.

@@ -9,6 +9,6 @@ for l in sys.stdin:
         d = json.loads(l); e = d['end_to_end']
         print('$1', 'step ms', round(d['ms_per_step'], 3), 'e2e f32', round(e['f32']['seconds'], 4), 'f64', round(e['f64']['seconds'], 4), 'list + download', e['f32']['split']['match_list_and_download_s'])"; }
 for i in $(seq $reps); do
-  HSA_ENABLE_SDMA=0 python bench.py --steps 20 --no-cpu-baseline --no-side-runs $E2E_ARGS 2>/dev/null | show "sdma off"
-  python bench.py --steps 20 --no-cpu-baseline --no-side-runs $E2E_ARGS 2>/dev/null | show "default "
+  HSA_ENABLE_SDMA=0 python bench.py --full --steps 20 --no-cpu-baseline --no-side-runs $E2E_ARGS 2>/dev/null | show "sdma off"
+  python bench.py --full --steps 20 --no-cpu-baseline --no-side-runs $E2E_ARGS 2>/dev/null | show "default "
 done
