@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <map>
@@ -79,6 +80,18 @@ struct sg_ctx {
     const char *opt(const char *name) const {    // value of a switch, or null: not set
         auto it = opts.find(name);
         return it == opts.end() ? nullptr : it->second.c_str();
+    }
+    int opt_int(const char *name, int dflt) const {            // unset or empty: dflt
+        const char *v = opt(name);
+        return v && *v ? atoi(v) : dflt;
+    }
+    double opt_double(const char *name, double dflt) const {
+        const char *v = opt(name);
+        return v && *v ? atof(v) : dflt;
+    }
+    bool opt_is(const char *name, char c) const {              // set, and its value starts with c
+        const char *v = opt(name);
+        return v && v[0] == c;
     }
     bool poison = false;                         // SG_POISON_ALLOC=1 (copied out of opts: read under the pool's lock)
 
@@ -330,6 +343,7 @@ struct sg_vocab {
 int sg_matchlist_device_view(const sg_matchlist *ml, int64_t *n_rows, int64_t *n_cols, int64_t *n_entries, int32_t *dtype,
                              const int64_t **row_ptr, const int32_t **cols, const void **vals);
 
+#define SG_POSTINGS_NO_COLLAPSE (1 << 8)   // sg_postings_build_flags (internal): index every row (the collapse wrapper's own inner call; the companion indexes)
 #define SG_POSTINGS_TILE_FORM (1 << 11)    // sg_postings_build_flags (internal): the pruned multiply's tile-by-tile form, 2048-column tiles, no 8-bit rows
 #define SG_POSTINGS_EXACT_ONLY (1 << 10)   // sg_postings_build_flags (internal): no filter postings, packed rows, 8-bit rows
 // sg_spgemm_pruned.hip

@@ -1058,9 +1058,8 @@ extern "C" int sg_postings_build(sg_ctx *ctx, const sg_csr *B, int32_t tile_cols
 }
 
 // internal flags of sg_postings_build_flags (above the public ones)
-#define SG_POSTINGS_NO_COLLAPSE (1 << 8)   // index every row (the collapse wrapper's own inner call; the on-demand plain index)
 #define SG_POSTINGS_INNER (1 << 9)         // called by the collapse wrapper: the wrapper's timer covers the build
-// (SG_POSTINGS_EXACT_ONLY, sg_internal.h: nothing of the pruned multiply's -- the exact kernel's own tile and postings)
+// (SG_POSTINGS_NO_COLLAPSE, SG_POSTINGS_EXACT_ONLY, SG_POSTINGS_TILE_FORM: sg_internal.h)
 
 // the groups whose representatives' rows the inner build of sg_postings_build_flags is to write (handed from the outer call
 // to the inner one of the same thread)

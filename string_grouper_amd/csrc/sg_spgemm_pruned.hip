@@ -1888,9 +1888,7 @@ __global__ void pair_sink_kernel(SgPairSink v, SgPairSink *out) { *out = v; }
 // at 0.7 and above it pays: 10 M x 1 M at 0.7 - 20 %).  SG_Q8_MIN_THRESHOLD moves the bar.
 bool sg_q8_applies(const sg_ctx *ctx, const sg_postings *Bt, double threshold) {
     if (!Bt->d_q8 || Bt->fold_log2 <= 0) return false;
-    double bar = 0.65;
-    if (const char *v = ctx->opt("SG_Q8_MIN_THRESHOLD")) bar = atof(v);
-    return threshold >= bar;
+    return threshold >= ctx->opt_double("SG_Q8_MIN_THRESHOLD", 0.65);
 }
 
 static size_t pruned_lds(int32_t tile_log2, int32_t fold_log2, int32_t dtype) {
@@ -1901,8 +1899,8 @@ static unsigned pruned_grid(const sg_ctx *ctx, int32_t tile_log2, int64_t n_rows
     int waves_per_cu = (int)(ctx->lds_per_cu / lds);
     if (waves_per_cu > 32) waves_per_cu = 32;
     if (waves_per_cu < 1) waves_per_cu = 1;
-    if (const char *v = ctx->opt("SG_PRUNE_WAVES_PER_CU"))
-        if (atoi(v) > 0) waves_per_cu = atoi(v);
+    const int forced = ctx->opt_int("SG_PRUNE_WAVES_PER_CU", 0);
+    if (forced > 0) waves_per_cu = forced;
     unsigned grid = (unsigned)ctx->num_cu * (unsigned)waves_per_cu;
     if ((int64_t)grid > n_rows) grid = (unsigned)(n_rows > 0 ? n_rows : 1);
     return grid;
@@ -1975,14 +1973,14 @@ static int launch_both(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int3
             //  after the others, on single rows.  Also tried and dropped, profiles/r03_sessionAR_parts_first.log: a classify
             //  launch that lists such rows BEFORE the multiply, whose launch then starts with their parts -- 4.5 instead
             //  of 4.15 ms for a half share at 663 k, 1.94 instead of 1.78 for an eighth)
-            double bar_share = 0.05;
-            if (const char *v = ctx->opt("SG_HEAVY_SHARE")) bar_share = atof(v) > 0.0 ? atof(v) : bar_share;
+            const double share = ctx->opt_double("SG_HEAVY_SHARE", 0.0);
+            const double bar_share = share > 0.0 ? share : 0.05;
             const double bar = bar_share * rows_per_wave * rounds_per_row;
             // (never below 128 rounds: at 663 k, eight ranges, bars of 64 / 128 / 256 / 512 rounds give 2.10 / 2.03 / 2.19 /
             //  2.57 ms for the slowest range -- profiles/r03_sessionAG_heavy_bar_ranges.log)
             heavy_rounds = bar < 128.0 ? 128u : (bar > 1.0e9 ? 1000000000u : (uint32_t)bar);
         }
-        if (const char *v = ctx->opt("SG_HEAVY_ROUNDS")) heavy_rounds = (uint32_t)atoi(v) & 0x7fffffffu;
+        heavy_rounds = (uint32_t)ctx->opt_int("SG_HEAVY_ROUNDS", (int)heavy_rounds) & 0x7fffffffu;
         if (heavy_rounds > 0x0fffffffu) heavy_rounds = 0x0fffffffu;
         // candidates per round of the bar from which a row hands its remaining visits to the parts (2^shift): about a
         // thousand candidates at the floor of the bar (128 rounds: the 663 k job), two per round of a large bar -- with the
@@ -1990,7 +1988,7 @@ static int launch_both(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int3
         // pass it and are scored exactly (5 M names, 8 shares, scripts/share_knob_sweep.sh: slowest share 23.2 -> 21.4 ms
         // with 2 instead of 8 per round; the 663 k shares lose 0.1 of 1.5 ms that way).  SG_HANDOVER_SHIFT overrides.
         uint32_t handover_shift = heavy_rounds >= 512u ? 1u : (heavy_rounds >= 256u ? 2u : 3u);
-        if (const char *v = ctx->opt("SG_HANDOVER_SHIFT")) handover_shift = (uint32_t)atoi(v) & 7u;
+        handover_shift = (uint32_t)ctx->opt_int("SG_HANDOVER_SHIFT", (int)handover_shift) & 7u;
         if (heavy_rounds) heavy_rounds |= handover_shift << 28;
         if (heavy_rounds) {
             st = sg_alloc(ctx, 2 * (size_t)A->n_rows + 8, &heavy);   // [4, 4 + n): the rows, [4 + n, 4 + 2 n): their first visit for the parts
@@ -2004,7 +2002,7 @@ static int launch_both(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int3
         st = launch_pruned<T, TILE_LOG2, SYM, false, FOLD_LOG2>(ctx, A, Bt, keep, r, thr, s_budget, heavy + 1, l1, l1 + 4, stats, pl,
                                                      heavy + 4, heavy, nullptr, nullptr, 0x80000000u);
     if (heavy) ctx->release(heavy);   // stream-ordered, like l1 below
-    if (st == SG_OK && !(ctx->opt("SG_PRUNE_WIDE") && ctx->opt("SG_PRUNE_WIDE")[0] == '0'))
+    if (st == SG_OK && !ctx->opt_is("SG_PRUNE_WIDE", '0'))
         st = launch_pruned<T, TILE_LOG2, SYM, true, FOLD_LOG2>(ctx, A, Bt, keep, r, thr, s_budget, l1 + 1, flagged_count, flagged_rows, stats,
                                                     pl, l1 + 4, l1);
     else if (st == SG_OK) {   // SG_PRUNE_WIDE=0: the first launch's list goes to the exact kernel as it is

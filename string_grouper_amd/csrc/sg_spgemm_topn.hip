@@ -33,6 +33,9 @@
 #include <cstring>
 #include <math.h>
 
+#include <memory>
+#include <optional>
+
 #include "sg_internal.h"
 
 #include "sg_k4_device.h"
@@ -576,31 +579,24 @@ __global__ void __launch_bounds__(64) topn_zip_kernel(const ZipPart<T> *__restri
 // ================================================================================================
 // host side
 // ================================================================================================
-static double env_double(const sg_ctx *ctx, const char *name, double dflt) {
-    const char *v = ctx->opt(name);
-    if (!v || !*v) return dflt;
-    return atof(v);
+// Dynamic LDS above the default 48 KiB has to be allowed for each kernel, once
+template <auto KERN>
+static int allow_dynamic_lds(size_t lds) {
+    static bool done = false;   // per instantiation
+    if (lds > 48 * 1024 && !done) {
+        SG_HIP_TRY(hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        done = true;
+    }
+    return SG_OK;
 }
 
-static int env_int(const sg_ctx *ctx, const char *name, int dflt) {
-    const char *v = ctx->opt(name);
-    if (!v || !*v) return dflt;
-    return atoi(v);
-}
-
-template <typename T, int TILE_LOG2, int DEPTH>
+template <typename T, int TILE_LOG2>
 static int launch_spgemm(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t tile_begin, int32_t tile_end,
                          int32_t keep, int32_t pass_off, sg_topn *r, T thr, uint32_t *counter, unsigned grid,
                          const uint32_t *row_list, const uint32_t *row_list_len) {
     const size_t lds = sizeof(T) << TILE_LOG2;
-    auto kern = spgemm_topn_kernel<T, TILE_LOG2, DEPTH>;
-    if (lds > 48 * 1024) {
-        static bool done = false;   // per instantiation
-        if (!done) {
-            SG_HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            done = true;
-        }
-    }
+    constexpr auto kern = spgemm_topn_kernel<T, TILE_LOG2, 8>;
+    SG_TRY(allow_dynamic_lds<kern>(lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64), lds, ctx->stream, A->d_indptr, A->d_indices, (const T *)A->d_data,
                        (uint32_t)A->n_rows, (const uint32_t *)Bt->d_seg, (const int32_t *)Bt->d_rows,
                        (const T *)Bt->d_vals, Bt->n_tiles, tile_begin, tile_end, keep, pass_off, r->stride, thr,
@@ -609,27 +605,15 @@ static int launch_spgemm(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, in
     return SG_OK;
 }
 
-template <typename T, int TILE_LOG2>
-static int dispatch_depth(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t tile_begin, int32_t tile_end,
-                          int32_t keep, int32_t pass_off, sg_topn *r, T thr, uint32_t *counter, unsigned grid,
-                          int depth, const uint32_t *row_list, const uint32_t *row_list_len) {
-    switch (depth) {
-        case 4: return launch_spgemm<T, TILE_LOG2, 4>(ctx, A, Bt, tile_begin, tile_end, keep, pass_off, r, thr, counter, grid, row_list, row_list_len);
-        case 16: return launch_spgemm<T, TILE_LOG2, 16>(ctx, A, Bt, tile_begin, tile_end, keep, pass_off, r, thr, counter, grid, row_list, row_list_len);
-        default: return launch_spgemm<T, TILE_LOG2, 8>(ctx, A, Bt, tile_begin, tile_end, keep, pass_off, r, thr, counter, grid, row_list, row_list_len);
-    }
-}
-
 template <typename T>
 static int dispatch_spgemm(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t tile_begin, int32_t tile_end,
                            int32_t keep, int32_t pass_off, sg_topn *r, T thr, uint32_t *counter, unsigned grid,
                            const uint32_t *row_list = nullptr, const uint32_t *row_list_len = nullptr) {
-    const int depth = env_int(ctx, "SG_DEPTH", 8);
     switch (Bt->tile_log2) {
-        case 10: return dispatch_depth<T, 10>(ctx, A, Bt, tile_begin, tile_end, keep, pass_off, r, thr, counter, grid, depth, row_list, row_list_len);
-        case 11: return dispatch_depth<T, 11>(ctx, A, Bt, tile_begin, tile_end, keep, pass_off, r, thr, counter, grid, depth, row_list, row_list_len);
-        case 12: return dispatch_depth<T, 12>(ctx, A, Bt, tile_begin, tile_end, keep, pass_off, r, thr, counter, grid, depth, row_list, row_list_len);
-        case 13: return dispatch_depth<T, 13>(ctx, A, Bt, tile_begin, tile_end, keep, pass_off, r, thr, counter, grid, depth, row_list, row_list_len);
+        case 10: return launch_spgemm<T, 10>(ctx, A, Bt, tile_begin, tile_end, keep, pass_off, r, thr, counter, grid, row_list, row_list_len);
+        case 11: return launch_spgemm<T, 11>(ctx, A, Bt, tile_begin, tile_end, keep, pass_off, r, thr, counter, grid, row_list, row_list_len);
+        case 12: return launch_spgemm<T, 12>(ctx, A, Bt, tile_begin, tile_end, keep, pass_off, r, thr, counter, grid, row_list, row_list_len);
+        case 13: return launch_spgemm<T, 13>(ctx, A, Bt, tile_begin, tile_end, keep, pass_off, r, thr, counter, grid, row_list, row_list_len);
         default:
             sg_set_error("postings tile of 2^%d columns is not supported by the multiply (2^10..2^13)", Bt->tile_log2);
             return SG_ERR_UNSUPPORTED;
@@ -652,14 +636,8 @@ static int launch_selfjoin_rows(sg_ctx *ctx, const sg_csr *A, const sg_postings 
                                 uint32_t *row_counter, const uint32_t *row_list, const uint32_t *row_list_len,
                                 const SgPairSink &sink, bool all_rows) {
     const size_t lds = sizeof(T) << TILE_LOG2;
-    auto kern = spgemm_topn_selfjoin_rows_kernel<T, TILE_LOG2, 8>;
-    if (lds > 48 * 1024) {
-        static bool done = false;   // per instantiation
-        if (!done) {
-            SG_HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            done = true;
-        }
-    }
+    constexpr auto kern = spgemm_topn_selfjoin_rows_kernel<T, TILE_LOG2, 8>;
+    SG_TRY(allow_dynamic_lds<kern>(lds));
     hipLaunchKernelGGL(kern, dim3(sg_spgemm_exact_selfjoin_grid(ctx, all_rows ? Bt : nullptr)), dim3(64), lds, ctx->stream, A->d_indptr, A->d_indices,
                        (const T *)A->d_data, (const uint32_t *)Bt->d_seg, (const int32_t *)Bt->d_rows, (const T *)Bt->d_vals,
                        Bt->n_tiles, keep, r->stride, thr, r->d_cols, (T *)r->d_vals, r->d_counts, row_counter, row_list,
@@ -691,8 +669,13 @@ int sg_spgemm_exact_selfjoin_rows(sg_ctx *ctx, const sg_csr *A, const sg_posting
     return dispatch_selfjoin_rows<float>(ctx, A, Bt, keep, r, (float)threshold, row_counter, row_list, row_list_len, sink, all_rows);
 }
 
-static int topn_alloc(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, int32_t stride, int32_t dtype, sg_topn **out) {
-    sg_topn *r = new (std::nothrow) sg_topn();
+struct TopnFree {
+    void operator()(sg_topn *r) const { sg_topn_free(r); }
+};
+using TopnPtr = std::unique_ptr<sg_topn, TopnFree>;   // a result under construction: freed on every early return
+
+static int topn_alloc(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, int32_t stride, int32_t dtype, TopnPtr *out) {
+    TopnPtr r(new (std::nothrow) sg_topn());
     if (!r) return SG_ERR_OOM;
     r->ctx = ctx;
     r->n_rows = n_rows;
@@ -700,15 +683,55 @@ static int topn_alloc(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, int32_t strid
     r->stride = stride;
     r->dtype = dtype;
     const size_t cells = (size_t)n_rows * (size_t)stride + 64;
-    int st = sg_alloc(ctx, cells, &r->d_cols);
-    if (st == SG_OK) st = ctx->alloc(cells * (dtype == SG_F64 ? 8 : 4), &r->d_vals);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_rows + 64, &r->d_counts);
-    if (st != SG_OK) {
-        sg_topn_free(r);
-        return st;
-    }
-    *out = r;
+    SG_TRY(sg_alloc(ctx, cells, &r->d_cols));
+    SG_TRY(ctx->alloc(cells * (dtype == SG_F64 ? 8 : 4), &r->d_vals));
+    SG_TRY(sg_alloc(ctx, (size_t)n_rows + 64, &r->d_counts));
+    *out = std::move(r);
     return SG_OK;
+}
+
+// The result's stride -- top_n, cut at the n_cols columns there are (at least one) -- and whether n_rows rows of it fit the
+// 32-bit result index
+static bool result_stride(int64_t n_rows, int64_t top_n, int64_t n_cols, int32_t *stride) {
+    *stride = (int32_t)(top_n < n_cols ? top_n : (n_cols > 0 ? n_cols : 1));
+    return (double)n_rows * (double)*stride <= 2.0e9;
+}
+
+static int result_overflow(int64_t n_rows, int32_t stride, const char *advice) {
+    sg_set_error("result of %lld rows x top_n %lld does not fit the 32-bit result index%s", (long long)n_rows, (long long)stride,
+                 advice);
+    return SG_ERR_OVERFLOW;
+}
+
+// Every row of an unsorted result (sort == 0) re-ordered by ascending column
+static int sort_rows_by_column(sg_ctx *ctx, sg_topn *r) {
+    if (r->n_rows <= 0) return SG_OK;
+    const unsigned grid = (unsigned)(r->n_rows < 65535 * 16 ? r->n_rows : 65535 * 16);
+    const size_t lds = (size_t)r->stride * (4 + (r->dtype == SG_F64 ? 8 : 4));
+    if (lds > 64 * 1024) {
+        sg_set_error("sort=0 with top_n=%d is not supported", r->stride);
+        return SG_ERR_UNSUPPORTED;
+    }
+    if (r->dtype == SG_F64)
+        hipLaunchKernelGGL(topn_sort_by_col_kernel<double>, dim3(grid), dim3(64), lds, ctx->stream, r->d_cols, (double *)r->d_vals,
+                           r->d_counts, r->n_rows, r->stride);
+    else
+        hipLaunchKernelGGL(topn_sort_by_col_kernel<float>, dim3(grid), dim3(64), lds, ctx->stream, r->d_cols, (float *)r->d_vals,
+                           r->d_counts, r->n_rows, r->stride);
+    return SG_OK;
+}
+
+// Algorithmic bytes of the multiply (stream model): macs*(4+s) + nnz(A)*(4+s) + (nL+V+2)*4 + out*(4+s); the MAC and
+// output terms are added in sg_ctx_stats once the device counters are read
+static void record_bytes(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, double threshold) {
+    const size_t s = A->dtype == SG_F64 ? 8 : 4;
+    ctx->spgemm_entry_bytes = (int64_t)(4 + s);
+    ctx->spgemm_fixed_bytes = A->nnz * (int64_t)(4 + s) + (A->n_rows + Bt->n_terms + 2) * 4;
+    // what a candidate of the first filter costs: with the second filter its 8-bit copy (header + 4 B an entry), and the
+    // packed row only for those that pass it (no pointer fetch: the header holds it); without: pointer + packed row
+    const double mean_row = Bt->n_right > 0 ? (double)Bt->nnz / (double)Bt->n_right : 0.0;
+    ctx->prune_q8_bytes = sg_q8_applies(ctx, Bt, s == 8 ? threshold : (double)(float)threshold) ? 16.0 + 4.0 * mean_row : 0.0;
+    ctx->prune_row_bytes = (ctx->prune_q8_bytes > 0.0 ? 0.0 : 8.0) + mean_row * (s == 8 ? 16.0 : 8.0);
 }
 
 // Three blocks of 512 left rows (start, middle, end) through the one-sided pruned kernel: what the filter passes per
@@ -717,7 +740,7 @@ static int prune_pilot(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int3
                        bool symmetric, bool *keep_pruned) {
     *keep_pruned = true;
     const int64_t block = 512;
-    sg_topn *scratch = nullptr;
+    TopnPtr scratch;
     SG_TRY(topn_alloc(ctx, block, Bt->n_right, stride, A->dtype, &scratch));
     uint32_t *words = nullptr;            // [0] row counter [1] flagged count, then flagged rows
     unsigned long long *d_stats = nullptr;   // [0] rows [1] postings [2] survivors [3] MACs of the whole multiply [4] pairs scored exactly (the kernel's; eight words like sg_spgemm_pruned_symmetric)
@@ -734,8 +757,8 @@ static int prune_pilot(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int3
         e = hipMemsetAsync(words, 0, 8 * sizeof(uint32_t), ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(scratch->d_counts, 0, sizeof(int32_t) * (size_t)block, ctx->stream);
         if (e == hipSuccess)
-            st = sg_spgemm_pruned_launch(ctx, &view, Bt, stride < SG_TOPN_LANES ? stride : SG_TOPN_LANES, scratch, threshold, delta, words,
-                                         words + 1, words + 8, d_stats);
+            st = sg_spgemm_pruned_launch(ctx, &view, Bt, stride < SG_TOPN_LANES ? stride : SG_TOPN_LANES, scratch.get(), threshold,
+                                         delta, words, words + 1, words + 8, d_stats);
     }
     if (st == SG_OK && e == hipSuccess) {
         hipLaunchKernelGGL(count_macs_kernel, dim3(512), dim3(256), 0, ctx->stream, A->d_indptr, A->d_indices, A->n_rows,
@@ -747,7 +770,6 @@ static int prune_pilot(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int3
     if (st == SG_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     ctx->release(words);
     ctx->release(d_stats);
-    sg_topn_free(scratch);
     if (st != SG_OK) return st;
     if (e != hipSuccess) {
         sg_set_error("pruning pilot: %s", hipGetErrorString(e));
@@ -770,69 +792,302 @@ static int prune_pilot(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int3
     return SG_OK;
 }
 
-// Threshold from which the pruned multiply takes a product: 0.45 in the stream form (below, its filter passes too much:
-// profiles/r01_prune_tuning.log), 0.40 for a self-join that can run the tile-by-tile form on an index of its own (200 k names
-// at 0.4: 9.9 ms against 12.1 for the exact kernel in the self-join form and 20.8 one-sided; at 0.35 the two are level:
-// profiles/r06b_form_sweep.log).  SG_PRUNE_MIN_THRESHOLD overrides both.
-static double prune_min_threshold(const sg_ctx *ctx, bool tile_form) { return env_double(ctx, "SG_PRUNE_MIN_THRESHOLD", tile_form ? 0.40 : 0.45); }
-static std::mutex g_exact_native_mu;   // guards sg_postings::exact_native's first build (two places in sg_spgemm_topn)
-
-// Can the pruned multiply (sg_spgemm_pruned.hip) take this product -- both sides cosine-like, one register list holds a
-// row's result, room below the threshold for its survivor bound -- and can it take its self-join form?
-// below_envelope (the one-GPU multiply asks): set when the threshold ALONE keeps the pruned kernel out -- *symmetric then says
-// whether the exact kernel can run the product in its self-join form (sg_spgemm_pruned_symmetric, exact_all); the same
-// caller's self-join form also takes a top_n of 65 .. 128 (the pass sends a row's own matches through the pair list, whose
-// second pass selects with two register lists).
-static bool pruned_applicable(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t stride, double threshold, double *delta,
-                              bool *symmetric, int *status, bool any_size = false, bool *below_envelope = nullptr) {
-    *symmetric = false;
-    *status = SG_OK;
-    if (below_envelope) *below_envelope = false;
-    const char *pr = ctx->opt("SG_PRUNE");
-    // (top_n of 65 .. 128: the pruned kernel keeps a row's best 64 in its register list; a row that fills the list may have
-    //  more matches and is handed to the exact kernel, which runs a pass per 64 entries -- rows_with_full_lists_kernel)
-    if ((pr && pr[0] == '0') || !Bt->cosine_like || !Bt->d_filt || stride > 2 * SG_TOPN_LANES || A->n_rows <= 0 || Bt->nnz <= 0 ||
-        !sg_pruned_supports_tile(Bt->tile_log2))
-        return false;
-    // ... and rows of more than 128 entries are beyond it altogether: where that is the AVERAGE row (strings of 130 characters
-    // and more) nearly every row would be passed on one by one -- 50 k strings of 155 entries: 68 ms that way, 37.5 the
-    // exact kernel alone (profiles/r06b_long_strings.log) -- the exact kernel takes the product as it does below the threshold
-    const bool thr_ok = threshold >= prune_min_threshold(ctx, Bt->tile_form) &&
-                        !((double)A->nnz > env_double(ctx, "SG_PRUNE_MAX_MEAN_ROW", 128.0) * (double)A->n_rows);   // below ~0.4 the filter passes too much (profiles/r01_prune_tuning.log)
-    if (!thr_ok && !below_envelope) return false;
-    // tuned at 663 k: the tile-by-tile form 0.05 (profiles/r01_prune_tuning.log); the stream form, whose rounds are cheaper
-    // next to the exact scorings, 0.03 (profiles/r03_sessionG_H_delta.log: 9.76 / 9.95 / 10.10 ms at 0.03 / 0.04 / 0.05;
-    // with identical rows grouped the optimum is flat from 0.02 to 0.04: profiles/r03_sessionU_delta_freq_ab.log)
-    // (0.03 only where rows are sparse next to the vocabulary -- name data; on small vocabularies, the regime of the
-    //  pruned-or-exact pilot below, a tighter bound passes too many candidates: 0.05 as before)
-    const bool sparse_rows = A->n_rows > 0 && (double)A->nnz / (double)A->n_rows <= 0.004 * (double)Bt->n_terms;
-    *delta = env_double(ctx, "SG_PRUNE_DELTA", Bt->fold_log2 > 0 && sparse_rows ? 0.03 : 0.05);
-    if (*delta > 0.5 * threshold) *delta = 0.5 * threshold;
-    if (*delta < 0.02) *delta = 0.02;
-    bool a_ok = false;
-    float a_n2 = 0.f;
-    *status = sg_csr_props(ctx, A, &a_ok, &a_n2, nullptr);     // (the longest row is not asked for: it alone needs a look)
-    if (*status != SG_OK || !a_ok) return false;
-    // self-join (A is the matrix the postings were built from): score every pair once, from the row with the larger
-    // index (sg_spgemm_pruned.hip, symmetric mode; rows the pruned kernel cannot take go through the exact kernel's
-    // self-join launch inside the same pass)
-    const char *sy = ctx->opt("SG_SYM");
-    // ... from the size at which halving the (row, tile) visits outweighs the second pass over the pair list
-    // and its host round trip: 0.58 vs 0.57 ms at 50 k rows, 0.95 vs 1.20 at 100 k, 14.0 vs 26.8 at 663 k
-    // (profiles/r02_sessionM_sym_sweep.log)
-    *symmetric = !(sy && sy[0] == '0') && stride <= (below_envelope ? 2 : 1) * SG_TOPN_LANES && A->n_rows == Bt->n_right && A->d_indptr == Bt->b_indptr &&
-                 A->d_indices == Bt->b_indices && A->d_data == Bt->b_data &&
-                 (any_size || A->n_rows >= (int64_t)env_int(ctx, "SG_SYM_MIN_ROWS", 65536) || (sy && sy[0] == '1') ||
-                  // (the bar was set on names, 19 entries a row; longer rows cost more each and the form pays earlier -- 50 k rows
-                  //  of 96 entries: 10.1 ms one-sided, 6.95 in the self-join form -- and the exact kernel in the self-join form
-                  //  halves a product that is many times dearer at the same size)
-                  A->nnz >= (int64_t)19 * (int64_t)env_int(ctx, "SG_SYM_MIN_ROWS", 65536) ||
-                  (!thr_ok && A->n_rows >= (int64_t)env_int(ctx, "SG_EXACT_SYM_MIN_ROWS", 16384)));
-    if (!thr_ok) {
-        *below_envelope = true;
-        return false;
+// Is A the matrix this index was built from -- a self-join?  (An index over groups of identical rows: the caller's matrix,
+// not the representatives'.)
+static bool built_from(const sg_csr *A, const sg_postings *Bt) {
+    if (Bt->collapse) {
+        const sg_csr *cb = &Bt->caller_b_copy;
+        return A->n_rows == Bt->collapse->n_orig && A->d_indptr == cb->d_indptr && A->d_indices == cb->d_indices &&
+               A->d_data == cb->d_data;
     }
-    return true;
+    return A->n_rows == Bt->n_right && A->d_indptr == Bt->b_indptr && A->d_indices == Bt->b_indices && A->d_data == Bt->b_data;
+}
+
+// The object that owns what is built on demand: a view is a copy on the caller's stack
+static const sg_postings *owner(const sg_postings *Bt) { return Bt->view_of ? Bt->view_of : Bt; }
+
+// The indexes kept with an index (sg_postings::plain, alt_tile, exact_native), built from `from` on first use and owned by
+// `home` (view_of resolved).  Two threads sharing the index must not both build one; no build nests inside
+// another, so one lock serves the three.  (The matrix has to be alive as long as the index is: include/sg_hip.h,
+// sg_postings_build.)
+enum class SgCompanion { plain, alt_tile, exact_native };
+static std::mutex g_companion_mu;
+
+static int companion(sg_ctx *ctx, const sg_postings *home, SgCompanion kind, const sg_csr *from, const sg_postings **out) {
+    sg_postings **slot = kind == SgCompanion::plain      ? &home->plain
+                         : kind == SgCompanion::alt_tile ? &home->alt_tile
+                                                         : &home->exact_native;
+    std::lock_guard<std::mutex> lock(g_companion_mu);
+    if (!*slot) {
+        if (kind == SgCompanion::plain) {   // every row, on the caller's own tile and flags
+            SG_TRY(sg_postings_build_flags(ctx, from, home->build_tile_cols, (home->build_flags & 0xff) | SG_POSTINGS_NO_COLLAPSE, slot));
+        } else {                            // the form's own tile and layout, from rows that may still be pending
+            SG_TRY(sg_csr_ensure_rows(ctx, from));
+            SG_TRY(sg_postings_build_flags(ctx, from, 0,
+                                           (home->build_flags & SG_POSTINGS_NO_PERMUTATION) | SG_POSTINGS_NO_COLLAPSE |
+                                               (kind == SgCompanion::alt_tile ? SG_POSTINGS_TILE_FORM : SG_POSTINGS_EXACT_ONLY),
+                                           slot));
+        }
+    }
+    *out = *slot;
+    return SG_OK;
+}
+
+// The matrix a companion of Bt is built from: A itself in a self-join, otherwise the matrix the caller's index was built from
+// (of an index over groups, whose view Bt is, the representatives' one); null: not known
+static const sg_csr *companion_source(const sg_csr *A, const sg_postings *Bt) {
+    if (built_from(A, Bt)) return A;
+    const sg_postings *home = owner(Bt);
+    return home->collapse ? home->collapse->unique : (Bt->built_from_valid ? &Bt->built_from : nullptr);
+}
+
+// ---- Which form runs: the exact kernel or the pruned one (sg_spgemm_pruned.hip), each one-sided or
+//      in the self-join form (A is the matrix the index was built from: every pair scored once, from the row with the larger
+//      index), and the index its launches run on
+struct SgPlan {
+    enum Form { EXACT, EXACT_SELFJOIN, PRUNED, PRUNED_SELFJOIN };
+    Form form = EXACT;
+    const sg_postings *index = nullptr;   // the caller's index, or one kept with it (sg_postings::alt_tile, exact_native)
+    int32_t stride = 0;                   // result columns per row
+    double threshold = 0.0;               // the caller's, clamped at 0
+    double delta = 0.0;                   // the pruned kernel's room below the threshold for its survivor bound
+};
+
+// row_range: the question of sg_selfjoin_range, a row range of a multi-GPU self-join -- can the pruned kernel's self-join
+// form take it on the index given, at any size and with one register list?  Anything else is not applicable there: no
+// index of the multiply's own, no exact kernel in the self-join form, no pilot.
+static int plan_multiply(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t top_n, double threshold, bool row_range,
+                         SgPlan *plan) {
+    *plan = SgPlan();
+    // only touched accumulators are candidates; with non-negative data (TF-IDF) touched == value > 0,
+    // so a negative threshold selects the same entries as 0
+    if (!(threshold > 0.0)) threshold = 0.0;
+    plan->threshold = threshold;
+    plan->index = Bt;
+    if (!result_stride(A->n_rows, top_n, Bt->n_right, &plan->stride))   // (row_range: not applicable, the caller's other path reports it)
+        return row_range ? SG_OK : result_overflow(A->n_rows, plan->stride, "; split the left matrix");
+    const int32_t stride = plan->stride;
+    const bool prune_on = !ctx->opt_is("SG_PRUNE", '0');
+    // Threshold from which the pruned multiply takes a product: 0.45 in the stream form (below, its filter passes too much:
+    // profiles/r01_prune_tuning.log), 0.40 for a self-join that can run the tile-by-tile form on an index of its own (200 k names
+    // at 0.4: 9.9 ms against 12.1 for the exact kernel in the self-join form and 20.8 one-sided; at 0.35 the two are level:
+    // profiles/r06b_form_sweep.log).  SG_PRUNE_MIN_THRESHOLD overrides both.
+    auto prune_min_threshold = [ctx](bool tile_form) { return ctx->opt_double("SG_PRUNE_MIN_THRESHOLD", tile_form ? 0.40 : 0.45); };
+
+    // ---- which form of the pruned multiply?  The stream form (the index as built: 4096-column tiles folded eight to an
+    //      accumulator tile, second filter) is the fastest where most candidates are false alarms -- name-matching thresholds.
+    //      As the threshold falls, sums of eight unrelated columns cross the bar ever more often: from SG_ALT_FORM_BELOW (0.65)
+    //      down a self-join runs the tile-by-tile form on an index of its own, built once and kept with the index
+    //      (scripts/form_sweep.py, 200 k / 663 k names at 0.6: 5.4 / 31.4 ms stream, 3.4 / 24.1 ms tile by tile; at 0.8:
+    //      1.3 / 5.1 against 1.8 / 11.7).
+    //      One-sided products (master x duplicates) too: the index is then built from the matrix the caller's index was.
+    if (!row_range && Bt->cosine_like && Bt->d_filt && Bt->fold_log2 > 0 && stride <= 2 * SG_TOPN_LANES && A->n_rows > 0 &&
+        Bt->n_right > 0 && threshold < ctx->opt_double("SG_ALT_FORM_BELOW", 0.65) && threshold >= prune_min_threshold(true) &&
+        ctx->opt_int("SG_ALT_FORM", 1) != 0 && prune_on) {
+        const sg_csr *from = companion_source(A, Bt);
+        if (from && from->n_rows == Bt->n_right) SG_TRY(companion(ctx, owner(Bt), SgCompanion::alt_tile, from, &Bt));
+    }
+
+    // ---- pruned multiply (sg_spgemm_pruned.hip) when both sides are cosine-like and one register list holds the row's
+    //      result, and there is room below the threshold for its survivor bound.  (top_n of 65 .. 128: the pruned kernel keeps
+    //      a row's best 64 in its register list; a row that fills the list may have more matches and is handed to the exact
+    //      kernel, which runs a pass per 64 entries -- rows_with_full_lists_kernel.)
+    bool prune = false, symmetric = false;
+    bool below = false;   // the threshold ALONE keeps the pruned kernel out: `symmetric` then says whether the EXACT kernel can
+                          // run the product in the self-join form (sg_spgemm_pruned_symmetric, exact_all)
+    if (prune_on && Bt->cosine_like && Bt->d_filt && stride <= 2 * SG_TOPN_LANES && A->n_rows > 0 && Bt->nnz > 0 &&
+        sg_pruned_supports_tile(Bt->tile_log2)) {
+        // ... and rows of more than 128 entries are beyond it altogether: where that is the AVERAGE row (strings of 130 characters
+        // and more) nearly every row would be passed on one by one -- 50 k strings of 155 entries: 68 ms that way, 37.5 the
+        // exact kernel alone (profiles/r06b_long_strings.log) -- the exact kernel takes the product as it does below the threshold
+        const bool thr_ok = threshold >= prune_min_threshold(Bt->tile_form) &&
+                            !((double)A->nnz > ctx->opt_double("SG_PRUNE_MAX_MEAN_ROW", 128.0) * (double)A->n_rows);   // below ~0.4 the filter passes too much (profiles/r01_prune_tuning.log)
+        if (thr_ok || !row_range) {
+            // tuned at 663 k: the tile-by-tile form 0.05 (profiles/r01_prune_tuning.log); the stream form, whose rounds are cheaper
+            // next to the exact scorings, 0.03 (profiles/r03_sessionG_H_delta.log: 9.76 / 9.95 / 10.10 ms at 0.03 / 0.04 / 0.05;
+            // with identical rows grouped the optimum is flat from 0.02 to 0.04: profiles/r03_sessionU_delta_freq_ab.log)
+            // (0.03 only where rows are sparse next to the vocabulary -- name data; on small vocabularies, the regime of the
+            //  pruned-or-exact pilot below, a tighter bound passes too many candidates: 0.05 as before)
+            const bool sparse_rows = A->n_rows > 0 && (double)A->nnz / (double)A->n_rows <= 0.004 * (double)Bt->n_terms;
+            double delta = ctx->opt_double("SG_PRUNE_DELTA", Bt->fold_log2 > 0 && sparse_rows ? 0.03 : 0.05);
+            if (delta > 0.5 * threshold) delta = 0.5 * threshold;
+            if (delta < 0.02) delta = 0.02;
+            plan->delta = delta;
+            bool a_ok = false;
+            float a_n2 = 0.f;
+            SG_TRY(sg_csr_props(ctx, A, &a_ok, &a_n2, nullptr));     // (the longest row is not asked for: it alone needs a look)
+            if (a_ok) {
+                // self-join: score every pair once, from the row with the larger index (sg_spgemm_pruned.hip, symmetric mode;
+                // rows the pruned kernel cannot take go through the exact kernel's self-join launch inside the same pass) --
+                // with a top_n of 65 .. 128 too, except on a row range (the pass sends a row's own matches through the pair
+                // list, whose second pass selects with two register lists) ...
+                // ... from the size at which halving the (row, tile) visits outweighs the second pass over the pair list
+                // and its host round trip: 0.58 vs 0.57 ms at 50 k rows, 0.95 vs 1.20 at 100 k, 14.0 vs 26.8 at 663 k
+                // (profiles/r02_sessionM_sym_sweep.log)
+                const int64_t sym_min_rows = ctx->opt_int("SG_SYM_MIN_ROWS", 65536);
+                symmetric = !ctx->opt_is("SG_SYM", '0') && stride <= (row_range ? 1 : 2) * SG_TOPN_LANES && built_from(A, Bt) &&
+                            (row_range || A->n_rows >= sym_min_rows || ctx->opt_is("SG_SYM", '1') ||
+                             // (the bar was set on names, 19 entries a row; longer rows cost more each and the form pays earlier --
+                             //  50 k rows of 96 entries: 10.1 ms one-sided, 6.95 in the self-join form -- and the exact kernel in
+                             //  the self-join form halves a product that is many times dearer at the same size)
+                             A->nnz >= (int64_t)19 * sym_min_rows ||
+                             (!thr_ok && A->n_rows >= (int64_t)ctx->opt_int("SG_EXACT_SYM_MIN_ROWS", 16384)));
+                prune = thr_ok;
+                below = !thr_ok;
+            }
+        }
+    }
+    const bool exact_sym_on = ctx->opt_int("SG_EXACT_SYM", 1) != 0;
+    bool exact_sym = !prune && below && symmetric && exact_sym_on;   // the EXACT kernel in the self-join form (every row through its self-join launch)
+    if (!prune) symmetric = false;
+
+    // ---- pruned or exact?  On a vocabulary that is small next to the rows (2-grams: a row holds 2 % of all terms) the
+    //      filter passes thousands of candidates per row and scoring them exactly costs more than the whole exact
+    //      multiply (119 vs 84 ms at 200 k 2-grams).  Nothing cheap predicts the candidates, so on such inputs three
+    //      blocks of 512 left rows are run through the pruned kernel first and the two costs are priced from what
+    //      they did (prune_pilot; constants fitted on the family sweep in profiles/r02_profile_k4p_v9b_sym.log).
+    if (!row_range && prune && A->n_rows >= 32768 && A->nnz > 0 && Bt->n_terms > 0 &&
+        (double)A->nnz / (double)A->n_rows > 0.004 * (double)Bt->n_terms && ctx->opt_int("SG_PRUNE_PILOT", 1) != 0) {
+        bool keep_pruned = true;
+        SG_TRY(sg_csr_ensure_rows(ctx, A));     // (the pilot runs the one-sided kernel over blocks of A's rows)
+        SG_TRY(prune_pilot(ctx, A, Bt, stride, threshold, plan->delta, symmetric, &keep_pruned));
+        // (the exact kernel in the self-join form walks half the (row, tile) visits -- 200 k 2-grams: 63 ms one-sided; the
+        //  same factor the pilot grants the pruned kernel's self-join form)
+        if (symmetric && exact_sym_on && keep_pruned && ctx->pilot_ms_pruned > 0.55 * ctx->pilot_ms_exact + 0.3) keep_pruned = false;
+        if (!keep_pruned) {
+            exact_sym = symmetric && exact_sym_on;
+            prune = symmetric = false;
+        }
+    }
+
+    const bool native_on = !row_range && ctx->opt_int("SG_EXACT_NATIVE", 1) != 0;
+    const int32_t native_tile_log2 = A->dtype == SG_F64 ? 10 : 11;
+    if (exact_sym && native_on && Bt->tile_log2 > native_tile_log2) {
+        // the exact kernel in the self-join form runs on ITS layout of the index (tile of 2048 / 1024 columns: twice the waves
+        // per CU), built once per index and kept with it -- also what the one-sided exact kernel runs on if the form is called
+        // off (pair list too small)
+        SG_TRY(companion(ctx, owner(Bt), SgCompanion::exact_native, A, &Bt));
+    } else if (!prune && !exact_sym && native_on && Bt->d_filt && Bt->nnz >= ((int64_t)1 << 20) && Bt->tile_log2 > native_tile_log2) {
+        // ... and the exact kernel ONE-SIDED (a master x duplicates product below the pruned multiply's thresholds, a self-join
+        // too small for the self-join form) on its own layout as well, where the product is worth a second index: the
+        // 4096-column tiles of the pruned multiply leave it half the waves per CU (200 k names at 0.4: 25.0 ms there, 20.8 on
+        // its own)
+        const sg_csr *from = companion_source(A, Bt);
+        if (from && from->n_rows == Bt->n_right) SG_TRY(companion(ctx, owner(Bt), SgCompanion::exact_native, from, &Bt));
+    }
+
+    plan->index = Bt;
+    plan->form = prune ? (symmetric ? SgPlan::PRUNED_SELFJOIN : SgPlan::PRUNED) : (exact_sym ? SgPlan::EXACT_SELFJOIN : SgPlan::EXACT);
+    return SG_OK;
+}
+
+// The launches of a plan: the self-join form's pass, the pruned kernel, and the exact kernel -- the whole product, the rows
+// the pruned kernel handed over, or what a self-join pass that was called off left
+static int run_plan(sg_ctx *ctx, const sg_csr *A, const SgPlan &plan, sg_topn *r) {
+    const sg_postings *Bt = plan.index;
+    const int32_t stride = plan.stride;
+    const double threshold = plan.threshold;
+    const bool prune = plan.form == SgPlan::PRUNED || plan.form == SgPlan::PRUNED_SELFJOIN;
+    const bool self_join = plan.form == SgPlan::PRUNED_SELFJOIN || plan.form == SgPlan::EXACT_SELFJOIN;
+    const size_t s = A->dtype == SG_F64 ? 8 : 4;
+
+    // tiles per launch: keep one launch's postings (~ nnz*(4+s)/n_tiles per tile) near 2 MiB so that
+    // they stay in every XCD's 4 MiB L2 while all rows stream over them
+    // Tile groups (separate launches over a few tiles each, running state kept in the output arrays)
+    // exist for right-hand sides whose postings exceed the 256 MiB Infinity Cache; below that one launch
+    // is faster (measured: 280 ms vs 415 ms at 663 k -- every launch has a tail and a state round trip).
+    int group = ctx->opt_int("SG_TILE_GROUP", 0);
+    if (group <= 0) {
+        const double bytes = (double)Bt->nnz * (double)(4 + s);
+        const double budget = 192.0 * 1024 * 1024;
+        group = bytes <= budget ? Bt->n_tiles : (int)((double)Bt->n_tiles * budget / bytes);
+        if (group < 1) group = 1;
+    }
+    if (group > Bt->n_tiles) group = Bt->n_tiles;
+    const int n_groups = (Bt->n_tiles + group - 1) / group;
+    const int n_pass = (stride + SG_TOPN_LANES - 1) / SG_TOPN_LANES;
+    const int n_launch = n_groups * n_pass;
+
+    const size_t lds = s << Bt->tile_log2;
+    int waves_per_cu = (int)(ctx->lds_per_cu / lds);
+    if (waves_per_cu > 32) waves_per_cu = 32;
+    if (waves_per_cu < 1) waves_per_cu = 1;
+    waves_per_cu = ctx->opt_int("SG_WAVES_PER_CU", waves_per_cu);
+    unsigned grid = (unsigned)ctx->num_cu * (unsigned)waves_per_cu;
+    if ((int64_t)grid > A->n_rows) grid = (unsigned)(A->n_rows > 0 ? A->n_rows : 1);
+
+    // counters: [0, n_launch] row counters of the exact launches; then the pruned kernel's row counter, the
+    // number of rows it handed over, and their list
+    const size_t n_words = (size_t)n_launch + 4;
+    uint32_t *counters = nullptr;
+    SG_TRY(sg_alloc(ctx, n_words + (prune ? (size_t)A->n_rows : 0), &counters));
+    uint32_t *handed_count = counters + n_launch + 2;
+    uint32_t *handed_rows = counters + n_words;
+    int st = SG_OK;
+    {
+        SgTimer timer(ctx, SG_K_SPGEMM);
+        st = SG_ZERO3(ctx, counters, sizeof(uint32_t) * n_words, r->d_counts, sizeof(int32_t) * (size_t)A->n_rows,
+                      ctx->d_stat_words, 7 * sizeof(int64_t));   // ([0], [1]: written by the counting kernels at the end)
+        bool sym_done = false;
+        if (self_join && st == SG_OK)
+            st = sg_spgemm_pruned_symmetric(ctx, A, Bt, stride, r, threshold, plan.delta, (unsigned long long *)(ctx->d_stat_words + 2),
+                                            &sym_done, 0, -1, nullptr, nullptr, 1, plan.form == SgPlan::EXACT_SELFJOIN);
+        ctx->prune_symmetric = sym_done;
+        // everything below reads the rows of A itself (the self-join form read the index's copy in position order): the
+        // representatives' matrix of an index over groups is written now if it is still pending
+        if (!sym_done && st == SG_OK) st = sg_csr_ensure_rows(ctx, A);
+        if (prune && !sym_done && st == SG_OK) {
+            SgTimer kt(ctx, SG_K_SPGEMM_KERNEL);
+            st = sg_spgemm_pruned_launch(ctx, A, Bt, stride < SG_TOPN_LANES ? stride : SG_TOPN_LANES, r, threshold, plan.delta,
+                                         counters + n_launch + 1, handed_count, handed_rows,
+                                         (unsigned long long *)(ctx->d_stat_words + 2));
+            if (st == SG_OK && stride > SG_TOPN_LANES && A->n_rows > 0) {
+                hipLaunchKernelGGL(rows_with_full_lists_kernel, dim3((unsigned)((A->n_rows + 255) / 256)), dim3(256), 0, ctx->stream,
+                                   (const int32_t *)r->d_counts, A->n_rows, (int32_t)SG_TOPN_LANES, handed_count, handed_rows);
+                if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
+            }
+        }
+        // The exact kernel: the whole product when the pruned multiply does not apply, or the rows it handed over -- whether
+        // there are any is read back (four bytes), because the index build leaves the exact kernel's postings out when
+        // the pruned multiply is expected to take everything (sg_postings_ensure_full writes them on demand).
+        bool need_exact = !prune && !sym_done;
+        if (prune && !sym_done && st == SG_OK && (Bt->d_vals != nullptr || Bt->nnz <= 0)) {
+            // the exact kernel's postings exist: its launch over the handed rows goes out on the device-side count, as
+            // before the postings became lazy -- blocked and zipped multiplies enqueue without a host round trip per part
+            need_exact = true;
+        } else if (prune && !sym_done && st == SG_OK) {
+            uint32_t *h_handed = (uint32_t *)(ctx->h_stat_words + 7);   // pinned
+            *h_handed = 0;
+            if (hipMemcpyAsync(h_handed, handed_count, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                hipStreamSynchronize(ctx->stream) != hipSuccess)
+                st = SG_ERR_HIP;
+            need_exact = *h_handed > 0;
+        }
+        if (need_exact && st == SG_OK) st = sg_postings_ensure_full(ctx, Bt);
+        std::optional<SgTimer> exact_timer;   // the exact kernel's launches, when they are the whole product
+        if (!prune && !sym_done) exact_timer.emplace(ctx, SG_K_SPGEMM_KERNEL);
+        int li = 0;
+        for (int pass = 0; pass < n_pass && st == SG_OK && A->n_rows > 0 && need_exact; ++pass) {
+            const int pass_off = pass * SG_TOPN_LANES;
+            const int keep = stride - pass_off < SG_TOPN_LANES ? stride - pass_off : SG_TOPN_LANES;
+            for (int g = 0; g < n_groups && st == SG_OK; ++g, ++li) {
+                const int tb = g * group;
+                const int te = tb + group < Bt->n_tiles ? tb + group : Bt->n_tiles;
+                if (A->dtype == SG_F64)
+                    st = dispatch_spgemm<double>(ctx, A, Bt, tb, te, keep, pass_off, r, (double)threshold,
+                                                 counters + li, grid, prune ? handed_rows : nullptr, handed_count);
+                else
+                    st = dispatch_spgemm<float>(ctx, A, Bt, tb, te, keep, pass_off, r, (float)threshold,
+                                                counters + li, grid, prune ? handed_rows : nullptr, handed_count);
+            }
+        }
+        exact_timer.reset();   // stop event of the exact kernel's launches
+        if (prune && !sym_done && st == SG_OK &&   // (the self-join form has left its own count there)
+            hipMemcpyAsync(ctx->d_stat_words + 5, handed_count, 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+            st = SG_ERR_HIP;
+    }
+    ctx->release(counters);
+    return st;
 }
 
 // The index was built over one representative per group of identical right-hand rows (sg_collapse.hip): multiply on the
@@ -844,58 +1099,37 @@ static int spgemm_topn_collapsed(sg_ctx *ctx, const sg_csr *A, const sg_postings
     if (stride64 > c->n_orig) stride64 = c->n_orig > 0 ? c->n_orig : 1;
     if (stride64 > 2 * SG_TOPN_LANES) {
         // more columns per row than the multiply on the groups keeps (two register lists since round 6; one before, and
-        // top_n of 65 .. 128 then multiplied every row: 663 k names, top 100: 9.1 ms): an index over all rows, built once,
-        // serves these calls
-        {
-            // (made on first use; two threads sharing the index must not both make it -- ADVICE r03.  It is built from the
-            //  caller's matrix, which has to be alive as long as the index is: include/sg_hip.h, sg_postings_build)
-            static std::mutex plain_mu;
-            std::lock_guard<std::mutex> lock(plain_mu);
-            if (!Bt->plain)
-                SG_TRY(sg_postings_build_flags(ctx, &Bt->caller_b_copy, Bt->build_tile_cols, (Bt->build_flags & 0xff) | (1 << 8), &Bt->plain));
-        }
-        return sg_spgemm_topn(ctx, A, Bt->plain, top_n, threshold, sort, out);
+        // top_n of 65 .. 128 then multiplied every row: 663 k names, top 100: 9.1 ms): an index over all rows, built once
+        // from the caller's matrix, serves these calls
+        const sg_postings *plain = nullptr;
+        SG_TRY(companion(ctx, Bt, SgCompanion::plain, &Bt->caller_b_copy, &plain));
+        return sg_spgemm_topn(ctx, A, plain, top_n, threshold, sort, out);
     }
-    const sg_csr *cb = &Bt->caller_b_copy;
-    const bool self = A->n_rows == c->n_orig && A->d_indptr == cb->d_indptr && A->d_indices == cb->d_indices &&
-                      A->d_data == cb->d_data;
+    const bool self = built_from(A, Bt);
     sg_postings view = *Bt;          // shallow: the same index, seen without the groups
     view.collapse = nullptr;
     view.plain = nullptr;
     view.view_of = Bt;
-    sg_topn *ru = nullptr;
+    sg_topn *groups = nullptr;
     ++ctx->inner_multiply_depth;
-    const int st_inner = sg_spgemm_topn(ctx, self ? c->unique : A, &view, top_n, threshold, 1, &ru);
+    const int st_inner = sg_spgemm_topn(ctx, self ? c->unique : A, &view, top_n, threshold, 1, &groups);
     --ctx->inner_multiply_depth;
     SG_TRY(st_inner);
-    sg_topn *r = nullptr;
-    int st = topn_alloc(ctx, A->n_rows, c->n_orig, (int32_t)stride64, A->dtype, &r);
-    if (st == SG_OK) {
+    const TopnPtr ru(groups);
+    TopnPtr r;
+    SG_TRY(topn_alloc(ctx, A->n_rows, c->n_orig, (int32_t)stride64, A->dtype, &r));
+    {
         SgTimer timer(ctx, SG_K_ZIP);    // the expansion is a merge by column, like the zip of column blocks
-        st = sg_collapse_expand(ctx, c, ru, self, r);   // (clears r's counts itself)
-        if (st == SG_OK && !sort && A->n_rows > 0) {
-            const unsigned g2 = (unsigned)(A->n_rows < 65535 * 16 ? A->n_rows : 65535 * 16);
-            const size_t l2 = (size_t)r->stride * (4 + (A->dtype == SG_F64 ? 8 : 4));
-            if (A->dtype == SG_F64)
-                hipLaunchKernelGGL(topn_sort_by_col_kernel<double>, dim3(g2), dim3(64), l2, ctx->stream, r->d_cols, (double *)r->d_vals,
-                                   r->d_counts, A->n_rows, r->stride);
-            else
-                hipLaunchKernelGGL(topn_sort_by_col_kernel<float>, dim3(g2), dim3(64), l2, ctx->stream, r->d_cols, (float *)r->d_vals,
-                                   r->d_counts, A->n_rows, r->stride);
-        }
-        if (st == SG_OK && A->n_rows > 0 && ctx->inner_multiply_depth == 0) {   // entries kept, counted on the expanded result
+        SG_TRY(sg_collapse_expand(ctx, c, ru.get(), self, r.get()));   // (clears r's counts itself)
+        if (!sort) SG_TRY(sort_rows_by_column(ctx, r.get()));
+        if (A->n_rows > 0 && ctx->inner_multiply_depth == 0) {   // entries kept, counted on the expanded result
             // (word [1] is still zero: the multiply on the groups cleared it and, being an inner one, did not count)
             hipLaunchKernelGGL(sum_counts_kernel, dim3(256), dim3(256), 0, ctx->stream, r->d_counts, A->n_rows,
                                (unsigned long long *)(ctx->d_stat_words + 1));
-            if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
+            if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
         }
     }
-    sg_topn_free(ru);
-    if (st != SG_OK) {
-        sg_topn_free(r);
-        return st;
-    }
-    *out = r;
+    *out = r.release();
     return SG_OK;
 }
 
@@ -939,15 +1173,16 @@ static int spgemm_topn_left_groups(sg_ctx *ctx, const sg_csr *A, const sg_postin
         if (!g) return SG_OK;
     }
     const SgCollapse *g = A->left_groups;
-    sg_topn *ru = nullptr;
+    sg_topn *groups = nullptr;
     g->unique->left_state = 1;                      // (representatives are distinct)
     ++ctx->inner_multiply_depth;
-    const int st_inner = sg_spgemm_topn(ctx, g->unique, Bt, top_n, threshold, sort, &ru);
+    const int st_inner = sg_spgemm_topn(ctx, g->unique, Bt, top_n, threshold, sort, &groups);
     --ctx->inner_multiply_depth;
     SG_TRY(st_inner);
-    sg_topn *r = nullptr;
-    int st = topn_alloc(ctx, A->n_rows, ru->n_cols, ru->stride, ru->dtype, &r);
-    if (st == SG_OK && A->n_rows > 0) {
+    const TopnPtr ru(groups);
+    TopnPtr r;
+    SG_TRY(topn_alloc(ctx, A->n_rows, ru->n_cols, ru->stride, ru->dtype, &r));
+    if (A->n_rows > 0) {
         SgTimer timer(ctx, SG_K_ZIP);
         const int64_t cells = A->n_rows * (int64_t)ru->stride;
         const unsigned grid = (unsigned)((cells + 255) / 256);
@@ -962,14 +1197,9 @@ static int spgemm_topn_left_groups(sg_ctx *ctx, const sg_csr *A, const sg_postin
         // entries kept: counted on all rows (word [1] is still zero: the inner multiplies clear it and do not count)
         hipLaunchKernelGGL(sum_counts_kernel, dim3(256), dim3(256), 0, ctx->stream, r->d_counts, A->n_rows,
                            (unsigned long long *)(ctx->d_stat_words + 1));
-        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
+        if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
     }
-    sg_topn_free(ru);
-    if (st != SG_OK) {
-        sg_topn_free(r);
-        return st;
-    }
-    *out = r;
+    *out = r.release();
     *done = true;
     return SG_OK;
 }
@@ -979,27 +1209,17 @@ extern "C" int sg_spgemm_topn(sg_ctx *ctx, const sg_csr *A, const sg_postings *B
     SG_REQUIRE(ctx && A && Bt && out, "null argument");
     {
         // one-sided product (A is not the matrix the index was built from: a self-join groups its rows with the index)
-        const sg_csr *own = Bt->collapse ? &Bt->caller_b_copy : nullptr;
-        const bool self = own ? (A->n_rows == Bt->collapse->n_orig && A->d_indptr == own->d_indptr && A->d_indices == own->d_indices &&
-                                 A->d_data == own->d_data)
-                              : (A->n_rows == Bt->n_right && A->d_indptr == Bt->b_indptr && A->d_indices == Bt->b_indices &&
-                                 A->d_data == Bt->b_data);
-        const char *sw = ctx->opt("SG_COLLAPSE"), *ls = ctx->opt("SG_COLLAPSE_LEFT");    // (asked on every call: groups kept
-        const bool off = (sw && sw[0] == '0') || (ls && ls[0] == '0');                      //  with A do not outlive the switch)
-        if (off && A->left_groups) {   // ... and are given back when it is turned off
+        const bool off = ctx->opt_is("SG_COLLAPSE", '0') || ctx->opt_is("SG_COLLAPSE_LEFT", '0');   // (asked on every call: groups
+        if (off && A->left_groups) {   // ... and are given back when it is turned off                //  kept with A do not outlive the switch)
             sg_collapse_free(A->left_groups);
             A->left_groups = nullptr;
             A->left_state = 0;
         }
-        if (!self && !off && A->left_state != 1 && A->n_cols == Bt->n_terms && A->dtype == Bt->dtype && top_n >= 1) {
+        if (!built_from(A, Bt) && !off && A->left_state != 1 && A->n_cols == Bt->n_terms && A->dtype == Bt->dtype && top_n >= 1) {
             // (the result is one row per row of A whatever the number of groups: the 32-bit result index must hold it)
-            const int64_t n_right = Bt->collapse ? Bt->collapse->n_orig : Bt->n_right;
-            const int64_t stride64 = top_n < n_right ? top_n : (n_right > 0 ? n_right : 1);
-            if ((double)A->n_rows * (double)stride64 > 2.0e9) {
-                sg_set_error("result of %lld rows x top_n %lld does not fit the 32-bit result index; split the left matrix",
-                             (long long)A->n_rows, (long long)stride64);
-                return SG_ERR_OVERFLOW;
-            }
+            int32_t stride = 0;
+            if (!result_stride(A->n_rows, top_n, Bt->collapse ? Bt->collapse->n_orig : Bt->n_right, &stride))
+                return result_overflow(A->n_rows, stride, "; split the left matrix");
             bool done = false;
             SG_TRY(spgemm_topn_left_groups(ctx, A, Bt, top_n, threshold, sort, out, &done));
             if (done) return SG_OK;
@@ -1012,274 +1232,26 @@ extern "C" int sg_spgemm_topn(sg_ctx *ctx, const sg_csr *A, const sg_postings *B
     SG_REQUIRE(A->n_cols == Bt->n_terms, "A and B have different numbers of columns (vocabulary size)");
     SG_REQUIRE(A->dtype == Bt->dtype, "A and B have different value types");
     SG_REQUIRE(top_n >= 1, "top_n must be >= 1");
-    // only touched accumulators are candidates; with non-negative data (TF-IDF) touched == value > 0,
-    // so a negative threshold selects the same entries as 0
-    if (!(threshold > 0.0)) threshold = 0.0;
-    int64_t stride64 = top_n;
-    if (stride64 > Bt->n_right) stride64 = Bt->n_right > 0 ? Bt->n_right : 1;
-    if ((double)A->n_rows * (double)stride64 > 2.0e9) {
-        sg_set_error("result of %lld rows x top_n %lld does not fit the 32-bit result index; split the left matrix",
-                     (long long)A->n_rows, (long long)stride64);
-        return SG_ERR_OVERFLOW;
-    }
-    const int32_t stride = (int32_t)stride64;
-    // ---- which form of the pruned multiply?  The stream form (the index as built: 4096-column tiles folded eight to an
-    //      accumulator tile, second filter) is the fastest where most candidates are false alarms -- name-matching thresholds.
-    //      As the threshold falls, sums of eight unrelated columns cross the bar ever more often: from SG_ALT_FORM_BELOW (0.65)
-    //      down a self-join runs the tile-by-tile form on an index of its own, built once and kept with the index
-    //      (scripts/form_sweep.py, 200 k / 663 k names at 0.6: 5.4 / 31.4 ms stream, 3.4 / 24.1 ms tile by tile; at 0.8:
-    //      1.3 / 5.1 against 1.8 / 11.7).
-    //      One-sided products (master x duplicates) too: the index is then built from the matrix the caller's index was.
-    if (Bt->cosine_like && Bt->d_filt && Bt->fold_log2 > 0 && stride <= 2 * SG_TOPN_LANES && A->n_rows > 0 && Bt->n_right > 0 &&
-        threshold < env_double(ctx, "SG_ALT_FORM_BELOW", 0.65) && threshold >= prune_min_threshold(ctx, true) &&
-        env_int(ctx, "SG_ALT_FORM", 1) != 0 && !(ctx->opt("SG_PRUNE") && ctx->opt("SG_PRUNE")[0] == '0')) {
-        const sg_postings *home = Bt->view_of ? Bt->view_of : Bt;   // (a view is a copy on the caller's stack)
-        const bool self = A->n_rows == Bt->n_right && A->d_indptr == Bt->b_indptr && A->d_indices == Bt->b_indices && A->d_data == Bt->b_data;
-        const sg_csr *from = self ? A : (home->collapse ? home->collapse->unique : (Bt->built_from_valid ? &Bt->built_from : nullptr));
-        if (from && from->n_rows == Bt->n_right) {
-            static std::mutex alt_mu;
-            std::lock_guard<std::mutex> lock(alt_mu);
-            if (!home->alt_tile) {
-                SG_TRY(sg_csr_ensure_rows(ctx, from));
-                SG_TRY(sg_postings_build_flags(ctx, from, 0, (Bt->build_flags & SG_POSTINGS_NO_PERMUTATION) | (1 << 8) | SG_POSTINGS_TILE_FORM,
-                                               &home->alt_tile));
-            }
-            Bt = home->alt_tile;
-        }
-    }
-    sg_topn *r = nullptr;
-    SG_TRY(topn_alloc(ctx, A->n_rows, Bt->n_right, stride, A->dtype, &r));
-    const size_t s = A->dtype == SG_F64 ? 8 : 4;
-
-    // ---- pruned multiply (sg_spgemm_pruned.hip) when both sides are cosine-like and one register list
-    //      holds the row's result; its survivor threshold needs some room below the threshold
-    bool prune = false, symmetric = false;
-    bool exact_sym = false;   // the EXACT kernel in the self-join form (every row through its self-join launch)
-    const bool exact_sym_on = env_int(ctx, "SG_EXACT_SYM", 1) != 0;
-    double delta = 0.0;
-    {
-        int pst = SG_OK;
-        bool below = false;
-        prune = pruned_applicable(ctx, A, Bt, stride, threshold, &delta, &symmetric, &pst, false, &below);
-        if (pst != SG_OK) {
-            sg_topn_free(r);
-            return pst;
-        }
-        if (!prune) {
-            exact_sym = below && symmetric && exact_sym_on;
-            symmetric = false;
-        }
-    }
-    // ---- pruned or exact?  On a vocabulary that is small next to the rows (2-grams: a row holds 2 % of all terms) the
-    //      filter passes thousands of candidates per row and scoring them exactly costs more than the whole exact
-    //      multiply (119 vs 84 ms at 200 k 2-grams).  Nothing cheap predicts the candidates, so on such inputs three
-    //      blocks of 512 left rows are run through the pruned kernel first and the two costs are priced from what
-    //      they did (prune_pilot; constants fitted on the family sweep in profiles/r02_profile_k4p_v9b_sym.log).
-    if (prune && A->n_rows >= 32768 && A->nnz > 0 && Bt->n_terms > 0 &&
-        (double)A->nnz / (double)A->n_rows > 0.004 * (double)Bt->n_terms && env_int(ctx, "SG_PRUNE_PILOT", 1) != 0) {
-        bool keep_pruned = true;
-        int pst = sg_csr_ensure_rows(ctx, A);     // (the pilot runs the one-sided kernel over blocks of A's rows)
-        if (pst == SG_OK) pst = prune_pilot(ctx, A, Bt, stride, threshold, delta, symmetric, &keep_pruned);
-        if (pst != SG_OK) {
-            sg_topn_free(r);
-            return pst;
-        }
-        // (the exact kernel in the self-join form walks half the (row, tile) visits -- 200 k 2-grams: 63 ms one-sided; the
-        //  same factor the pilot grants the pruned kernel's self-join form)
-        if (symmetric && exact_sym_on && keep_pruned && ctx->pilot_ms_pruned > 0.55 * ctx->pilot_ms_exact + 0.3) keep_pruned = false;
-        if (!keep_pruned) {
-            exact_sym = symmetric && exact_sym_on;
-            prune = symmetric = false;
-        }
-    }
-
-    // the exact kernel in the self-join form runs on ITS layout of the index (tile of 2048 / 1024 columns: twice the waves per
-    // CU), built once per index and kept with it
-    const sg_postings *Bx = Bt;
-    if (exact_sym && env_int(ctx, "SG_EXACT_NATIVE", 1) != 0 && Bt->tile_log2 > (A->dtype == SG_F64 ? 10 : 11)) {
-        std::lock_guard<std::mutex> lock(g_exact_native_mu);
-        const sg_postings *home = Bt->view_of ? Bt->view_of : Bt;   // (a view is a copy on the caller's stack)
-        if (!home->exact_native) {
-            int bst = sg_csr_ensure_rows(ctx, A);
-            if (bst == SG_OK)
-                bst = sg_postings_build_flags(ctx, A, 0, (Bt->build_flags & SG_POSTINGS_NO_PERMUTATION) | (1 << 8) | SG_POSTINGS_EXACT_ONLY,
-                                              &home->exact_native);
-            if (bst != SG_OK) {
-                sg_topn_free(r);
-                return bst;
-            }
-        }
-        Bx = home->exact_native;
-        Bt = Bx;   // (also what the one-sided exact kernel runs on if the form is called off: pair list too small)
-    }
-
-    // ... and the exact kernel ONE-SIDED (a master x duplicates product below the pruned multiply's thresholds, a self-join too
-    // small for the self-join form) on its own layout as well, where the product is worth a second index: the 4096-column
-    // tiles of the pruned multiply leave it half the waves per CU (200 k names at 0.4: 25.0 ms there, 20.8 on its own)
-    if (!prune && !exact_sym && env_int(ctx, "SG_EXACT_NATIVE", 1) != 0 && Bt->d_filt && Bt->nnz >= ((int64_t)1 << 20) &&
-        Bt->tile_log2 > (A->dtype == SG_F64 ? 10 : 11)) {
-        const sg_postings *home = Bt->view_of ? Bt->view_of : Bt;
-        const bool self = A->n_rows == Bt->n_right && A->d_indptr == Bt->b_indptr && A->d_indices == Bt->b_indices && A->d_data == Bt->b_data;
-        const sg_csr *from = self ? A : (home->collapse ? home->collapse->unique : (Bt->built_from_valid ? &Bt->built_from : nullptr));
-        if (from && from->n_rows == Bt->n_right) {
-            std::lock_guard<std::mutex> lock(g_exact_native_mu);
-            if (!home->exact_native) {
-                int bst = sg_csr_ensure_rows(ctx, from);
-                if (bst == SG_OK)
-                    bst = sg_postings_build_flags(ctx, from, 0, (Bt->build_flags & SG_POSTINGS_NO_PERMUTATION) | (1 << 8) | SG_POSTINGS_EXACT_ONLY,
-                                                  &home->exact_native);
-                if (bst != SG_OK) {
-                    sg_topn_free(r);
-                    return bst;
-                }
-            }
-            Bt = home->exact_native;
-        }
-    }
-
-    // tiles per launch: keep one launch's postings (~ nnz*(4+s)/n_tiles per tile) near 2 MiB so that
-    // they stay in every XCD's 4 MiB L2 while all rows stream over them
-    // Tile groups (separate launches over a few tiles each, running state kept in the output arrays)
-    // exist for right-hand sides whose postings exceed the 256 MiB Infinity Cache; below that one launch
-    // is faster (measured: 280 ms vs 415 ms at 663 k -- every launch has a tail and a state round trip).
-    int group = env_int(ctx, "SG_TILE_GROUP", 0);
-    if (group <= 0) {
-        const double bytes = (double)Bt->nnz * (double)(4 + s);
-        const double budget = 192.0 * 1024 * 1024;
-        group = bytes <= budget ? Bt->n_tiles : (int)((double)Bt->n_tiles * budget / bytes);
-        if (group < 1) group = 1;
-    }
-    if (group > Bt->n_tiles) group = Bt->n_tiles;
-    const int n_groups = (Bt->n_tiles + group - 1) / group;
-    const int n_pass = (stride + SG_TOPN_LANES - 1) / SG_TOPN_LANES;
-    const int n_launch = n_groups * n_pass;
-
-    const size_t lds = s << Bt->tile_log2;
-    int waves_per_cu = (int)(ctx->lds_per_cu / lds);
-    if (waves_per_cu > 32) waves_per_cu = 32;
-    if (waves_per_cu < 1) waves_per_cu = 1;
-    waves_per_cu = env_int(ctx, "SG_WAVES_PER_CU", waves_per_cu);
-    unsigned grid = (unsigned)ctx->num_cu * (unsigned)waves_per_cu;
-    if ((int64_t)grid > A->n_rows) grid = (unsigned)(A->n_rows > 0 ? A->n_rows : 1);
-
-    // counters: [0, n_launch] row counters of the exact launches; then the pruned kernel's row counter, the
-    // number of rows it handed over, and their list
-    const size_t n_words = (size_t)n_launch + 4;
-    uint32_t *counters = nullptr;
-    int st = sg_alloc(ctx, n_words + (prune ? (size_t)A->n_rows : 0), &counters);
-    if (st != SG_OK) {
-        sg_topn_free(r);
-        return st;
-    }
-    uint32_t *handed_count = counters + n_launch + 2;
-    uint32_t *handed_rows = counters + n_words;
-    {
-        SgTimer timer(ctx, SG_K_SPGEMM);
-        st = SG_OK;
-        st = SG_ZERO3(ctx, counters, sizeof(uint32_t) * n_words, r->d_counts, sizeof(int32_t) * (size_t)A->n_rows,
-                      ctx->d_stat_words, 7 * sizeof(int64_t));   // ([0], [1]: written by the counting kernels at the end)
-        bool sym_done = false;
-        if ((symmetric || exact_sym) && st == SG_OK)
-            st = sg_spgemm_pruned_symmetric(ctx, A, exact_sym ? Bx : Bt, stride, r, threshold, delta,
-                                            (unsigned long long *)(ctx->d_stat_words + 2), &sym_done, 0, -1, nullptr, nullptr, 1, exact_sym);
-        ctx->prune_symmetric = sym_done;
-        // everything below reads the rows of A itself (the self-join form read the index's copy in position order): the
-        // representatives' matrix of an index over groups is written now if it is still pending
-        if (!sym_done && st == SG_OK) st = sg_csr_ensure_rows(ctx, A);
-        if (prune && !sym_done && st == SG_OK) {
-            SgTimer kt(ctx, SG_K_SPGEMM_KERNEL);
-            st = sg_spgemm_pruned_launch(ctx, A, Bt, stride < SG_TOPN_LANES ? stride : SG_TOPN_LANES, r, threshold, delta,
-                                         counters + n_launch + 1, handed_count, handed_rows,
-                                         (unsigned long long *)(ctx->d_stat_words + 2));
-            if (st == SG_OK && stride > SG_TOPN_LANES && A->n_rows > 0) {
-                hipLaunchKernelGGL(rows_with_full_lists_kernel, dim3((unsigned)((A->n_rows + 255) / 256)), dim3(256), 0, ctx->stream,
-                                   (const int32_t *)r->d_counts, A->n_rows, (int32_t)SG_TOPN_LANES, handed_count, handed_rows);
-                if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-            }
-        }
-        // The exact kernel: the whole product when the pruned multiply does not apply, or the rows it handed over -- whether
-        // there are any is read back (four bytes), because the index build leaves the exact kernel's postings out when
-        // the pruned multiply is expected to take everything (sg_postings_ensure_full writes them on demand).
-        bool need_exact = !prune && !sym_done;
-        if (prune && !sym_done && st == SG_OK && (Bt->d_vals != nullptr || Bt->nnz <= 0)) {
-            // the exact kernel's postings exist: its launch over the handed rows goes out on the device-side count, as
-            // before the postings became lazy -- blocked and zipped multiplies enqueue without a host round trip per part
-            need_exact = true;
-        } else if (prune && !sym_done && st == SG_OK) {
-            uint32_t *h_handed = (uint32_t *)(ctx->h_stat_words + 7);   // pinned
-            *h_handed = 0;
-            if (hipMemcpyAsync(h_handed, handed_count, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess)
-                st = SG_ERR_HIP;
-            need_exact = *h_handed > 0;
-        }
-        if (need_exact && st == SG_OK) st = sg_postings_ensure_full(ctx, Bt);
-        SgTimer *exact_timer = (!prune && !sym_done) ? new (std::nothrow) SgTimer(ctx, SG_K_SPGEMM_KERNEL) : nullptr;
-        int li = 0;
-        for (int pass = 0; pass < n_pass && st == SG_OK && A->n_rows > 0 && need_exact; ++pass) {
-            const int pass_off = pass * SG_TOPN_LANES;
-            const int keep = stride - pass_off < SG_TOPN_LANES ? stride - pass_off : SG_TOPN_LANES;
-            for (int g = 0; g < n_groups && st == SG_OK; ++g, ++li) {
-                const int tb = g * group;
-                const int te = tb + group < Bt->n_tiles ? tb + group : Bt->n_tiles;
-                if (A->dtype == SG_F64)
-                    st = dispatch_spgemm<double>(ctx, A, Bt, tb, te, keep, pass_off, r, (double)threshold,
-                                                 counters + li, grid, prune ? handed_rows : nullptr, handed_count);
-                else
-                    st = dispatch_spgemm<float>(ctx, A, Bt, tb, te, keep, pass_off, r, (float)threshold,
-                                                counters + li, grid, prune ? handed_rows : nullptr, handed_count);
-            }
-        }
-        delete exact_timer;   // stop event of the exact kernel's launches
-        if (prune && !sym_done && st == SG_OK &&   // (the self-join form has left its own count there)
-            hipMemcpyAsync(ctx->d_stat_words + 5, handed_count, 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-            st = SG_ERR_HIP;
-    }
-    if (st == SG_OK && !sort && A->n_rows > 0) {
-        unsigned g2 = (unsigned)(A->n_rows < 65535 * 16 ? A->n_rows : 65535 * 16);
-        const size_t l2 = (size_t)stride * (4 + s);
-        if (l2 > 64 * 1024) {
-            sg_set_error("sort=0 with top_n=%d is not supported", stride);
-            st = SG_ERR_UNSUPPORTED;
-        } else if (A->dtype == SG_F64)
-            hipLaunchKernelGGL(topn_sort_by_col_kernel<double>, dim3(g2), dim3(64), l2, ctx->stream, r->d_cols,
-                               (double *)r->d_vals, r->d_counts, A->n_rows, stride);
-        else
-            hipLaunchKernelGGL(topn_sort_by_col_kernel<float>, dim3(g2), dim3(64), l2, ctx->stream, r->d_cols,
-                               (float *)r->d_vals, r->d_counts, A->n_rows, stride);
-    }
+    SgPlan plan;
+    SG_TRY(plan_multiply(ctx, A, Bt, top_n, threshold, /*row_range=*/false, &plan));
+    Bt = plan.index;
+    TopnPtr r;
+    SG_TRY(topn_alloc(ctx, A->n_rows, Bt->n_right, plan.stride, A->dtype, &r));
+    SG_TRY(run_plan(ctx, A, plan, r.get()));
+    if (!sort) SG_TRY(sort_rows_by_column(ctx, r.get()));
     // measurement words: MACs and kept entries of this multiply
-    if (st == SG_OK) {
-        const bool own = A->n_rows == Bt->n_right && A->d_indptr == Bt->b_indptr && A->d_indices == Bt->b_indices &&
-                         A->d_data == Bt->b_data;
-        if (A->nnz > 0 && own)      // (10 M gathers less per multiply: 54 -> 3 us at 663 k)
-            hipLaunchKernelGGL(count_macs_selfjoin_kernel, dim3(64), dim3(256), 0, ctx->stream, (const uint32_t *)Bt->d_term_len,
-                               Bt->n_terms, (unsigned long long *)ctx->d_stat_words);
-        else if (A->nnz > 0)
-            hipLaunchKernelGGL(count_macs_kernel, dim3(512), dim3(256), 0, ctx->stream, A->d_indptr, A->d_indices,
-                               A->n_rows, (const uint32_t *)Bt->d_term_len, (unsigned long long *)ctx->d_stat_words);
-        if (A->n_rows > 0 && ctx->inner_multiply_depth == 0)   // (an inner multiply's rows are not the caller's: its wrapper counts)
-            hipLaunchKernelGGL(sum_counts_kernel, dim3(256), dim3(256), 0, ctx->stream, r->d_counts, A->n_rows,
-                               (unsigned long long *)(ctx->d_stat_words + 1));
-        // algorithmic bytes (stream model): macs*(4+s) + nnz(A)*(4+s) + (nL+V+2)*4 + out*(4+s);
-        // the MAC and output terms are added in sg_ctx_stats once the device counters are read
-        ctx->spgemm_entry_bytes = (int64_t)(4 + s);
-        ctx->spgemm_fixed_bytes = A->nnz * (int64_t)(4 + s) + (A->n_rows + Bt->n_terms + 2) * 4;
-        {
-            // what a candidate of the first filter costs: with the second filter its 8-bit copy (header + 4 B an entry), and the
-            // packed row only for those that pass it (no pointer fetch: the header holds it); without: pointer + packed row
-            const double mean_row = Bt->n_right > 0 ? (double)Bt->nnz / (double)Bt->n_right : 0.0;
-            ctx->prune_q8_bytes = sg_q8_applies(ctx, Bt, s == 8 ? threshold : (double)(float)threshold) ? 16.0 + 4.0 * mean_row : 0.0;
-            ctx->prune_row_bytes = (ctx->prune_q8_bytes > 0.0 ? 0.0 : 8.0) + mean_row * (s == 8 ? 16.0 : 8.0);
-        }
-        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-    }
-    ctx->release(counters);
-    if (st != SG_OK) {
-        sg_topn_free(r);
-        return st;
-    }
-    *out = r;
+    if (A->nnz > 0 && built_from(A, Bt))      // (10 M gathers less per multiply: 54 -> 3 us at 663 k)
+        hipLaunchKernelGGL(count_macs_selfjoin_kernel, dim3(64), dim3(256), 0, ctx->stream, (const uint32_t *)Bt->d_term_len,
+                           Bt->n_terms, (unsigned long long *)ctx->d_stat_words);
+    else if (A->nnz > 0)
+        hipLaunchKernelGGL(count_macs_kernel, dim3(512), dim3(256), 0, ctx->stream, A->d_indptr, A->d_indices,
+                           A->n_rows, (const uint32_t *)Bt->d_term_len, (unsigned long long *)ctx->d_stat_words);
+    if (A->n_rows > 0 && ctx->inner_multiply_depth == 0)   // (an inner multiply's rows are not the caller's: its wrapper counts)
+        hipLaunchKernelGGL(sum_counts_kernel, dim3(256), dim3(256), 0, ctx->stream, r->d_counts, A->n_rows,
+                           (unsigned long long *)(ctx->d_stat_words + 1));
+    record_bytes(ctx, A, Bt, plan.threshold);
+    if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
+    *out = r.release();
     return SG_OK;
 }
 
@@ -1301,9 +1273,7 @@ extern "C" int sg_selfjoin_range(sg_ctx *ctx, const sg_csr *A, const sg_postings
         // an index over groups of identical rows: the ranges are ranges of the GROUPS' positions (sg_postings_rows), the
         // result has one row per group; sg_topn_expand_groups turns the gathered result into the caller's rows
         const SgCollapse *c = Bt->collapse;
-        const sg_csr *cb = &Bt->caller_b_copy;
-        if (!(A->n_rows == c->n_orig && A->d_indptr == cb->d_indptr && A->d_indices == cb->d_indices && A->d_data == cb->d_data))
-            return SG_OK;                 // not the matrix the index was built from: the row-block form
+        if (!built_from(A, Bt)) return SG_OK;                 // not the matrix the index was built from: the row-block form
         if (row_hi > c->n_u) {
             sg_set_error("row range [%lld, %lld) outside the %lld groups of the index (sg_postings_rows)", (long long)row_lo,
                          (long long)row_hi, (long long)c->n_u);
@@ -1317,44 +1287,24 @@ extern "C" int sg_selfjoin_range(sg_ctx *ctx, const sg_csr *A, const sg_postings
         if (st_u == SG_OK && *out) (*out)->top_n_asked = top_n;      // (fewer groups than top_n: the rows over MEMBERS are wider)
         return st_u;
     }
-    if (!(threshold > 0.0)) threshold = 0.0;
-    int64_t stride64 = top_n;
-    if (stride64 > Bt->n_right) stride64 = Bt->n_right > 0 ? Bt->n_right : 1;
-    if ((double)A->n_rows * (double)stride64 > 2.0e9) return SG_OK;   // not applicable: the caller's other path reports it
-    const int32_t stride = (int32_t)stride64;
-    double delta = 0.0;
-    bool symmetric = false;
-    int pst = SG_OK;
-    const bool prune = pruned_applicable(ctx, A, Bt, stride, threshold, &delta, &symmetric, &pst, /*any_size=*/true);
-    if (pst != SG_OK) return pst;
-    if (!prune || !symmetric) return SG_OK;
-    sg_topn *r = nullptr;
-    SG_TRY(topn_alloc(ctx, A->n_rows, Bt->n_right, stride, A->dtype, &r));
+    SgPlan plan;
+    SG_TRY(plan_multiply(ctx, A, Bt, top_n, threshold, /*row_range=*/true, &plan));
+    if (plan.form != SgPlan::PRUNED_SELFJOIN) return SG_OK;
+    TopnPtr r;
+    SG_TRY(topn_alloc(ctx, A->n_rows, Bt->n_right, plan.stride, A->dtype, &r));
     int st = SG_OK;
     bool done = false;
     {
         SgTimer timer(ctx, SG_K_SPGEMM);
         st = SG_ZERO2(ctx, r->d_counts, sizeof(int32_t) * (size_t)A->n_rows, ctx->d_stat_words, 8 * sizeof(int64_t));
         if (st == SG_OK)
-            st = sg_spgemm_pruned_symmetric(ctx, A, Bt, stride, r, threshold, delta, (unsigned long long *)(ctx->d_stat_words + 2),
-                                            &done, row_lo, row_hi, d_pairs, n_pairs, row_step);
+            st = sg_spgemm_pruned_symmetric(ctx, A, Bt, plan.stride, r.get(), plan.threshold, plan.delta,
+                                            (unsigned long long *)(ctx->d_stat_words + 2), &done, row_lo, row_hi, d_pairs, n_pairs, row_step);
     }
-    const size_t s = A->dtype == SG_F64 ? 8 : 4;
-    ctx->spgemm_entry_bytes = (int64_t)(4 + s);
-    ctx->spgemm_fixed_bytes = A->nnz * (int64_t)(4 + s) + (A->n_rows + Bt->n_terms + 2) * 4;
-    {
-        // what a candidate of the first filter costs: with the second filter its 8-bit copy (header + 4 B an entry), and the
-        // packed row only for those that pass it (no pointer fetch: the header holds it); without: pointer + packed row
-        const double mean_row = Bt->n_right > 0 ? (double)Bt->nnz / (double)Bt->n_right : 0.0;
-        ctx->prune_q8_bytes = sg_q8_applies(ctx, Bt, s == 8 ? threshold : (double)(float)threshold) ? 16.0 + 4.0 * mean_row : 0.0;
-        ctx->prune_row_bytes = (ctx->prune_q8_bytes > 0.0 ? 0.0 : 8.0) + mean_row * (s == 8 ? 16.0 : 8.0);
-    }
+    record_bytes(ctx, A, Bt, plan.threshold);
     ctx->prune_symmetric = done;
-    if (st != SG_OK || !done) {   // a row for the exact kernel, or the pair list was full: the one-sided form is the caller's
-        sg_topn_free(r);
-        return st;
-    }
-    *out = r;
+    if (st != SG_OK || !done) return st;   // a row for the exact kernel, or the pair list was full: the one-sided form is the caller's
+    *out = r.release();
     *applicable = 1;
     return SG_OK;
 }
@@ -1408,24 +1358,16 @@ extern "C" int sg_topn_expand_groups(sg_ctx *ctx, const sg_postings *Bt, const s
     SG_REQUIRE(n_rows >= 0 && n_rows <= c->n_orig, "more rows than the matrix has");
     // a row over members holds up to min(top_n, rows) columns -- as spgemm_topn_collapsed sizes it --, not the groups' stride,
     // which is cut at the number of GROUPS (eight distinct names in 200 k rows, top_n 20: 20 columns per row, not 8)
-    int64_t stride64 = groups->top_n_asked > groups->stride ? groups->top_n_asked : groups->stride;
-    if (stride64 > c->n_orig) stride64 = c->n_orig > 0 ? c->n_orig : 1;
-    if ((double)n_rows * (double)stride64 > 2.0e9) {
-        sg_set_error("result of %lld rows x top_n %lld does not fit the 32-bit result index", (long long)n_rows, (long long)stride64);
-        return SG_ERR_OVERFLOW;
-    }
-    sg_topn *r = nullptr;
-    SG_TRY(topn_alloc(ctx, n_rows, c->n_orig, (int32_t)stride64, groups->dtype, &r));
-    int st = SG_OK;
+    int32_t stride = 0;
+    if (!result_stride(n_rows, groups->top_n_asked > groups->stride ? groups->top_n_asked : groups->stride, c->n_orig, &stride))
+        return result_overflow(n_rows, stride, "");
+    TopnPtr r;
+    SG_TRY(topn_alloc(ctx, n_rows, c->n_orig, stride, groups->dtype, &r));
     {
         SgTimer timer(ctx, SG_K_ZIP);
-        st = sg_collapse_expand(ctx, c, groups, true, r, d_rows);   // (clears r's counts itself)
+        SG_TRY(sg_collapse_expand(ctx, c, groups, true, r.get(), d_rows));   // (clears r's counts itself)
     }
-    if (st != SG_OK) {
-        sg_topn_free(r);
-        return st;
-    }
-    *out = r;
+    *out = r.release();
     return SG_OK;
 }
 
@@ -1566,7 +1508,7 @@ extern "C" int sg_topn_from_host(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, in
                                  const int32_t *cols, const void *vals, const int32_t *counts, sg_topn **out) {
     SG_REQUIRE(ctx && counts && out && n_rows >= 0 && stride >= 1, "bad argument");
     SG_REQUIRE(dtype == SG_F32 || dtype == SG_F64, "dtype must be SG_F32 or SG_F64");
-    sg_topn *r = nullptr;
+    TopnPtr r;
     SG_TRY(topn_alloc(ctx, n_rows, n_cols, stride, dtype, &r));
     const size_t cells = (size_t)n_rows * (size_t)stride;
     const size_t s = dtype == SG_F64 ? 8 : 4;
@@ -1579,10 +1521,9 @@ extern "C" int sg_topn_from_host(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, in
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
         sg_set_error("sg_topn_from_host: %s", hipGetErrorString(e));
-        sg_topn_free(r);
         return SG_ERR_HIP;
     }
-    *out = r;
+    *out = r.release();
     return SG_OK;
 }
 
@@ -1590,7 +1531,7 @@ extern "C" int sg_topn_from_device(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, 
                                    const int32_t *d_cols, const void *d_vals, const int32_t *d_counts, sg_topn **out) {
     SG_REQUIRE(ctx && d_counts && out && n_rows >= 0 && stride >= 1, "bad argument");
     SG_REQUIRE(dtype == SG_F32 || dtype == SG_F64, "dtype must be SG_F32 or SG_F64");
-    sg_topn *r = nullptr;
+    TopnPtr r;
     SG_TRY(topn_alloc(ctx, n_rows, n_cols, stride, dtype, &r));
     const size_t cells = (size_t)n_rows * (size_t)stride;
     const size_t s = dtype == SG_F64 ? 8 : 4;
@@ -1602,10 +1543,9 @@ extern "C" int sg_topn_from_device(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, 
     }
     if (e != hipSuccess) {
         sg_set_error("sg_topn_from_device: %s", hipGetErrorString(e));
-        sg_topn_free(r);
         return SG_ERR_HIP;
     }
-    *out = r;
+    *out = r.release();
     return SG_OK;
 }
 
@@ -1637,7 +1577,7 @@ extern "C" int sg_topn_zip(sg_ctx *ctx, const sg_topn *const *parts, const int64
     int64_t stride64 = top_n < total_stride ? top_n : total_stride;
     if (stride64 < 1) stride64 = 1;
     const int32_t stride = (int32_t)stride64;
-    sg_topn *r = nullptr;
+    TopnPtr r;
     SG_TRY(topn_alloc(ctx, n_rows, total_cols, stride, dtype, &r));
     const size_t s = dtype == SG_F64 ? 8 : 4;
     // part descriptors: host-pinned scratch would add a dependency; a tiny pooled device buffer + sync copy
@@ -1654,11 +1594,7 @@ extern "C" int sg_topn_zip(sg_ctx *ctx, const sg_topn *const *parts, const int64
         }
     }
     void *d_desc = nullptr;
-    int st = ctx->alloc(host_desc.size(), &d_desc);
-    if (st != SG_OK) {
-        sg_topn_free(r);
-        return st;
-    }
+    SG_TRY(ctx->alloc(host_desc.size(), &d_desc));
     (void)s;
     hipError_t he = hipMemcpyAsync(d_desc, host_desc.data(), host_desc.size(), hipMemcpyHostToDevice, ctx->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);   // host_desc is a local
@@ -1666,7 +1602,6 @@ extern "C" int sg_topn_zip(sg_ctx *ctx, const sg_topn *const *parts, const int64
     if (he != hipSuccess) {
         sg_set_error("sg_topn_zip: %s", hipGetErrorString(he));
         ctx->release(d_desc);
-        sg_topn_free(r);
         return he == hipErrorOutOfMemory ? SG_ERR_OOM : SG_ERR_HIP;
     }
     {
@@ -1686,13 +1621,10 @@ extern "C" int sg_topn_zip(sg_ctx *ctx, const sg_topn *const *parts, const int64
                                    (float *)r->d_vals, r->d_counts);
         }
     }
-    st = hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
+    const int st = hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
     ctx->release(d_desc);
-    if (st != SG_OK) {
-        sg_topn_free(r);
-        return st;
-    }
-    *out = r;
+    SG_TRY(st);
+    *out = r.release();
     return SG_OK;
 }
 
