@@ -58,9 +58,9 @@ typedef struct sg_topn sg_topn;         /* device-resident fixed-stride top-n re
 /* ------------------------------------------------------------------ library / context */
 const char *sg_last_error(void);
 /* Bumped whenever a signature or a struct of this header changes (round 4: 2 -- row_step arguments of round 3, sg_stats
- * grew; round 5: 3 -- sg_stats.prune_scored); a binding compares it with the value it was written for right after loading
- * the library. */
-#define SG_ABI_VERSION 3
+ * grew; round 5: 3 -- sg_stats.prune_scored; 4 -- sg_topn_transpose_select); a binding compares it with the value it was
+ * written for right after loading the library. */
+#define SG_ABI_VERSION 4
 int sg_abi_version(void);
 int sg_device_count(int *count);
 /* hip_stream: a hipStream_t to launch on (e.g. torch.cuda.current_stream().cuda_stream), or NULL
@@ -300,6 +300,21 @@ int sg_topn_expand_range(sg_ctx *ctx, const sg_postings *Bt, const sg_topn *grou
 /* device tables of Bt's row permutation, one entry per index row: position -> row, row -> position (both null: none) */
 int sg_postings_permutation(const sg_postings *Bt, const uint32_t **d_orig_of, const uint32_t **d_pos_of);
 int sg_device_free(sg_ctx *ctx, void *d_ptr);
+
+/* ------------------------------------------------------------------ resident corpus: the reverse path */
+/* A corpus whose index stays on the device answers match_strings(corpus, new) / match_most_similar(corpus, new) -- the
+ * reference's sp_matmul_topn(M, D.T, top_n, threshold) with top_n per MASTER row (string_grouper.py:725-732; top_n = 1 for
+ * match_most_similar, :120) -- from the product computed the other way round, D . M^T: every new row against the corpus
+ * index (sg_spgemm_topn with a cap that no row filled, so that it holds EVERY pair above the threshold).
+ * sg_topn_transpose_select turns such a pair list into the result over the corpus rows: row m of *out holds the at most
+ * top_n pairs (r, m) of `pairs` -- r a row of `pairs` -- ordered by score descending, then r ascending, as sg_spgemm_topn
+ * orders and cuts a row; *out has n_rows_out rows, pairs->n_rows columns and the stride min(top_n, columns).  The rows of
+ * `pairs` must not name one column twice and its columns must lie in [0, n_rows_out).  top_n <= 2048 (larger:
+ * SG_ERR_BADARG).  The result feeds sg_matchlist_build and sg_matchlist_best_master like a multiply's.  Bit for bit the
+ * forward product's rows: a score is the sum of the separately rounded products of the shared terms in ascending term
+ * order from either side.  (The reference has no analogue: it re-fits and re-multiplies the whole
+ * master list every call, string_grouper.py:685-707.) */
+int sg_topn_transpose_select(sg_ctx *ctx, const sg_topn *pairs, int64_t n_rows_out, int32_t top_n, sg_topn **out);
 
 /* ------------------------------------------------------------------ measurement */
 enum { SG_K_TOKENIZE = 0, SG_K_WEIGHT = 1, SG_K_POSTINGS = 2, SG_K_SPGEMM = 3 /* the multiply's whole launch group */,

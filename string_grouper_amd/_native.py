@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SG_HIP_LIB") or os.path.join(_HERE, "libsg_hip.so")
 
 SG_OK, SG_ERR_BADARG, SG_ERR_OOM, SG_ERR_OVERFLOW, SG_ERR_HIP, SG_ERR_NODEVICE, SG_ERR_UNSUPPORTED = range(7)
 SG_F32, SG_F64 = 0, 1
-ABI_VERSION = 3          # include/sg_hip.h: SG_ABI_VERSION
+ABI_VERSION = 4          # include/sg_hip.h: SG_ABI_VERSION
 SG_K_TOKENIZE, SG_K_WEIGHT, SG_K_POSTINGS, SG_K_SPGEMM, SG_K_ZIP, SG_K_VOCAB, SG_K_SPGEMM_KERNEL, SG_K_COUNT = range(8)
 KERNEL_NAMES = ("tokenize", "weight", "postings", "spgemm_topn", "zip", "vocab", "spgemm_kernel")
 
@@ -105,6 +105,7 @@ ABI = {
     "sg_topn_expand_groups": (C.c_int, [_P, _P, _P, _P, C.c_int64, _PP]),
     "sg_topn_expand_range": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _PP, _PP, _P, C.c_int64]),
     "sg_device_free": (C.c_int, [_P, _P]),
+    "sg_topn_transpose_select": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _PP]),
     "sg_csr_rowwise_dot": (C.c_int, [_P, _P, _P, _P]),
     "sg_ctx_stats": (C.c_int, [_P, C.POINTER(SgStats)]),
 }
@@ -605,6 +606,13 @@ class Context:
         out = C.c_void_p()
         check(lib().sg_topn_from_device(self.h, int(n_rows), int(n_cols), int(stride), np_dtype_code(np.dtype(dtype)),
                                         C.c_void_p(d_cols), C.c_void_p(d_vals), C.c_void_p(d_counts), C.byref(out)))
+        return TopN(self, out)
+
+    def topn_transpose_select(self, pairs: TopN, n_rows_out: int, top_n: int) -> TopN:
+        """The result over the COLUMNS of a complete pair list: row m holds the top_n pairs (r, m) of ``pairs`` by score
+        descending, then r ascending (include/sg_hip.h: sg_topn_transpose_select)."""
+        out = C.c_void_p()
+        check(lib().sg_topn_transpose_select(self.h, pairs.h, int(n_rows_out), int(top_n), C.byref(out)))
         return TopN(self, out)
 
     def topn_zip(self, parts, col_offsets, top_n: int) -> TopN:

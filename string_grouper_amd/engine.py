@@ -17,6 +17,7 @@ import scipy.sparse as sp
 
 from . import _hostops
 from . import _native as N
+from .strprep import _ascii_lower
 from .vectorizer import HipTfidfVectorizer
 
 
@@ -64,8 +65,42 @@ class DeviceMatchList:
             self.ml = None
 
 
+class CorpusState:
+    """What a resident corpus keeps on the device (string_grouper_amd/corpus.py): the fitted vectoriser (vocabulary + idf),
+    its own TF-IDF rows and, from the first call that needs it, the inverted index over them (K3, with the extras the
+    multiply caches on an index).  ``stats`` counts the work, so that tests can prove the reuse."""
+
+    def __init__(self, vec: HipTfidfVectorizer, column, matrix: "CorpusMatrix"):
+        self.vec = vec
+        self.column = column
+        self.matrix = matrix
+        self.index: Optional["N.Postings"] = None
+        self.index_overflow = False           # the corpus does not fit one index: every call takes today's blocked path
+        self.placeholder: Optional[int] = None
+        self.stats = {"tokenisations": 1, "index_builds": 0, "transforms": 0, "resident_index": 0, "forward": 0,
+                      "reverse": 0, "reverse_fallbacks": 0}
+
+
+class CorpusMatrix(DeviceMatrix):
+    """The TF-IDF rows of a resident corpus: the multiply uses the corpus's index instead of building one."""
+
+    def __init__(self, csr: "N.Csr", corpus: CorpusState):
+        super().__init__(csr)
+        self.corpus = corpus
+
+
 class HipEngine:
     name = "hip"
+    # reverse path of a resident corpus (DESIGN.md section 9): the pair slots (new rows x per-row cap) it may hold; a call
+    # whose complete pair list would need more takes the forward path
+    CORPUS_PAIR_BUDGET = 1 << 27
+    CORPUS_FIRST_CAP = 64
+    CORPUS_MAX_TOP_N = 2048                   # sg_topn_transpose_select
+    # the rule: the reverse path for batches of at most this many rows.  Measured (scripts/corpus_latency.py,
+    # profiles/corpus_latency_*.log): the forward path costs about what streaming the corpus costs, whatever the batch
+    # (4.4 ms at 663 k names, 35 ms at 5 M); the reverse path what the batch's rows cost against the corpus index -- it is
+    # the faster one up to 32 rows and the slower one from 64 on, at both sizes
+    CORPUS_REVERSE_MAX_ROWS = 32
 
     def __init__(self, ctx: Optional[N.Context] = None):
         self._ctx = ctx
@@ -113,13 +148,140 @@ class HipEngine:
         d = DeviceMatrix(self.ctx.csr_from_scipy(m))
         return d
 
+    # ------------------------------------------------------------------ resident corpus (string_grouper_amd/corpus.py)
+    def corpus_fit(self, strings, ngram_size, regex, ignore_case, normalize_to_ascii, dtype) -> CorpusState:
+        """TfidfVectorizer(min_df=1, analyzer=n_grams, dtype).fit(strings), once; the corpus's own rows stay on the device."""
+        vec = HipTfidfVectorizer(ngram_size=ngram_size, regex=regex, ignore_case=ignore_case,
+                                 normalize_to_ascii=normalize_to_ascii, dtype=dtype, ctx=self.ctx)
+        col = vec.prepare(strings)
+        vec.fit_prepared([col])
+        state = CorpusState(vec, col, None)
+        state.matrix = CorpusMatrix(vec.transform_prepared(col), state)
+        return state
+
+    def corpus_transform(self, state: CorpusState, strings) -> DeviceMatrix:
+        """The rows of ``strings`` under the corpus's vocabulary and idf: n-grams the corpus never had are dropped."""
+        vec = state.vec
+        col = vec.prepare(strings)
+        if col.kind == "symbols" and vec._alphabet is None:
+            # characters beyond ASCII (normalize_to_ascii=False) against a vocabulary of ASCII n-grams: every n-gram with one
+            # of them is out of vocabulary.  Each such character becomes one byte the corpus never had, so that the device
+            # drops exactly those n-grams (its own treatment of bytes >= 0x80 would join the neighbours instead).
+            col = self._corpus_bytes_column(state, col)
+        state.stats["transforms"] += 1
+        m = DeviceMatrix(vec.transform_prepared(col))
+        if col.dev is not None:
+            col.dev.free()
+        return m
+
+    @staticmethod
+    def _corpus_bytes_column(state: CorpusState, col):
+        from .strprep import StringColumn
+        if state.placeholder is None:
+            data = state.column.data if state.column.kind == "bytes" else np.zeros(0, np.uint8)
+            seen = np.zeros(256, bool)
+            seen[np.unique(data)] = True
+            seen[np.unique(_ascii_lower(data))] = True
+            deleted = state.vec._delete_table.astype(bool)
+            free = [c for c in range(1, 128) if not seen[c] and not deleted[c] and not (65 <= c <= 90)]
+            if not free:
+                raise NotImplementedError("the corpus uses every ASCII character: no byte is left to stand for the "
+                                          "characters it never had")
+            state.placeholder = free[0]
+        cps = col.data
+        data = np.where(cps < 128, cps, state.placeholder).astype(np.uint8)
+        return StringColumn("bytes", data, col.offsets, prelowered=True)
+
+    def corpus_matrix(self, state: CorpusState) -> "CorpusMatrix":
+        return state.matrix
+
+    def corpus_index(self, state: CorpusState) -> Optional["N.Postings"]:
+        """The inverted index over the corpus rows, built on first need and kept; None when the corpus is too large for one
+        index (the callers then take the blocked path of _topn_device)."""
+        if state.index is None and not state.index_overflow:
+            try:
+                state.index = self.ctx.postings_build(state.matrix.csr)
+                state.stats["index_builds"] += 1
+            except OverflowError:
+                state.index_overflow = True
+        return state.index
+
+    def corpus_free(self, state: CorpusState) -> None:
+        handles = [state.index, state.matrix.csr if state.matrix is not None else None, state.vec._vocab]
+        for col in list(getattr(state.vec, "_fit_sets", [])) + list(getattr(state.vec, "_fit_originals", [])) + [state.column]:
+            handles.append(getattr(col, "dev", None))
+        for h in handles:
+            if h is not None:
+                h.free()
+        state.vec._dev_of = {}
+        state.index = None
+
+    def _corpus_reverse_mode(self) -> Optional[bool]:
+        v = self.ctx.options().get("SG_CORPUS_REVERSE")
+        return None if v in (None, "") else v.strip() not in ("0", "false", "False")
+
+    def _corpus_topn(self, A: DeviceMatrix, B: DeviceMatrix, top_n: int, threshold: float) -> Optional["N.TopN"]:
+        """The multiply of a call on a resident corpus, or None for the generic path of _topn_device.
+        B the corpus (a self-join of it included): the new rows against the corpus's own index.
+        A the corpus, B new rows: the forward path (the corpus rows against an index of the new rows: the generic path) or
+        the reverse path (the new rows against the corpus index, turned round by sg_topn_transpose_select)."""
+        if isinstance(B, CorpusMatrix):
+            idx = self.corpus_index(B.corpus)
+            if idx is None:
+                return None
+            B.corpus.stats["resident_index"] += 1
+            return self.ctx.spgemm_topn(A.csr, idx, top_n, threshold, True)
+        state = A.corpus
+        mode = self._corpus_reverse_mode()
+        if mode is None:
+            mode = B.shape[0] <= self.CORPUS_REVERSE_MAX_ROWS and B.shape[0] < A.shape[0]
+        if mode:
+            res = self._corpus_reverse(state, A, B, top_n, threshold)
+            if res is not None:
+                state.stats["reverse"] += 1
+                return res
+            state.stats["reverse_fallbacks"] += 1
+        state.stats["forward"] += 1
+        return None
+
+    def _corpus_reverse(self, state: CorpusState, A: DeviceMatrix, B: DeviceMatrix, top_n: int,
+                        threshold: float) -> Optional["N.TopN"]:
+        """Every pair above the threshold from the new rows' side -- the cap per new row grows until no row comes back
+        full -- then the top_n per corpus row.  None (nothing returned, the caller takes the forward path) when the pair
+        list would exceed the budget or top_n exceeds what the select kernel takes."""
+        n_corpus, n_new = A.shape[0], B.shape[0]
+        if top_n > self.CORPUS_MAX_TOP_N or n_new == 0 or n_corpus == 0:
+            return None
+        idx = self.corpus_index(state)
+        if idx is None:
+            return None
+        cap = self.CORPUS_FIRST_CAP
+        while True:
+            stride = min(cap, n_corpus)
+            if n_new * stride > self.CORPUS_PAIR_BUDGET:
+                return None
+            pairs = self.ctx.spgemm_topn(B.csr, idx, stride, threshold, True)
+            cnt = pairs.counts()
+            if stride >= n_corpus or int(cnt.max()) < stride:
+                break
+            pairs.free()
+            cap *= 8
+        res = self.ctx.topn_transpose_select(pairs, n_corpus, top_n)
+        pairs.free()
+        return res
+
     # ------------------------------------------------------------------ seam b2
     def _topn_device(self, A: DeviceMatrix, B: DeviceMatrix, top_n: int, threshold: float) -> "N.TopN":
         """Top-n multiply with the result left on the device.  One inverted index normally; when the
         right-hand side is too large for one (SG_ERR_OVERFLOW -> OverflowError, what the reference's
         fit() reacts to by splitting, string_grouper.py:397-413) it is cut into the fewest row blocks that
-        fit and the partial results are merged on the device (K5 = zip_sp_matmul_topn)."""
+        fit and the partial results are merged on the device (K5 = zip_sp_matmul_topn).  A resident corpus on
+        either side: _corpus_topn."""
         ctx = self.ctx
+        if isinstance(A, CorpusMatrix) or isinstance(B, CorpusMatrix):
+            res = self._corpus_topn(A, B, top_n, threshold)
+            if res is not None:
+                return res
         try:
             post = ctx.postings_build(B.csr)
         except OverflowError:
