@@ -58,9 +58,9 @@ typedef struct sg_topn sg_topn;         /* device-resident fixed-stride top-n re
 /* ------------------------------------------------------------------ library / context */
 const char *sg_last_error(void);
 /* Bumped whenever a signature or a struct of this header changes (round 4: 2 -- row_step arguments of round 3, sg_stats
- * grew; round 5: 3 -- sg_stats.prune_scored; 4 -- sg_topn_transpose_select); a binding compares it with the value it was
- * written for right after loading the library. */
-#define SG_ABI_VERSION 4
+ * grew; round 5: 3 -- sg_stats.prune_scored; 4 -- sg_topn_transpose_select; 5 -- sg_csr_concat); a binding compares it with the
+ * value it was written for right after loading the library. */
+#define SG_ABI_VERSION 5
 int sg_abi_version(void);
 int sg_device_count(int *count);
 /* hip_stream: a hipStream_t to launch on (e.g. torch.cuda.current_stream().cuda_stream), or NULL
@@ -160,6 +160,15 @@ int sg_csr_to_host(sg_ctx *ctx, const sg_csr *m, int64_t *indptr, int32_t *indic
 /* Rows [r0, r1) as a view (no copy); the parent must outlive the view.  (A view derives its own groups of identical
  * rows when it is multiplied; it never shares the parent's.) */
 int sg_csr_row_block(sg_ctx *ctx, const sg_csr *m, int64_t r0, int64_t r1, sg_csr **out);
+/* The rows of parts[0], then parts[1], ... in one new matrix that owns its arrays: scipy's vstack of transformed blocks
+ * (the reference stacks result blocks with it, string_grouper.py:750; vstack of master_matrix's rows and the transform of
+ * new strings is the host analogue of growing a master list).  Every part has the same n_cols and dtype (SG_ERR_BADARG
+ * otherwise); a part may be a row-block view, have no rows, or rows without entries; the parts are only read and may be
+ * freed once the call has returned and the context's stream has passed it (sg_csr_free after the call is safe: the pool
+ * is stream-ordered).  One pass on the device, nothing is read back.  When every part was made by sg_vec_transform the
+ * result counts as made by it too (cosine-like by construction: the pruned multiply needs no scan of it), and the words
+ * the vectoriser left with the parts are merged.  More than INT32_MAX rows: SG_ERR_OVERFLOW. */
+int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_parts, sg_csr **out);
 int sg_csr_free(sg_csr *m);
 
 /* Row-wise similarity of two matrices of the same shape (StringGrouper.dot / compute_pairwise_similarities,

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SG_HIP_LIB") or os.path.join(_HERE, "libsg_hip.so")
 
 SG_OK, SG_ERR_BADARG, SG_ERR_OOM, SG_ERR_OVERFLOW, SG_ERR_HIP, SG_ERR_NODEVICE, SG_ERR_UNSUPPORTED = range(7)
 SG_F32, SG_F64 = 0, 1
-ABI_VERSION = 4          # include/sg_hip.h: SG_ABI_VERSION
+ABI_VERSION = 5          # include/sg_hip.h: SG_ABI_VERSION
 SG_K_TOKENIZE, SG_K_WEIGHT, SG_K_POSTINGS, SG_K_SPGEMM, SG_K_ZIP, SG_K_VOCAB, SG_K_SPGEMM_KERNEL, SG_K_COUNT = range(8)
 KERNEL_NAMES = ("tokenize", "weight", "postings", "spgemm_topn", "zip", "vocab", "spgemm_kernel")
 
@@ -74,6 +74,7 @@ ABI = {
     "sg_csr_device_ptrs": (C.c_int, [_P, _PP, _PP, _PP]),
     "sg_csr_to_host": (C.c_int, [_P, _P, _P, _P, _P]),
     "sg_csr_row_block": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _PP]),
+    "sg_csr_concat": (C.c_int, [_P, _PP, C.c_int32, _PP]),
     "sg_csr_free": (C.c_int, [_P]),
     "sg_postings_build": (C.c_int, [_P, _P, C.c_int32, _PP]),
     "sg_postings_build_flags": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PP]),
@@ -490,6 +491,15 @@ class Context:
         out = C.c_void_p()
         check(lib().sg_csr_from_host(self.h, m.shape[0], m.shape[1], _ptr(indptr), _ptr(indices), _ptr(data),
                                      np_dtype_code(data.dtype), C.byref(out)))
+        return Csr(self, out)
+
+    def csr_concat(self, parts) -> Csr:
+        """The rows of ``parts`` (Csr handles, row-block views included) one after the other in a new owned matrix
+        (include/sg_hip.h: sg_csr_concat; scipy.sparse.vstack on the device)."""
+        parts = list(parts)
+        arr = (C.c_void_p * max(len(parts), 1))(*[p.h for p in parts])
+        out = C.c_void_p()
+        check(lib().sg_csr_concat(self.h, arr, len(parts), C.byref(out)))
         return Csr(self, out)
 
     def csr_from_device(self, n_rows, n_cols, nnz, d_indptr: int, d_indices: int, d_data: int, dtype,

@@ -8,6 +8,9 @@ the fixed-corpus form:
     corpus = Corpus(master)                      # vocabulary + idf of TfidfVectorizer(...).fit(master), once
     corpus.match_strings(master, new_batch)      # new_batch.transform()ed with them; master's rows and index are resident
 
+A corpus may grow: ``corpus.append(new_strings)`` puts new rows behind the last one, transformed with the SAME vocabulary and
+idf (nothing is refitted, no score between two old rows changes), ``corpus.master`` is then the longer Series.
+
 Every Series a method receives is transformed with the corpus's vocabulary and idf (an n-gram the corpus never had is
 dropped, as sklearn's transform drops it); everything after that is what ``StringGrouper.fit()`` and its frames do with the
 two matrices.  The methods have the signatures of the module-level functions (string_grouper.py:55-153).
@@ -24,6 +27,51 @@ from .string_grouper import StringGrouper, StringGrouperConfig
 
 # options that define the vectoriser: a call may not change them (the corpus was fitted with them)
 VECTORISER_OPTIONS = ("ngram_size", "regex", "ignore_case", "normalize_to_ascii", "tfidf_matrix_dtype")
+
+
+class _GrowingSeries:
+    """A Series that grows at its end: ``pd.concat([series] + parts)`` without copying the old rows every time.  pd.concat
+    costs what the WHOLE list costs (9 ms at 663 k strings, and as much again to drop the old copy) -- per append that was
+    more than everything the device does.  Object-dtype values (and int64 labels) are kept in buffers with spare capacity;
+    every joined Series is a view of the buffer's head, which later appends never write to.  Anything else (extension
+    dtypes, other label types) is joined by pandas."""
+
+    def __init__(self, series: pd.Series):
+        self.series = series
+        self._values: Optional[np.ndarray] = None
+        self._labels: Optional[np.ndarray] = None
+
+    @staticmethod
+    def _room(buffer, old: np.ndarray, total: int, dtype) -> np.ndarray:
+        if buffer is not None and total <= len(buffer):
+            return buffer
+        grown = np.empty(total + total // 2 + 1024, dtype=dtype)
+        grown[:len(old)] = old
+        return grown
+
+    def extend(self, parts) -> pd.Series:
+        s = self.series
+        if s.dtype != object or any(p.dtype != object for p in parts):
+            self.series, self._values, self._labels = pd.concat([s] + list(parts)), None, None
+            return self.series
+        n, total = len(s), len(s) + sum(len(p) for p in parts)
+        self._values = self._room(self._values, s.to_numpy(), total, object)
+        plain = all(type(x.index) in (pd.Index, pd.RangeIndex) and x.index.dtype == np.int64 for x in [s] + list(parts))
+        if plain:
+            self._labels = self._room(self._labels, s.index.to_numpy(), total, np.int64)
+        at = n
+        for p in parts:
+            self._values[at:at + len(p)] = p.to_numpy()
+            if plain:
+                self._labels[at:at + len(p)] = p.index.to_numpy()
+            at += len(p)
+        if plain:
+            index = pd.Index(self._labels[:total], name=s.index.name if all(p.index.name == s.index.name for p in parts) else None)
+        else:
+            index, self._labels = s.index.append([p.index for p in parts]), None
+        name = s.name if all(p.name == s.name for p in parts) else None
+        self.series = pd.Series(self._values[:total], index=index, name=name, copy=False)
+        return self.series
 
 
 class _CorpusGrouper(StringGrouper):
@@ -66,13 +114,16 @@ class Corpus:
         self._engine = eng
         self._master = master
         self._master_id = master_id
+        self._pending = []                    # (strings, ids) appended since ``master`` was last asked for
+        self._grown = _GrowingSeries(master)
+        self._grown_id = _GrowingSeries(master_id) if master_id is not None else None
         cfg = self._config
         self._state = eng.corpus_fit(master, cfg.ngram_size, cfg.regex, cfg.ignore_case, cfg.normalize_to_ascii,
                                      cfg.tfidf_matrix_dtype)
 
     # ------------------------------------------------------------------ resources
     def close(self) -> None:
-        """Free everything the corpus holds on the device (vocabulary, idf, its rows, its index)."""
+        """Free everything the corpus holds on the device (vocabulary, idf, its rows and indexes, segment by segment)."""
         if self._state is not None:
             self._engine.corpus_free(self._state)
             self._state = None
@@ -96,7 +147,67 @@ class Corpus:
 
     @property
     def master(self) -> pd.Series:
+        """The corpus's strings: the Series it was built from, or after an append the concatenation of the parts (a new
+        object after every append).  Only THIS object stands for the resident rows in a call; any other Series -- an older
+        ``corpus.master`` included -- is transformed like a batch (the same result, just slower)."""
+        self._join_pending()
         return self._master
+
+    @property
+    def master_id(self) -> Optional[pd.Series]:
+        """The ids that go with ``master`` (None when the corpus was built without)."""
+        self._join_pending()
+        return self._master_id
+
+    def _join_pending(self) -> None:
+        if self._pending:
+            self._master = self._grown.extend([s for s, _ in self._pending])
+            if self._master_id is not None:
+                self._master_id = self._grown_id.extend([i for _, i in self._pending])
+            self._pending = []
+
+    # ------------------------------------------------------------------ growing
+    def append(self, new_strings: pd.Series, new_ids: Optional[pd.Series] = None) -> None:
+        """Put ``new_strings`` behind the corpus's last row; ``new_ids`` is required when the corpus has ``master_id`` and
+        refused when it has none.  An empty Series changes nothing.
+
+        The vocabulary and the idf do NOT change: the new strings are transformed as every batch is (n-grams the corpus
+        never had are dropped; a string with none it knows is an empty row that still matches itself in a self-join), and
+        every result afterwards is what ``TfidfVectorizer.fit(original master).transform(all strings)`` gives, row numbers
+        counting through the concatenated list.  The idf therefore drifts from what a refit on the grown list would give;
+        ``Corpus(corpus.master, corpus.master_id)`` is the refit.  The cost follows the batch, not the corpus: the new rows
+        wait in a second segment with an index of its own, which is folded into the first once it exceeds
+        ``engine.HipEngine.CORPUS_COMPACT_SHARE`` of it (or by ``compact()``).  Rows cannot be removed."""
+        state = self._live()
+        self._same_engine()
+        if not hasattr(self._engine, "corpus_append"):
+            raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} grows no corpus")
+        if not StringGrouper._is_series_of_strings(new_strings):
+            raise TypeError('Appended input does not consist of pandas.Series containing only Strings')
+        if self._master_id is None and new_ids is not None:
+            raise ValueError("the corpus has no master_id: new_ids cannot be kept")
+        if self._master_id is not None and new_ids is None:
+            raise ValueError("the corpus has master_id: new_ids is required")
+        if new_ids is not None and (not isinstance(new_ids, pd.Series) or len(new_ids) != len(new_strings)):
+            raise Exception('Both new_strings and new_ids must be pandas.Series of the same length.')
+        if len(new_strings) == 0:
+            return
+        self._engine.corpus_append(state, new_strings)
+        # the Series are joined when they are next asked for: a run of appends copies the list once, not once per append
+        self._pending.append((new_strings, new_ids))
+
+    def compact(self) -> None:
+        """Fold the appended rows into the corpus's first segment now (one matrix, one index) instead of when they exceed
+        their share.  Results do not change; nothing to do when nothing was appended since the last compaction."""
+        state = self._live()
+        self._same_engine()
+        if hasattr(self._engine, "corpus_compact"):
+            self._engine.corpus_compact(state)
+
+    def _same_engine(self) -> None:
+        if _engine_mod.get_engine() is not self._engine:
+            raise RuntimeError("the engine has changed since the corpus was built (engine.set_engine / enable_distributed): "
+                               "its device state belongs to the old one")
 
     @property
     def vectorizer(self):
@@ -107,12 +218,15 @@ class Corpus:
     def stats(self) -> dict:
         """Work done so far: corpus tokenisations, index builds, transforms of other Series and the calls per path
         (``resident_index``: against the corpus's index; ``forward`` / ``reverse``: the corpus rows against new rows, and
-        ``reverse_fallbacks``: reverse calls whose pair list exceeded the budget)."""
+        ``reverse_fallbacks``: reverse calls whose pair list exceeded the budget); ``appends`` / ``rows_appended``,
+        ``compactions``, ``segments`` (1, or 2 while appended rows wait in their own segment) and ``base_index_builds``
+        (builds of the first segment's index: 1 + compactions at most, whatever the number of appends; ``index_builds``
+        counts every build, the second segment's included)."""
         return dict(self._live().stats)
 
     def _rows_of(self, series, made):
         state = self._live()
-        if series is self._master:
+        if not self._pending and series is self._master:
             return self._engine.corpus_matrix(state)
         m = self._engine.corpus_transform(state, series)
         made.append(m)
@@ -135,9 +249,7 @@ class Corpus:
 
     def _run(self, master, duplicates, master_id, duplicates_id, kwargs, finish):
         self._live()
-        if _engine_mod.get_engine() is not self._engine:
-            raise RuntimeError("the engine has changed since the corpus was built (engine.set_engine / enable_distributed): "
-                               "its device state belongs to the old one")
+        self._same_engine()
         g = _CorpusGrouper(self, master, duplicates, master_id, duplicates_id, **self._options(kwargs))
         try:
             return finish(g)

@@ -1,0 +1,210 @@
+// sg_csr_ops.hip -- operations on whole CSR matrices on the device.  So far one: sg_csr_concat, the rows of several matrices
+// in one.
+//
+// The reference stacks transformed blocks on the host: scipy's vstack (string_grouper.py:750 does it for the blocks of a
+// result; a master list that grows would vstack the rows of master_matrix and the transform of the new strings).  A resident
+// corpus keeps its rows in HBM and an inverted index borrows the arrays of the matrix it was built
+// over, so growing the corpus means a NEW matrix: rows of parts[0], then parts[1], ...
+//
+// One kernel, one pass over the bytes, nothing read back:
+//   csr_concat_kernel   (a) row pointers: out[row_off[p] + i] = indptr_p[i] - indptr_p[0] + nnz_off[p] -- a row-block view
+//                           holds absolute offsets into its parent's arrays, so every part is rebased by its own first entry,
+//                           which the kernel reads where it lies;
+//                       (b) column indices and values in units of four OUTPUT entries: the 16-byte (f64 values: 2 x 16-byte)
+//                           stores are aligned whatever the parts' sizes, the loads are 16 bytes wide at the alignment the
+//                           source happens to have (the hardware takes any); a unit that straddles two parts, and the tail,
+//                           go entry by entry.  The part of an entry: binary search over the <= n_parts offsets.
+//                       (c) when every part carries the words the vectoriser leaves (violations, max ||row||^2, longest
+//                           row), thread 0 merges them: sum, max, max.
+#include "sg_internal.h"
+
+#include <memory>
+#include <vector>
+
+namespace {
+
+constexpr int CONCAT_BLOCK = 256;
+constexpr int CONCAT_UNIT = 4;                // output entries per thread and step
+
+struct ConcatPart {
+    const int64_t *indptr;                    // n_rows + 1 absolute offsets into indices / data
+    const int32_t *indices;
+    const void *data;
+    const uint32_t *props;                    // the vectoriser's three words, or null
+    int64_t row_off;                          // rows of the parts before this one
+    int64_t nnz_off;                          // entries of the parts before this one
+};
+// parts[n_parts] is a sentinel: row_off = all rows, nnz_off = all entries
+
+// the part that holds position x of a prefix array (the last p with off[p] <= x; empty parts share an offset with their
+// successor and are skipped by taking the LAST)
+template <bool ROWS>
+__device__ inline int part_of(const ConcatPart *__restrict__ parts, int n_parts, int64_t x) {
+    int lo = 0, hi = n_parts - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        const int64_t off = ROWS ? parts[mid].row_off : parts[mid].nnz_off;
+        if (off <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// 16 bytes of a source array at the alignment of its entries.  The descriptors' pointers come out of memory, so the compiler
+// knows no address space for them: said to be global here, the loads are global_load_dwordx4 instead of flat loads.
+#define SG_GLOBAL __attribute__((address_space(1)))
+typedef uint32_t Words4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t Words4x8 __attribute__((ext_vector_type(4), aligned(8)));
+template <typename V, typename U>
+__device__ inline uint4 load16(const U *src) {
+    const V v = *reinterpret_cast<const SG_GLOBAL V *>((const SG_GLOBAL U *)src);
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+template <typename U>
+__device__ inline U load_global(const U *src) {
+    return *(const SG_GLOBAL U *)src;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(CONCAT_BLOCK) csr_concat_kernel(const ConcatPart *__restrict__ parts, int n_parts,
+                                                                  int64_t *__restrict__ out_indptr,
+                                                                  int32_t *__restrict__ out_indices,
+                                                                  T *__restrict__ out_data,
+                                                                  uint32_t *__restrict__ out_props) {
+    const int64_t tid = (int64_t)blockIdx.x * CONCAT_BLOCK + threadIdx.x;
+    const int64_t step = (int64_t)gridDim.x * CONCAT_BLOCK;
+    const int64_t n_rows = parts[n_parts].row_off;
+    const int64_t nnz = parts[n_parts].nnz_off;
+
+    // (a) row pointers
+    for (int64_t r = tid; r < n_rows; r += step) {
+        const int p = part_of<true>(parts, n_parts, r);
+        const int64_t *ip = parts[p].indptr;
+        out_indptr[r] = load_global(ip + (r - parts[p].row_off)) - load_global(ip) + parts[p].nnz_off;
+    }
+    if (tid == 0) out_indptr[n_rows] = nnz;
+
+    // (b) indices and values, four output entries a step
+    const int64_t n_units = (nnz + CONCAT_UNIT - 1) / CONCAT_UNIT;
+    for (int64_t u = tid; u < n_units; u += step) {
+        const int64_t e0 = u * CONCAT_UNIT;
+        int p = part_of<false>(parts, n_parts, e0);
+        const int64_t src0 = load_global(parts[p].indptr) + (e0 - parts[p].nnz_off);
+        if (e0 + CONCAT_UNIT <= parts[p + 1].nnz_off) {          // the whole unit lies in part p (and so below nnz)
+            *reinterpret_cast<uint4 *>(out_indices + e0) = load16<Words4>(parts[p].indices + src0);
+            const T *src = (const T *)parts[p].data + src0;
+            uint4 *dst = reinterpret_cast<uint4 *>(out_data + e0);
+            if (sizeof(T) == 4) {
+                dst[0] = load16<Words4>(src);
+            } else {
+                const uint4 d0 = load16<Words4x8>(src), d1 = load16<Words4x8>(src + 2);
+                dst[0] = d0;
+                dst[1] = d1;
+            }
+        } else {
+            const int64_t e1 = e0 + CONCAT_UNIT < nnz ? e0 + CONCAT_UNIT : nnz;
+            for (int64_t e = e0; e < e1; ++e) {
+                while (e >= parts[p + 1].nnz_off) ++p;           // (e < nnz = the sentinel's offset: p stays < n_parts)
+                const int64_t s = load_global(parts[p].indptr) + (e - parts[p].nnz_off);
+                out_indices[e] = load_global(parts[p].indices + s);
+                out_data[e] = load_global((const T *)parts[p].data + s);
+            }
+        }
+    }
+
+    // (c) the vectoriser's words
+    if (out_props != nullptr && tid == 0) {
+        uint32_t bad = 0, norm2 = 0, longest = 0;                // (a squared norm is >= 0: its float bits order as integers)
+        for (int p = 0; p < n_parts; ++p) {
+            const uint32_t *w = parts[p].props;
+            bad += load_global(w);
+            norm2 = max(norm2, load_global(w + 1));
+            longest = max(longest, load_global(w + 2));
+        }
+        out_props[0] = bad;
+        out_props[1] = norm2;
+        out_props[2] = longest;
+        out_props[3] = 0;
+    }
+}
+
+struct CsrDeleter {
+    void operator()(sg_csr *m) const { sg_csr_free(m); }
+};
+
+}   // namespace
+
+extern "C" int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_parts, sg_csr **out) {
+    SG_REQUIRE(ctx && parts && out && n_parts >= 1, "null argument or no parts");
+    int64_t n_rows = 0, nnz = 0;
+    bool all_vec = true, all_words = true;
+    for (int p = 0; p < n_parts; ++p) {
+        SG_REQUIRE(parts[p] != nullptr, "a part is null");
+        SG_REQUIRE(parts[p]->n_cols == parts[0]->n_cols && parts[p]->dtype == parts[0]->dtype,
+                   "parts disagree in columns or dtype");
+        // the representatives' matrix of a group structure may not have its rows yet
+        if (parts[p]->rows_of) SG_TRY(sg_csr_ensure_rows(ctx, parts[p]));
+        n_rows += parts[p]->n_rows;
+        nnz += parts[p]->nnz;
+        all_vec = all_vec && parts[p]->from_vectoriser;
+        all_words = all_words && parts[p]->d_props_words != nullptr;
+    }
+    if (n_rows > INT32_MAX) {
+        sg_set_error("sg_csr_concat: %lld rows exceed int32 indices", (long long)n_rows);
+        return SG_ERR_OVERFLOW;
+    }
+    const int32_t dtype = parts[0]->dtype;
+    const size_t s = dtype == SG_F64 ? 8 : 4;
+    std::unique_ptr<sg_csr, CsrDeleter> m(new (std::nothrow) sg_csr());
+    if (!m) return SG_ERR_OOM;
+    m->ctx = ctx;
+    m->n_rows = n_rows;
+    m->n_cols = parts[0]->n_cols;
+    m->nnz = nnz;
+    m->dtype = dtype;
+    m->owned = true;
+    m->from_vectoriser = all_vec;
+    int64_t *dp = nullptr;
+    int32_t *di = nullptr;
+    void *dd = nullptr;
+    SG_TRY(sg_alloc(ctx, (size_t)n_rows + 1, &dp));
+    m->d_indptr = dp;
+    SG_TRY(sg_alloc(ctx, (size_t)nnz + 4, &di));
+    m->d_indices = di;
+    SG_TRY(ctx->alloc(((size_t)nnz + 4) * s, &dd));
+    m->d_data = dd;
+    if (all_vec && all_words) SG_TRY(sg_alloc(ctx, (size_t)4, &m->d_props_words));
+
+    std::vector<ConcatPart> desc((size_t)n_parts + 1);
+    int64_t row_off = 0, nnz_off = 0;
+    for (int p = 0; p < n_parts; ++p) {
+        desc[p] = ConcatPart{parts[p]->d_indptr, parts[p]->d_indices, parts[p]->d_data, parts[p]->d_props_words, row_off,
+                             nnz_off};
+        row_off += parts[p]->n_rows;
+        nnz_off += parts[p]->nnz;
+    }
+    desc[n_parts] = ConcatPart{nullptr, nullptr, nullptr, nullptr, row_off, nnz_off};
+    void *d_desc = nullptr;
+    SG_TRY(ctx->alloc(desc.size() * sizeof(ConcatPart), &d_desc));
+    hipError_t e = hipMemcpyAsync(d_desc, desc.data(), desc.size() * sizeof(ConcatPart), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // desc is a local
+    if (e == hipSuccess) {
+        const int64_t work = std::max<int64_t>(std::max<int64_t>((nnz + CONCAT_UNIT - 1) / CONCAT_UNIT, n_rows), 1);
+        const int64_t want = (work + CONCAT_BLOCK - 1) / CONCAT_BLOCK;
+        const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)ctx->num_cu * 32);
+        if (dtype == SG_F64)
+            hipLaunchKernelGGL(csr_concat_kernel<double>, dim3(grid), dim3(CONCAT_BLOCK), 0, ctx->stream,
+                               (const ConcatPart *)d_desc, (int)n_parts, dp, di, (double *)dd, m->d_props_words);
+        else
+            hipLaunchKernelGGL(csr_concat_kernel<float>, dim3(grid), dim3(CONCAT_BLOCK), 0, ctx->stream,
+                               (const ConcatPart *)d_desc, (int)n_parts, dp, di, (float *)dd, m->d_props_words);
+        e = hipGetLastError();
+    }
+    ctx->release(d_desc);          // (stream-ordered pool: a later taker of the block runs behind the kernel)
+    if (e != hipSuccess) {
+        sg_set_error("sg_csr_concat: %s", hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? SG_ERR_OOM : SG_ERR_HIP;
+    }
+    *out = m.release();
+    return SG_OK;
+}

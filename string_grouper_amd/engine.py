@@ -65,28 +65,89 @@ class DeviceMatchList:
             self.ml = None
 
 
-class CorpusState:
-    """What a resident corpus keeps on the device (string_grouper_amd/corpus.py): the fitted vectoriser (vocabulary + idf),
-    its own TF-IDF rows and, from the first call that needs it, the inverted index over them (K3, with the extras the
-    multiply caches on an index).  ``stats`` counts the work, so that tests can prove the reuse."""
+class CorpusSegment:
+    """A run of corpus rows and the inverted index over them (K3), built on first need.  The index borrows the arrays of the
+    matrix it was built over (include/sg_hip.h: sg_postings_build), so the two live and die together: index first."""
 
-    def __init__(self, vec: HipTfidfVectorizer, column, matrix: "CorpusMatrix"):
+    def __init__(self, csr: "N.Csr"):
+        self.csr = csr
+        self.index: Optional["N.Postings"] = None
+        self.n_rows, _, self.nnz, _ = csr.dims()
+
+    def free(self) -> None:
+        for h in (self.index, self.csr):
+            if h is not None:
+                h.free()
+        self.index = self.csr = None
+
+
+class CorpusState:
+    """What a resident corpus keeps on the device (string_grouper_amd/corpus.py): the fitted vectoriser (vocabulary + idf)
+    and its own TF-IDF rows in one or two segments -- ``base``, and ``delta`` for the rows appended since the last
+    compaction -- each with its own inverted index from the first call that needs it.  ``whole`` is
+    the concatenation of the two for the calls that need every row in one matrix (made on first need after an append, kept
+    until the next).  ``stats`` counts the work, so that tests can prove the reuse."""
+
+    def __init__(self, vec: HipTfidfVectorizer, column, base: Optional["N.Csr"] = None):
         self.vec = vec
         self.column = column
-        self.matrix = matrix
-        self.index: Optional["N.Postings"] = None
-        self.index_overflow = False           # the corpus does not fit one index: every call takes today's blocked path
+        self.base: Optional[CorpusSegment] = None
+        self.delta: Optional[CorpusSegment] = None
+        self.whole: Optional["N.Csr"] = None
+        self.matrix: Optional["CorpusMatrix"] = None
+        self.index_overflow = False           # the corpus does not fit its indexes: every call takes today's blocked path
         self.placeholder: Optional[int] = None
         self.stats = {"tokenisations": 1, "index_builds": 0, "transforms": 0, "resident_index": 0, "forward": 0,
-                      "reverse": 0, "reverse_fallbacks": 0}
+                      "reverse": 0, "reverse_fallbacks": 0, "appends": 0, "rows_appended": 0, "compactions": 0,
+                      "segments": 1, "base_index_builds": 0}
+        if base is not None:
+            self.set_segments(CorpusSegment(base), None)
+
+    def set_segments(self, base: CorpusSegment, delta: Optional[CorpusSegment]) -> None:
+        """New rows: whoever holds the old ``matrix`` object keeps its (now stale) view; every call asks for the new one."""
+        self.base, self.delta = base, delta
+        self.stats["segments"] = 1 if delta is None else 2
+        self.matrix = CorpusMatrix(self)
+
+    @property
+    def segments(self) -> List[CorpusSegment]:
+        return [self.base] if self.delta is None else [self.base, self.delta]
+
+    @property
+    def index(self) -> Optional["N.Postings"]:
+        """The base segment's index (the whole corpus's as long as nothing has been appended since the last compaction)."""
+        return self.base.index if self.base is not None else None
+
+    def rows(self) -> "N.Csr":
+        """Every row in one matrix: the base segment itself, or the cached concatenation (sg_csr_concat)."""
+        if self.delta is None:
+            return self.base.csr
+        if self.whole is None:
+            self.whole = self.base.csr.ctx.csr_concat([self.base.csr, self.delta.csr])
+        return self.whole
+
+    def drop_whole(self) -> None:
+        if self.whole is not None:
+            self.whole.free()
+            self.whole = None
 
 
 class CorpusMatrix(DeviceMatrix):
-    """The TF-IDF rows of a resident corpus: the multiply uses the corpus's index instead of building one."""
+    """The TF-IDF rows of a resident corpus: the multiply uses the corpus's indexes instead of building one.  ``shape``,
+    ``nnz`` and ``dtype`` come from the segments; ``csr`` (every row in one matrix) is only made when something reads it."""
 
-    def __init__(self, csr: "N.Csr", corpus: CorpusState):
-        super().__init__(csr)
+    def __init__(self, corpus: CorpusState):
         self.corpus = corpus
+        segs = corpus.segments
+        _, n_cols, _, d = segs[0].csr.dims()
+        self.shape = (sum(s.n_rows for s in segs), n_cols)
+        self.nnz = sum(s.nnz for s in segs)
+        self.dtype = N.code_np_dtype(d)
+        self._host = None
+
+    @property
+    def csr(self) -> "N.Csr":
+        return self.corpus.rows()
 
 
 class HipEngine:
@@ -101,6 +162,13 @@ class HipEngine:
     # (4.4 ms at 663 k names, 35 ms at 5 M); the reverse path what the batch's rows cost against the corpus index -- it is
     # the faster one up to 32 rows and the slower one from 64 on, at both sizes
     CORPUS_REVERSE_MAX_ROWS = 32
+    # appended rows wait in a delta segment with an index of its own until they exceed this share of the base segment's
+    # rows; then the two are folded into one (corpus_compact).  Measured (scripts/corpus_append_latency.py,
+    # profiles/corpus_append_latency.log): a step of a living list (append one row, match one name) costs the more the larger
+    # the delta is -- its index is rebuilt after every append: 3.8 -> 5.1 ms at 663 k names from an empty delta to a quarter
+    # of the base -- while a compaction costs 1-1.4 ms at 663 k and 5-30 ms at 5 M, under 0.001 ms per appended row at any
+    # share: the cheapest of the measured shares (1/64, 1/16, 1/8, 1/4) is the smallest at both sizes
+    CORPUS_COMPACT_SHARE = 1 / 64
 
     def __init__(self, ctx: Optional[N.Context] = None):
         self._ctx = ctx
@@ -155,12 +223,14 @@ class HipEngine:
                                  normalize_to_ascii=normalize_to_ascii, dtype=dtype, ctx=self.ctx)
         col = vec.prepare(strings)
         vec.fit_prepared([col])
-        state = CorpusState(vec, col, None)
-        state.matrix = CorpusMatrix(vec.transform_prepared(col), state)
-        return state
+        return CorpusState(vec, col, vec.transform_prepared(col))
 
     def corpus_transform(self, state: CorpusState, strings) -> DeviceMatrix:
         """The rows of ``strings`` under the corpus's vocabulary and idf: n-grams the corpus never had are dropped."""
+        state.stats["transforms"] += 1
+        return DeviceMatrix(self._corpus_rows_of(state, strings))
+
+    def _corpus_rows_of(self, state: CorpusState, strings) -> "N.Csr":
         vec = state.vec
         col = vec.prepare(strings)
         if col.kind == "symbols" and vec._alphabet is None:
@@ -168,11 +238,10 @@ class HipEngine:
             # of them is out of vocabulary.  Each such character becomes one byte the corpus never had, so that the device
             # drops exactly those n-grams (its own treatment of bytes >= 0x80 would join the neighbours instead).
             col = self._corpus_bytes_column(state, col)
-        state.stats["transforms"] += 1
-        m = DeviceMatrix(vec.transform_prepared(col))
+        csr = vec.transform_prepared(col)
         if col.dev is not None:
             col.dev.free()
-        return m
+        return csr
 
     @staticmethod
     def _corpus_bytes_column(state: CorpusState, col):
@@ -195,26 +264,80 @@ class HipEngine:
     def corpus_matrix(self, state: CorpusState) -> "CorpusMatrix":
         return state.matrix
 
-    def corpus_index(self, state: CorpusState) -> Optional["N.Postings"]:
-        """The inverted index over the corpus rows, built on first need and kept; None when the corpus is too large for one
-        index (the callers then take the blocked path of _topn_device)."""
-        if state.index is None and not state.index_overflow:
+    def corpus_append(self, state: CorpusState, strings) -> None:
+        """The rows of ``strings`` (under the corpus's vocabulary and idf, as corpus_transform makes them) join the corpus
+        behind its last row.  The cost follows the batch and the delta segment, not the corpus: the new rows are
+        concatenated to the delta's (sg_csr_concat), whose index is dropped and rebuilt on first need; the base segment and
+        its index are not touched until the delta outgrows CORPUS_COMPACT_SHARE of the base (corpus_compact)."""
+        n_new = len(strings)
+        if n_new == 0:
+            return
+        new = self._corpus_rows_of(state, strings)
+        state.drop_whole()
+        if state.delta is None:
+            delta = CorpusSegment(new)
+        else:
+            delta = CorpusSegment(self.ctx.csr_concat([state.delta.csr, new]))
+            state.delta.free()
+            new.free()
+        state.set_segments(state.base, delta)
+        state.stats["appends"] += 1
+        state.stats["rows_appended"] += n_new
+        if delta.n_rows > self.CORPUS_COMPACT_SHARE * state.base.n_rows:
+            self.corpus_compact(state)
+
+    def corpus_compact(self, state: CorpusState) -> None:
+        """Fold the delta segment into the base: one matrix, one index (built on first need), and with them the self-join
+        form of the multiply for a self-join of the corpus.  Nothing to do without a delta."""
+        if state.delta is None:
+            return
+        whole = state.rows()
+        state.whole = None                    # (handed to the new base segment)
+        old = state.segments
+        state.set_segments(CorpusSegment(whole), None)
+        for seg in old:
+            seg.free()
+        state.stats["compactions"] += 1
+
+    def _segment_index(self, state: CorpusState, seg: CorpusSegment) -> Optional["N.Postings"]:
+        if seg.index is None and not state.index_overflow:
             try:
-                state.index = self.ctx.postings_build(state.matrix.csr)
+                seg.index = self.ctx.postings_build(seg.csr)
                 state.stats["index_builds"] += 1
+                if seg is state.base:
+                    state.stats["base_index_builds"] += 1
             except OverflowError:
                 state.index_overflow = True
-        return state.index
+        return None if state.index_overflow else seg.index
+
+    def corpus_index(self, state: CorpusState) -> Optional["N.Postings"]:
+        """The inverted index over the base segment's rows (all rows as long as no delta exists), built on first need and
+        kept; None when the corpus is too large for its indexes (the callers then take the blocked path of _topn_device)."""
+        return self._segment_index(state, state.base)
+
+    def corpus_indexes(self, state: CorpusState) -> Optional[List[Tuple["N.Postings", int, int]]]:
+        """(index, first row, rows) of every segment, or None when one of them does not fit an index."""
+        out, first = [], 0
+        for seg in state.segments:
+            idx = self._segment_index(state, seg)
+            if idx is None:
+                return None
+            out.append((idx, first, seg.n_rows))
+            first += seg.n_rows
+        return out
 
     def corpus_free(self, state: CorpusState) -> None:
-        handles = [state.index, state.matrix.csr if state.matrix is not None else None, state.vec._vocab]
+        state.drop_whole()
+        for seg in state.segments if state.base is not None else []:
+            seg.free()
+        handles = [state.vec._vocab]
         for col in list(getattr(state.vec, "_fit_sets", [])) + list(getattr(state.vec, "_fit_originals", [])) + [state.column]:
             handles.append(getattr(col, "dev", None))
         for h in handles:
             if h is not None:
                 h.free()
         state.vec._dev_of = {}
-        state.index = None
+        state.base = state.delta = state.matrix = None
 
     def _corpus_reverse_mode(self) -> Optional[bool]:
         v = self.ctx.options().get("SG_CORPUS_REVERSE")
@@ -226,11 +349,12 @@ class HipEngine:
         A the corpus, B new rows: the forward path (the corpus rows against an index of the new rows: the generic path) or
         the reverse path (the new rows against the corpus index, turned round by sg_topn_transpose_select)."""
         if isinstance(B, CorpusMatrix):
-            idx = self.corpus_index(B.corpus)
-            if idx is None:
+            segs = self.corpus_indexes(B.corpus)
+            if segs is None:
                 return None
             B.corpus.stats["resident_index"] += 1
-            return self.ctx.spgemm_topn(A.csr, idx, top_n, threshold, True)
+            parts = [self.ctx.spgemm_topn(A.csr, idx, top_n, threshold, True) for idx, _, _ in segs]
+            return self._zip_segments(parts, segs, top_n)
         state = A.corpus
         mode = self._corpus_reverse_mode()
         if mode is None:
@@ -244,28 +368,45 @@ class HipEngine:
         state.stats["forward"] += 1
         return None
 
+    def _zip_segments(self, parts: List["N.TopN"], segs, top_n: int) -> "N.TopN":
+        """The results against the segments' indexes as one over the corpus's rows: columns offset by the segment's first
+        row, merged by score descending, then row ascending (K5), cut at top_n."""
+        if len(parts) == 1:
+            return parts[0]
+        res = self.ctx.topn_zip(parts, np.array([first for _, first, _ in segs], dtype=np.int64), top_n)
+        for p in parts:
+            p.free()
+        return res
+
     def _corpus_reverse(self, state: CorpusState, A: DeviceMatrix, B: DeviceMatrix, top_n: int,
                         threshold: float) -> Optional["N.TopN"]:
-        """Every pair above the threshold from the new rows' side -- the cap per new row grows until no row comes back
-        full -- then the top_n per corpus row.  None (nothing returned, the caller takes the forward path) when the pair
-        list would exceed the budget or top_n exceeds what the select kernel takes."""
+        """Every pair above the threshold from the new rows' side -- per segment, the cap per new row grows until no row
+        comes back full -- then the top_n per corpus row.  None (nothing returned, the caller takes the forward path) when
+        the pair lists of the segments together would exceed the budget or top_n exceeds what the select kernel takes."""
         n_corpus, n_new = A.shape[0], B.shape[0]
         if top_n > self.CORPUS_MAX_TOP_N or n_new == 0 or n_corpus == 0:
             return None
-        idx = self.corpus_index(state)
-        if idx is None:
+        segs = self.corpus_indexes(state)
+        if segs is None:
             return None
-        cap = self.CORPUS_FIRST_CAP
-        while True:
-            stride = min(cap, n_corpus)
-            if n_new * stride > self.CORPUS_PAIR_BUDGET:
-                return None
-            pairs = self.ctx.spgemm_topn(B.csr, idx, stride, threshold, True)
-            cnt = pairs.counts()
-            if stride >= n_corpus or int(cnt.max()) < stride:
-                break
-            pairs.free()
-            cap *= 8
+        parts, slots = [], 0                  # slots: what the complete parts so far hold per new row
+        for idx, _, n_seg in segs:
+            cap = self.CORPUS_FIRST_CAP
+            while True:
+                stride = min(cap, n_seg)
+                if n_new * (slots + stride) > self.CORPUS_PAIR_BUDGET:
+                    for p in parts:
+                        p.free()
+                    return None
+                pairs = self.ctx.spgemm_topn(B.csr, idx, stride, threshold, True)
+                cnt = pairs.counts()
+                if stride >= n_seg or int(cnt.max()) < stride:
+                    break
+                pairs.free()
+                cap *= 8
+            parts.append(pairs)
+            slots += stride
+        pairs = self._zip_segments(parts, segs, slots)      # asked for the sum of the strides: nothing is cut
         res = self.ctx.topn_transpose_select(pairs, n_corpus, top_n)
         pairs.free()
         return res
