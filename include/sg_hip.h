@@ -58,9 +58,10 @@ typedef struct sg_topn sg_topn;         /* device-resident fixed-stride top-n re
 /* ------------------------------------------------------------------ library / context */
 const char *sg_last_error(void);
 /* Bumped whenever a signature or a struct of this header changes (round 4: 2 -- row_step arguments of round 3, sg_stats
- * grew; round 5: 3 -- sg_stats.prune_scored; 4 -- sg_topn_transpose_select; 5 -- sg_csr_concat); a binding compares it with the
- * value it was written for right after loading the library. */
-#define SG_ABI_VERSION 5
+ * grew; round 5: 3 -- sg_stats.prune_scored; 4 -- sg_topn_transpose_select; 5 -- sg_csr_concat; 6 -- sg_csr_select_rows,
+ * sg_topn_drop_columns, sg_device_upload); a binding compares it with the value it was written for right after loading the
+ * library. */
+#define SG_ABI_VERSION 6
 int sg_abi_version(void);
 int sg_device_count(int *count);
 /* hip_stream: a hipStream_t to launch on (e.g. torch.cuda.current_stream().cuda_stream), or NULL
@@ -169,6 +170,17 @@ int sg_csr_row_block(sg_ctx *ctx, const sg_csr *m, int64_t r0, int64_t r1, sg_cs
  * result counts as made by it too (cosine-like by construction: the pruned multiply needs no scan of it), and the words
  * the vectoriser left with the parts are merged.  More than INT32_MAX rows: SG_ERR_OVERFLOW. */
 int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_parts, sg_csr **out);
+/* m without the rows d_drop_sorted[0 .. n_drop) in a new matrix that owns its arrays: scipy's m[keep] with keep the
+ * complement of the list (what a master list that forgets rows does to master_matrix on the host; the reference has no such
+ * operation, it refits).  d_drop_sorted: DEVICE memory (sg_device_upload), row numbers of m ascending and distinct, each in
+ * [0, n_rows) -- anything else is SG_ERR_BADARG, seen on the device before anything is copied.  A kept row's new number is
+ * its old one minus the dropped rows before it.  m may be a row-block view and may have rows without entries; n_drop == 0 is
+ * a copy, n_drop == n_rows a matrix without rows.  The kept rows between two dropped ones are contiguous in m, so the copy is
+ * sg_csr_concat's over the gaps: one pass at the width of that kernel however the dropped rows lie.  One synchronisation:
+ * the number of kept entries comes back to size the result.  m is only read and may be freed after the call, as the parts
+ * of sg_csr_concat.  A matrix made by sg_vec_transform stays one (cosine-like by construction); the words the vectoriser
+ * left are carried over and are then UPPER bounds: the largest norm and the longest row may have been dropped. */
+int sg_csr_select_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d_drop_sorted, int64_t n_drop, sg_csr **out);
 int sg_csr_free(sg_csr *m);
 
 /* Row-wise similarity of two matrices of the same shape (StringGrouper.dot / compute_pairwise_similarities,
@@ -309,6 +321,10 @@ int sg_topn_expand_range(sg_ctx *ctx, const sg_postings *Bt, const sg_topn *grou
 /* device tables of Bt's row permutation, one entry per index row: position -> row, row -> position (both null: none) */
 int sg_postings_permutation(const sg_postings *Bt, const uint32_t **d_orig_of, const uint32_t **d_pos_of);
 int sg_device_free(sg_ctx *ctx, void *d_ptr);
+/* bytes of host memory copied into device memory of the library (the context's pool; sg_device_free): how a caller hands
+ * a small list to sg_csr_select_rows / sg_topn_drop_columns and keeps it resident between calls.  The host memory may be
+ * reused once the call returns. */
+int sg_device_upload(sg_ctx *ctx, const void *host, int64_t bytes, void **d_out);
 
 /* ------------------------------------------------------------------ resident corpus: the reverse path */
 /* A corpus whose index stays on the device answers match_strings(corpus, new) / match_most_similar(corpus, new) -- the
@@ -324,6 +340,18 @@ int sg_device_free(sg_ctx *ctx, void *d_ptr);
  * order from either side.  (The reference has no analogue: it re-fits and re-multiplies the whole
  * master list every call, string_grouper.py:685-707.) */
 int sg_topn_transpose_select(sg_ctx *ctx, const sg_topn *pairs, int64_t n_rows_out, int32_t top_n, sg_topn **out);
+/* A corpus that has forgotten rows keeps them in its segments and indexes until the next compaction, so a product against
+ * its index still names them.  sg_topn_drop_columns is scipy's C[:, keep] on a fixed-stride result, followed by the cut: per
+ * row of r the entries whose column is in d_dead_sorted[0 .. n_dead) (DEVICE memory, ascending and distinct -- the caller's
+ * responsibility, nothing is read back to check it) are dropped, every other column is lowered by the number of dead
+ * columns below it, the order of the entries is kept and at most top_n of them stay; *out has r's rows, r's columns minus
+ * n_dead and the stride min(top_n, r's stride) (top_n >= r's stride: nothing is cut).  Because a row of a product is ordered
+ * by score descending, then column ascending, and the renumbering is monotonic, the rows of
+ * sg_topn_drop_columns(sg_spgemm_topn(A, Bt, top_n + n_dead, ...), dead, top_n) are bit for bit those of
+ * sg_spgemm_topn(A, index of sg_csr_select_rows(B, dead), top_n, ...): at most n_dead of the first top_n + n_dead entries
+ * are dead.  No synchronisation. */
+int sg_topn_drop_columns(sg_ctx *ctx, const sg_topn *r, const int32_t *d_dead_sorted, int32_t n_dead, int32_t top_n,
+                         sg_topn **out);
 
 /* ------------------------------------------------------------------ measurement */
 enum { SG_K_TOKENIZE = 0, SG_K_WEIGHT = 1, SG_K_POSTINGS = 2, SG_K_SPGEMM = 3 /* the multiply's whole launch group */,

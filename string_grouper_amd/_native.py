@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SG_HIP_LIB") or os.path.join(_HERE, "libsg_hip.so")
 
 SG_OK, SG_ERR_BADARG, SG_ERR_OOM, SG_ERR_OVERFLOW, SG_ERR_HIP, SG_ERR_NODEVICE, SG_ERR_UNSUPPORTED = range(7)
 SG_F32, SG_F64 = 0, 1
-ABI_VERSION = 5          # include/sg_hip.h: SG_ABI_VERSION
+ABI_VERSION = 6          # include/sg_hip.h: SG_ABI_VERSION
 SG_K_TOKENIZE, SG_K_WEIGHT, SG_K_POSTINGS, SG_K_SPGEMM, SG_K_ZIP, SG_K_VOCAB, SG_K_SPGEMM_KERNEL, SG_K_COUNT = range(8)
 KERNEL_NAMES = ("tokenize", "weight", "postings", "spgemm_topn", "zip", "vocab", "spgemm_kernel")
 
@@ -75,6 +75,7 @@ ABI = {
     "sg_csr_to_host": (C.c_int, [_P, _P, _P, _P, _P]),
     "sg_csr_row_block": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _PP]),
     "sg_csr_concat": (C.c_int, [_P, _PP, C.c_int32, _PP]),
+    "sg_csr_select_rows": (C.c_int, [_P, _P, _P, C.c_int64, _PP]),
     "sg_csr_free": (C.c_int, [_P]),
     "sg_postings_build": (C.c_int, [_P, _P, C.c_int32, _PP]),
     "sg_postings_build_flags": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PP]),
@@ -106,7 +107,9 @@ ABI = {
     "sg_topn_expand_groups": (C.c_int, [_P, _P, _P, _P, C.c_int64, _PP]),
     "sg_topn_expand_range": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _PP, _PP, _P, C.c_int64]),
     "sg_device_free": (C.c_int, [_P, _P]),
+    "sg_device_upload": (C.c_int, [_P, _P, C.c_int64, _PP]),
     "sg_topn_transpose_select": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _PP]),
+    "sg_topn_drop_columns": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _PP]),
     "sg_csr_rowwise_dot": (C.c_int, [_P, _P, _P, _P]),
     "sg_ctx_stats": (C.c_int, [_P, C.POINTER(SgStats)]),
 }
@@ -317,6 +320,37 @@ class MatchList(_Handle):
         return row_ptr, cols[:m.value], vals[:m.value]
 
 
+class DeviceInts:
+    """A sorted list of distinct int32 numbers kept in device memory (sg_device_upload), with its host copy."""
+
+    def __init__(self, ctx: "Context", values):
+        host = np.asarray(values)
+        if host.ndim != 1 or (host.size and host.dtype.kind not in "iu"):
+            raise ValueError("a one-dimensional array of integers is expected")
+        host = np.ascontiguousarray(host, dtype=np.int64)
+        if host.size and (host[0] < 0 or host[-1] > np.iinfo(np.int32).max or np.any(host[1:] <= host[:-1])):
+            raise ValueError("bad argument: the list must be ascending, distinct and hold row numbers (0 .. 2^31 - 1)")
+        self.host = host.astype(np.int32)
+        self.ctx = ctx
+        out = C.c_void_p()
+        check(lib().sg_device_upload(ctx.h, _ptr(self.host), int(self.host.nbytes), C.byref(out)))
+        self.ptr = out.value
+
+    def __len__(self) -> int:
+        return len(self.host)
+
+    def free(self) -> None:
+        if self.ptr and self.ctx.h is not None:
+            lib().sg_device_free(self.ctx.h, C.c_void_p(self.ptr))
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Context:
     """One per (process, GPU).  ``stream``: an integer hipStream_t (e.g. torch's current stream)."""
 
@@ -502,6 +536,17 @@ class Context:
         check(lib().sg_csr_concat(self.h, arr, len(parts), C.byref(out)))
         return Csr(self, out)
 
+    def csr_select_rows(self, m: Csr, drop: "DeviceInts") -> Csr:
+        """``m`` without the rows of ``drop`` in a new owned matrix (include/sg_hip.h: sg_csr_select_rows; scipy's m[keep])."""
+        out = C.c_void_p()
+        check(lib().sg_csr_select_rows(self.h, m.h, C.c_void_p(drop.ptr), len(drop), C.byref(out)))
+        return Csr(self, out)
+
+    def upload_sorted_ints(self, values) -> "DeviceInts":
+        """An ascending list of distinct non-negative row / column numbers in device memory, for ``csr_select_rows`` and
+        ``topn_drop_columns``.  Anything else: ValueError (checked here, on the host copy, where it costs nothing)."""
+        return DeviceInts(self, values)
+
     def csr_from_device(self, n_rows, n_cols, nnz, d_indptr: int, d_indices: int, d_data: int, dtype,
                         keepalive=None) -> Csr:
         out = C.c_void_p()
@@ -623,6 +668,13 @@ class Context:
         descending, then r ascending (include/sg_hip.h: sg_topn_transpose_select)."""
         out = C.c_void_p()
         check(lib().sg_topn_transpose_select(self.h, pairs.h, int(n_rows_out), int(top_n), C.byref(out)))
+        return TopN(self, out)
+
+    def topn_drop_columns(self, res: TopN, dead: "DeviceInts", top_n: int) -> TopN:
+        """``res`` without the columns of ``dead``, the others renumbered, every row cut at ``top_n`` (include/sg_hip.h:
+        sg_topn_drop_columns)."""
+        out = C.c_void_p()
+        check(lib().sg_topn_drop_columns(self.h, res.h, C.c_void_p(dead.ptr), len(dead), int(top_n), C.byref(out)))
         return TopN(self, out)
 
     def topn_zip(self, parts, col_offsets, top_n: int) -> TopN:

@@ -559,3 +559,18 @@ int sg_exclusive_scan_i32_to_i64(sg_ctx *ctx, const int32_t *d_in, int64_t *d_ou
     // d_out has n + 1 entries; d_out[n] = total
     return scan_impl<int32_t, int64_t>(ctx, d_in, d_out, n, d_out + n);
 }
+
+extern "C" int sg_device_upload(sg_ctx *ctx, const void *host, int64_t bytes, void **d_out) {
+    SG_REQUIRE(ctx && d_out && bytes >= 0 && (bytes == 0 || host != nullptr), "null argument or negative size");
+    void *d = nullptr;
+    SG_TRY(ctx->alloc((size_t)std::max<int64_t>(bytes, 16), &d));
+    hipError_t e = bytes > 0 ? hipMemcpyAsync(d, host, (size_t)bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // (the caller's memory may go once this returns)
+    if (e != hipSuccess) {
+        ctx->release(d);
+        sg_set_error("sg_device_upload: %s", hipGetErrorString(e));
+        return SG_ERR_HIP;
+    }
+    *d_out = d;
+    return SG_OK;
+}

@@ -17,6 +17,15 @@
 //                        row's, by a 64 x 64 compare through lane shuffles; rank < top_n is written at its slot
 //   tsel_block_kernel    a workgroup per larger row (a hub: a batch with thousands of copies of one corpus name): radix
 //                        select of the top_n-th best (score, d) in LDS histograms, then the rank of the selected few
+//
+// And the filter of a corpus that has forgotten rows ("A corpus that forgets"): a removed row stays in its
+// segment and its index until the next compaction, so a multiply still names it.  The multiply is asked for top_n + dead
+// entries; sg_topn_drop_columns takes the dead columns out of every result row, renumbers the others (column - dead columns
+// below it) and cuts at top_n.  A row is ordered by (score descending, column ascending), dropping entries keeps the order
+// of the rest and the renumbering is monotonic, so what is left IS the top_n over the live rows (scipy: C[:, keep] of the
+// uncut product, then the cut).
+//   drop_columns_kernel  a wave per result row, 64 entries a round: a binary search per lane in the sorted dead list (in
+//                        LDS up to DROP_LDS_MAX columns), the survivors' positions by ballot + popcount on a running base
 #include "sg_internal.h"
 
 #include <algorithm>
@@ -247,6 +256,72 @@ __global__ void __launch_bounds__(TSEL_BLOCK) tsel_block_kernel(const uint32_t *
     }
 }
 
+// ---- sg_topn_drop_columns
+constexpr int DROP_LDS_MAX = 2048;            // dead columns kept in LDS (8 KiB); a longer list is searched where it lies
+
+template <typename T, bool IN_LDS>
+__global__ void __launch_bounds__(TSEL_BLOCK) drop_columns_kernel(const int32_t *__restrict__ cols,
+                                                                  const T *__restrict__ vals,
+                                                                  const int32_t *__restrict__ counts, int64_t n_rows,
+                                                                  int32_t stride_in, const int32_t *__restrict__ dead,
+                                                                  int32_t n_dead, int32_t stride_out,
+                                                                  int32_t *__restrict__ out_cols, T *__restrict__ out_vals,
+                                                                  int32_t *__restrict__ out_counts) {
+    __shared__ int32_t lds_dead[IN_LDS ? DROP_LDS_MAX : 1];
+    if (IN_LDS) {
+        for (int i = threadIdx.x; i < n_dead; i += TSEL_BLOCK) lds_dead[i] = dead[i];
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & (SG_WAVE - 1);
+    const uint64_t below = (1ull << lane) - 1ull;                // the lanes before this one
+    const int64_t step = (int64_t)gridDim.x * TSEL_WAVES;
+    for (int64_t r = (int64_t)blockIdx.x * TSEL_WAVES + threadIdx.x / SG_WAVE; r < n_rows; r += step) {
+        const int32_t c = min(max(counts[r], 0), stride_in);
+        const int32_t *row_cols = cols + r * (int64_t)stride_in;
+        const T *row_vals = vals + r * (int64_t)stride_in;
+        int32_t base = 0;                                        // survivors so far (wave-uniform, as are the loop's bounds)
+        for (int32_t j0 = 0; j0 < c && base < stride_out; j0 += SG_WAVE) {
+            const int32_t j = j0 + lane;
+            const bool mine = j < c;
+            const int32_t col = mine ? row_cols[j] : 0;
+            const T v = mine ? row_vals[j] : T(0);
+            int32_t lo = 0, hi = n_dead;                         // lo: dead columns below col
+            while (lo < hi) {
+                const int32_t mid = (lo + hi) >> 1;
+                const int32_t d = IN_LDS ? lds_dead[mid] : dead[mid];
+                if (d < col) lo = mid + 1;
+                else hi = mid;
+            }
+            const bool gone = lo < n_dead && (IN_LDS ? lds_dead[lo] : dead[lo]) == col;
+            const bool keep = mine && !gone;
+            const uint64_t kept = __ballot(keep);
+            const int32_t pos = base + (int32_t)__popcll(kept & below);
+            if (keep && pos < stride_out) {
+                out_cols[r * (int64_t)stride_out + pos] = col - lo;
+                out_vals[r * (int64_t)stride_out + pos] = v;
+            }
+            base += (int32_t)__popcll(kept);
+        }
+        if (lane == 0) out_counts[r] = min(base, stride_out);
+    }
+}
+
+template <typename T>
+int drop_columns(sg_ctx *ctx, const sg_topn *in, const int32_t *d_dead, int32_t n_dead, sg_topn *r) {
+    const int64_t waves = in->n_rows > 0 ? in->n_rows : 1;
+    const int grid = (int)std::min<int64_t>((waves + TSEL_WAVES - 1) / TSEL_WAVES, (int64_t)ctx->num_cu * 16);
+    if (n_dead <= DROP_LDS_MAX)
+        hipLaunchKernelGGL((drop_columns_kernel<T, true>), dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream,
+                           (const int32_t *)in->d_cols, (const T *)in->d_vals, (const int32_t *)in->d_counts, in->n_rows,
+                           in->stride, d_dead, n_dead, r->stride, r->d_cols, (T *)r->d_vals, r->d_counts);
+    else
+        hipLaunchKernelGGL((drop_columns_kernel<T, false>), dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream,
+                           (const int32_t *)in->d_cols, (const T *)in->d_vals, (const int32_t *)in->d_counts, in->n_rows,
+                           in->stride, d_dead, n_dead, r->stride, r->d_cols, (T *)r->d_vals, r->d_counts);
+    SG_HIP_TRY(hipGetLastError());
+    return SG_OK;
+}
+
 template <typename T>
 int transpose_select(sg_ctx *ctx, const sg_topn *pairs, int64_t n_out, int32_t top_n, sg_topn *r, uint32_t *cnt,
                      uint32_t *off, uint32_t *flags, uint32_t *big_rows, int32_t *b_rows, T *b_vals) {
@@ -337,6 +412,30 @@ extern "C" int sg_topn_transpose_select(sg_ctx *ctx, const sg_topn *pairs, int64
     ctx->release(b_rows);
     ctx->release(b_vals);
     if (st != SG_OK) return st;
+    *out = guard.release();
+    return SG_OK;
+}
+
+extern "C" int sg_topn_drop_columns(sg_ctx *ctx, const sg_topn *r_in, const int32_t *d_dead_sorted, int32_t n_dead,
+                                    int32_t top_n, sg_topn **out) {
+    SG_REQUIRE(ctx && r_in && out, "null argument");
+    SG_REQUIRE(top_n >= 1, "top_n must be at least 1");
+    SG_REQUIRE(n_dead >= 0 && (int64_t)n_dead <= r_in->n_cols, "more dead columns than the result has columns");
+    SG_REQUIRE(n_dead == 0 || d_dead_sorted != nullptr, "the list of dead columns is null");
+    sg_topn *r = new (std::nothrow) sg_topn();
+    if (!r) return SG_ERR_OOM;
+    std::unique_ptr<sg_topn, int (*)(sg_topn *)> guard(r, sg_topn_free);
+    r->ctx = ctx;
+    r->n_rows = r_in->n_rows;
+    r->n_cols = r_in->n_cols - n_dead;
+    r->stride = std::max<int32_t>(std::min<int32_t>(top_n, r_in->stride), 1);
+    r->dtype = r_in->dtype;
+    const size_t cells = (size_t)r->n_rows * (size_t)r->stride + 64;
+    SG_TRY(sg_alloc(ctx, cells, &r->d_cols));
+    SG_TRY(ctx->alloc(cells * (r->dtype == SG_F64 ? 8 : 4), &r->d_vals));
+    SG_TRY(sg_alloc(ctx, (size_t)r->n_rows + 64, &r->d_counts));
+    SG_TRY(r->dtype == SG_F64 ? drop_columns<double>(ctx, r_in, d_dead_sorted, n_dead, r)
+                              : drop_columns<float>(ctx, r_in, d_dead_sorted, n_dead, r));
     *out = guard.release();
     return SG_OK;
 }

@@ -1,5 +1,5 @@
-// sg_csr_ops.hip -- operations on whole CSR matrices on the device.  So far one: sg_csr_concat, the rows of several matrices
-// in one.
+// sg_csr_ops.hip -- operations on whole CSR matrices on the device: sg_csr_concat, the rows of several matrices in one, and
+// sg_csr_select_rows, a matrix without some of its rows.
 //
 // The reference stacks transformed blocks on the host: scipy's vstack (string_grouper.py:750 does it for the blocks of a
 // result; a master list that grows would vstack the rows of master_matrix and the transform of the new strings).  A resident
@@ -16,6 +16,15 @@
 //                           go entry by entry.  The part of an entry: binary search over the <= n_parts offsets.
 //                       (c) when every part carries the words the vectoriser leaves (violations, max ||row||^2, longest
 //                           row), thread 0 merges them: sum, max, max.
+//
+// sg_csr_select_rows is scipy's m[keep] for a corpus that forgets rows ("A corpus that forgets").  Between two
+// dropped rows the kept rows are CONTIGUOUS in the source, so a selection is a concatenation of the gaps of ONE matrix:
+//   csr_select_gaps_kernel   one workgroup: checks the sorted drop list (ascending, distinct, inside the matrix) and writes
+//                            a part descriptor per gap -- its first row pointer, the kept rows before it (first row - gap
+//                            number) and the kept entries before it (a scan over the <= n_drop + 1 gaps' sizes, which it
+//                            reads from the source's row pointers) -- and the totals, the only thing read back: they size
+//                            the result;
+//   csr_select_kernel        (a) and (b) above over those descriptors; the vectoriser's words are the source's own.
 #include "sg_internal.h"
 
 #include <memory>
@@ -65,14 +74,10 @@ __device__ inline U load_global(const U *src) {
     return *(const SG_GLOBAL U *)src;
 }
 
+// (a) and (b) of the header: the row pointers, then the indices and values, of the parts one after the other
 template <typename T>
-__global__ void __launch_bounds__(CONCAT_BLOCK) csr_concat_kernel(const ConcatPart *__restrict__ parts, int n_parts,
-                                                                  int64_t *__restrict__ out_indptr,
-                                                                  int32_t *__restrict__ out_indices,
-                                                                  T *__restrict__ out_data,
-                                                                  uint32_t *__restrict__ out_props) {
-    const int64_t tid = (int64_t)blockIdx.x * CONCAT_BLOCK + threadIdx.x;
-    const int64_t step = (int64_t)gridDim.x * CONCAT_BLOCK;
+__device__ inline void copy_parts(const ConcatPart *__restrict__ parts, int n_parts, int64_t *__restrict__ out_indptr,
+                                  int32_t *__restrict__ out_indices, T *__restrict__ out_data, int64_t tid, int64_t step) {
     const int64_t n_rows = parts[n_parts].row_off;
     const int64_t nnz = parts[n_parts].nnz_off;
 
@@ -111,6 +116,17 @@ __global__ void __launch_bounds__(CONCAT_BLOCK) csr_concat_kernel(const ConcatPa
             }
         }
     }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(CONCAT_BLOCK) csr_concat_kernel(const ConcatPart *__restrict__ parts, int n_parts,
+                                                                  int64_t *__restrict__ out_indptr,
+                                                                  int32_t *__restrict__ out_indices,
+                                                                  T *__restrict__ out_data,
+                                                                  uint32_t *__restrict__ out_props) {
+    const int64_t tid = (int64_t)blockIdx.x * CONCAT_BLOCK + threadIdx.x;
+    const int64_t step = (int64_t)gridDim.x * CONCAT_BLOCK;
+    copy_parts<T>(parts, n_parts, out_indptr, out_indices, out_data, tid, step);
 
     // (c) the vectoriser's words
     if (out_props != nullptr && tid == 0) {
@@ -124,6 +140,86 @@ __global__ void __launch_bounds__(CONCAT_BLOCK) csr_concat_kernel(const ConcatPa
         out_props[0] = bad;
         out_props[1] = norm2;
         out_props[2] = longest;
+        out_props[3] = 0;
+    }
+}
+
+// ---- sg_csr_select_rows: the gaps between the dropped rows as parts of a concatenation.  info[0] = kept entries,
+// info[1] != 0: the drop list is not ascending, not distinct or names a row outside the matrix (nothing else is written).
+__global__ void __launch_bounds__(CONCAT_BLOCK) csr_select_gaps_kernel(const int64_t *__restrict__ indptr,
+                                                                       const int32_t *__restrict__ indices,
+                                                                       const void *__restrict__ data, int64_t n_rows,
+                                                                       const int32_t *__restrict__ drop, int64_t n_drop,
+                                                                       ConcatPart *__restrict__ parts,
+                                                                       int64_t *__restrict__ info) {
+    __shared__ int64_t scan[CONCAT_BLOCK];
+    __shared__ int64_t carry;
+    __shared__ int bad;
+    const int tid = threadIdx.x;
+    const int64_t n_gaps = n_drop + 1;
+    if (tid == 0) {
+        carry = 0;
+        bad = 0;
+    }
+    __syncthreads();
+    for (int64_t k = tid; k < n_drop; k += CONCAT_BLOCK) {
+        const int64_t d = drop[k], before = k > 0 ? (int64_t)drop[k - 1] : -1;
+        if (d <= before || d >= n_rows) atomicOr(&bad, 1);
+    }
+    __syncthreads();
+    if (bad) {                                 // (uniform: read after the barrier)
+        if (tid == 0) {
+            info[0] = 0;
+            info[1] = 1;
+        }
+        return;
+    }
+    // gap g = the rows between dropped row g - 1 and dropped row g; CONCAT_BLOCK gaps a round, their sizes scanned in LDS
+    for (int64_t g0 = 0; g0 < n_gaps; g0 += CONCAT_BLOCK) {
+        const int64_t g = g0 + tid;
+        int64_t first = 0, len = 0;
+        if (g < n_gaps) {
+            first = g > 0 ? (int64_t)drop[g - 1] + 1 : 0;
+            const int64_t end = g < n_drop ? (int64_t)drop[g] : n_rows;
+            len = indptr[end] - indptr[first];
+        }
+        scan[tid] = len;
+        __syncthreads();
+        for (int off = 1; off < CONCAT_BLOCK; off <<= 1) {
+            const int64_t v = tid >= off ? scan[tid - off] : 0;
+            __syncthreads();
+            scan[tid] += v;
+            __syncthreads();
+        }
+        const int64_t before = carry + scan[tid] - len;
+        if (g < n_gaps) parts[g] = ConcatPart{indptr + first, indices, data, nullptr, first - g, before};
+        __syncthreads();
+        if (tid == CONCAT_BLOCK - 1) carry += scan[tid];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        parts[n_gaps] = ConcatPart{nullptr, nullptr, nullptr, nullptr, n_rows - n_drop, carry};
+        info[0] = carry;
+        info[1] = 0;
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(CONCAT_BLOCK) csr_select_kernel(const ConcatPart *__restrict__ parts, int n_parts,
+                                                                  int64_t *__restrict__ out_indptr,
+                                                                  int32_t *__restrict__ out_indices,
+                                                                  T *__restrict__ out_data,
+                                                                  const uint32_t *__restrict__ src_props,
+                                                                  uint32_t *__restrict__ out_props) {
+    const int64_t tid = (int64_t)blockIdx.x * CONCAT_BLOCK + threadIdx.x;
+    const int64_t step = (int64_t)gridDim.x * CONCAT_BLOCK;
+    copy_parts<T>(parts, n_parts, out_indptr, out_indices, out_data, tid, step);
+    // the vectoriser's words of the source hold for any subset of its rows as UPPER bounds: violations (0 stays 0), the
+    // largest squared norm and the longest row may have belonged to a dropped row
+    if (out_props != nullptr && tid == 0) {
+        out_props[0] = src_props[0];
+        out_props[1] = src_props[1];
+        out_props[2] = src_props[2];
         out_props[3] = 0;
     }
 }
@@ -206,5 +302,80 @@ extern "C" int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_
         return e == hipErrorOutOfMemory ? SG_ERR_OOM : SG_ERR_HIP;
     }
     *out = m.release();
+    return SG_OK;
+}
+
+namespace {
+
+template <typename T>
+int select_rows(sg_ctx *ctx, const sg_csr *m, const ConcatPart *d_desc, int64_t n_gaps, int64_t n_rows, int64_t nnz,
+                sg_csr *r) {
+    int64_t *dp = nullptr;
+    int32_t *di = nullptr;
+    T *dd = nullptr;
+    SG_TRY(sg_alloc(ctx, (size_t)n_rows + 1, &dp));
+    r->d_indptr = dp;
+    SG_TRY(sg_alloc(ctx, (size_t)nnz + 4, &di));
+    r->d_indices = di;
+    SG_TRY(sg_alloc(ctx, (size_t)nnz + 4, &dd));
+    r->d_data = dd;
+    if (m->from_vectoriser && m->d_props_words) SG_TRY(sg_alloc(ctx, (size_t)4, &r->d_props_words));
+    const int64_t work = std::max<int64_t>(std::max<int64_t>((nnz + CONCAT_UNIT - 1) / CONCAT_UNIT, n_rows), 1);
+    const int64_t want = (work + CONCAT_BLOCK - 1) / CONCAT_BLOCK;
+    const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)ctx->num_cu * 32);
+    hipLaunchKernelGGL(csr_select_kernel<T>, dim3(grid), dim3(CONCAT_BLOCK), 0, ctx->stream, d_desc, (int)n_gaps, dp, di, dd,
+                       (const uint32_t *)m->d_props_words, r->d_props_words);
+    SG_HIP_TRY(hipGetLastError());
+    return SG_OK;
+}
+
+}   // namespace
+
+extern "C" int sg_csr_select_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d_drop_sorted, int64_t n_drop, sg_csr **out) {
+    SG_REQUIRE(ctx && m && out, "null argument");
+    SG_REQUIRE(n_drop >= 0 && n_drop <= m->n_rows, "more rows to drop than the matrix has");
+    SG_REQUIRE(n_drop == 0 || d_drop_sorted != nullptr, "the drop list is null");
+    if (m->rows_of) SG_TRY(sg_csr_ensure_rows(ctx, m));
+    const int64_t n_gaps = n_drop + 1;
+    std::unique_ptr<sg_csr, CsrDeleter> r(new (std::nothrow) sg_csr());
+    if (!r) return SG_ERR_OOM;
+    r->ctx = ctx;
+    r->n_rows = m->n_rows - n_drop;
+    r->n_cols = m->n_cols;
+    r->dtype = m->dtype;
+    r->owned = true;
+    r->from_vectoriser = m->from_vectoriser;
+    // the gaps' descriptors and the totals; the totals are the one thing that comes back: they size the result
+    ConcatPart *d_desc = nullptr;
+    int64_t *d_info = nullptr;
+    SG_TRY(sg_alloc(ctx, (size_t)n_gaps + 1, &d_desc));
+    int st = sg_alloc(ctx, (size_t)2, &d_info);
+    int64_t info[2] = {0, 0};
+    if (st == SG_OK) {
+        hipLaunchKernelGGL(csr_select_gaps_kernel, dim3(1), dim3(CONCAT_BLOCK), 0, ctx->stream, m->d_indptr, m->d_indices,
+                           m->d_data, m->n_rows, d_drop_sorted, n_drop, d_desc, d_info);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_fetch, d_info, sizeof(info), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            sg_set_error("sg_csr_select_rows: %s", hipGetErrorString(e));
+            st = SG_ERR_HIP;
+        } else {
+            memcpy(info, ctx->h_fetch, sizeof(info));
+        }
+    }
+    if (st == SG_OK && info[1] != 0) {
+        sg_set_error("bad argument: the rows to drop must be ascending, distinct and inside the matrix");
+        st = SG_ERR_BADARG;
+    }
+    if (st == SG_OK) {
+        r->nnz = info[0];
+        st = m->dtype == SG_F64 ? select_rows<double>(ctx, m, d_desc, n_gaps, r->n_rows, r->nnz, r.get())
+                                : select_rows<float>(ctx, m, d_desc, n_gaps, r->n_rows, r->nnz, r.get());
+    }
+    ctx->release(d_info);
+    ctx->release(d_desc);          // (stream-ordered pool: a later taker of the block runs behind the kernel)
+    if (st != SG_OK) return st;
+    *out = r.release();
     return SG_OK;
 }

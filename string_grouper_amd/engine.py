@@ -86,11 +86,19 @@ class CorpusState:
     and its own TF-IDF rows in one or two segments -- ``base``, and ``delta`` for the rows appended since the last
     compaction -- each with its own inverted index from the first call that needs it.  ``whole`` is
     the concatenation of the two for the calls that need every row in one matrix (made on first need after an append, kept
-    until the next).  ``stats`` counts the work, so that tests can prove the reuse."""
+    until the next).  ``stats`` counts the work, so that tests can prove the reuse.
 
-    def __init__(self, vec: HipTfidfVectorizer, column, base: Optional["N.Csr"] = None):
+    Removed rows stay in their segment until the next compaction: ``dead`` is the sorted list of their PHYSICAL numbers
+    (counting through base, then delta), ``dead_dev`` its copy on the device.  A live row's physical number is its own plus
+    the dead rows up to it (``physical_rows``); the calls against the indexes filter the dead columns out
+    (HipEngine._corpus_topn), every call that reads the rows as one matrix compacts first (``rows``)."""
+
+    def __init__(self, vec: HipTfidfVectorizer, column, base: Optional["N.Csr"] = None, engine: Optional["HipEngine"] = None):
         self.vec = vec
         self.column = column
+        self.engine = engine
+        self.dead = np.zeros(0, np.int64)
+        self.dead_dev: Optional["N.DeviceInts"] = None
         self.base: Optional[CorpusSegment] = None
         self.delta: Optional[CorpusSegment] = None
         self.whole: Optional["N.Csr"] = None
@@ -99,7 +107,7 @@ class CorpusState:
         self.placeholder: Optional[int] = None
         self.stats = {"tokenisations": 1, "index_builds": 0, "transforms": 0, "resident_index": 0, "forward": 0,
                       "reverse": 0, "reverse_fallbacks": 0, "appends": 0, "rows_appended": 0, "compactions": 0,
-                      "segments": 1, "base_index_builds": 0}
+                      "segments": 1, "base_index_builds": 0, "removals": 0, "rows_removed": 0, "dead_rows": 0}
         if base is not None:
             self.set_segments(CorpusSegment(base), None)
 
@@ -118,8 +126,40 @@ class CorpusState:
         """The base segment's index (the whole corpus's as long as nothing has been appended since the last compaction)."""
         return self.base.index if self.base is not None else None
 
+    def set_dead(self, dead: np.ndarray) -> None:
+        """The dead physical rows are now ``dead`` (sorted, distinct): uploaded, the old device copy freed."""
+        if self.dead_dev is not None:
+            self.dead_dev.free()
+        self.dead = dead
+        self.dead_dev = self.base.csr.ctx.upload_sorted_ints(dead) if len(dead) else None
+        self.stats["dead_rows"] = len(dead)
+        self.matrix = CorpusMatrix(self)
+
+    def physical_rows(self, live: np.ndarray) -> np.ndarray:
+        """Where the live rows ``live`` lie in the segments: dead row i has dead[i] - i live rows before it."""
+        return live + np.searchsorted(self.dead - np.arange(len(self.dead)), live, side="right")
+
+    def dead_nnz(self) -> int:
+        """Entries of the dead rows, read from the segments' row pointers (one small read-back per dead row, CORPUS_MAX_DEAD
+        of them at the most: only when somebody asks for ``nnz`` while rows are dead)."""
+        total, first = 0, 0
+        for seg in self.segments:
+            for d in self.dead[(self.dead >= first) & (self.dead < first + seg.n_rows)]:
+                view = seg.csr.row_block(int(d) - first, int(d) - first + 1)
+                total += view.dims()[2]
+                view.free()
+            first += seg.n_rows
+        return total
+
     def rows(self) -> "N.Csr":
-        """Every row in one matrix: the base segment itself, or the cached concatenation (sg_csr_concat)."""
+        """Every LIVE row in one matrix: the base segment itself, or the cached concatenation (sg_csr_concat); with dead rows
+        pending, the new base segment of a compaction."""
+        if len(self.dead):
+            self.engine.corpus_compact(self)
+        return self.physical()
+
+    def physical(self) -> "N.Csr":
+        """Every row of the segments, dead ones included, in one matrix."""
         if self.delta is None:
             return self.base.csr
         if self.whole is None:
@@ -134,16 +174,30 @@ class CorpusState:
 
 class CorpusMatrix(DeviceMatrix):
     """The TF-IDF rows of a resident corpus: the multiply uses the corpus's indexes instead of building one.  ``shape``,
-    ``nnz`` and ``dtype`` come from the segments; ``csr`` (every row in one matrix) is only made when something reads it."""
+    ``nnz`` and ``dtype`` come from the segments and count the LIVE rows only; ``csr`` (every live row in one matrix) is
+    only made when something reads it -- which compacts a corpus that has removed rows pending."""
 
     def __init__(self, corpus: CorpusState):
         self.corpus = corpus
         segs = corpus.segments
         _, n_cols, _, d = segs[0].csr.dims()
-        self.shape = (sum(s.n_rows for s in segs), n_cols)
-        self.nnz = sum(s.nnz for s in segs)
+        self.n_dead = len(corpus.dead)
+        self.shape = (sum(s.n_rows for s in segs) - self.n_dead, n_cols)
+        self._nnz_physical = sum(s.nnz for s in segs)
+        self._nnz: Optional[int] = None if self.n_dead else self._nnz_physical
         self.dtype = N.code_np_dtype(d)
         self._host = None
+
+    @property
+    def nnz(self) -> int:
+        if self._nnz is None:                  # (dead rows: their entries are read back when first asked for)
+            if self.corpus.matrix is self:
+                self._nnz = self._nnz_physical - self.corpus.dead_nnz()
+            elif self.corpus.matrix is None:
+                raise ValueError("the corpus is closed")
+            else:                              # the corpus has moved on (compacted): its live rows are these rows
+                return self.corpus.matrix.nnz
+        return self._nnz
 
     @property
     def csr(self) -> "N.Csr":
@@ -169,6 +223,18 @@ class HipEngine:
     # of the base -- while a compaction costs 1-1.4 ms at 663 k and 5-30 ms at 5 M, under 0.001 ms per appended row at any
     # share: the cheapest of the measured shares (1/64, 1/16, 1/8, 1/4) is the smallest at both sizes
     CORPUS_COMPACT_SHARE = 1 / 64
+    # removed rows stay in their segment, and every multiply against the indexes is asked for top_n + dead rows, until there
+    # are more than this many; then a compaction drops them (corpus_compact).  Measured (scripts/corpus_remove_latency.py,
+    # profiles/corpus_remove_latency.log; caps 8, 32, 64, 128, two rounds each): the step of a living list (remove one row,
+    # append one, match one name) does not separate the caps -- 663 k names: 20.0, 20.1 / 18.0, 21.4 / 21.7, 21.4 / 18.3, 21.4 ms;
+    # 5 M: 143, 133 / 126, 138 / 122, 131 / 129, 133 ms (64 the cheapest of both rounds there, by 3-5 %, where one cap moves by
+    # 10 % between rounds): 11-15 and 90-110 ms of a step are the host's copy of the Series, which no cap touches, the rest
+    # is 6.1-6.7 and 29.4-32.9 ms at every cap (a compaction is 0.2 / 0.7 ms, the index rebuild behind it 1.2 / 5.5 ms).  What
+    # does separate them is the 1 000-name batch against the index, asked for 20 + dead entries a row: 2.1 ms at 0, 8, 32
+    # and 64 dead rows and 9.3 at 128 (663 k); 9.6-10.5 ms at 0, 8 and 32, 42.6 at 64 and 89.9 at 128 (5 M).  32 is the largest
+    # measured cap that costs no query anything at either size -- the default max_n_matches of 20 plus 32 stays inside the
+    # one register list of 64 (plan_multiply) -- and a step gains nothing measurable beyond it
+    CORPUS_MAX_DEAD = 32
 
     def __init__(self, ctx: Optional[N.Context] = None):
         self._ctx = ctx
@@ -223,7 +289,7 @@ class HipEngine:
                                  normalize_to_ascii=normalize_to_ascii, dtype=dtype, ctx=self.ctx)
         col = vec.prepare(strings)
         vec.fit_prepared([col])
-        return CorpusState(vec, col, vec.transform_prepared(col))
+        return CorpusState(vec, col, vec.transform_prepared(col), engine=self)
 
     def corpus_transform(self, state: CorpusState, strings) -> DeviceMatrix:
         """The rows of ``strings`` under the corpus's vocabulary and idf: n-grams the corpus never had are dropped."""
@@ -286,14 +352,40 @@ class HipEngine:
         if delta.n_rows > self.CORPUS_COMPACT_SHARE * state.base.n_rows:
             self.corpus_compact(state)
 
-    def corpus_compact(self, state: CorpusState) -> None:
-        """Fold the delta segment into the base: one matrix, one index (built on first need), and with them the self-join
-        form of the multiply for a self-join of the corpus.  Nothing to do without a delta."""
-        if state.delta is None:
+    def corpus_remove(self, state: CorpusState, positions) -> None:
+        """The rows ``positions`` (sorted, distinct, numbered as the corpus's live rows are now) leave the corpus.  Nothing on
+        the device is touched but the list of dead rows: they stay in their segment and its index, the multiplies against
+        the indexes ask for as many entries more and drop them (_corpus_topn), and a compaction (corpus_compact: explicit, by
+        an append's share rule, by a call that needs the rows in one matrix, or here once more than CORPUS_MAX_DEAD are
+        pending) takes them out."""
+        positions = np.asarray(positions, dtype=np.int64)
+        if len(positions) == 0:
             return
-        whole = state.rows()
+        n_live = state.matrix.shape[0]
+        if positions[0] < 0 or positions[-1] >= n_live or np.any(positions[1:] <= positions[:-1]):
+            raise IndexError(f"positions must be ascending, distinct and inside [0, {n_live})")
+        if len(positions) == n_live:
+            raise ValueError("every row of the corpus would be removed: build a new corpus instead")
+        state.set_dead(np.union1d(state.dead, state.physical_rows(positions)))
+        state.stats["removals"] += 1
+        state.stats["rows_removed"] += len(positions)
+        if len(state.dead) > self.CORPUS_MAX_DEAD:
+            self.corpus_compact(state)
+
+    def corpus_compact(self, state: CorpusState) -> None:
+        """Fold the delta segment into the base and drop the dead rows: one matrix of the live rows (sg_csr_concat, then
+        sg_csr_select_rows), one index (built on first need), and with them the self-join form of the multiply for a self-join
+        of the corpus.  Nothing to do without a delta and without dead rows."""
+        if state.delta is None and not len(state.dead):
+            return
+        whole = state.physical()
+        if len(state.dead):
+            live = self.ctx.csr_select_rows(whole, state.dead_dev)
+            state.drop_whole()
+            whole = live
         state.whole = None                    # (handed to the new base segment)
         old = state.segments
+        state.set_dead(np.zeros(0, np.int64))
         state.set_segments(CorpusSegment(whole), None)
         for seg in old:
             seg.free()
@@ -328,6 +420,9 @@ class HipEngine:
 
     def corpus_free(self, state: CorpusState) -> None:
         state.drop_whole()
+        if state.dead_dev is not None:
+            state.dead_dev.free()
+        state.dead_dev, state.dead = None, np.zeros(0, np.int64)
         for seg in state.segments if state.base is not None else []:
             seg.free()
         handles = [state.vec._vocab]
@@ -349,12 +444,20 @@ class HipEngine:
         A the corpus, B new rows: the forward path (the corpus rows against an index of the new rows: the generic path) or
         the reverse path (the new rows against the corpus index, turned round by sg_topn_transpose_select)."""
         if isinstance(B, CorpusMatrix):
-            segs = self.corpus_indexes(B.corpus)
+            state = B.corpus
+            if isinstance(A, CorpusMatrix) and len(state.dead):
+                self.corpus_compact(state)    # a self-join reads the rows as one matrix: no dead rows in it
+            segs = self.corpus_indexes(state)
             if segs is None:
                 return None
-            B.corpus.stats["resident_index"] += 1
-            parts = [self.ctx.spgemm_topn(A.csr, idx, top_n, threshold, True) for idx, _, _ in segs]
-            return self._zip_segments(parts, segs, top_n)
+            state.stats["resident_index"] += 1
+            # dead rows are still in the indexes: at most that many of a row's first top_n + dead entries are dead, so the
+            # first top_n live ones of the longer list are the top_n over the live rows (DESIGN.md section 9)
+            n_dead = len(state.dead)
+            ask = top_n + n_dead
+            parts = [self.ctx.spgemm_topn(A.csr, idx, ask, threshold, True) for idx, _, _ in segs]
+            res = self._zip_segments(parts, segs, ask)
+            return self._drop_dead(state, res, top_n) if n_dead else res
         state = A.corpus
         mode = self._corpus_reverse_mode()
         if mode is None:
@@ -377,6 +480,13 @@ class HipEngine:
         for p in parts:
             p.free()
         return res
+
+    def _drop_dead(self, state: CorpusState, res: "N.TopN", top_n: int) -> "N.TopN":
+        """``res`` over the segments' physical rows as the result over the live rows: dead columns out, the others
+        renumbered, rows cut at top_n (sg_topn_drop_columns).  ``res`` is freed."""
+        live = self.ctx.topn_drop_columns(res, state.dead_dev, top_n)
+        res.free()
+        return live
 
     def _corpus_reverse(self, state: CorpusState, A: DeviceMatrix, B: DeviceMatrix, top_n: int,
                         threshold: float) -> Optional["N.TopN"]:
@@ -407,6 +517,8 @@ class HipEngine:
             parts.append(pairs)
             slots += stride
         pairs = self._zip_segments(parts, segs, slots)      # asked for the sum of the strides: nothing is cut
+        if len(state.dead):                   # (a dead row counted towards a full row and the budget like any other)
+            pairs = self._drop_dead(state, pairs, pairs.dims()[1])
         res = self.ctx.topn_transpose_select(pairs, n_corpus, top_n)
         pairs.free()
         return res
