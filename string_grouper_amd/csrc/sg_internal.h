@@ -349,8 +349,8 @@ int sg_matchlist_device_view(const sg_matchlist *ml, int64_t *n_rows, int64_t *n
 // sg_spgemm_pruned.hip
 int sg_csr_props(sg_ctx *ctx, const sg_csr *m, bool *cosine_like, float *max_norm2, uint32_t *max_nnz = nullptr);
 bool sg_pruned_supports_tile(int32_t tile_log2);
-int sg_postings_ensure_full(sg_ctx *ctx, const sg_postings *p);
-bool sg_q8_applies(const sg_ctx *ctx, const sg_postings *Bt, double threshold);   // sg_spgemm_pruned.hip: second filter in this call?   // sg_postings.hip: the exact kernel's postings, on demand
+int sg_postings_ensure_full(sg_ctx *ctx, const sg_postings *p);   // sg_postings.hip: the exact kernel's postings, on demand
+bool sg_q8_applies(const sg_ctx *ctx, const sg_postings *Bt, double threshold);   // sg_spgemm_pruned.hip: second filter in this call?
 int sg_spgemm_pruned_launch(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t keep, sg_topn *r,
                             double threshold, double delta, uint32_t *row_counter,
                             uint32_t *flagged_count, uint32_t *flagged_rows, unsigned long long *stats);

@@ -1862,19 +1862,47 @@ int sg_csr_props(sg_ctx *ctx, const sg_csr *m, bool *cosine_like, float *max_nor
 }
 
 // ------------------------------------------------------------------------------------------------
+// Host driver.  Two helpers of this file alone: scratch that goes back to the pool by itself, and the dtype dispatch.
+struct Scratch {   // blocks of the context's pool, released -- in the order they were taken -- when the scope ends
+    sg_ctx *ctx;
+    std::vector<void *> blocks;
+    explicit Scratch(sg_ctx *c) : ctx(c) {}
+    Scratch(const Scratch &) = delete;
+    ~Scratch() {
+        for (void *p : blocks) ctx->release(p);
+    }
+    int alloc_bytes(size_t bytes, void **out) {
+        const int st = ctx->alloc(bytes, out);
+        if (st == SG_OK) blocks.push_back(*out);
+        return st;
+    }
+    template <typename T>
+    int alloc(size_t count, T **out) {
+        void *p = nullptr;
+        const int st = alloc_bytes(count * sizeof(T), &p);
+        *out = (T *)p;
+        return st;
+    }
+    template <typename T>
+    T *keep(T *p) {   // the block outlives the scope: it is the caller's now
+        for (void *&b : blocks)
+            if (b == p) b = nullptr;
+        return p;
+    }
+    void release(void *p) { ctx->release(keep(p)); }   // ... or goes back early (stream-ordered, like every release)
+};
+
+template <typename F>
+static int by_dtype(int32_t dtype, F &&f) {   // f(double{}) or f(float{}): every launch below is written once
+    return dtype == SG_F64 ? f(double{}) : f(float{});
+}
+
 struct PairList {   // symmetric mode: the mirrored pairs (i, j < i) above the threshold, in chunks of SG_PAIR_CHUNK entries
-    uint32_t *d_i = nullptr;
-    uint32_t *d_j = nullptr;
-    void *d_s = nullptr;
-    uint32_t *d_row_count = nullptr;           // mirrored matches per row (counted by pass 1)
-    uint32_t *d_chunk_count = nullptr;         // entries used of every chunk
-    uint32_t *d_chunks_used = nullptr;         // chunks handed out
-    unsigned long long *d_totals = nullptr;    // pairs
-    uint32_t chunks = 0;
+    SgPairSink sink;                           // the lists and their counters (sg_internal.h): what the exact kernel's launch is handed
+    const SgPairSink *d_sink = nullptr;        // the same struct in device memory: what the pruned kernel is handed
     uint32_t row_lo = 0, row_hi = 0;           // the left rows to score (the whole matrix on one GPU):
     uint32_t row_step = 1;                     // row_hi - 1, row_hi - 1 - row_step, ... >= row_lo
     uint32_t rows() const { return (row_hi - row_lo + row_step - 1u) / row_step; }
-    const SgPairSink *d_sink = nullptr;        // the same pointers as a struct in device memory: what the kernel is handed
 };
 
 __global__ void pair_sink_kernel(SgPairSink v, SgPairSink *out) { *out = v; }
@@ -1906,11 +1934,45 @@ static unsigned pruned_grid(const sg_ctx *ctx, int32_t tile_log2, int64_t n_rows
     return grid;
 }
 
+struct PrunedJob {   // one multiply: what all its launches share
+    sg_ctx *ctx;
+    const sg_csr *A;
+    const sg_postings *Bt;
+    int32_t keep;
+    sg_topn *r;
+    double threshold;
+    float s_budget;
+    unsigned long long *stats = nullptr;                            // [0..2] rows / postings / survivors, [4] pairs scored exactly
+    uint32_t *row_counter = nullptr;                                // the first launch's (zeroed by the caller)
+    uint32_t *flagged_count = nullptr, *flagged_rows = nullptr;     // the rows no launch could take: for the exact kernel
+    const PairList *pl = nullptr;                                   // self-join form: the pair list and the rows to score
+};
+
+struct PrunedLaunch {   // ... and what varies from launch to launch
+    uint32_t *row_counter;
+    uint32_t *out_count, *out_rows;                            // the rows this launch passes on
+    const uint32_t *in_rows = nullptr, *in_len = nullptr;      // the rows it works on (null: every row of the range)
+    uint32_t *heavy_count = nullptr, *heavy_rows = nullptr;    // where it sets rows aside for the parts (null: nowhere)
+    uint32_t part_cfg = 0;                                     // heavy_part_cfg's bar; bit 31: this launch works the parts off
+};
+
+// A list of rows that one launch writes and the next one works off: [0] its length, [1] the row counter of the launch that
+// reads it, [4 ..) the rows.  (The heavy rows' list has their first visit for the parts behind the rows: [4 + n, 4 + 2 n).)
+struct RowList {
+    uint32_t *base = nullptr;
+    uint32_t *count() const { return base; }
+    uint32_t *counter() const { return base ? base + 1 : nullptr; }
+    uint32_t *rows() const { return base ? base + 4 : nullptr; }
+};
+
 template <typename T, int TILE_LOG2, bool SYM, bool WIDE, int FOLD_LOG2>
-static int launch_pruned(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t keep, sg_topn *r, T thr,
-                         float s_budget, uint32_t *row_counter, uint32_t *flagged_count, uint32_t *flagged_rows,
-                         unsigned long long *stats, const PairList &pl, const uint32_t *row_list, const uint32_t *row_list_len,
-                         uint32_t *heavy_count = nullptr, uint32_t *heavy_rows = nullptr, uint32_t part_cfg = 0) {
+static int launch_pruned(const PrunedJob &job, const PrunedLaunch &l) {
+    sg_ctx *ctx = job.ctx;
+    const sg_csr *A = job.A;
+    const sg_postings *Bt = job.Bt;
+    const sg_topn *r = job.r;
+    const PairList &pl = *job.pl;
+    const T thr = (T)job.threshold;
     const size_t lds = pruned_lds(TILE_LOG2, FOLD_LOG2, A->dtype);
     unsigned grid = pruned_grid(ctx, TILE_LOG2, SYM ? (int64_t)pl.rows() : A->n_rows, FOLD_LOG2, A->dtype);
     // the wide launch: few rows, if any, in a list of names (idle waves leave at once) -- unless the rows are long on average
@@ -1919,118 +1981,120 @@ static int launch_pruned(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, in
     if (WIDE && grid > (unsigned)ctx->num_cu * 4u && (double)A->nnz <= 48.0 * (double)A->n_rows) grid = (unsigned)ctx->num_cu * 4u;
     // (SHARE: see the kernel; only the forms that can run in parts have the second instantiation)
     constexpr bool SPLITS = SYM && !WIDE && FOLD_LOG2 > 0;
-    const bool share = SPLITS && (heavy_count != nullptr || part_cfg != 0u);
+    const bool share = SPLITS && (l.heavy_count != nullptr || l.part_cfg != 0u);
     auto kernel = share ? spgemm_topn_pruned_kernel<T, TILE_LOG2, SYM, WIDE, FOLD_LOG2, SPLITS>
                         : spgemm_topn_pruned_kernel<T, TILE_LOG2, SYM, WIDE, FOLD_LOG2, false>;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, ctx->stream, A->d_indptr,
                        A->d_indices, (const T *)A->d_data, (uint32_t)A->n_rows, (const uint32_t *)Bt->d_seg,
                        (const uint32_t *)Bt->d_ends, Bt->nt_pad, (uint32_t)Bt->n_terms,
                        (const uint32_t *)Bt->d_filt, Bt->n_tiles,
-                       (const SgScoreCtx *)Bt->d_score_ctx + (sg_q8_applies(ctx, Bt, (double)thr) ? 0 : 1), keep, r->stride, thr, s_budget,
-                       Bt->norm_up, Bt->freq_min, r->d_cols,
+                       (const SgScoreCtx *)Bt->d_score_ctx + (sg_q8_applies(ctx, Bt, (double)thr) ? 0 : 1), job.keep, r->stride, thr,
+                       job.s_budget, Bt->norm_up, Bt->freq_min, r->d_cols,
                        (T *)r->d_vals,
-                       r->d_counts, row_counter, flagged_count, flagged_rows, stats, pl.d_sink, pl.chunks, pl.row_lo, pl.row_hi, row_list,
-                       row_list_len, (const uint32_t *)Bt->d_ends8, Bt->nv_pad, (uint32_t)(Bt->nnz * 4), (uint32_t)Bt->n_right,
-                       heavy_count, heavy_rows, pl.row_step, part_cfg);
+                       r->d_counts, l.row_counter, l.out_count, l.out_rows, job.stats, pl.d_sink, pl.sink.chunks, pl.row_lo, pl.row_hi,
+                       l.in_rows, l.in_len, (const uint32_t *)Bt->d_ends8, Bt->nv_pad, (uint32_t)(Bt->nnz * 4), (uint32_t)Bt->n_right,
+                       l.heavy_count, l.heavy_rows, pl.row_step, l.part_cfg);
     SG_HIP_TRY(hipGetLastError());
     return SG_OK;
 }
 
-// Both launches of one multiply: every row through the 64-term kernel; the rows it passes on (65 .. 128 non-zeros)
+// Stream + self-join form: rows that need many rounds -- a chain of dependent loads in one wave, milliseconds for the
+// slowest -- are set aside by the first launch and worked off in SG_ROW_PARTS parts each by a launch of their own
+// (see the kernel).  The whole-matrix pass hides such rows behind the others; a rank's RANGE of the multi-GPU form
+// ends with its slowest row (scripts/range_probe.py, scripts/sim_scaling.py).  SG_HEAVY_ROUNDS: rounds from which a
+// row is set aside (0: never).
+// Returns the first launch's part_cfg: the bar in rounds, the hand-over shift in bits [28, 31); 0: no parts.
+static uint32_t heavy_part_cfg(const sg_ctx *ctx, const sg_csr *A, const PairList &range, int32_t tile_log2, int32_t fold_log2) {
+    uint32_t heavy_rounds = 0;
+    // (the whole matrix in one pass: 6.0 ms without, 6.35 with the second launch at 663 k -- it has a ramp and a tail of
+    //  its own; a range of an eighth: 3.2 -> 2.25 ms, profiles/r03_sessionS_*)
+    // ... and a launch over at least half the rows still hides them better than parts do: a half share of the 663 k job
+    // takes 3.6 ms without parts (the longest row: 3.4), 4.06 with; a quarter 3.2 without, 2.8 with
+    // (profiles/r03_sessionAU_shares_without_parts.log)
+    if ((range.row_lo > 0 || (int64_t)range.row_hi < A->n_rows || range.row_step > 1) && 2 * (int64_t)range.rows() < A->n_rows) {
+        // A row is worth parts when it is a noticeable share of what ONE wave of the range does.  Rounds per wave,
+        // estimated: rows per wave x rounds per row at the range's position (a row's stream grows with its position
+        // and with the lists, i.e. with n: 40 rounds per row on average at 553 k index rows, 290 at 3.9 M --
+        // 7.2e-5 n).  A fixed bar of 256 rounds sent nearly every row of the 5 M job through parts: eight ranges took
+        // 278 ms in all against 204 ms for the whole (profiles/r03_sessionV_sim_scaling_5M.log).
+        const double n_idx = (double)A->n_rows;
+        const double rows_per_wave = (double)range.rows() / (double)pruned_grid(ctx, tile_log2, (int64_t)range.rows(), fold_log2, A->dtype);
+        const double rounds_per_row = 2.0 * 7.2e-5 * n_idx * (0.5 * ((double)range.row_lo + (double)range.row_hi) / n_idx);
+        // (a twentieth: the tail a row of `bar` rounds can leave is then ~5 % of the launch's time.  A quarter was
+        //  tried twice -- for contiguous ranges and for interleaved shares: shares of the 5 M job then ended 10-15 ms
+        //  after the others, on single rows.  Also tried and dropped, profiles/r03_sessionAR_parts_first.log: a classify
+        //  launch that lists such rows BEFORE the multiply, whose launch then starts with their parts -- 4.5 instead
+        //  of 4.15 ms for a half share at 663 k, 1.94 instead of 1.78 for an eighth)
+        const double share = ctx->opt_double("SG_HEAVY_SHARE", 0.0);
+        const double bar_share = share > 0.0 ? share : 0.05;
+        const double bar = bar_share * rows_per_wave * rounds_per_row;
+        // (never below 128 rounds: at 663 k, eight ranges, bars of 64 / 128 / 256 / 512 rounds give 2.10 / 2.03 / 2.19 /
+        //  2.57 ms for the slowest range -- profiles/r03_sessionAG_heavy_bar_ranges.log)
+        heavy_rounds = bar < 128.0 ? 128u : (bar > 1.0e9 ? 1000000000u : (uint32_t)bar);
+    }
+    heavy_rounds = (uint32_t)ctx->opt_int("SG_HEAVY_ROUNDS", (int)heavy_rounds) & 0x7fffffffu;
+    if (heavy_rounds > 0x0fffffffu) heavy_rounds = 0x0fffffffu;
+    // candidates per round of the bar from which a row hands its remaining visits to the parts (2^shift): about a
+    // thousand candidates at the floor of the bar (128 rounds: the 663 k job), two per round of a large bar -- with the
+    // second filter a candidate costs a fifth of what it did, and what keeps a wave late is a HUB's candidates, which
+    // pass it and are scored exactly (5 M names, 8 shares, scripts/share_knob_sweep.sh: slowest share 23.2 -> 21.4 ms
+    // with 2 instead of 8 per round; the 663 k shares lose 0.1 of 1.5 ms that way).  SG_HANDOVER_SHIFT overrides.
+    uint32_t handover_shift = heavy_rounds >= 512u ? 1u : (heavy_rounds >= 256u ? 2u : 3u);
+    handover_shift = (uint32_t)ctx->opt_int("SG_HANDOVER_SHIFT", (int)handover_shift) & 7u;
+    if (heavy_rounds) heavy_rounds |= handover_shift << 28;
+    return heavy_rounds;
+}
+
+// The launches of one multiply: every row through the 64-term kernel; the rows it passes on (65 .. 128 non-zeros)
 // through the wide one; what THAT passes on (more than 128 non-zeros, more than 64 prefix terms, delta too small for
 // the fixed point) lands in (flagged_count, flagged_rows) for the exact kernel.
 template <typename T, int TILE_LOG2, bool SYM, int FOLD_LOG2>
-static int launch_both(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t keep, sg_topn *r, T thr,
-                       float s_budget, uint32_t *row_counter, uint32_t *flagged_count, uint32_t *flagged_rows,
-                       unsigned long long *stats, const PairList &pl) {
-    uint32_t *l1 = nullptr;
-    SG_TRY(sg_alloc(ctx, (size_t)A->n_rows + 8, &l1));
-    int st = hipMemsetAsync(l1, 0, 4 * sizeof(uint32_t), ctx->stream) == hipSuccess ? SG_OK : SG_ERR_HIP;
-    // Stream + self-join form: rows that need many rounds -- a chain of dependent loads in one wave, milliseconds for the
-    // slowest -- are set aside by the first launch and worked off in SG_ROW_PARTS parts each by a launch of their own
-    // (see the kernel).  The whole-matrix pass hides such rows behind the others; a rank's RANGE of the multi-GPU form
-    // ends with its slowest row (scripts/range_probe.py, scripts/sim_scaling.py).  SG_HEAVY_ROUNDS: rounds from which a
-    // row is set aside (0: never).
-    uint32_t *heavy = nullptr;   // [0] count [1] the parts' row counter [4 ..) rows
-    uint32_t heavy_rounds = 0;
-    if (SYM && FOLD_LOG2 > 0 && st == SG_OK) {
-        // (the whole matrix in one pass: 6.0 ms without, 6.35 with the second launch at 663 k -- it has a ramp and a tail of
-        //  its own; a range of an eighth: 3.2 -> 2.25 ms, profiles/r03_sessionS_*)
-        // ... and a launch over at least half the rows still hides them better than parts do: a half share of the 663 k job
-        // takes 3.6 ms without parts (the longest row: 3.4), 4.06 with; a quarter 3.2 without, 2.8 with
-        // (profiles/r03_sessionAU_shares_without_parts.log)
-        if ((pl.row_lo > 0 || (int64_t)pl.row_hi < A->n_rows || pl.row_step > 1) && 2 * (int64_t)pl.rows() < A->n_rows) {
-            // A row is worth parts when it is a noticeable share of what ONE wave of the range does.  Rounds per wave,
-            // estimated: rows per wave x rounds per row at the range's position (a row's stream grows with its position
-            // and with the lists, i.e. with n: 40 rounds per row on average at 553 k index rows, 290 at 3.9 M --
-            // 7.2e-5 n).  A fixed bar of 256 rounds sent nearly every row of the 5 M job through parts: eight ranges took
-            // 278 ms in all against 204 ms for the whole (profiles/r03_sessionV_sim_scaling_5M.log).
-            const double n_idx = (double)A->n_rows;
-            const double rows_per_wave = (double)pl.rows() / (double)pruned_grid(ctx, TILE_LOG2, (int64_t)pl.rows(), FOLD_LOG2, A->dtype);
-            const double rounds_per_row = 2.0 * 7.2e-5 * n_idx * (0.5 * ((double)pl.row_lo + (double)pl.row_hi) / n_idx);
-            // (a twentieth: the tail a row of `bar` rounds can leave is then ~5 % of the launch's time.  A quarter was
-            //  tried twice -- for contiguous ranges and for interleaved shares: shares of the 5 M job then ended 10-15 ms
-            //  after the others, on single rows.  Also tried and dropped, profiles/r03_sessionAR_parts_first.log: a classify
-            //  launch that lists such rows BEFORE the multiply, whose launch then starts with their parts -- 4.5 instead
-            //  of 4.15 ms for a half share at 663 k, 1.94 instead of 1.78 for an eighth)
-            const double share = ctx->opt_double("SG_HEAVY_SHARE", 0.0);
-            const double bar_share = share > 0.0 ? share : 0.05;
-            const double bar = bar_share * rows_per_wave * rounds_per_row;
-            // (never below 128 rounds: at 663 k, eight ranges, bars of 64 / 128 / 256 / 512 rounds give 2.10 / 2.03 / 2.19 /
-            //  2.57 ms for the slowest range -- profiles/r03_sessionAG_heavy_bar_ranges.log)
-            heavy_rounds = bar < 128.0 ? 128u : (bar > 1.0e9 ? 1000000000u : (uint32_t)bar);
-        }
-        heavy_rounds = (uint32_t)ctx->opt_int("SG_HEAVY_ROUNDS", (int)heavy_rounds) & 0x7fffffffu;
-        if (heavy_rounds > 0x0fffffffu) heavy_rounds = 0x0fffffffu;
-        // candidates per round of the bar from which a row hands its remaining visits to the parts (2^shift): about a
-        // thousand candidates at the floor of the bar (128 rounds: the 663 k job), two per round of a large bar -- with the
-        // second filter a candidate costs a fifth of what it did, and what keeps a wave late is a HUB's candidates, which
-        // pass it and are scored exactly (5 M names, 8 shares, scripts/share_knob_sweep.sh: slowest share 23.2 -> 21.4 ms
-        // with 2 instead of 8 per round; the 663 k shares lose 0.1 of 1.5 ms that way).  SG_HANDOVER_SHIFT overrides.
-        uint32_t handover_shift = heavy_rounds >= 512u ? 1u : (heavy_rounds >= 256u ? 2u : 3u);
-        handover_shift = (uint32_t)ctx->opt_int("SG_HANDOVER_SHIFT", (int)handover_shift) & 7u;
-        if (heavy_rounds) heavy_rounds |= handover_shift << 28;
-        if (heavy_rounds) {
-            st = sg_alloc(ctx, 2 * (size_t)A->n_rows + 8, &heavy);   // [4, 4 + n): the rows, [4 + n, 4 + 2 n): their first visit for the parts
-            if (st == SG_OK && hipMemsetAsync(heavy, 0, 4 * sizeof(uint32_t), ctx->stream) != hipSuccess) st = SG_ERR_HIP;
-        }
+static int launch_both(const PrunedJob &job) {
+    sg_ctx *ctx = job.ctx;
+    const int64_t n_rows = job.A->n_rows;
+    Scratch scratch(ctx);
+    RowList l1, heavy;   // the first launch's two lists: for the wide launch, for the parts
+    SG_TRY(scratch.alloc((size_t)n_rows + 8, &l1.base));
+    if (hipMemsetAsync(l1.base, 0, 4 * sizeof(uint32_t), ctx->stream) != hipSuccess) return SG_ERR_HIP;
+    uint32_t part_cfg = 0;
+    if (SYM && FOLD_LOG2 > 0) part_cfg = heavy_part_cfg(ctx, job.A, *job.pl, TILE_LOG2, FOLD_LOG2);
+    if (part_cfg) {
+        SG_TRY(scratch.alloc(2 * (size_t)n_rows + 8, &heavy.base));
+        if (hipMemsetAsync(heavy.base, 0, 4 * sizeof(uint32_t), ctx->stream) != hipSuccess) return SG_ERR_HIP;
     }
-    if (st == SG_OK)
-        st = launch_pruned<T, TILE_LOG2, SYM, false, FOLD_LOG2>(ctx, A, Bt, keep, r, thr, s_budget, row_counter, l1, l1 + 4, stats, pl,
-                                                     nullptr, nullptr, heavy, heavy ? heavy + 4 : nullptr, heavy ? heavy_rounds : 0u);
-    if (st == SG_OK && heavy)
-        st = launch_pruned<T, TILE_LOG2, SYM, false, FOLD_LOG2>(ctx, A, Bt, keep, r, thr, s_budget, heavy + 1, l1, l1 + 4, stats, pl,
-                                                     heavy + 4, heavy, nullptr, nullptr, 0x80000000u);
-    if (heavy) ctx->release(heavy);   // stream-ordered, like l1 below
-    if (st == SG_OK && !ctx->opt_is("SG_PRUNE_WIDE", '0'))
-        st = launch_pruned<T, TILE_LOG2, SYM, true, FOLD_LOG2>(ctx, A, Bt, keep, r, thr, s_budget, l1 + 1, flagged_count, flagged_rows, stats,
-                                                    pl, l1 + 4, l1);
-    else if (st == SG_OK) {   // SG_PRUNE_WIDE=0: the first launch's list goes to the exact kernel as it is
-        if (hipMemcpyAsync(flagged_count, l1, 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(flagged_rows, l1 + 4, sizeof(uint32_t) * (size_t)A->n_rows, hipMemcpyDeviceToDevice, ctx->stream) !=
-                hipSuccess)
-            st = SG_ERR_HIP;
+    const PrunedLaunch first{job.row_counter, l1.count(), l1.rows(), nullptr, nullptr, heavy.count(), heavy.rows(), part_cfg};
+    SG_TRY((launch_pruned<T, TILE_LOG2, SYM, false, FOLD_LOG2>(job, first)));
+    if (heavy.base) {
+        const PrunedLaunch parts{heavy.counter(), l1.count(), l1.rows(), heavy.rows(), heavy.count(), nullptr, nullptr, 0x80000000u};
+        SG_TRY((launch_pruned<T, TILE_LOG2, SYM, false, FOLD_LOG2>(job, parts)));
+        scratch.release(heavy.base);   // stream-ordered: the pool hands it out again only to work queued behind these launches
     }
-    ctx->release(l1);   // stream-ordered: the pool hands it out again only to work queued behind these launches
-    return st;
+    if (!ctx->opt_is("SG_PRUNE_WIDE", '0')) {
+        const PrunedLaunch wide{l1.counter(), job.flagged_count, job.flagged_rows, l1.rows(), l1.count()};
+        return launch_pruned<T, TILE_LOG2, SYM, true, FOLD_LOG2>(job, wide);
+    }
+    // SG_PRUNE_WIDE=0: the first launch's list goes to the exact kernel as it is
+    if (hipMemcpyAsync(job.flagged_count, l1.count(), 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(job.flagged_rows, l1.rows(), sizeof(uint32_t) * (size_t)n_rows, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+        return SG_ERR_HIP;
+    return SG_OK;
 }
 
 template <typename T, bool SYM>
-static int dispatch_pruned(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t keep, sg_topn *r, T thr,
-                           float s_budget, uint32_t *row_counter, uint32_t *flagged_count, uint32_t *flagged_rows,
-                           unsigned long long *stats, const PairList &pl) {
+static int dispatch_pruned(const PrunedJob &job) {
+    const sg_postings *Bt = job.Bt;
     if (Bt->fold_log2 > 0) {   // stream form: the postings were written for it (sg_postings.hip)
         if (Bt->fold_log2 != 3 || Bt->tile_log2 != 12 || !Bt->d_ends8) {
             sg_set_error("postings folded 2^%d over tiles of 2^%d columns are not supported by the pruned multiply", Bt->fold_log2,
                          Bt->tile_log2);
             return SG_ERR_UNSUPPORTED;
         }
-        return launch_both<T, 12, SYM, 3>(ctx, A, Bt, keep, r, thr, s_budget, row_counter, flagged_count, flagged_rows, stats, pl);
+        return launch_both<T, 12, SYM, 3>(job);
     }
     switch (Bt->tile_log2) {
-        case 11: return launch_both<T, 11, SYM, 0>(ctx, A, Bt, keep, r, thr, s_budget, row_counter, flagged_count, flagged_rows, stats, pl);
-        case 12: return launch_both<T, 12, SYM, 0>(ctx, A, Bt, keep, r, thr, s_budget, row_counter, flagged_count, flagged_rows, stats, pl);
-        case 13: return launch_both<T, 13, SYM, 0>(ctx, A, Bt, keep, r, thr, s_budget, row_counter, flagged_count, flagged_rows, stats, pl);
+        case 11: return launch_both<T, 11, SYM, 0>(job);
+        case 12: return launch_both<T, 12, SYM, 0>(job);
+        case 13: return launch_both<T, 13, SYM, 0>(job);
         default:
             sg_set_error("postings tile of 2^%d columns is not supported by the pruned multiply (2^11..2^13)", Bt->tile_log2);
             return SG_ERR_UNSUPPORTED;
@@ -2050,23 +2114,138 @@ static float prune_budget(const sg_postings *Bt, double threshold, double delta)
 int sg_spgemm_pruned_launch(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t keep, sg_topn *r,
                             double threshold, double delta, uint32_t *row_counter, uint32_t *flagged_count,
                             uint32_t *flagged_rows, unsigned long long *stats) {
-    const float s_budget = prune_budget(Bt, threshold, delta);
     PairList none;
-    if (A->dtype == SG_F64)
-        return dispatch_pruned<double, false>(ctx, A, Bt, keep, r, (double)threshold, s_budget, row_counter, flagged_count,
-                                              flagged_rows, stats, none);
-    return dispatch_pruned<float, false>(ctx, A, Bt, keep, r, (float)threshold, s_budget, row_counter, flagged_count,
-                                         flagged_rows, stats, none);
+    const PrunedJob job{ctx, A, Bt, keep, r, threshold, prune_budget(Bt, threshold, delta), stats, row_counter, flagged_count, flagged_rows, &none};
+    return by_dtype(A->dtype, [&](auto tag) { return dispatch_pruned<decltype(tag), false>(job); });
 }
 
-// Self-join form: pass 1 (the pruned kernel over the pairs j <= i, then the exact kernel's self-join launch over the
-// rows the pruned kernel passed on) + the decision whether the pair list is complete (one host round trip: pair
-// count, chunks handed out) + pass 2 (lists, top-n).
-// *done == false: nothing usable was produced (too many pairs for the list) and the caller runs the one-sided
-// form; the statistics words are untouched then (the result rows are overwritten by that form).
-// exact_all: every row is handed to the exact kernel's self-join launch, from the last position down (a row's cost grows
-// with its position) -- thresholds below the pruned kernel's envelope, or products its pilot prices dearer than the exact
-// multiply: half the (row, tile) visits of the one-sided exact kernel, the same pair list and second pass.
+// ------------------------------------------------------------------------------------------------ self-join form
+// The control words of one self-join pass, a block of SJ_CHUNK_COUNT + chunks words zeroed before pass 1:
+//   [0] row counter of the pruned launches            }
+//   [1] rows handed to the exact kernel (exact_all:   }  the 24 bytes read_words brings back: h[0] = {row counter, handed
+//       rows listed so far)                           }  over}, h[1] = pairs, (uint32_t)h[2] = chunks handed out
+//   [2..3] pairs in the list (64 bits)                }
+//   [4] chunks handed out                             }
+//   [5] row counter of the exact kernel's launch      }
+//   [6] length of its list (exact_all); [7] / [8]: counter and length of exact_all's second launch, behind a pilot
+//   [64, 80) the pair list as a struct (SgPairSink): what the pruned kernel is handed
+//   [128 ..) entries per chunk
+// (the struct has a cache line of its own, 256 bytes from the counters: every access to the line of the row counter and the
+//  chunk counter queues behind their atomics -- with the struct next to them the kernel took twice its time)
+enum : size_t {
+    SJ_ROW_COUNTER = 0, SJ_HANDED_OVER = 1, SJ_PAIRS = 2, SJ_CHUNKS_USED = 4, SJ_EXACT_COUNTER = 5, SJ_EXACT_LEN = 6,
+    SJ_EXACT_COUNTER2 = 7, SJ_EXACT_LEN2 = 8, SJ_SINK = 64, SJ_CHUNK_COUNT = 128
+};
+static_assert(sizeof(SgPairSink) <= 64, "the pair list's struct must fit the sixteen words reserved for it");
+
+// One call of sg_spgemm_pruned_symmetric: the job of its pruned launches (`stats` are this pass's own statistics: they only
+// count when the pass does), its pair list and its scratch.
+struct SelfJoin : PrunedJob {
+    bool exact_all;
+    int64_t n;                                 // rows of A
+    bool whole = false;                        // every row in one pass whose result stays here: the forms that may pilot
+    bool cap_forced = false;                   // SG_SYM_PAIR_CAP set the list's size
+    PairList list;                             // (`pl` points here)
+    uint32_t *words = nullptr;                 // the control words above
+    uint32_t *cnt = nullptr, *cursor = nullptr;   // per row: mirrored matches (pass 1 counts, pass 2 scans), pass 2's fill cursor
+    const unsigned long long *h() const { return (const unsigned long long *)ctx->h_stat_words; }   // pinned; read before anything else uses it
+};
+
+static int read_words(const SelfJoin &sj) {   // the one host stop: 24 bytes, then h()
+    hipError_t e = hipMemcpyAsync(sj.ctx->h_stat_words, sj.words, 24, hipMemcpyDeviceToHost, sj.ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(sj.ctx->stream);
+    if (e != hipSuccess) {
+        sg_set_error("symmetric multiply: %s", hipGetErrorString(e));
+        return SG_ERR_HIP;
+    }
+    return SG_OK;
+}
+
+// The size of the pair list, in chunks.
+static void size_pair_list(SelfJoin &sj) {
+    sg_ctx *ctx = sj.ctx;
+    const sg_postings *Bt = sj.Bt;
+    const int64_t n = sj.n;
+    const size_t vs = sj.A->dtype == SG_F64 ? 8 : 4;
+    // A name list has a few matches per row, but hubs of identical names have h^2 / 2 pairs each, and the largest hubs
+    // grow with the list (5 M synthetic names: 53 M pairs above 0.8 for 18 M matches kept -- with room for 8 n pairs the
+    // pass was thrown away after 630 ms and the one-sided form took another 1300; scripts/full_configs.py).  The list
+    // costs nothing until it is written: room for 64 n pairs, at most a sixteenth of the device memory.
+    // (every row through the exact kernel = thresholds below the pruned kernel's: at 0.3 a name has 70 and more matches
+    //  above it on average, 200 k names overran 64 n: room for 512 n there)
+    // ... and where a row's own matches travel through the list as well (top_n above one register list), or the threshold is
+    //  below the name-matching range (the tile-by-tile form's index): 256 n
+    int64_t cap = (sj.exact_all ? 512 : ((sj.keep > SG_TOPN_LANES || Bt->tile_form) ? 256 : 64)) * n + ((int64_t)1 << 20);
+    if (ctx->total_mem > 0) {
+        const int64_t by_memory = (int64_t)(ctx->total_mem / 16 / (8 + vs));
+        if (cap > by_memory) cap = by_memory;
+    }
+    if (cap < 8 * n + ((int64_t)1 << 20)) cap = 8 * n + ((int64_t)1 << 20);
+    if (const char *v = ctx->opt("SG_SYM_PAIR_CAP"))   // test hook: a list that is too small
+        if (atoll(v) > 0) {
+            cap = atoll(v);
+            sj.cap_forced = true;
+        }
+    if (cap >= ((int64_t)1 << 31)) cap = ((int64_t)1 << 31) - 1;   // list offsets are 32-bit
+    // every wave of the kernel holds one open chunk: count those in
+    uint32_t chunks = (uint32_t)(cap / SG_PAIR_CHUNK);
+    if (!sj.cap_forced) chunks += 2u * pruned_grid(ctx, Bt->tile_log2, n, Bt->fold_log2, sj.A->dtype) + (uint32_t)ctx->num_cu * 4u +
+                                  sg_spgemm_exact_selfjoin_grid(ctx, Bt);   // (every wave of every launch holds one open chunk)
+    sj.list.sink.chunks = chunks < 1 ? 1 : chunks;
+}
+
+// The pair list, the control words, the per-row counts and this pass's statistics; zeroed by one launch, and the
+// sink's struct put into the words.
+static int alloc_and_zero(Scratch &scratch, SelfJoin &sj) {
+    sg_ctx *ctx = sj.ctx;
+    SgPairSink &sink = sj.list.sink;
+    const size_t cap = (size_t)sink.chunks * SG_PAIR_CHUNK, rows = (size_t)sj.n + 2;
+    SG_TRY(scratch.alloc(SJ_CHUNK_COUNT + sink.chunks, &sj.words));
+    SG_TRY(scratch.alloc(cap, &sink.d_i));
+    SG_TRY(scratch.alloc(cap, &sink.d_j));
+    SG_TRY(scratch.alloc_bytes(cap * (sj.A->dtype == SG_F64 ? 8 : 4), &sink.d_s));
+    SG_TRY(scratch.alloc(rows, &sj.cnt));
+    SG_TRY(scratch.alloc(rows, &sj.cursor));
+    SG_TRY(scratch.alloc(rows, &sj.flagged_rows));
+    SG_TRY(scratch.alloc((size_t)8, &sj.stats));
+    sj.row_counter = sj.words + SJ_ROW_COUNTER;
+    sj.flagged_count = sj.words + SJ_HANDED_OVER;
+    sink.d_totals = (unsigned long long *)(sj.words + SJ_PAIRS);
+    sink.d_chunks_used = sj.words + SJ_CHUNKS_USED;
+    sink.d_row_count = sj.cnt;
+    sink.d_chunk_count = sj.words + SJ_CHUNK_COUNT;
+    SgPairSink *d_sink = reinterpret_cast<SgPairSink *>(sj.words + SJ_SINK);
+    sj.list.d_sink = d_sink;
+    SG_TRY(SG_ZERO4(ctx, sj.words, (SJ_CHUNK_COUNT + (size_t)sink.chunks) * sizeof(uint32_t), sj.stats, 8 * sizeof(unsigned long long),
+                    sj.cnt, sizeof(uint32_t) * rows, sj.cursor, sizeof(uint32_t) * rows));   // (one launch, not four)
+    hipLaunchKernelGGL(pair_sink_kernel, dim3(1), dim3(1), 0, ctx->stream, sink, d_sink);
+    return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
+}
+
+// The pilot of pass 1 on a large matrix: the most expensive rows -- the last k_first positions, which see every column -- go
+// first (`first`), and what THEY put into the pair list says whether the list will hold the pass: a row at position p
+// mirrors the matches j < p, so the whole pass writes about n / (2 k) times what the last k rows do.  Above 0.9 of the list
+// the form is called off (*called_off; the caller of sg_spgemm_pruned_symmetric runs the one-sided form); otherwise `rest`
+// runs.  open_grid: the waves of `first`, each of which holds one open chunk.  One host stop.
+template <typename First, typename Rest>
+static int pass1_piloted(const SelfJoin &sj, uint32_t k_first, unsigned open_grid, bool reset_row_counter, First &&first, Rest &&rest,
+                         bool *called_off) {
+    SG_TRY(first());
+    SG_TRY(read_words(sj));
+    const double open_chunks = 0.5 * (double)open_grid;   // (every wave's last chunk is half full on average)
+    const double used = (double)(uint32_t)sj.h()[2] > open_chunks ? (double)(uint32_t)sj.h()[2] - open_chunks : 0.0;
+    if (used * (double)sj.n / (2.0 * (double)k_first) > 0.9 * (double)sj.list.sink.chunks) {
+        *called_off = true;
+        return SG_OK;
+    }
+    if (reset_row_counter && hipMemsetAsync(sj.words + SJ_ROW_COUNTER, 0, sizeof(uint32_t), sj.ctx->stream) != hipSuccess) return SG_ERR_HIP;
+    return rest();
+}
+static uint32_t pilot_rows_by_size(int64_t n) { return (uint32_t)(n / 256 > 4096 ? n / 256 : 4096); }   // the last 0.4 % of the positions
+
+// Pass 1, exact_all: every row is handed to the exact kernel's self-join launch, from the last position down (a row's cost
+// grows with its position) -- thresholds below the pruned kernel's envelope, or products its pilot prices dearer than the
+// exact multiply: half the (row, tile) visits of the one-sided exact kernel, the same pair list and second pass.
 // rows[i] = n - 1 - first - i for i < count; *len = count (what the launch reads), *listed = first + count (the statistics)
 __global__ void __launch_bounds__(256) all_rows_descending_kernel(uint32_t n, uint32_t first, uint32_t count, uint32_t *__restrict__ rows,
                                                                   uint32_t *len, uint32_t *listed) {
@@ -2078,6 +2257,133 @@ __global__ void __launch_bounds__(256) all_rows_descending_kernel(uint32_t n, ui
     }
 }
 
+static int pass1_exact_all(const SelfJoin &sj, bool *called_off) {
+    sg_ctx *ctx = sj.ctx;
+    const uint32_t n = (uint32_t)sj.n;
+    uint32_t *words = sj.words;
+    SgTimer kt(ctx, SG_K_SPGEMM_KERNEL);
+    SG_TRY(sg_postings_ensure_full(ctx, sj.Bt));
+    // Large matrices: the pilot (pass1_piloted).  At thresholds far below name matching the pairs outgrow any list (5 M
+    // names at 0.38: more than 1.5 G pairs; the pass wrote 18 GB for 6.5 s before it ran out of chunks, and the one-sided
+    // form took its 10 s after that): then the form is called off here, for 1 % of its work.
+    uint32_t k_first = 0;
+    if (sj.n >= (int64_t)1000000 && !sj.cap_forced) k_first = pilot_rows_by_size(sj.n);
+    if (const char *v = ctx->opt("SG_EXACT_SYM_PILOT_ROWS")) k_first = (uint32_t)atoll(v) < n ? (uint32_t)atoll(v) : 0u;   // (test hook)
+    auto list_and_launch = [&](uint32_t first, uint32_t count, uint32_t *len_word, uint32_t *counter_word) {
+        hipLaunchKernelGGL(all_rows_descending_kernel, dim3((count + 255u) / 256u), dim3(256), 0, ctx->stream, n, first, count,
+                           sj.flagged_rows + first, len_word, words + SJ_HANDED_OVER);
+        if (hipGetLastError() != hipSuccess) return (int)SG_ERR_HIP;
+        return sg_spgemm_exact_selfjoin_rows(ctx, sj.A, sj.Bt, sj.keep, sj.r, sj.threshold, counter_word, sj.flagged_rows + first, len_word,
+                                             sj.list.sink, /*all_rows=*/true);
+    };
+    if (sj.n <= 0) return SG_OK;
+    if (k_first == 0) return list_and_launch(0u, n, words + SJ_EXACT_LEN, words + SJ_EXACT_COUNTER);
+    return pass1_piloted(
+        sj, k_first, sg_spgemm_exact_selfjoin_grid(ctx, sj.Bt), /*reset_row_counter=*/false,
+        [&] { return list_and_launch(0u, k_first, words + SJ_EXACT_LEN, words + SJ_EXACT_COUNTER); },
+        [&] { return list_and_launch(k_first, n - k_first, words + SJ_EXACT_LEN2, words + SJ_EXACT_COUNTER2); }, called_off);
+}
+
+// Pass 1, otherwise: the pruned kernel over the pairs j <= i of the range.
+static int pass1_pruned(const SelfJoin &sj, bool *called_off) {
+    sg_ctx *ctx = sj.ctx;
+    const sg_postings *Bt = sj.Bt;
+    SgTimer kt(ctx, SG_K_SPGEMM_KERNEL);   // the kernel alone (the launch group's timer also covers the second pass)
+    auto pruned_pass = [&](const PairList &range) {
+        PrunedJob job = sj;   // (the job alone, over `range`)
+        job.pl = &range;
+        return by_dtype(sj.A->dtype, [&](auto tag) { return dispatch_pruned<decltype(tag), true>(job); });
+    };
+    // The tile-by-tile form on a large matrix (thresholds below the name-matching range, a million rows and more): the
+    // last 0.4 % of the positions first, as the exact kernel's form does above, and their pairs decide whether the list
+    // will hold the pass -- 5 M names at 0.42 have more than 1 G pairs above the threshold, the pass wrote them for four
+    // seconds before it ran out of chunks and was repeated one-sided (scripts/big_low_thresholds.py).
+    uint32_t k_first = 0;
+    if (Bt->tile_form && sj.whole && sj.n >= (int64_t)1000000 && !sj.cap_forced) k_first = pilot_rows_by_size(sj.n);
+    if (const char *v = ctx->opt("SG_SYM_PILOT_ROWS"))    // (test hook, any form of the pruned multiply)
+        k_first = sj.whole && atoll(v) > 0 && atoll(v) < sj.n ? (uint32_t)atoll(v) : 0u;
+    if (k_first == 0) return pruned_pass(sj.list);
+    PairList first = sj.list, rest = sj.list;
+    first.row_lo = (uint32_t)sj.n - k_first;
+    rest.row_hi = (uint32_t)sj.n - k_first;
+    return pass1_piloted(
+        sj, k_first, pruned_grid(ctx, Bt->tile_log2, (int64_t)k_first, Bt->fold_log2, sj.A->dtype), /*reset_row_counter=*/true,
+        [&] { return pruned_pass(first); }, [&] { return pruned_pass(rest); }, called_off);
+}
+
+// After pass 1: the rows neither launch of the pruned kernel could take (more than 128 non-zeros, more than 64 prefix terms, no
+// room for the fixed-point filter, or -- stream form -- none at all): through the exact kernel, in the same form --
+// pairs (i, j <= i), mirrored ones into the pair list.  Its postings are written now if the index build left them
+// out (name lists have no such rows), and the counts are read again: one more host stop, only if there are such rows.
+static int handed_over_rows(const SelfJoin &sj) {
+    const uint32_t handed_over = (uint32_t)(sj.h()[0] >> 32);
+    if (handed_over == 0) return SG_OK;
+    SG_TRY(sg_postings_ensure_full(sj.ctx, sj.Bt));
+    // (a list of long strings hands over most of its rows: then the launch is sized like one over all rows, not like the
+    //  usual handful -- 50 k strings of ~170 characters: scripts/family_sweep.py, "very long")
+    const bool many = handed_over > 2u * sg_spgemm_exact_selfjoin_grid(sj.ctx);
+    SG_TRY(sg_spgemm_exact_selfjoin_rows(sj.ctx, sj.A, sj.Bt, sj.keep, sj.r, sj.threshold, sj.words + SJ_EXACT_COUNTER, sj.flagged_rows,
+                                         sj.words + SJ_HANDED_OVER, sj.list.sink, many));
+    return read_words(sj);
+}
+
+// Multi-GPU, in place of pass 2: hand the pair list out as one flat array (the caller gathers the lists of all ranks, then
+// sg_selfjoin_merge_pairs); the export kernel also publishes the pass's statistics.
+static int export_pair_list(Scratch &scratch, const SelfJoin &sj, unsigned long long n_pairs, uint32_t chunks_used,
+                            unsigned long long *stats, int32_t **export_pairs, int64_t *export_n) {
+    sg_ctx *ctx = sj.ctx;
+    const SgPairSink &sink = sj.list.sink;
+    const int W = sj.A->dtype == SG_F64 ? 4 : 3;
+    uint32_t *chunk_start = nullptr;
+    int32_t *flat = nullptr;
+    SG_TRY(scratch.alloc((size_t)chunks_used + 2, &chunk_start));
+    if (chunks_used > 0) SG_TRY(sg_exclusive_scan_u32(ctx, sink.d_chunk_count, chunk_start, chunks_used, nullptr));
+    SG_TRY(scratch.alloc((size_t)(n_pairs + 1) * W, &flat));
+    if (chunks_used > 0) {
+        SG_TRY(by_dtype(sj.A->dtype, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(pairs_export_kernel<T>, dim3(chunks_used), dim3(SG_PAIR_CHUNK), 0, ctx->stream, sink.d_i, sink.d_j,
+                               (const T *)sink.d_s, sink.d_chunk_count, chunk_start, flat, (const unsigned long long *)sj.stats,
+                               (const uint32_t *)(sj.words + SJ_HANDED_OVER), stats);
+            return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
+        }));
+    } else if (hipMemcpyAsync(stats, sj.stats, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+               hipMemcpyAsync(stats + 4, sj.stats + 4, sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+               hipMemcpyAsync(stats + 3, sj.words + SJ_HANDED_OVER, 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
+        return SG_ERR_HIP;   // (no pairs, no export kernel: the statistics go by copy)
+    }
+    *export_pairs = scratch.keep(flat);
+    *export_n = (int64_t)n_pairs;
+    return SG_OK;
+}
+
+// Pass 2, for the self-join on one GPU and for the merge of the multi-GPU form: scan the per-row counts (cnt becomes ptr,
+// n + 1 entries), allocate the two lists, `fill(lcol, lval)` them, and select every row's top `keep` of its own matches in
+// `r` and its list.  pairs_select also publishes the pass's statistics (st_dst null: none to publish).
+template <typename T, typename Fill>
+static int second_pass(Scratch &scratch, sg_ctx *ctx, sg_topn *r, int64_t n, uint32_t *cnt, size_t n_list, int32_t keep,
+                       const unsigned long long *st_src, const uint32_t *st_word, unsigned long long *st_dst, Fill &&fill) {
+    int32_t *lcol = nullptr;
+    T *lval = nullptr;
+    SG_TRY(sg_exclusive_scan_u32(ctx, cnt, cnt, n + 1, nullptr));
+    SG_TRY(scratch.alloc(n_list, &lcol));
+    SG_TRY(scratch.alloc(n_list, &lval));
+    const unsigned sgrid = (unsigned)((n + 63) / 64 > 0 ? (n + 63) / 64 : 1);
+    fill(lcol, lval);
+    hipLaunchKernelGGL(pairs_select_kernel<T>, dim3(sgrid), dim3(64), 0, ctx->stream, cnt, lcol, (const T *)lval, (uint32_t)n, keep,
+                       r->stride, r->d_cols, (T *)r->d_vals, r->d_counts, st_src, st_word, st_dst);
+    return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
+}
+
+// Self-join form, stage by stage:
+//   size_pair_list -> alloc_and_zero
+//   -> pass 1: pass1_pruned (the pruned kernel over the pairs j <= i), or pass1_exact_all (every row through the exact
+//      kernel's self-join launch); each behind pass1_piloted where a pilot applies
+//   -> read_words (the one host round trip: rows handed over, pair count, chunks handed out)
+//   -> handed_over_rows (the exact kernel's self-join launch over the rows the pruned kernel passed on)
+//   -> did the list hold -> export_pair_list (multi-GPU), or second_pass (lists, top-n).
+// *done == false: nothing usable was produced (too many pairs for the list) and the caller runs the one-sided
+// form; the statistics words are untouched then (the result rows are overwritten by that form).
 int sg_spgemm_pruned_symmetric(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t keep, sg_topn *r,
                                double threshold, double delta, unsigned long long *stats, bool *done, int64_t row_lo,
                                int64_t row_hi, int32_t **export_pairs, int64_t *export_n, int64_t row_step, bool exact_all) {
@@ -2086,281 +2392,45 @@ int sg_spgemm_pruned_symmetric(sg_ctx *ctx, const sg_csr *A, const sg_postings *
     // the self-join runs in position space: its left matrix is the one the index was built over (sg_postings.hip)
     if (Bt->permuted) A = Bt->permuted;
     else SG_TRY(sg_csr_ensure_rows(ctx, A));   // (no copy in position order: the rows of A itself are read)
-    const size_t vs = A->dtype == SG_F64 ? 8 : 4;
-    const int64_t n = A->n_rows;
+    SelfJoin sj{{ctx, A, Bt, keep, r, threshold, prune_budget(Bt, threshold, delta)}, exact_all, A->n_rows};
+    sj.pl = &sj.list;
+    const int64_t n = sj.n;
     if (row_hi < 0) row_hi = n;   // the whole matrix
-    PairList pl;
-    pl.row_lo = (uint32_t)row_lo;
-    pl.row_hi = (uint32_t)row_hi;
-    pl.row_step = row_step > 1 ? (uint32_t)row_step : 1u;
-    // A name list has a few matches per row, but hubs of identical names have h^2 / 2 pairs each, and the largest hubs
-    // grow with the list (5 M synthetic names: 53 M pairs above 0.8 for 18 M matches kept -- with room for 8 n pairs the
-    // pass was thrown away after 630 ms and the one-sided form took another 1300; scripts/full_configs.py).  The list
-    // costs nothing until it is written: room for 64 n pairs, at most a sixteenth of the device memory.
-    // (every row through the exact kernel = thresholds below the pruned kernel's: at 0.3 a name has 70 and more matches
-    //  above it on average, 200 k names overran 64 n: room for 512 n there)
-    // ... and where a row's own matches travel through the list as well (top_n above one register list), or the threshold is
-    //  below the name-matching range (the tile-by-tile form's index): 256 n
-    int64_t cap = (exact_all ? 512 : ((keep > SG_TOPN_LANES || Bt->tile_form) ? 256 : 64)) * n + ((int64_t)1 << 20);
-    if (ctx->total_mem > 0) {
-        const int64_t by_memory = (int64_t)(ctx->total_mem / 16 / (8 + vs));
-        if (cap > by_memory) cap = by_memory;
-    }
-    if (cap < 8 * n + ((int64_t)1 << 20)) cap = 8 * n + ((int64_t)1 << 20);
-    bool cap_forced = false;
-    if (const char *v = ctx->opt("SG_SYM_PAIR_CAP"))   // test hook: a list that is too small
-        if (atoll(v) > 0) {
-            cap = atoll(v);
-            cap_forced = true;
-        }
-    if (cap >= ((int64_t)1 << 31)) cap = ((int64_t)1 << 31) - 1;   // list offsets are 32-bit
-    // every wave of the kernel holds one open chunk: count those in
-    pl.chunks = (uint32_t)(cap / SG_PAIR_CHUNK);
-    if (!cap_forced) pl.chunks += 2u * pruned_grid(ctx, Bt->tile_log2, n, Bt->fold_log2, A->dtype) + (uint32_t)ctx->num_cu * 4u +
-                                  sg_spgemm_exact_selfjoin_grid(ctx, Bt);   // (every wave of every launch holds one open chunk)
-    if (pl.chunks < 1) pl.chunks = 1;
-    cap = (int64_t)pl.chunks * SG_PAIR_CHUNK;
-    // [0] row counter [1] flagged count [2..3] pairs [4] chunks handed out [5] row counter of the exact kernel's launch;
-    // [64, 80) the pair list as a struct; [128 ..) entries per chunk
-    uint32_t *words = nullptr;
-    uint32_t *cnt = nullptr, *cursor = nullptr;
-    int32_t *lcol = nullptr;
-    void *lval = nullptr;
-    uint32_t *flagged_rows = nullptr;
-    int st = sg_alloc(ctx, (size_t)128 + pl.chunks, &words);   // ([64, 80): the SgPairSink handed to the kernels)
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)cap, &pl.d_i);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)cap, &pl.d_j);
-    if (st == SG_OK) st = ctx->alloc((size_t)cap * vs, &pl.d_s);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 2, &cnt);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 2, &cursor);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 2, &flagged_rows);
-    unsigned long long *h = (unsigned long long *)ctx->h_stat_words;   // pinned; read before anything else uses it
-    auto cleanup = [&]() {
-        ctx->release(words);
-        ctx->release(pl.d_i);
-        ctx->release(pl.d_j);
-        ctx->release(pl.d_s);
-        ctx->release(cnt);
-        ctx->release(cursor);
-        ctx->release(flagged_rows);
-        ctx->release(lcol);
-        ctx->release(lval);
-    };
-    if (st != SG_OK) {
-        cleanup();
-        return st;
-    }
-    pl.d_totals = (unsigned long long *)(words + 2);
-    pl.d_chunks_used = words + 4;
-    pl.d_row_count = cnt;
-    pl.d_chunk_count = words + 128;
-    // (a cache line of its own, 256 bytes from the counters: every access to the line of the row counter and the chunk
-    //  counter queues behind their atomics -- with the struct next to them the kernel took twice its time)
-    pl.d_sink = reinterpret_cast<const SgPairSink *>(words + 64);
-    static_assert(sizeof(SgPairSink) <= 64, "the pair list's struct must fit the sixteen words reserved for it");
-    unsigned long long *d_stats3 = nullptr;   // this pass's own statistics: they only count when the pass does
-    st = sg_alloc(ctx, (size_t)8, &d_stats3);   // [0..2] rows / postings / survivors, [4] pairs scored exactly
-    hipError_t e = hipSuccess;
-    if (st == SG_OK) {
-        st = SG_ZERO4(ctx, words, (128 + (size_t)pl.chunks) * sizeof(uint32_t), d_stats3, 8 * sizeof(unsigned long long), cnt,
-                      sizeof(uint32_t) * (size_t)(n + 2), cursor, sizeof(uint32_t) * (size_t)(n + 2));   // (one launch, not four)
-    }
-    const float s_budget = prune_budget(Bt, threshold, delta);
-    SgPairSink sink;
-    sink.d_i = pl.d_i;
-    sink.d_j = pl.d_j;
-    sink.d_s = pl.d_s;
-    sink.d_row_count = pl.d_row_count;
-    sink.d_chunk_count = pl.d_chunk_count;
-    sink.d_chunks_used = pl.d_chunks_used;
-    sink.d_totals = pl.d_totals;
-    sink.chunks = pl.chunks;
-    if (st == SG_OK) {
-        hipLaunchKernelGGL(pair_sink_kernel, dim3(1), dim3(1), 0, ctx->stream, sink, (SgPairSink *)(words + 64));
-        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-    }
-    if (st == SG_OK && exact_all) {
-        SgTimer kt(ctx, SG_K_SPGEMM_KERNEL);
-        st = sg_postings_ensure_full(ctx, Bt);
-        // Large matrices: the most expensive rows -- the last 0.4 % of the positions, which see every column -- go first, in a
-        // launch of their own, and what THEY put into the pair list says whether the list will hold the pass: a row at
-        // position p mirrors the matches j < p, so the whole pass writes about n / (2 k) times what the last k rows do.  At
-        // thresholds far below name matching the pairs outgrow any list (5 M names at 0.38: more than 1.5 G pairs; the pass
-        // wrote 18 GB for 6.5 s before it ran out of chunks, and the one-sided form took its 10 s after that): then the
-        // form is called off here, for 1 % of its work.  [6] / [8]: the two lists' lengths, [5] / [7]: their row counters.
-        uint32_t k_first = 0;
-        if (n >= (int64_t)1000000 && !cap_forced) k_first = (uint32_t)(n / 256 > 4096 ? n / 256 : 4096);
-        if (const char *v = ctx->opt("SG_EXACT_SYM_PILOT_ROWS")) k_first = (uint32_t)atoll(v) < (uint32_t)n ? (uint32_t)atoll(v) : 0u;   // (test hook)
-        auto list_and_launch = [&](uint32_t first, uint32_t count, uint32_t *len_word, uint32_t *counter_word) {
-            hipLaunchKernelGGL(all_rows_descending_kernel, dim3((count + 255u) / 256u), dim3(256), 0, ctx->stream, (uint32_t)n, first, count,
-                               flagged_rows + first, len_word, words + 1);
-            if (hipGetLastError() != hipSuccess) return (int)SG_ERR_HIP;
-            return sg_spgemm_exact_selfjoin_rows(ctx, A, Bt, keep, r, threshold, counter_word, flagged_rows + first, len_word, sink,
-                                                 /*all_rows=*/true);
-        };
-        if (st == SG_OK && n > 0 && k_first > 0) {
-            st = list_and_launch(0u, k_first, words + 6, words + 5);
-            if (st == SG_OK) {
-                e = hipMemcpyAsync(h, words, 24, hipMemcpyDeviceToHost, ctx->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                if (e != hipSuccess) st = SG_ERR_HIP;
-            }
-            if (st == SG_OK) {
-                const double open_chunks = 0.5 * (double)sg_spgemm_exact_selfjoin_grid(ctx, Bt);   // (every wave's last chunk is half full on average)
-                const double used = (double)(uint32_t)h[2] > open_chunks ? (double)(uint32_t)h[2] - open_chunks : 0.0;
-                if (used * (double)n / (2.0 * (double)k_first) > 0.9 * (double)pl.chunks) {
-                    ctx->release(d_stats3);
-                    cleanup();
-                    return SG_OK;   // *done stays false: the caller runs the one-sided form
-                }
-                st = list_and_launch(k_first, (uint32_t)n - k_first, words + 8, words + 7);
-            }
-        } else if (st == SG_OK && n > 0) {
-            st = list_and_launch(0u, (uint32_t)n, words + 6, words + 5);
-        }
-    } else if (st == SG_OK) {
-        SgTimer kt(ctx, SG_K_SPGEMM_KERNEL);   // the kernel alone (the launch group's timer also covers the second pass)
-        auto pruned_pass = [&](const PairList &range) {
-            if (A->dtype == SG_F64)
-                return dispatch_pruned<double, true>(ctx, A, Bt, keep, r, (double)threshold, s_budget, words, words + 1, flagged_rows,
-                                                     d_stats3, range);
-            return dispatch_pruned<float, true>(ctx, A, Bt, keep, r, (float)threshold, s_budget, words, words + 1, flagged_rows, d_stats3,
-                                                range);
-        };
-        // The tile-by-tile form on a large matrix (thresholds below the name-matching range, a million rows and more): the
-        // last 0.4 % of the positions first, as the exact kernel's form does above, and their pairs decide whether the list
-        // will hold the pass -- 5 M names at 0.42 have more than 1 G pairs above the threshold, the pass wrote them for four
-        // seconds before it ran out of chunks and was repeated one-sided (scripts/big_low_thresholds.py).
-        uint32_t k_first = 0;
-        const bool whole = pl.row_lo == 0 && (int64_t)pl.row_hi == n && pl.row_step == 1 && !export_pairs;
-        if (Bt->tile_form && whole && n >= (int64_t)1000000 && !cap_forced) k_first = (uint32_t)(n / 256 > 4096 ? n / 256 : 4096);
-        if (const char *v = ctx->opt("SG_SYM_PILOT_ROWS"))    // (test hook, any form of the pruned multiply)
-            k_first = whole && atoll(v) > 0 && atoll(v) < n ? (uint32_t)atoll(v) : 0u;
-        if (k_first > 0) {
-            PairList first = pl, rest = pl;
-            first.row_lo = (uint32_t)n - k_first;
-            rest.row_hi = (uint32_t)n - k_first;
-            st = pruned_pass(first);
-            if (st == SG_OK) {
-                e = hipMemcpyAsync(h, words, 24, hipMemcpyDeviceToHost, ctx->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                if (e != hipSuccess) st = SG_ERR_HIP;
-            }
-            if (st == SG_OK) {
-                const double open_chunks = 0.5 * (double)pruned_grid(ctx, Bt->tile_log2, (int64_t)k_first, Bt->fold_log2, A->dtype);
-                const double used = (double)(uint32_t)h[2] > open_chunks ? (double)(uint32_t)h[2] - open_chunks : 0.0;
-                if (used * (double)n / (2.0 * (double)k_first) > 0.9 * (double)pl.chunks) {
-                    ctx->release(d_stats3);
-                    cleanup();
-                    return SG_OK;   // *done stays false: the caller runs the one-sided form
-                }
-                if (hipMemsetAsync(words, 0, sizeof(uint32_t), ctx->stream) != hipSuccess) st = SG_ERR_HIP;   // the row counter
-            }
-            if (st == SG_OK) st = pruned_pass(rest);
-        } else {
-            st = pruned_pass(pl);
-        }
-    }
-    // h[0] = {row counter, flagged}, h[1] = pairs, h[2] = chunks handed out
-    auto read_back = [&]() {
-        e = hipMemcpyAsync(h, words, 24, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            sg_set_error("symmetric multiply: %s", hipGetErrorString(e));
-            st = SG_ERR_HIP;
-        }
-    };
-    if (st == SG_OK) read_back();
-    if (st == SG_OK && (uint32_t)(h[0] >> 32) > 0 && !exact_all) {
-        // the rows neither launch of the pruned kernel could take (more than 128 non-zeros, more than 64 prefix terms, no
-        // room for the fixed-point filter, or -- stream form -- none at all): through the exact kernel, in the same form --
-        // pairs (i, j <= i), mirrored ones into the pair list.  Its postings are written now if the index build left them
-        // out (name lists have no such rows), and the counts are read again.
-        st = sg_postings_ensure_full(ctx, Bt);
-        // (a list of long strings hands over most of its rows: then the launch is sized like one over all rows, not like the
-        //  usual handful -- 50 k strings of ~170 characters: scripts/family_sweep.py, "very long")
-        const bool many = (uint32_t)(h[0] >> 32) > 2u * sg_spgemm_exact_selfjoin_grid(ctx);
-        if (st == SG_OK) st = sg_spgemm_exact_selfjoin_rows(ctx, A, Bt, keep, r, threshold, words + 5, flagged_rows, words + 1, sink, many);
-        if (st == SG_OK) read_back();
-    }
-    if (st != SG_OK) {
-        ctx->release(d_stats3);
-        cleanup();
-        return st;
-    }
-    const unsigned long long n_pairs = h[1];
-    const uint32_t chunks_used = (uint32_t)h[2];
-    if (chunks_used > pl.chunks) {   // more pairs than the list holds (hubs of thousands of identical names)
-        ctx->release(d_stats3);
-        cleanup();
-        return SG_OK;   // *done stays false
-    }
-    const dim3 pgrid(chunks_used > 0 ? chunks_used : 1);
-    if (export_pairs) {
-        // ---- multi-GPU: hand the pair list out (the caller gathers the lists of all ranks, then sg_selfjoin_merge)
-        const int W = A->dtype == SG_F64 ? 4 : 3;
-        uint32_t *chunk_start = nullptr;
-        int32_t *flat = nullptr;
-        st = sg_alloc(ctx, (size_t)chunks_used + 2, &chunk_start);
-        if (st == SG_OK && chunks_used > 0)
-            st = sg_exclusive_scan_u32(ctx, pl.d_chunk_count, chunk_start, chunks_used, nullptr);
-        if (st == SG_OK) st = sg_alloc(ctx, (size_t)(n_pairs + 1) * W, &flat);
-        if (st == SG_OK && chunks_used > 0) {
-            if (A->dtype == SG_F64)
-                hipLaunchKernelGGL(pairs_export_kernel<double>, pgrid, dim3(SG_PAIR_CHUNK), 0, ctx->stream, pl.d_i, pl.d_j,
-                                   (const double *)pl.d_s, pl.d_chunk_count, chunk_start, flat,
-                                   (const unsigned long long *)d_stats3, (const uint32_t *)(words + 1), stats);
-            else
-                hipLaunchKernelGGL(pairs_export_kernel<float>, pgrid, dim3(SG_PAIR_CHUNK), 0, ctx->stream, pl.d_i, pl.d_j,
-                                   (const float *)pl.d_s, pl.d_chunk_count, chunk_start, flat,
-                                   (const unsigned long long *)d_stats3, (const uint32_t *)(words + 1), stats);
-            if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-        } else if (st == SG_OK && (hipMemcpyAsync(stats, d_stats3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToDevice,
-                                                  ctx->stream) != hipSuccess ||
-                                   hipMemcpyAsync(stats + 4, d_stats3 + 4, sizeof(unsigned long long), hipMemcpyDeviceToDevice,
-                                                  ctx->stream) != hipSuccess ||
-                                   hipMemcpyAsync(stats + 3, words + 1, 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess))
-            st = SG_ERR_HIP;   // (no pairs, no export kernel: the statistics go by copy)
-        ctx->release(chunk_start);
-        ctx->release(d_stats3);
-        cleanup();
-        if (st != SG_OK) {
-            ctx->release(flat);
-            return st;
-        }
-        *export_pairs = flat;
-        *export_n = (int64_t)n_pairs;
-        *done = true;
-        return SG_OK;
-    }
-    // ---- pass 2
-    st = sg_exclusive_scan_u32(ctx, cnt, cnt, n + 1, nullptr);   // cnt becomes ptr (n + 1 entries)
-    const size_t n_list = (size_t)(n_pairs + 64);
-    if (st == SG_OK) st = sg_alloc(ctx, n_list, &lcol);
-    if (st == SG_OK) st = ctx->alloc(n_list * vs, &lval);
-    if (st == SG_OK) {
-        unsigned sgrid = (unsigned)((n + 63) / 64 > 0 ? (n + 63) / 64 : 1);
-        if (A->dtype == SG_F64) {
-            hipLaunchKernelGGL(pairs_fill_kernel<double>, pgrid, dim3(SG_PAIR_CHUNK), 0, ctx->stream, pl.d_i, pl.d_j,
-                               (const double *)pl.d_s, pl.d_chunk_count, cnt, cursor, lcol, (double *)lval);
-            hipLaunchKernelGGL(pairs_select_kernel<double>, dim3(sgrid), dim3(64), 0, ctx->stream, cnt, lcol, (const double *)lval,
-                               (uint32_t)n, keep, r->stride, r->d_cols, (double *)r->d_vals, r->d_counts,
-                               (const unsigned long long *)d_stats3, (const uint32_t *)(words + 1), stats);
-        } else {
-            hipLaunchKernelGGL(pairs_fill_kernel<float>, pgrid, dim3(SG_PAIR_CHUNK), 0, ctx->stream, pl.d_i, pl.d_j,
-                               (const float *)pl.d_s, pl.d_chunk_count, cnt, cursor, lcol, (float *)lval);
-            hipLaunchKernelGGL(pairs_select_kernel<float>, dim3(sgrid), dim3(64), 0, ctx->stream, cnt, lcol, (const float *)lval,
-                               (uint32_t)n, keep, r->stride, r->d_cols, (float *)r->d_vals, r->d_counts,
-                               (const unsigned long long *)d_stats3, (const uint32_t *)(words + 1), stats);
-        }
-        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;   // (pairs_select also publishes the pass's statistics)
-    }
-    ctx->release(d_stats3);
-    cleanup();
-    if (st == SG_OK) *done = true;
-    return st;
-}
+    sj.list.row_lo = (uint32_t)row_lo;
+    sj.list.row_hi = (uint32_t)row_hi;
+    sj.list.row_step = row_step > 1 ? (uint32_t)row_step : 1u;
+    sj.whole = sj.list.row_lo == 0 && (int64_t)sj.list.row_hi == n && sj.list.row_step == 1 && !export_pairs;
+    size_pair_list(sj);
+    Scratch scratch(ctx);   // everything below is released when this function returns, whichever way
+    SG_TRY(alloc_and_zero(scratch, sj));
 
+    bool called_off = false;
+    SG_TRY(exact_all ? pass1_exact_all(sj, &called_off) : pass1_pruned(sj, &called_off));
+    if (called_off) return SG_OK;   // *done stays false: the caller runs the one-sided form
+    SG_TRY(read_words(sj));
+    if (!exact_all) SG_TRY(handed_over_rows(sj));
+
+    const unsigned long long n_pairs = sj.h()[1];
+    const uint32_t chunks_used = (uint32_t)sj.h()[2];
+    if (chunks_used > sj.list.sink.chunks) return SG_OK;   // more pairs than the list holds (hubs of thousands of identical names): *done stays false
+
+    if (export_pairs) {
+        SG_TRY(export_pair_list(scratch, sj, n_pairs, chunks_used, stats, export_pairs, export_n));
+    } else {
+        const SgPairSink &sink = sj.list.sink;
+        SG_TRY(by_dtype(A->dtype, [&](auto tag) {
+            using T = decltype(tag);
+            return second_pass<T>(scratch, ctx, r, n, sj.cnt, (size_t)(n_pairs + 64), keep, sj.stats, sj.words + SJ_HANDED_OVER, stats,
+                                  [&](int32_t *lcol, T *lval) {
+                                      hipLaunchKernelGGL(pairs_fill_kernel<T>, dim3(chunks_used > 0 ? chunks_used : 1), dim3(SG_PAIR_CHUNK), 0,
+                                                         ctx->stream, sink.d_i, sink.d_j, (const T *)sink.d_s, sink.d_chunk_count, sj.cnt,
+                                                         sj.cursor, lcol, lval);
+                                  });
+        }));
+    }
+    *done = true;
+    return SG_OK;
+}
 
 // Second pass of the multi-GPU self-join: merge the mirrored pairs (of all ranks) whose row lies in [row_lo, row_hi)
 // into those rows of `r` (which hold their own matches from sg_spgemm_pruned_symmetric over the same range).
@@ -2369,49 +2439,20 @@ int sg_selfjoin_merge_pairs(sg_ctx *ctx, sg_topn *r, const int32_t *d_pairs, int
     const uint32_t step = row_step > 1 ? (uint32_t)row_step : 1u;
     const int64_t n = r->n_rows;
     if (n_pairs <= 0 || row_hi <= row_lo) return SG_OK;
-    const size_t vs = r->dtype == SG_F64 ? 8 : 4;
+    Scratch scratch(ctx);
     uint32_t *cnt = nullptr, *cursor = nullptr;
-    int32_t *lcol = nullptr;
-    void *lval = nullptr;
-    int st = sg_alloc(ctx, (size_t)n + 2, &cnt);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 2, &cursor);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_pairs + 64, &lcol);
-    if (st == SG_OK) st = ctx->alloc(((size_t)n_pairs + 64) * vs, &lval);
-    if (st == SG_OK) {
-        st = SG_ZERO2(ctx, cnt, sizeof(uint32_t) * (size_t)(n + 2), cursor, sizeof(uint32_t) * (size_t)(n + 2));
-    }
-    if (st == SG_OK) {
-        const unsigned pg = (unsigned)((n_pairs + 255) / 256);
-        if (r->dtype == SG_F64)
-            hipLaunchKernelGGL(pairs_flat_count_kernel<4>, dim3(pg), dim3(256), 0, ctx->stream, d_pairs, n_pairs, (uint32_t)row_lo,
-                               (uint32_t)row_hi, step, pos_of, cnt);
-        else
-            hipLaunchKernelGGL(pairs_flat_count_kernel<3>, dim3(pg), dim3(256), 0, ctx->stream, d_pairs, n_pairs, (uint32_t)row_lo,
-                               (uint32_t)row_hi, step, pos_of, cnt);
-        st = sg_exclusive_scan_u32(ctx, cnt, cnt, n + 1, nullptr);
-        if (st == SG_OK) {
-            const unsigned sgrid = (unsigned)((n + 63) / 64 > 0 ? (n + 63) / 64 : 1);
-            if (r->dtype == SG_F64) {
-                hipLaunchKernelGGL(pairs_flat_fill_kernel<double>, dim3(pg), dim3(256), 0, ctx->stream, d_pairs, n_pairs,
-                                   (uint32_t)row_lo, (uint32_t)row_hi, step, pos_of, cnt, cursor, lcol, (double *)lval);
-                hipLaunchKernelGGL(pairs_select_kernel<double>, dim3(sgrid), dim3(64), 0, ctx->stream, cnt, lcol,
-                                   (const double *)lval, (uint32_t)n, r->stride, r->stride, r->d_cols, (double *)r->d_vals,
-                                   r->d_counts, (const unsigned long long *)nullptr, (const uint32_t *)nullptr,
-                                   (unsigned long long *)nullptr);
-            } else {
-                hipLaunchKernelGGL(pairs_flat_fill_kernel<float>, dim3(pg), dim3(256), 0, ctx->stream, d_pairs, n_pairs,
-                                   (uint32_t)row_lo, (uint32_t)row_hi, step, pos_of, cnt, cursor, lcol, (float *)lval);
-                hipLaunchKernelGGL(pairs_select_kernel<float>, dim3(sgrid), dim3(64), 0, ctx->stream, cnt, lcol,
-                                   (const float *)lval, (uint32_t)n, r->stride, r->stride, r->d_cols, (float *)r->d_vals,
-                                   r->d_counts, (const unsigned long long *)nullptr, (const uint32_t *)nullptr,
-                                   (unsigned long long *)nullptr);
-            }
-            if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-        }
-    }
-    ctx->release(cnt);
-    ctx->release(cursor);
-    ctx->release(lcol);
-    ctx->release(lval);
-    return st;
+    SG_TRY(scratch.alloc((size_t)n + 2, &cnt));
+    SG_TRY(scratch.alloc((size_t)n + 2, &cursor));
+    SG_TRY(SG_ZERO2(ctx, cnt, sizeof(uint32_t) * (size_t)(n + 2), cursor, sizeof(uint32_t) * (size_t)(n + 2)));
+    const dim3 pgrid((unsigned)((n_pairs + 255) / 256));
+    return by_dtype(r->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(pairs_flat_count_kernel<(sizeof(T) == 8 ? 4 : 3)>, pgrid, dim3(256), 0, ctx->stream, d_pairs, n_pairs,
+                           (uint32_t)row_lo, (uint32_t)row_hi, step, pos_of, cnt);
+        return second_pass<T>(scratch, ctx, r, n, cnt, (size_t)n_pairs + 64, r->stride, nullptr, nullptr, nullptr,
+                              [&](int32_t *lcol, T *lval) {
+                                  hipLaunchKernelGGL(pairs_flat_fill_kernel<T>, pgrid, dim3(256), 0, ctx->stream, d_pairs, n_pairs,
+                                                     (uint32_t)row_lo, (uint32_t)row_hi, step, pos_of, cnt, cursor, lcol, lval);
+                              });
+    });
 }
