@@ -258,7 +258,9 @@ int sg_matchlist_free(sg_matchlist *ml);
  * sg_matchlist_group_reps (group_similar_strings, string_grouper.py:851-904: scipy connected_components
  *   + group_rep): out_rep[i] = the representative of string i's group -- centroid == 0: the member with
  *   the lowest index ('first'); centroid != 0: the member with the largest row sum of similarities, the
- *   lowest index among equals.  Needs a square list (self-join).  out_rep: n_rows (host). */
+ *   lowest index among equals.  Needs a square list (self-join).  out_rep: n_rows (host).
+ * Both need similarities GREATER THAN 0 (what passed a threshold >= 0 is): sg_matchlist_best_master and the arg-max of
+ *   the centroid compare the IEEE bit patterns of the values as unsigned integers, which orders positive values only. */
 int sg_matchlist_best_master(sg_ctx *ctx, const sg_matchlist *ml, int32_t *out_best);
 int sg_matchlist_group_reps(sg_ctx *ctx, const sg_matchlist *ml, int32_t centroid, int32_t *out_rep);
 
