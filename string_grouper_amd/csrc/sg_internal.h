@@ -133,6 +133,52 @@ struct SgTimer {   // records start/stop events of one kernel group on the conte
     }
 };
 
+// Two helpers of the host drivers: scratch that goes back to the pool by itself, and the dtype dispatch.
+struct Scratch {   // blocks of the context's pool, released -- in the order they were taken -- when the scope ends
+    sg_ctx *ctx;
+    std::vector<void *> blocks;
+    explicit Scratch(sg_ctx *c) : ctx(c) {}
+    Scratch(const Scratch &) = delete;
+    ~Scratch() {
+        for (void *p : blocks) ctx->release(p);
+    }
+    int alloc_bytes(size_t bytes, void **out) {
+        const int st = ctx->alloc(bytes, out);
+        if (st == SG_OK) blocks.push_back(*out);
+        return st;
+    }
+    template <typename T>
+    int alloc(size_t count, T **out) {
+        void *p = nullptr;
+        const int st = alloc_bytes(count * sizeof(T), &p);
+        *out = (T *)p;
+        return st;
+    }
+    template <typename T>
+    T *keep(T *p) {   // the block outlives the scope: it is the caller's now
+        for (void *&b : blocks)
+            if (b == p) b = nullptr;
+        return p;
+    }
+    void release(void *p) { ctx->release(keep(p)); }   // ... or goes back early (stream-ordered, like every release)
+};
+
+template <typename F>
+static int by_dtype(int32_t dtype, F &&f) {   // f(double{}) or f(float{}): every launch below is written once
+    return dtype == SG_F64 ? f(double{}) : f(float{});
+}
+
+// Dynamic LDS above the default 48 KiB has to be allowed for each kernel, once
+template <auto KERN>
+static int allow_dynamic_lds(size_t lds) {
+    static bool done = false;   // per instantiation
+    if (lds > 48 * 1024 && !done) {
+        SG_HIP_TRY(hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        done = true;
+    }
+    return SG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 struct sg_strings {
     sg_ctx *ctx = nullptr;
@@ -343,7 +389,7 @@ struct sg_vocab {
 int sg_matchlist_device_view(const sg_matchlist *ml, int64_t *n_rows, int64_t *n_cols, int64_t *n_entries, int32_t *dtype,
                              const int64_t **row_ptr, const int32_t **cols, const void **vals);
 
-#define SG_POSTINGS_NO_COLLAPSE (1 << 8)   // sg_postings_build_flags (internal): index every row (the collapse wrapper's own inner call; the companion indexes)
+#define SG_POSTINGS_NO_COLLAPSE (1 << 8)   // sg_postings_build_flags (internal): index every row, identical ones not grouped (the companion indexes)
 #define SG_POSTINGS_TILE_FORM (1 << 11)    // sg_postings_build_flags (internal): the pruned multiply's tile-by-tile form, 2048-column tiles, no 8-bit rows
 #define SG_POSTINGS_EXACT_ONLY (1 << 10)   // sg_postings_build_flags (internal): no filter postings, packed rows, 8-bit rows
 // sg_spgemm_pruned.hip

@@ -16,6 +16,9 @@
 // write postings once, histogram + scan of the segment table).
 #include <stdlib.h>
 
+#include <memory>
+#include <optional>
+
 #include "sg_internal.h"
 #include "sg_scan.h"
 
@@ -955,6 +958,199 @@ __global__ void score_ctx_kernel(SgScoreCtx v, SgScoreCtx *out) {
     out[1] = v;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Host side.  sg_postings_build_flags decides whether identical rows are grouped and hands the matrix to index -- the
+// representatives' or the caller's -- to build_index, which reads as its stages: plan_build, alloc_early_rows,
+// build_permuted, alloc_index, fill_lds_path or fill_global_path + tables_from_seg, pack_rows, write_aux.
+struct PostingsFree {
+    void operator()(sg_postings *p) const { sg_postings_free(p); }
+};
+using PostingsPtr = std::unique_ptr<sg_postings, PostingsFree>;   // a half-built index goes back whole, whichever way a stage fails
+
+static sg_csr borrowed(const sg_csr &m) {   // the struct itself, copied: the arrays stay the owner's, and so does what it has cached
+    sg_csr c = m;
+    c.owned = false;
+    c.d_props_words = nullptr;
+    c.left_groups = nullptr;
+    c.left_state = 0;
+    return c;
+}
+
+static SgScoreCtx score_ctx_of(const sg_postings *p) {
+    SgScoreCtx sc;
+    if (!p->d_fwd_ptr) return sc;
+    sc.fwd_ptr = p->d_fwd_ptr;
+    sc.fwd = p->d_fwd;
+    sc.blk = p->d_blk;
+    sc.blk_bytes = p->blk_bytes;
+    sc.orig_of = p->d_orig_of;
+    sc.q8 = (const uint4 *)p->d_q8;
+    sc.q8_scale = p->d_q8 ? __builtin_nextafterf((float)(255.0 / (double)p->norm_up * (1.0 - 1e-6)), 0.f) : 0.f;
+    return sc;
+}
+
+// a tile's counters ([term], a workgroup's own) + one bit per term (frequent or not) in LDS
+static size_t lds_counter_bytes(int64_t n_cols) { return (size_t)n_cols * 4 + ((size_t)(n_cols + 31) / 32) * 4; }
+
+struct BuildPlan {   // everything the build decides before it allocates (plan_build); nothing below asks a second time
+    bool cosine_like = false;
+    float max_norm2 = 0.f;
+    int32_t tile_cols = 0, tile_log2 = 0;
+    int64_t n_tiles = 0, n_bins = 0;
+    bool want_pruned = false, will_filter = false, want_q8 = false, want_blk = false;
+    bool permute = false;          // a copy of the rows in position order may be made (build_permuted decides)
+    bool early_rows = false;       // ... and it writes the packed rows and their 8-bit copies along
+    bool lds_path = false, lazy_full = false;
+    int32_t fold_log2 = 0, nt_pad = 0, nv_pad = 0;
+    float norm_up = 0.f;
+    uint32_t freq_min = 0;
+    // the staged fill's geometry (LDS path)
+    bool staged = false;
+    int32_t chunk_rows = 0;
+    uint32_t stage_cap = 0;
+    size_t staged_lds = 0;
+    int32_t split = 1;
+};
+
+static int plan_build(sg_ctx *ctx, const sg_csr *B, int32_t tile_cols, int32_t flags, bool cosine_like, float max_norm2,
+                      BuildPlan *out) {
+    BuildPlan pl;
+    pl.cosine_like = cosine_like;
+    pl.max_norm2 = max_norm2;
+    // cosine-like right-hand sides (non-negative, sorted rows, norms <= 1: TF-IDF) take the pruned multiply,
+    // whose 16-bit accumulators make a 4096-column tile 8 KiB; everything else the exact kernel with 8 KiB
+    // of float / double accumulators per wave
+    pl.want_pruned = cosine_like && !ctx->opt_is("SG_PRUNE", '0') && !(flags & SG_POSTINGS_EXACT_ONLY);
+    if (tile_cols == 0) {
+        tile_cols = B->dtype == SG_F64 ? 1024 : 2048;
+        if (pl.want_pruned) {
+            tile_cols = 4096;
+            if (flags & SG_POSTINGS_TILE_FORM) tile_cols = 2048;   // (the tile-by-tile form's own index: sg_spgemm_topn.hip, "which form")
+            else if (const char *v = ctx->opt("SG_PRUNE_TILE")) tile_cols = atoi(v) == 13 ? 8192 : (atoi(v) == 11 ? 2048 : 4096);
+        }
+    }
+    SG_REQUIRE(tile_cols >= 256 && tile_cols <= 32768 && (tile_cols & (tile_cols - 1)) == 0,
+               "tile_cols must be a power of two in [256, 32768]");
+    pl.tile_cols = tile_cols;
+    int64_t max_entries = (int64_t)1 << 29;   // the multiply addresses postings with 32-bit BYTE offsets (8 B entries)
+    if (const char *v = ctx->opt("SG_MAX_POSTINGS")) {   // test hook: force the right-hand split at small sizes
+        const long long o = atoll(v);
+        if (o > 0 && o < max_entries) max_entries = o;
+    }
+    if (B->nnz + 64 >= max_entries) {
+        sg_set_error("right-hand matrix has %lld non-zeros; one postings block holds < 2^29 (use more right-hand blocks)",
+                     (long long)B->nnz);
+        return SG_ERR_OVERFLOW;
+    }
+    while ((1 << pl.tile_log2) < tile_cols) ++pl.tile_log2;
+    pl.n_tiles = B->n_rows == 0 ? 1 : ((B->n_rows + tile_cols - 1) >> pl.tile_log2);
+    pl.n_bins = B->n_cols * pl.n_tiles;
+    if (pl.n_bins + 1 >= (int64_t)1 << 31) {
+        sg_set_error("segment table of %lld x %lld entries is too large; use more right-hand blocks",
+                     (long long)B->n_cols, (long long)pl.n_tiles);
+        return SG_ERR_OVERFLOW;
+    }
+    pl.norm_up = __builtin_nextafterf(sqrtf(max_norm2) * 1.000001f, 2.f);
+    // second filter: terms must fit 24 bits; a sixteenth of the device memory at most; SG_Q8=0 switches it off
+    // ... and rows of a name list's length: the filter walks the candidate's entries like the exact scoring does and saves its
+    // memory round trips -- on rows of 60 entries (a record of two lines, fifteen units) it costs more than it saves (100 k
+    // long names, SG_Q8 = 1 / 0: 8.9 / 5.8 ms; profiles/r05_family_sweep_q8.log).  SG_Q8=1 forces it for any length.
+    // Where the bar lies (round 6, scripts/q8_band_sweep.py, profiles/r06b_q8_band_sweep.log: 100 k rows cut to 16 .. 57 entries a
+    // row): with the records is the faster up to 45 entries a row (by 3 - 30 %), level at 50, and 50 - 75 % slower at 57 (rows
+    // beyond 60 entries have no copy and pass unseen, a record of two lines costs fifteen units) -- 40 in round 5, 45 now.
+    const bool q8_forced = ctx->opt_is("SG_Q8", '1');
+    pl.want_q8 = pl.want_pruned && !(flags & SG_POSTINGS_TILE_FORM) && B->n_cols < ((int64_t)1 << 24) && !ctx->opt_is("SG_Q8", '0') &&
+                 (q8_forced || (double)B->nnz <= 45.0 * (double)B->n_rows) &&
+                 (ctx->total_mem == 0 || (size_t)SG_Q8_STRIDE * ((size_t)B->n_rows + 1) < ctx->total_mem / 16);
+    pl.will_filter = pl.want_pruned && sg_pruned_supports_tile(pl.tile_log2) &&
+                     (B->n_cols + 1) * ((pl.n_tiles + 3) & ~(int64_t)3) < ((int64_t)1 << 30);
+    // rows at a fixed stride for the exact scoring (opt-in; what it takes and what it costs: row_block_bytes)
+    pl.want_blk = ctx->opt_is("SG_ROW_BLOCKS", '1');
+    pl.permute = !(flags & SG_POSTINGS_NO_PERMUTATION);
+    pl.early_rows = pl.will_filter && !pl.want_blk && pl.permute && B->n_rows > 0;
+    // The postings proper ({accumulator slot, value}: 8 bytes each, 100 MB at 663 k) are what the EXACT kernel streams.  When
+    // the pruned multiply will take the product they are only needed for the rows it hands over (wider than 128 non-zeros
+    // ...: none in a list of names), and scattering them is half of the index build: they are then written on demand
+    // (sg_postings_ensure_full), from the same segment table.
+    // the tile's counters fit in LDS: one workgroup per tile (part), LDS atomics (otherwise global ones)
+    pl.lds_path = B->n_rows > 0 && lds_counter_bytes(B->n_cols) <= 124 * 1024 && B->n_cols > 0;
+    if (const char *e = ctx->opt("SG_POSTINGS_LDS")) pl.lds_path = pl.lds_path && e[0] != '0';
+    pl.lazy_full = pl.will_filter && pl.lds_path && !ctx->opt_is("SG_POSTINGS_LAZY", '0');
+    if (pl.will_filter) {
+        pl.nt_pad = (int32_t)((pl.n_tiles + 3) & ~(int64_t)3);
+        // stream form of the pruned multiply (sg_spgemm_pruned.hip): eight tiles share one accumulator tile
+        if (pl.tile_log2 == 12 && !ctx->opt_is("SG_K4_STREAM", '0')) pl.fold_log2 = 3;
+        if (pl.fold_log2 > 0) {
+            const int64_t n_super = (pl.n_tiles + ((int64_t)1 << pl.fold_log2) - 1) >> pl.fold_log2;
+            pl.nv_pad = (int32_t)((n_super + 3) & ~(int64_t)3);
+        }
+        // a term is "frequent" when it occurs in at least this share of the right-hand rows: the suffix of a
+        // left row is drawn from frequent terms only, which lets the survivor test use each candidate's own
+        // frequent-part norm instead of 1 (profiles/r01_prune_tuning.log)
+        double frac = 0.005;   // (round 5, with the second filter: 0.0045 -> 0.005, 30.8 M -> 22.5 M candidates, kernel - 2 % at 663 k; 0.004 + 5 %, 0.007 + 4 %)
+        if (const char *v = ctx->opt("SG_PRUNE_FREQ")) frac = atof(v);
+        const double fm = frac * (double)B->n_rows;
+        pl.freq_min = fm < 1.0 ? 1u : (uint32_t)fm;
+    }
+    if (pl.lds_path) {
+        // Round 6: filter postings staged in LDS and written cell by cell (postings_fill_staged) -- when only the filter
+        // postings are written (the exact kernel's are lazy) and a chunk of at least 64 rows fits the stage.  The stage
+        // takes what the packed counters leave of 158 KiB: one workgroup per CU, so tiles are split until there are two
+        // workgroups per CU (parts of >= 512 rows) and a launch does not end with a few CUs working alone.
+        pl.staged = pl.lazy_full && !ctx->opt_is("SG_FILL_STAGED", '0');
+        const double mean_nnz = B->n_rows > 0 ? (double)B->nnz / (double)B->n_rows : 1.0;
+        if (pl.staged) {
+            const size_t fixed0 = ((((size_t)B->n_cols + 1) / 2 + 3) & ~(size_t)3) * 4 + (((size_t)B->n_cols + 31) / 32) * 4 + 32 * 4;
+            pl.chunk_rows = 2048;
+            for (;;) {
+                const size_t fixed = fixed0 + (size_t)pl.chunk_rows * 4;
+                const size_t room = fixed + 16384 < 158 * 1024 ? 158 * 1024 - fixed : 0;
+                pl.stage_cap = (uint32_t)(room / 4);
+                if (pl.stage_cap > 65535u) pl.stage_cap = 65535u;
+                if ((double)pl.chunk_rows * mean_nnz * 1.2 + 64.0 <= (double)pl.stage_cap || pl.chunk_rows <= 64) break;
+                pl.chunk_rows >>= 1;
+            }
+            pl.staged = (double)pl.chunk_rows * mean_nnz * 1.2 + 64.0 <= (double)pl.stage_cap;
+            pl.staged_lds = fixed0 + (size_t)pl.chunk_rows * 4 + (size_t)pl.stage_cap * 4;
+            if (const char *v = ctx->opt("SG_FILL_STAGE_CAP"))    // test hook: chunks that do not fit go posting by posting
+                if (atoi(v) > 0 && (uint32_t)atoi(v) < pl.stage_cap) pl.stage_cap = (uint32_t)atoi(v);
+        }
+        // fewer tiles than CUs: split every tile between 2 or 4 workgroups (parts of >= 1024 rows)
+        int32_t split = 1;
+        while (split < 4 && pl.n_tiles * split < ctx->num_cu && (tile_cols / (split * 2)) >= 1024 &&
+               (pl.n_bins * split * 2 + 1) < ((int64_t)1 << 31))
+            split *= 2;
+        if (pl.staged)
+            while (split < 8 && pl.n_tiles * split < 2 * (int64_t)ctx->num_cu && (tile_cols / (split * 2)) >= 512 &&
+                   (pl.n_bins * split * 2 + 1) < ((int64_t)1 << 31))
+                split *= 2;
+        if (const char *e = ctx->opt("SG_POSTINGS_SPLIT")) {
+            const int o = atoi(e);
+            if ((o == 1 || o == 2 || o == 4) && tile_cols / o >= 64 && pl.n_bins * o + 1 < ((int64_t)1 << 31)) split = o;
+        }
+        pl.split = split;
+    }
+    *out = pl;
+    return SG_OK;
+}
+
+// the packed rows of the pruned multiply are written by the same pass that copies the rows into position order
+// ... and so are the 8-bit copies of the second filter
+struct EarlyRows {
+    void *fwd = nullptr;
+    uint32_t *fwd_ptr = nullptr;
+    void *q8 = nullptr;
+    bool written = false;   // build_permuted made the copy and filled them
+};
+
+static int alloc_early_rows(Scratch &early, const sg_csr *B, const BuildPlan &plan, EarlyRows *rows) {
+    if (!plan.early_rows) return SG_OK;
+    SG_TRY(early.alloc_bytes(((size_t)B->nnz + 8) * (B->dtype == SG_F64 ? 16 : 8), &rows->fwd));
+    SG_TRY(early.alloc(2 * ((size_t)B->n_rows + 2), &rows->fwd_ptr));
+    if (plan.want_q8) SG_TRY(early.alloc_bytes((size_t)SG_Q8_STRIDE * ((size_t)B->n_rows + 1), &rows->q8));
+    return SG_OK;
+}
+
 static uint64_t gcd_u64(uint64_t a, uint64_t b) {
     while (b) {
         const uint64_t t = a % b;
@@ -964,16 +1160,11 @@ static uint64_t gcd_u64(uint64_t a, uint64_t b) {
     return a;
 }
 
-// B with its rows in position order + the two tables; *out_perm stays null when the permutation is off or pointless
-static int build_permuted(sg_ctx *ctx, const sg_csr *B, int64_t tile_cols, sg_csr **out_perm, uint32_t **out_orig_of,
-                          uint32_t **out_pos_of, SgCollapse *pending /* B = pending->unique, its rows not written yet; or null */,
-                          uint32_t *fwd_ptr, void *fwd /* packed rows to write along (null: none) */, bool *fwd_done,
-                          void *q8 = nullptr /* 8-bit copies to write along */, float inv_norm = 0.f) {
-    *fwd_done = false;
-    *out_perm = nullptr;
-    *out_orig_of = *out_pos_of = nullptr;
-    const char *e = ctx->opt("SG_PERMUTE");
-    if ((e && e[0] == '0') || B->n_rows <= 2 * tile_cols || B->n_rows >= ((int64_t)1 << 31) || B->nnz <= 0) return SG_OK;
+// B with its rows in position order + the two tables, into p; p->permuted stays null when the permutation is off or pointless
+static int build_permuted(sg_ctx *ctx, const sg_csr *B, int64_t tile_cols, sg_postings *p,
+                          SgCollapse *pending /* B = pending->unique, its rows not written yet; or null */,
+                          EarlyRows *rows /* packed rows and 8-bit copies to write along (null members: none) */, float inv_norm) {
+    if (ctx->opt_is("SG_PERMUTE", '0') || B->n_rows <= 2 * tile_cols || B->n_rows >= ((int64_t)1 << 31) || B->nnz <= 0) return SG_OK;
     const uint64_t n = (uint64_t)B->n_rows;
     uint64_t mult = (uint64_t)(0.6180339887498949 * (double)n) | 1ull;
     while (gcd_u64(mult, n) != 1) mult += 2;
@@ -991,7 +1182,8 @@ static int build_permuted(sg_ctx *ctx, const sg_csr *B, int64_t tile_cols, sg_cs
         }
         minv = (uint64_t)(t0 < 0 ? t0 + (long long)n : t0);
     }
-    uint32_t *orig_of = nullptr, *pos_of = nullptr, *len_by_pos = nullptr;
+    Scratch scratch(ctx);   // (the five arrays are the index's and the copy's once the copy exists)
+    uint32_t *orig_of = nullptr, *pos_of = nullptr;
     int64_t *ptr = nullptr;
     int32_t *idx = nullptr;
     void *val = nullptr;
@@ -999,57 +1191,323 @@ static int build_permuted(sg_ctx *ctx, const sg_csr *B, int64_t tile_cols, sg_cs
     // the rows of B itself, or -- B the representatives' matrix of `pending`, not written -- of the matrix they come from
     const bool from_groups = pending && pending->pending_src;
     const bool by_group = from_groups && pending->d_rep_len != nullptr;   // (table path: start and length per group; else B's row pointers are there)
-    int st = sg_alloc(ctx, (size_t)n + 1, &orig_of);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &pos_of);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 2, &ptr);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)B->nnz + 64, &idx);
-    if (st == SG_OK) st = ctx->alloc(((size_t)B->nnz + 64) * vs, &val);
-    if (st == SG_OK)
-        st = sg_scan_launch<int64_t>(ctx, PermutedLenLoad{n, minv, (uint64_t)(~0ull / n) + 1ull, by_group ? pending->d_rep_len : (const int32_t *)nullptr, B->d_indptr, pos_of, orig_of},
-                                     SgScanStoreArray<int64_t>{ptr}, (int64_t)n, ptr + n);
-    if (st == SG_OK) {
-        const unsigned grid = (unsigned)((((n + 1 + SG_GATHER_ROWS - 1) / SG_GATHER_ROWS) * 16 + 255) / 256);
-        const sg_csr *src = from_groups ? pending->pending_src : B;
-        const uint32_t *rep_rows = from_groups ? pending->d_rep_rows : nullptr;
-        const int64_t *rep_start = by_group ? pending->d_rep_start : nullptr;
-        const int32_t *rep_len = by_group ? pending->d_rep_len : nullptr;
-        if (B->dtype == SG_F64)
-            hipLaunchKernelGGL(gather_rows_kernel<double>, dim3(grid), dim3(256), 0, ctx->stream, src->d_indptr, src->d_indices,
-                               (const double *)src->d_data, B->n_rows, (const uint32_t *)orig_of, rep_rows, rep_start, rep_len,
-                               (const int64_t *)ptr, idx, (double *)val, fwd_ptr, fwd, (uint4 *)(fwd_ptr ? q8 : nullptr), inv_norm);
-        else
-            hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(grid), dim3(256), 0, ctx->stream, src->d_indptr, src->d_indices,
-                               (const float *)src->d_data, B->n_rows, (const uint32_t *)orig_of, rep_rows, rep_start, rep_len,
-                               (const int64_t *)ptr, idx, (float *)val, fwd_ptr, fwd, (uint4 *)(fwd_ptr ? q8 : nullptr), inv_norm);
-        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-        if (st == SG_OK) *fwd_done = fwd_ptr != nullptr;     // (the representatives' matrix in group order stays pending)
-    }
-    ctx->release(len_by_pos);
-    sg_csr *m = st == SG_OK ? new (std::nothrow) sg_csr() : nullptr;
-    if (st == SG_OK && !m) st = SG_ERR_OOM;
-    if (st != SG_OK) {
-        ctx->release(orig_of);
-        ctx->release(pos_of);
-        ctx->release(ptr);
-        ctx->release(idx);
-        ctx->release(val);
-        return st;
-    }
+    SG_TRY(scratch.alloc((size_t)n + 1, &orig_of));
+    SG_TRY(scratch.alloc((size_t)n + 1, &pos_of));
+    SG_TRY(scratch.alloc((size_t)n + 2, &ptr));
+    SG_TRY(scratch.alloc((size_t)B->nnz + 64, &idx));
+    SG_TRY(scratch.alloc_bytes(((size_t)B->nnz + 64) * vs, &val));
+    SG_TRY(sg_scan_launch<int64_t>(ctx, PermutedLenLoad{n, minv, (uint64_t)(~0ull / n) + 1ull, by_group ? pending->d_rep_len : (const int32_t *)nullptr, B->d_indptr, pos_of, orig_of},
+                                   SgScanStoreArray<int64_t>{ptr}, (int64_t)n, ptr + n));
+    const unsigned grid = (unsigned)((((n + 1 + SG_GATHER_ROWS - 1) / SG_GATHER_ROWS) * 16 + 255) / 256);
+    const sg_csr *src = from_groups ? pending->pending_src : B;
+    const uint32_t *rep_rows = from_groups ? pending->d_rep_rows : nullptr;
+    const int64_t *rep_start = by_group ? pending->d_rep_start : nullptr;
+    const int32_t *rep_len = by_group ? pending->d_rep_len : nullptr;
+    by_dtype(B->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(grid), dim3(256), 0, ctx->stream, src->d_indptr, src->d_indices,
+                           (const T *)src->d_data, B->n_rows, (const uint32_t *)orig_of, rep_rows, rep_start, rep_len,
+                           (const int64_t *)ptr, idx, (T *)val, rows->fwd_ptr, rows->fwd, (uint4 *)(rows->fwd_ptr ? rows->q8 : nullptr), inv_norm);
+        return SG_OK;
+    });
+    if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
+    sg_csr *m = new (std::nothrow) sg_csr();
+    if (!m) return SG_ERR_OOM;
+    rows->written = rows->fwd_ptr != nullptr;     // (the representatives' matrix in group order stays pending)
     m->ctx = ctx;
     m->n_rows = B->n_rows;
     m->n_cols = B->n_cols;
     m->nnz = B->nnz;
     m->dtype = B->dtype;
-    m->d_indptr = ptr;
-    m->d_indices = idx;
-    m->d_data = val;
+    m->d_indptr = scratch.keep(ptr);
+    m->d_indices = scratch.keep(idx);
+    m->d_data = scratch.keep(val);
     m->owned = true;
     m->props_state = B->props_state;         // same rows: same properties
     m->props_max_norm2 = B->props_max_norm2;
     m->props_max_nnz = B->props_max_nnz;
-    *out_perm = m;
-    *out_orig_of = orig_of;
-    *out_pos_of = pos_of;
+    p->permuted = m;
+    p->d_orig_of = scratch.keep(orig_of);
+    p->d_pos_of = scratch.keep(pos_of);
+    return SG_OK;
+}
+
+// rows at a fixed stride for the exact scoring, when the longest row fits 1 KiB (127 entries f32 / 63 f64)
+// (*out: the stride; 0: no blocks)
+static int row_block_bytes(sg_ctx *ctx, const sg_csr *B, uint32_t *out) {
+    *out = 0;
+    uint32_t max_nnz = 0;
+    bool cl = false;
+    float n2 = 0.f;
+    // the longest row is measured only for this (a vectoriser-made matrix, and what is derived from it, is known
+    // to be cosine-like without a look: sg_csr_props)
+    if (B->props_max_nnz == 0 && !B->d_props_words) B->props_state = 0;
+    SG_TRY(sg_csr_props(ctx, B, &cl, &n2, &max_nnz));
+    const size_t es = B->dtype == SG_F64 ? 16 : 8;
+    const size_t need = (((size_t)max_nnz + 1) * es + 127) / 128 * 128;
+    // Opt-in (SG_ROW_BLOCKS=1): the blocks cut the memory-side traffic of the multiply by a fifth (57.9 -> 43 GB per
+    // launch at 663 k) but not its time -- the kernel is not bound by bytes -- and their scorer's extra loop
+    // trips cost 0.3 - 0.7 ms (9.76 ms packed / 10.08 ms with 64-byte units / 10.50 ms with 32-byte units:
+    // profiles/r03_row_blocks_ab.log); the index build pays 0.11 ms for them.
+    if (need <= 1024 && (double)need * (double)B->n_rows < 3.5e9 &&
+        (ctx->total_mem == 0 || need * (size_t)B->n_rows < ctx->total_mem / 8))
+        *out = (uint32_t)need;
+    return SG_OK;
+}
+
+// the fields of the index and every array that lives as long as it does (B: the rows in position order, or B_in itself)
+static int alloc_index(sg_ctx *ctx, sg_postings *p, const sg_csr *B_in, const sg_csr *B, const BuildPlan &plan, int32_t flags,
+                       Scratch &early, EarlyRows *rows) {
+    p->n_right = B->n_rows;
+    p->n_terms = B->n_cols;
+    p->nnz = B->nnz;
+    p->dtype = B->dtype;
+    p->tile_log2 = plan.tile_log2;
+    p->tile_form = (flags & SG_POSTINGS_TILE_FORM) != 0;
+    p->built_from = borrowed(*B_in);
+    p->built_from_valid = true;
+    p->n_tiles = (int32_t)plan.n_tiles;
+    p->b_indptr = B_in->d_indptr;      // the caller's matrix: what "A is the matrix the postings were built from" compares
+    p->b_indices = B_in->d_indices;
+    p->b_data = B_in->d_data;
+    p->cosine_like = plan.cosine_like;
+    p->max_norm2 = plan.max_norm2;
+    p->src = borrowed(*B);
+    p->split = plan.split;
+    const size_t vs = 8;   // f64 value, or packed {row, f32 value}
+    SG_TRY(sg_alloc(ctx, (size_t)plan.n_bins + 1, &p->d_seg));
+    SG_TRY(sg_alloc(ctx, (size_t)B->n_cols + 1, &p->d_term_len));
+    if (!plan.lazy_full && B->dtype == SG_F64) SG_TRY(sg_alloc(ctx, (size_t)B->nnz + 64, &p->d_rows));
+    if (!plan.lazy_full) SG_TRY(ctx->alloc(((size_t)B->nnz + 64) * vs, &p->d_vals));
+    if (!plan.will_filter) return SG_OK;
+    if (plan.want_blk) {
+        SG_TRY(row_block_bytes(ctx, B, &p->blk_bytes));
+        if (p->blk_bytes) SG_TRY(ctx->alloc((size_t)p->blk_bytes * ((size_t)B->n_rows + 1), &p->d_blk));
+    }
+    if (rows->written) {          // written along with the rows' copy in position order (build_permuted)
+        p->d_fwd = early.keep(rows->fwd);
+        p->d_fwd_ptr = early.keep(rows->fwd_ptr);
+        p->d_q8 = early.keep(rows->q8);
+    } else {
+        if (!p->d_blk) SG_TRY(ctx->alloc(((size_t)B->nnz + 8) * (B->dtype == SG_F64 ? 16 : 8), &p->d_fwd));
+        SG_TRY(sg_alloc(ctx, 2 * ((size_t)B->n_rows + 2), &p->d_fwd_ptr));   // uint2 per row
+        if (plan.want_q8 && !p->d_blk) SG_TRY(ctx->alloc((size_t)SG_Q8_STRIDE * ((size_t)B->n_rows + 1), &p->d_q8));
+    }
+    // slack: the pruned multiply loads a lane's four slots of a segment unconditionally (<= 4 * 63 entries past it)
+    SG_TRY(sg_alloc(ctx, (size_t)B->nnz + 512, &p->d_filt));
+    // the stream form points lanes without a posting at the slack behind the array: entries that add 0 (bq = 0), each to
+    // an accumulator of its own (64 lanes adding to ONE LDS word are serialised: 3 ms at 663 k)
+    // (written by postings_tables_kernel on the LDS build path, by a launch of its own otherwise: below)
+    p->nt_pad = plan.nt_pad;
+    SG_TRY(sg_alloc(ctx, (size_t)(B->n_cols + 1) * (size_t)p->nt_pad + 4, &p->d_ends));
+    p->fold_log2 = plan.fold_log2;
+    p->nv_pad = plan.nv_pad;
+    if (p->fold_log2 > 0) SG_TRY(sg_alloc(ctx, (size_t)(B->n_cols + 1) * (size_t)p->nv_pad + 4, &p->d_ends8));
+    p->norm_up = plan.norm_up;
+    p->freq_min = plan.freq_min;
+    return SG_OK;
+}
+
+// LDS path: count -> column scan -> fill over the rows of p->src, one workgroup per tile (part).  The build makes the terms'
+// list lengths, their frequent flags and the lists' starts on the way and writes the filter postings too; `values_only`
+// (sg_postings_ensure_full) re-reads the starts and writes the postings proper alone.
+static int lds_count_scan_fill(sg_ctx *ctx, sg_postings *p, uint32_t *cnt /* [workgroup][term] (see postings_count_lds) */,
+                               uint32_t *term_len, uint8_t *is_frequent, bool values_only, bool fill) {
+    const sg_csr *B = &p->src;
+    const int32_t split = p->split > 0 ? p->split : 1;
+    const int64_t wgs64 = (int64_t)p->n_tiles * split;
+    const unsigned wgs = (unsigned)wgs64;
+    const size_t lds = lds_counter_bytes(B->n_cols);
+    uint32_t *filt = values_only ? nullptr : p->d_filt;
+    const float inv_norm = filt ? 1.0f / p->norm_up : 0.f;
+    const int32_t fold_log2 = values_only ? 0 : p->fold_log2;
+    SG_TRY(allow_dynamic_lds<postings_count_lds>(124 * 1024));
+    hipLaunchKernelGGL(postings_count_lds, dim3(wgs), dim3(1024), (size_t)B->n_cols * 4, ctx->stream, B->d_indptr, B->d_indices,
+                       B->n_rows, p->tile_log2, (int32_t)B->n_cols, split, cnt);
+    hipLaunchKernelGGL(postings_colscan_kernel, dim3((unsigned)((B->n_cols + 63) / 64)), dim3(1024), 0, ctx->stream, cnt,
+                       (int32_t)wgs64, (int32_t)B->n_cols, values_only ? 0u : p->freq_min, term_len, is_frequent);
+    // the terms' lists back to back: starts of the lists, the last entry receives the total (= nnz)
+    if (!values_only) SG_TRY(sg_exclusive_scan_u32(ctx, term_len, p->d_term_start, B->n_cols, p->d_term_start + B->n_cols));
+    if (fill)
+        SG_TRY(by_dtype(B->dtype, [&](auto tag) -> int {
+            using T = decltype(tag);
+            constexpr auto kern = postings_fill_lds<T>;
+            SG_TRY(allow_dynamic_lds<kern>(124 * 1024));
+            hipLaunchKernelGGL(kern, dim3(wgs), dim3(1024), lds, ctx->stream, B->d_indptr, B->d_indices,
+                               (const T *)B->d_data, B->n_rows, p->tile_log2, (int32_t)B->n_cols, split, (const uint32_t *)cnt,
+                               (const uint32_t *)p->d_term_start, (const uint8_t *)is_frequent, p->d_rows, (T *)p->d_vals, filt,
+                               inv_norm, fold_log2);
+            return SG_OK;
+        }));
+    return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
+}
+
+static int fill_lds_path(sg_ctx *ctx, sg_postings *p, const BuildPlan &plan) {
+    const sg_csr *B = &p->src;
+    const unsigned wgs = (unsigned)((int64_t)p->n_tiles * plan.split);
+    Scratch scratch(ctx);
+    uint32_t *cnt = nullptr;
+    uint8_t *is_frequent = nullptr;
+    SG_TRY(scratch.alloc((size_t)((int64_t)p->n_tiles * plan.split * B->n_cols) + 1, &cnt));
+    SG_TRY(scratch.alloc((size_t)B->n_cols + 4, &is_frequent));
+    SG_TRY(sg_alloc(ctx, (size_t)B->n_cols + 2, &p->d_term_start));
+    // (the staged fill comes after the tables: it advances the workgroups' rows of `cnt`)
+    SG_TRY(lds_count_scan_fill(ctx, p, cnt, p->d_term_len, is_frequent, /*values_only=*/false, /*fill=*/!plan.staged));
+    // the tables kernel writes the null postings and the scoring context as well (write_aux has them on the other path)
+    if (p->d_fwd_ptr) SG_TRY(ctx->alloc(256, (void **)&p->d_score_ctx));
+    hipLaunchKernelGGL(postings_tables_kernel, dim3((unsigned)((B->n_cols + 64) / 64)), dim3(1024), 0, ctx->stream, (const uint32_t *)cnt,
+                       (const uint32_t *)p->d_term_start, (int32_t)B->n_cols, p->n_tiles, plan.split, p->d_seg, p->d_ends,
+                       p->nt_pad, p->d_ends8, p->nv_pad, p->fold_log2, score_ctx_of(p), p->d_score_ctx,
+                       p->d_filt ? p->d_filt + B->nnz : (uint32_t *)nullptr);
+    if (plan.staged)
+        SG_TRY(by_dtype(B->dtype, [&](auto tag) -> int {
+            using T = decltype(tag);
+            constexpr auto kern = postings_fill_staged<T>;
+            SG_TRY(allow_dynamic_lds<kern>(160 * 1024));
+            hipLaunchKernelGGL(kern, dim3(wgs), dim3(1024), plan.staged_lds, ctx->stream, B->d_indptr,
+                               B->d_indices, (const T *)B->d_data, B->n_rows, p->tile_log2, (int32_t)B->n_cols, plan.split,
+                               plan.chunk_rows, plan.stage_cap, cnt, (const uint32_t *)p->d_term_start, (const uint8_t *)is_frequent,
+                               p->d_filt, 1.0f / p->norm_up, p->fold_log2);
+            return SG_OK;
+        }));
+    return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
+}
+
+// the counters do not fit in LDS: global ones, one thread per row
+static int fill_global_path(sg_ctx *ctx, sg_postings *p, const BuildPlan &plan) {
+    const sg_csr *B = &p->src;
+    const int64_t n_bins = plan.n_bins;
+    // one thread per slot of the (tile x row-in-tile) grid: covers every row, see row_of_thread
+    const unsigned grid = (unsigned)((((int64_t)p->n_tiles << p->tile_log2) + 255) / 256);
+    const float inv_norm = p->d_filt ? 1.0f / p->norm_up : 0.f;
+    Scratch scratch(ctx);
+    uint32_t *cursor = nullptr;
+    SG_TRY(scratch.alloc((size_t)n_bins + 1, &cursor));
+    SG_HIP_TRY(hipMemsetAsync(p->d_seg, 0, sizeof(uint32_t) * (size_t)(n_bins + 1), ctx->stream));
+    SG_HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(uint32_t) * (size_t)(n_bins + 1), ctx->stream));
+    if (grid > 0) {
+        by_dtype(B->dtype, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(postings_count<T>, dim3(grid), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices, B->n_rows,
+                               p->tile_log2, p->n_tiles, p->d_seg);
+            return SG_OK;
+        });
+        SG_HIP_TRY(hipGetLastError());
+    }
+    // counts -> offsets, in place; seg[n_bins] receives the total (= nnz)
+    SG_TRY(sg_exclusive_scan_u32(ctx, p->d_seg, p->d_seg, n_bins, p->d_seg + n_bins));
+    if (grid > 0) {
+        by_dtype(B->dtype, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(postings_fill<T>, dim3(grid), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
+                               (const T *)B->d_data, B->n_rows, p->tile_log2, p->n_tiles, p->d_seg, cursor, p->d_rows,
+                               (T *)p->d_vals, p->d_filt, p->freq_min, inv_norm, p->fold_log2);
+            return SG_OK;
+        });
+        if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
+    }
+    return SG_OK;
+}
+
+// (the path with global counters builds the term-major table itself; lists and ends are read off it)
+static int tables_from_seg(sg_ctx *ctx, sg_postings *p) {
+    if (p->n_terms <= 0) return SG_OK;
+    hipLaunchKernelGGL(term_len_kernel, dim3((unsigned)((p->n_terms + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const uint32_t *)p->d_seg, p->n_terms, p->n_tiles, p->d_term_len);
+    if (p->d_ends || p->d_ends8)
+        hipLaunchKernelGGL(ends_from_seg_kernel, dim3((unsigned)((p->n_terms + 256) / 256)), dim3(256), 0, ctx->stream,
+                           (const uint32_t *)p->d_seg, p->n_terms, p->n_tiles, p->d_ends, p->nt_pad, p->d_ends8, p->nv_pad,
+                           p->fold_log2);
+    return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
+}
+
+// the rows as the pruned multiply's exact scoring reads them -- unless the copy into position order wrote them already
+static int pack_rows(sg_ctx *ctx, sg_postings *p, bool rows_written) {
+    const sg_csr *B = &p->src;
+    if (p->d_fwd && !rows_written) {   // (packed rows in use: no row blocks; the fused pass writes the pad itself)
+        // the exact scoring reads packed rows in rounds of eight entries and multiplies the slots past a row's end by
+        // a = 0: the pad behind the LAST row must hold finite values (0 * NaN would poison that row's score)
+        const size_t es = B->dtype == SG_F64 ? 16 : 8;
+        if (hipMemsetAsync((char *)p->d_fwd + (size_t)B->nnz * es, 0, 8 * es, ctx->stream) != hipSuccess) return SG_ERR_HIP;
+    }
+    if (p->d_blk && B->n_rows > 0) {
+        const int64_t work = B->n_rows * (int64_t)(p->blk_bytes / 16);
+        const unsigned g3 = (unsigned)((work + 255) / 256);
+        by_dtype(B->dtype, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(row_blocks_kernel<T>, dim3(g3), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
+                               (const T *)B->d_data, B->n_rows, (const uint32_t *)p->d_orig_of, p->blk_bytes, p->d_blk);
+            return SG_OK;
+        });
+        if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
+    }
+    if (p->d_fwd_ptr && !rows_written) {
+        const int64_t work = B->nnz > B->n_rows + 1 ? B->nnz : B->n_rows + 1;
+        const unsigned g2 = (unsigned)((work + 255) / 256);
+        const unsigned g4 = (unsigned)((B->n_rows * 16 + 255) / 256);
+        by_dtype(B->dtype, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(fwd_pack<T>, dim3(g2), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
+                               (const T *)B->d_data, B->n_rows, B->nnz, (const uint32_t *)p->d_orig_of, p->d_fwd_ptr, p->d_fwd);
+            if (p->d_q8 && B->n_rows > 0)
+                hipLaunchKernelGGL(q8_pack_kernel<T>, dim3(g4), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
+                                   (const T *)B->d_data, B->n_rows, (const uint32_t *)p->d_orig_of, (uint4 *)p->d_q8, 1.0f / p->norm_up);
+            return SG_OK;
+        });
+        if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
+    }
+    return SG_OK;
+}
+
+// the null postings and the scoring context, where the tables kernel has not written them (the path with global counters)
+static int write_aux(sg_ctx *ctx, sg_postings *p) {
+    if (p->d_filt) {
+        hipLaunchKernelGGL(null_postings_kernel, dim3(2), dim3(256), 0, ctx->stream, p->d_filt + p->nnz);
+        if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
+    }
+    if (p->d_fwd_ptr) {
+        SG_TRY(ctx->alloc(256, (void **)&p->d_score_ctx));
+        hipLaunchKernelGGL(score_ctx_kernel, dim3(1), dim3(1), 0, ctx->stream, score_ctx_of(p), p->d_score_ctx);
+        if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
+    }
+    return SG_OK;
+}
+
+// the index over the rows of B_in; `pending`: B_in is the representatives' matrix of these groups, its rows not written yet
+static int build_index(sg_ctx *ctx, const sg_csr *B_in, int32_t tile_cols, int32_t flags, SgCollapse *pending,
+                       std::optional<SgTimer> &timer, sg_postings **out) {
+    bool cosine_like = false;
+    float max_norm2 = 0.f;
+    SG_TRY(sg_csr_props(ctx, B_in, &cosine_like, &max_norm2));
+    BuildPlan plan;
+    SG_TRY(plan_build(ctx, B_in, tile_cols, flags, cosine_like, max_norm2, &plan));
+    if (!timer) timer.emplace(ctx, SG_K_POSTINGS);   // the whole build, the permuted copy included
+    PostingsPtr p(new (std::nothrow) sg_postings());
+    if (!p) return SG_ERR_OOM;
+    p->ctx = ctx;
+    Scratch early(ctx);   // (after p: goes back before a half-built index does)
+    EarlyRows rows;
+    SG_TRY(alloc_early_rows(early, B_in, plan, &rows));
+    if (plan.permute) SG_TRY(build_permuted(ctx, B_in, plan.tile_cols, p.get(), pending, &rows, 1.0f / plan.norm_up));
+    if (!rows.written) {
+        early.release(rows.fwd);
+        early.release(rows.fwd_ptr);
+        early.release(rows.q8);
+        rows = EarlyRows();
+    }
+    // no copy in position order was made: the index reads the representatives' matrix itself
+    if (pending && pending->pending_src && !p->permuted) SG_TRY(sg_collapse_materialize(ctx, pending));
+    const sg_csr *B = p->permuted ? p->permuted : B_in;   // everything below indexes right-hand rows by POSITION
+    SG_TRY(alloc_index(ctx, p.get(), B_in, B, plan, flags, early, &rows));
+    if (plan.lds_path) {
+        SG_TRY(fill_lds_path(ctx, p.get(), plan));
+    } else {
+        SG_TRY(fill_global_path(ctx, p.get(), plan));
+        SG_TRY(tables_from_seg(ctx, p.get()));
+    }
+    SG_TRY(pack_rows(ctx, p.get(), rows.written));
+    if (!plan.lds_path) SG_TRY(write_aux(ctx, p.get()));
+    *out = p.release();
     return SG_OK;
 }
 
@@ -1057,556 +1515,66 @@ extern "C" int sg_postings_build(sg_ctx *ctx, const sg_csr *B, int32_t tile_cols
     return sg_postings_build_flags(ctx, B, tile_cols, 0, out);
 }
 
-// internal flags of sg_postings_build_flags (above the public ones)
-#define SG_POSTINGS_INNER (1 << 9)         // called by the collapse wrapper: the wrapper's timer covers the build
-// (SG_POSTINGS_NO_COLLAPSE, SG_POSTINGS_EXACT_ONLY, SG_POSTINGS_TILE_FORM: sg_internal.h)
-
-// the groups whose representatives' rows the inner build of sg_postings_build_flags is to write (handed from the outer call
-// to the inner one of the same thread)
-static thread_local SgCollapse *tl_pending_groups = nullptr;
-
+// (internal flags, above the public ones -- SG_POSTINGS_NO_COLLAPSE, SG_POSTINGS_EXACT_ONLY, SG_POSTINGS_TILE_FORM: sg_internal.h)
 extern "C" int sg_postings_build_flags(sg_ctx *ctx, const sg_csr *B_in, int32_t tile_cols, int32_t flags, sg_postings **out) {
     SG_REQUIRE(ctx && B_in && out, "null argument");
-    SgCollapse *pending = tl_pending_groups;
-    tl_pending_groups = nullptr;
-    if (!(flags & SG_POSTINGS_NO_COLLAPSE)) {
+    const bool group = !(flags & SG_POSTINGS_NO_COLLAPSE);
+    std::optional<SgTimer> timer;
+    SgCollapse *col = nullptr;
+    if (group) {
         // identical rows (identical strings): one representative per group is indexed (sg_collapse.hip)
         bool cl = false;
         float n2 = 0.f;
         SG_TRY(sg_csr_props(ctx, B_in, &cl, &n2));
-        SgCollapse *col = nullptr;
-        SgTimer timer(ctx, SG_K_POSTINGS);   // grouping + the index over the representatives
+        timer.emplace(ctx, SG_K_POSTINGS);   // grouping + the index over the representatives
         if (cl) SG_TRY(sg_collapse_build(ctx, B_in, &col, /*left_side=*/false, /*defer_rows=*/true));
-        if (col) {
-            sg_postings *inner = nullptr;
-            tl_pending_groups = col;      // (the inner build writes the representatives' rows with its own copies of them)
-            const int st = sg_postings_build_flags(ctx, col->unique, tile_cols, flags | SG_POSTINGS_NO_COLLAPSE | SG_POSTINGS_INNER, &inner);
-            tl_pending_groups = nullptr;
-            if (st != SG_OK) {
-                sg_collapse_free(col);
-                return st;
-            }
-            inner->collapse = col;
-            inner->caller_b_copy = *B_in;
-            inner->caller_b_copy.owned = false;
-            inner->caller_b_copy.d_props_words = nullptr;
-            inner->caller_b_copy.left_groups = nullptr;
-            inner->caller_b_copy.left_state = 0;
-            inner->caller_b = &inner->caller_b_copy;
-            inner->n_right_caller = B_in->n_rows;
-            inner->build_tile_cols = tile_cols;
-            inner->build_flags = flags;
-            *out = inner;
-            return SG_OK;
-        }
-        flags |= SG_POSTINGS_INNER;          // (no groups: this call goes on under the timer above)
-        const int st = sg_postings_build_flags(ctx, B_in, tile_cols, flags | SG_POSTINGS_NO_COLLAPSE, out);
-        if (st == SG_OK) {
-            (*out)->build_tile_cols = tile_cols;
-            (*out)->build_flags = flags & 0xff;
-        }
-        return st;
     }
-    const sg_csr *B = B_in;
-    // cosine-like right-hand sides (non-negative, sorted rows, norms <= 1: TF-IDF) take the pruned multiply,
-    // whose 16-bit accumulators make a 4096-column tile 8 KiB; everything else the exact kernel with 8 KiB
-    // of float / double accumulators per wave
-    bool cosine_like = false;
-    float max_norm2 = 0.f;
-    SG_TRY(sg_csr_props(ctx, B, &cosine_like, &max_norm2));
-    const char *pr = ctx->opt("SG_PRUNE");
-    const bool want_pruned = cosine_like && !(pr && pr[0] == '0') && !(flags & SG_POSTINGS_EXACT_ONLY);
-    if (tile_cols == 0) {
-        tile_cols = B->dtype == SG_F64 ? 1024 : 2048;
-        if (want_pruned) {
-            tile_cols = 4096;
-            if (flags & SG_POSTINGS_TILE_FORM) tile_cols = 2048;   // (the tile-by-tile form's own index: sg_spgemm_topn.hip, "which form")
-            else if (const char *v = ctx->opt("SG_PRUNE_TILE")) tile_cols = atoi(v) == 13 ? 8192 : (atoi(v) == 11 ? 2048 : 4096);
-        }
-    }
-    SG_REQUIRE(tile_cols >= 256 && tile_cols <= 32768 && (tile_cols & (tile_cols - 1)) == 0,
-               "tile_cols must be a power of two in [256, 32768]");
-    int64_t max_entries = (int64_t)1 << 29;   // the multiply addresses postings with 32-bit BYTE offsets (8 B entries)
-    if (const char *v = ctx->opt("SG_MAX_POSTINGS")) {   // test hook: force the right-hand split at small sizes
-        const long long o = atoll(v);
-        if (o > 0 && o < max_entries) max_entries = o;
-    }
-    if (B->nnz + 64 >= max_entries) {
-        sg_set_error("right-hand matrix has %lld non-zeros; one postings block holds < 2^29 (use more right-hand blocks)",
-                     (long long)B->nnz);
-        return SG_ERR_OVERFLOW;
-    }
-    int32_t tile_log2 = 0;
-    while ((1 << tile_log2) < tile_cols) ++tile_log2;
-    const int64_t n_tiles64 = B->n_rows == 0 ? 1 : ((B->n_rows + tile_cols - 1) >> tile_log2);
-    const int64_t n_bins = B->n_cols * n_tiles64;
-    if (n_bins + 1 >= (int64_t)1 << 31) {
-        sg_set_error("segment table of %lld x %lld entries is too large; use more right-hand blocks",
-                     (long long)B->n_cols, (long long)n_tiles64);
-        return SG_ERR_OVERFLOW;
-    }
-    sg_csr *permuted = nullptr;
-    uint32_t *orig_of = nullptr, *pos_of = nullptr;
-    SgTimer *timer = (flags & SG_POSTINGS_INNER) ? nullptr : new (std::nothrow) SgTimer(ctx, SG_K_POSTINGS);   // the whole build, the permuted copy included
-    struct TimerGuard {
-        SgTimer *t;
-        ~TimerGuard() { delete t; }
-    } timer_guard{timer};
-    // the packed rows of the pruned multiply are written by the same pass that copies the rows into position order
-    void *early_fwd = nullptr;
-    uint32_t *early_fwd_ptr = nullptr;
-    void *early_q8 = nullptr;   // ... and so are the 8-bit copies of the second filter
-    const float norm_up_build = __builtin_nextafterf(sqrtf(max_norm2) * 1.000001f, 2.f);   // (= p->norm_up below)
-    // second filter: terms must fit 24 bits; a sixteenth of the device memory at most; SG_Q8=0 switches it off
-    // ... and rows of a name list's length: the filter walks the candidate's entries like the exact scoring does and saves its
-    // memory round trips -- on rows of 60 entries (a record of two lines, fifteen units) it costs more than it saves (100 k
-    // long names, SG_Q8 = 1 / 0: 8.9 / 5.8 ms; profiles/r05_family_sweep_q8.log).  SG_Q8=1 forces it for any length.
-    // Where the bar lies (round 6, scripts/q8_band_sweep.py, profiles/r06b_q8_band_sweep.log: 100 k rows cut to 16 .. 57 entries a
-    // row): with the records is the faster up to 45 entries a row (by 3 - 30 %), level at 50, and 50 - 75 % slower at 57 (rows
-    // beyond 60 entries have no copy and pass unseen, a record of two lines costs fifteen units) -- 40 in round 5, 45 now.
-    const bool q8_forced = ctx->opt("SG_Q8") && ctx->opt("SG_Q8")[0] == '1';
-    const bool want_q8 = want_pruned && !(flags & SG_POSTINGS_TILE_FORM) && B_in->n_cols < ((int64_t)1 << 24) && !(ctx->opt("SG_Q8") && ctx->opt("SG_Q8")[0] == '0') &&
-                         (q8_forced || (double)B_in->nnz <= 45.0 * (double)B_in->n_rows) &&
-                         (ctx->total_mem == 0 || (size_t)SG_Q8_STRIDE * ((size_t)B_in->n_rows + 1) < ctx->total_mem / 16);
-    bool fwd_done = false;
-    bool aux_written = false;   // the scoring context and the null postings were written by the tables kernel
-    {
-        const bool filt = want_pruned && sg_pruned_supports_tile(tile_log2) &&
-                          (B->n_cols + 1) * ((n_tiles64 + 3) & ~(int64_t)3) < ((int64_t)1 << 30);
-        const bool blk = ctx->opt("SG_ROW_BLOCKS") && ctx->opt("SG_ROW_BLOCKS")[0] == '1';
-        if (filt && !blk && !(flags & SG_POSTINGS_NO_PERMUTATION) && B_in->n_rows > 0) {
-            int st0 = ctx->alloc(((size_t)B_in->nnz + 8) * (B_in->dtype == SG_F64 ? 16 : 8), &early_fwd);
-            if (st0 == SG_OK) st0 = sg_alloc(ctx, 2 * ((size_t)B_in->n_rows + 2), &early_fwd_ptr);
-            if (st0 == SG_OK && want_q8) st0 = ctx->alloc((size_t)SG_Q8_STRIDE * ((size_t)B_in->n_rows + 1), &early_q8);
-            if (st0 != SG_OK) {
-                ctx->release(early_fwd);
-                ctx->release(early_fwd_ptr);
-                return st0;
-            }
-        }
-    }
-    if (!(flags & SG_POSTINGS_NO_PERMUTATION)) {
-        const int stp = build_permuted(ctx, B_in, tile_cols, &permuted, &orig_of, &pos_of, pending, early_fwd_ptr, early_fwd, &fwd_done,
-                                       early_q8, 1.0f / norm_up_build);
-        if (stp != SG_OK) {
-            ctx->release(early_fwd);
-            ctx->release(early_fwd_ptr);
-            ctx->release(early_q8);
-            return stp;
-        }
-    }
-    if (!fwd_done) {
-        ctx->release(early_fwd);
-        ctx->release(early_fwd_ptr);
-        ctx->release(early_q8);
-        early_fwd = nullptr;
-        early_fwd_ptr = nullptr;
-        early_q8 = nullptr;
-    }
-    if (pending && pending->pending_src && !permuted) {      // no copy in position order was made: the index reads the representatives' matrix itself
-        const int stm = sg_collapse_materialize(ctx, pending);
-        if (stm != SG_OK) {
-            sg_csr_free(permuted);
-            ctx->release(orig_of);
-            ctx->release(pos_of);
-            return stm;
-        }
-    }
-    if (permuted) B = permuted;   // everything below indexes right-hand rows by POSITION
-    sg_postings *p = new (std::nothrow) sg_postings();
-    if (!p) {
-        sg_csr_free(permuted);
-        ctx->release(orig_of);
-        ctx->release(pos_of);
-        ctx->release(early_fwd);
-        ctx->release(early_fwd_ptr);
-        ctx->release(early_q8);
-        return SG_ERR_OOM;
-    }
-    p->permuted = permuted;
-    p->d_orig_of = orig_of;
-    p->d_pos_of = pos_of;
-    p->ctx = ctx;
-    p->n_right = B->n_rows;
-    p->n_terms = B->n_cols;
-    p->nnz = B->nnz;
-    p->dtype = B->dtype;
-    p->tile_log2 = tile_log2;
-    p->tile_form = (flags & SG_POSTINGS_TILE_FORM) != 0;
-    p->built_from = *B_in;
-    p->built_from.owned = false;
-    p->built_from.d_props_words = nullptr;
-    p->built_from.left_groups = nullptr;
-    p->built_from.left_state = 0;
-    p->built_from_valid = true;
-    p->n_tiles = (int32_t)n_tiles64;
-    p->b_indptr = B_in->d_indptr;      // the caller's matrix: what "A is the matrix the postings were built from" compares
-    p->b_indices = B_in->d_indices;
-    p->b_data = B_in->d_data;
-    p->cosine_like = cosine_like;
-    p->max_norm2 = max_norm2;
-    const size_t vs = 8;   // f64 value, or packed {row, f32 value}
-    int st = sg_alloc(ctx, (size_t)n_bins + 1, &p->d_seg);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)B->n_cols + 1, &p->d_term_len);
-    // The postings proper ({accumulator slot, value}: 8 bytes each, 100 MB at 663 k) are what the EXACT kernel streams.  When
-    // the pruned multiply will take the product they are only needed for the rows it hands over (wider than 128 non-zeros
-    // ...: none in a list of names), and scattering them is half of the index build: they are then written on demand
-    // (sg_postings_ensure_full), from the same segment table.
-    const bool will_filter = want_pruned && sg_pruned_supports_tile(tile_log2) &&
-                             (B->n_cols + 1) * ((n_tiles64 + 3) & ~(int64_t)3) < ((int64_t)1 << 30);
-    const size_t lds_need = (size_t)B->n_cols * 4 + ((size_t)(B->n_cols + 31) / 32) * 4;
-    bool lds_path = B->n_rows > 0 && lds_need <= 124 * 1024 && B->n_cols > 0;
-    if (const char *e = ctx->opt("SG_POSTINGS_LDS")) lds_path = lds_path && e[0] != '0';
-    const bool lazy_full = will_filter && lds_path && !(ctx->opt("SG_POSTINGS_LAZY") && ctx->opt("SG_POSTINGS_LAZY")[0] == '0');
-    p->src = *B;
-    p->src.owned = false;
-    p->src.d_props_words = nullptr;
-    p->src.left_groups = nullptr;
-    p->src.left_state = 0;
-    if (st == SG_OK && !lazy_full && B->dtype == SG_F64) st = sg_alloc(ctx, (size_t)B->nnz + 64, &p->d_rows);
-    if (st == SG_OK && !lazy_full) st = ctx->alloc(((size_t)B->nnz + 64) * vs, &p->d_vals);
-    if (st == SG_OK && will_filter) {
-        {
-            // rows at a fixed stride for the exact scoring, when the longest row fits 1 KiB (127 entries f32 / 63 f64)
-            uint32_t max_nnz = 0;
-            bool cl = false;
-            float n2 = 0.f;
-            const bool want_blk = ctx->opt("SG_ROW_BLOCKS") && ctx->opt("SG_ROW_BLOCKS")[0] == '1';
-            if (want_blk) {
-                // the longest row is measured only for this (a vectoriser-made matrix, and what is derived from it, is known
-                // to be cosine-like without a look: sg_csr_props)
-                if (B->props_max_nnz == 0 && !B->d_props_words) B->props_state = 0;
-                st = sg_csr_props(ctx, B, &cl, &n2, &max_nnz);
-            }
-            const size_t es = B->dtype == SG_F64 ? 16 : 8;
-            const size_t need = (((size_t)max_nnz + 1) * es + 127) / 128 * 128;
-            // Opt-in (SG_ROW_BLOCKS=1): the blocks cut the memory-side traffic of the multiply by a fifth (57.9 -> 43 GB per
-            // launch at 663 k) but not its time -- the kernel is not bound by bytes -- and their scorer's extra loop
-            // trips cost 0.3 - 0.7 ms (9.76 ms packed / 10.08 ms with 64-byte units / 10.50 ms with 32-byte units:
-            // profiles/r03_row_blocks_ab.log); the index build pays 0.11 ms for them.
-            if (st == SG_OK && want_blk && need <= 1024 && (double)need * (double)B->n_rows < 3.5e9 &&
-                (ctx->total_mem == 0 || need * (size_t)B->n_rows < ctx->total_mem / 8)) {
-                p->blk_bytes = (uint32_t)need;
-                st = ctx->alloc(need * ((size_t)B->n_rows + 1), &p->d_blk);
-            }
-        }
-        if (early_fwd && !p->d_blk) {          // written along with the rows' copy in position order (build_permuted)
-            p->d_fwd = early_fwd;
-            p->d_fwd_ptr = early_fwd_ptr;
-            p->d_q8 = early_q8;
-            early_fwd = nullptr;
-            early_fwd_ptr = nullptr;
-            early_q8 = nullptr;
-        } else {
-            if (st == SG_OK && !p->d_blk) st = ctx->alloc(((size_t)B->nnz + 8) * (B->dtype == SG_F64 ? 16 : 8), &p->d_fwd);
-            if (st == SG_OK) st = sg_alloc(ctx, 2 * ((size_t)B->n_rows + 2), &p->d_fwd_ptr);   // uint2 per row
-            if (st == SG_OK && want_q8 && !p->d_blk) st = ctx->alloc((size_t)SG_Q8_STRIDE * ((size_t)B->n_rows + 1), &p->d_q8);
-            fwd_done = false;
-        }
-        // slack: the pruned multiply loads a lane's four slots of a segment unconditionally (<= 4 * 63 entries past it)
-        if (st == SG_OK) st = sg_alloc(ctx, (size_t)B->nnz + 512, &p->d_filt);
-        // the stream form points lanes without a posting at the slack behind the array: entries that add 0 (bq = 0), each to
-        // an accumulator of its own (64 lanes adding to ONE LDS word are serialised: 3 ms at 663 k)
-        // (written by postings_tables_kernel on the LDS build path, by a launch of its own otherwise: below)
-        p->nt_pad = (int32_t)((n_tiles64 + 3) & ~(int64_t)3);
-        if (st == SG_OK) st = sg_alloc(ctx, (size_t)(B->n_cols + 1) * (size_t)p->nt_pad + 4, &p->d_ends);
-        // stream form of the pruned multiply (sg_spgemm_pruned.hip): eight tiles share one accumulator tile
-        p->fold_log2 = 0;
-        if (tile_log2 == 12 && !(ctx->opt("SG_K4_STREAM") && ctx->opt("SG_K4_STREAM")[0] == '0')) p->fold_log2 = 3;
-        if (p->fold_log2 > 0) {
-            const int64_t n_super = (n_tiles64 + ((int64_t)1 << p->fold_log2) - 1) >> p->fold_log2;
-            p->nv_pad = (int32_t)((n_super + 3) & ~(int64_t)3);
-            if (st == SG_OK) st = sg_alloc(ctx, (size_t)(B->n_cols + 1) * (size_t)p->nv_pad + 4, &p->d_ends8);
-        }
-        p->norm_up = norm_up_build;
-        // a term is "frequent" when it occurs in at least this share of the right-hand rows: the suffix of a
-        // left row is drawn from frequent terms only, which lets the survivor test use each candidate's own
-        // frequent-part norm instead of 1 (profiles/r01_prune_tuning.log)
-        double frac = 0.005;   // (round 5, with the second filter: 0.0045 -> 0.005, 30.8 M -> 22.5 M candidates, kernel - 2 % at 663 k; 0.004 + 5 %, 0.007 + 4 %)
-        if (const char *v = ctx->opt("SG_PRUNE_FREQ")) frac = atof(v);
-        const double fm = frac * (double)B->n_rows;
-        p->freq_min = fm < 1.0 ? 1u : (uint32_t)fm;
-    }
-    ctx->release(early_fwd);      // (only when the build took another turn than the one they were made for)
-    ctx->release(early_fwd_ptr);
-    ctx->release(early_q8);
+    // (with groups the build writes the representatives' rows with its own copies of them)
+    sg_postings *p = nullptr;
+    const int st = build_index(ctx, col ? col->unique : B_in, tile_cols, flags, col, timer, &p);
     if (st != SG_OK) {
-        sg_postings_free(p);
+        sg_collapse_free(col);
         return st;
     }
-    {
-        // one thread per slot of the (tile x row-in-tile) grid: covers every row, see row_of_thread
-        const unsigned grid = (unsigned)((((int64_t)p->n_tiles << tile_log2) + 255) / 256);
-        // the tile's counters fit in LDS: one workgroup per tile (part), LDS atomics (otherwise global ones)
-        const size_t lds = (size_t)B->n_cols * 4 + ((size_t)(B->n_cols + 31) / 32) * 4;
-        bool in_lds = B->n_rows > 0 && lds <= 124 * 1024 && B->n_cols > 0;
-        if (const char *e = ctx->opt("SG_POSTINGS_LDS")) in_lds = in_lds && e[0] != '0';
-        const float inv_norm = p->d_filt ? 1.0f / p->norm_up : 0.f;
-        bool tables_done = false;
-        if (in_lds) {
-            static bool attr_done = false;
-            if (!attr_done) {
-                (void)hipFuncSetAttribute((const void *)postings_count_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 124 * 1024);
-                (void)hipFuncSetAttribute((const void *)postings_fill_lds<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 124 * 1024);
-                (void)hipFuncSetAttribute((const void *)postings_fill_lds<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 124 * 1024);
-                (void)hipFuncSetAttribute((const void *)postings_fill_staged<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void *)postings_fill_staged<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr_done = true;
-            }
-            // Round 6: filter postings staged in LDS and written cell by cell (postings_fill_staged) -- when only the filter
-            // postings are written (the exact kernel's are lazy) and a chunk of at least 64 rows fits the stage.  The stage
-            // takes what the packed counters leave of 158 KiB: one workgroup per CU, so tiles are split until there are two
-            // workgroups per CU (parts of >= 512 rows) and a launch does not end with a few CUs working alone.
-            bool staged = p->d_filt != nullptr && p->d_vals == nullptr && !(ctx->opt("SG_FILL_STAGED") && ctx->opt("SG_FILL_STAGED")[0] == '0');
-            uint32_t stage_cap = 0;
-            int32_t chunk_rows = 0;
-            size_t staged_lds = 0;
-            const double mean_nnz = B->n_rows > 0 ? (double)B->nnz / (double)B->n_rows : 1.0;
-            if (staged) {
-                const size_t fixed0 = ((((size_t)B->n_cols + 1) / 2 + 3) & ~(size_t)3) * 4 + (((size_t)B->n_cols + 31) / 32) * 4 + 32 * 4;
-                chunk_rows = 2048;
-                for (;;) {
-                    const size_t fixed = fixed0 + (size_t)chunk_rows * 4;
-                    const size_t room = fixed + 16384 < 158 * 1024 ? 158 * 1024 - fixed : 0;
-                    stage_cap = (uint32_t)(room / 4);
-                    if (stage_cap > 65535u) stage_cap = 65535u;
-                    if ((double)chunk_rows * mean_nnz * 1.2 + 64.0 <= (double)stage_cap || chunk_rows <= 64) break;
-                    chunk_rows >>= 1;
-                }
-                staged = (double)chunk_rows * mean_nnz * 1.2 + 64.0 <= (double)stage_cap;
-                staged_lds = fixed0 + (size_t)chunk_rows * 4 + (size_t)stage_cap * 4;
-                if (const char *v = ctx->opt("SG_FILL_STAGE_CAP"))    // test hook: chunks that do not fit go posting by posting
-                    if (atoi(v) > 0 && (uint32_t)atoi(v) < stage_cap) stage_cap = (uint32_t)atoi(v);
-            }
-            // fewer tiles than CUs: split every tile between 2 or 4 workgroups (parts of >= 1024 rows)
-            int32_t split = 1;
-            while (split < 4 && (int64_t)p->n_tiles * split < ctx->num_cu && (tile_cols / (split * 2)) >= 1024 &&
-                   (n_bins * split * 2 + 1) < ((int64_t)1 << 31))
-                split *= 2;
-            if (staged)
-                while (split < 8 && (int64_t)p->n_tiles * split < 2 * (int64_t)ctx->num_cu && (tile_cols / (split * 2)) >= 512 &&
-                       (n_bins * split * 2 + 1) < ((int64_t)1 << 31))
-                    split *= 2;
-            if (const char *e = ctx->opt("SG_POSTINGS_SPLIT")) {
-                const int o = atoi(e);
-                if ((o == 1 || o == 2 || o == 4) && tile_cols / o >= 64 && n_bins * o + 1 < ((int64_t)1 << 31)) split = o;
-            }
-            p->split = split;
-            const int64_t wgs64 = (int64_t)p->n_tiles * split;
-            uint32_t *cnt = nullptr;            // [workgroup][term] (see postings_count_lds)
-            uint8_t *is_frequent = nullptr;
-            st = sg_alloc(ctx, (size_t)(wgs64 * B->n_cols) + 1, &cnt);
-            if (st == SG_OK) st = sg_alloc(ctx, (size_t)B->n_cols + 4, &is_frequent);
-            if (st == SG_OK) st = sg_alloc(ctx, (size_t)B->n_cols + 2, &p->d_term_start);
-            if (st == SG_OK) {
-                const unsigned wgs = (unsigned)wgs64;
-                const unsigned strips = (unsigned)((B->n_cols + 63) / 64), strips1 = (unsigned)((B->n_cols + 64) / 64);
-                hipLaunchKernelGGL(postings_count_lds, dim3(wgs), dim3(1024), (size_t)B->n_cols * 4, ctx->stream, B->d_indptr,
-                                   B->d_indices, B->n_rows, tile_log2, (int32_t)B->n_cols, split, cnt);
-                hipLaunchKernelGGL(postings_colscan_kernel, dim3(strips), dim3(1024), 0, ctx->stream, cnt, (int32_t)wgs64,
-                                   (int32_t)B->n_cols, p->freq_min, p->d_term_len, is_frequent);
-                // the terms' lists back to back: starts of the lists, the last entry receives the total (= nnz)
-                st = sg_exclusive_scan_u32(ctx, p->d_term_len, p->d_term_start, B->n_cols, p->d_term_start + B->n_cols);
-                if (st == SG_OK) {
-                    if (staged)
-                        ;     // (after the tables: the staged fill advances the workgroups' rows of `cnt`)
-                    else if (B->dtype == SG_F64)
-                        hipLaunchKernelGGL(postings_fill_lds<double>, dim3(wgs), dim3(1024), lds, ctx->stream, B->d_indptr,
-                                           B->d_indices, (const double *)B->d_data, B->n_rows, tile_log2, (int32_t)B->n_cols, split,
-                                           (const uint32_t *)cnt, (const uint32_t *)p->d_term_start, (const uint8_t *)is_frequent,
-                                           p->d_rows, (double *)p->d_vals, p->d_filt, inv_norm, p->fold_log2);
-                    else
-                        hipLaunchKernelGGL(postings_fill_lds<float>, dim3(wgs), dim3(1024), lds, ctx->stream, B->d_indptr,
-                                           B->d_indices, (const float *)B->d_data, B->n_rows, tile_log2, (int32_t)B->n_cols, split,
-                                           (const uint32_t *)cnt, (const uint32_t *)p->d_term_start, (const uint8_t *)is_frequent,
-                                           p->d_rows, (float *)p->d_vals, p->d_filt, inv_norm, p->fold_log2);
-                    SgScoreCtx sc;
-                    if (p->d_fwd_ptr) {
-                        st = ctx->alloc(256, (void **)&p->d_score_ctx);
-                        sc.fwd_ptr = p->d_fwd_ptr;
-                        sc.fwd = p->d_fwd;
-                        sc.blk = p->d_blk;
-                        sc.blk_bytes = p->blk_bytes;
-                        sc.orig_of = p->d_orig_of;
-                        sc.q8 = (const uint4 *)p->d_q8;
-                        sc.q8_scale = p->d_q8 ? __builtin_nextafterf((float)(255.0 / (double)p->norm_up * (1.0 - 1e-6)), 0.f) : 0.f;
-                    }
-                    if (st == SG_OK) {
-                        hipLaunchKernelGGL(postings_tables_kernel, dim3(strips1), dim3(1024), 0, ctx->stream, (const uint32_t *)cnt,
-                                           (const uint32_t *)p->d_term_start, (int32_t)B->n_cols, p->n_tiles, split, p->d_seg, p->d_ends,
-                                           p->nt_pad, p->d_ends8, p->nv_pad, p->fold_log2, sc, p->d_score_ctx,
-                                           p->d_filt ? p->d_filt + B->nnz : (uint32_t *)nullptr);
-                        if (staged && B->dtype == SG_F64)
-                            hipLaunchKernelGGL(postings_fill_staged<double>, dim3(wgs), dim3(1024), staged_lds, ctx->stream, B->d_indptr,
-                                               B->d_indices, (const double *)B->d_data, B->n_rows, tile_log2, (int32_t)B->n_cols, split,
-                                               chunk_rows, stage_cap, cnt, (const uint32_t *)p->d_term_start, (const uint8_t *)is_frequent,
-                                               p->d_filt, inv_norm, p->fold_log2);
-                        else if (staged)
-                            hipLaunchKernelGGL(postings_fill_staged<float>, dim3(wgs), dim3(1024), staged_lds, ctx->stream, B->d_indptr,
-                                               B->d_indices, (const float *)B->d_data, B->n_rows, tile_log2, (int32_t)B->n_cols, split,
-                                               chunk_rows, stage_cap, cnt, (const uint32_t *)p->d_term_start, (const uint8_t *)is_frequent,
-                                               p->d_filt, inv_norm, p->fold_log2);
-                        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-                        aux_written = st == SG_OK;
-                    }
-                }
-            }
-            ctx->release(cnt);
-            ctx->release(is_frequent);
-            tables_done = true;
-        } else {
-            uint32_t *cursor = nullptr;
-            st = sg_alloc(ctx, (size_t)n_bins + 1, &cursor);
-            if (st == SG_OK) {
-                SG_HIP_TRY(hipMemsetAsync(p->d_seg, 0, sizeof(uint32_t) * (size_t)(n_bins + 1), ctx->stream));
-                SG_HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(uint32_t) * (size_t)(n_bins + 1), ctx->stream));
-            }
-            if (st == SG_OK && grid > 0) {
-                if (B->dtype == SG_F64)
-                    hipLaunchKernelGGL(postings_count<double>, dim3(grid), dim3(256), 0, ctx->stream, B->d_indptr,
-                                       B->d_indices, B->n_rows, tile_log2, p->n_tiles, p->d_seg);
-                else
-                    hipLaunchKernelGGL(postings_count<float>, dim3(grid), dim3(256), 0, ctx->stream, B->d_indptr,
-                                       B->d_indices, B->n_rows, tile_log2, p->n_tiles, p->d_seg);
-                SG_HIP_TRY(hipGetLastError());
-            }
-            // counts -> offsets, in place; seg[n_bins] receives the total (= nnz)
-            if (st == SG_OK) st = sg_exclusive_scan_u32(ctx, p->d_seg, p->d_seg, n_bins, p->d_seg + n_bins);
-            if (st == SG_OK && grid > 0) {
-                if (B->dtype == SG_F64)
-                    hipLaunchKernelGGL(postings_fill<double>, dim3(grid), dim3(256), 0, ctx->stream, B->d_indptr,
-                                       B->d_indices, (const double *)B->d_data, B->n_rows, tile_log2, p->n_tiles,
-                                       p->d_seg, cursor, p->d_rows, (double *)p->d_vals, p->d_filt, p->freq_min, inv_norm, p->fold_log2);
-                else
-                    hipLaunchKernelGGL(postings_fill<float>, dim3(grid), dim3(256), 0, ctx->stream, B->d_indptr,
-                                       B->d_indices, (const float *)B->d_data, B->n_rows, tile_log2, p->n_tiles,
-                                       p->d_seg, cursor, p->d_rows, (float *)p->d_vals, p->d_filt, p->freq_min, inv_norm, p->fold_log2);
-                if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-            }
-            ctx->release(cursor);
-        }
-        if (st == SG_OK && !tables_done && B->n_cols > 0) {
-            // (the path with global counters builds the term-major table itself; lists and ends are read off it)
-            hipLaunchKernelGGL(term_len_kernel, dim3((unsigned)((B->n_cols + 255) / 256)), dim3(256), 0, ctx->stream,
-                               (const uint32_t *)p->d_seg, B->n_cols, p->n_tiles, p->d_term_len);
-            if (p->d_ends || p->d_ends8)
-                hipLaunchKernelGGL(ends_from_seg_kernel, dim3((unsigned)((B->n_cols + 256) / 256)), dim3(256), 0, ctx->stream,
-                                   (const uint32_t *)p->d_seg, B->n_cols, p->n_tiles, p->d_ends, p->nt_pad, p->d_ends8, p->nv_pad,
-                                   p->fold_log2);
-            if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-        }
-        if (st == SG_OK && p->d_fwd && !fwd_done) {   // (packed rows in use: no row blocks; the fused pass writes the pad itself)
-            // the exact scoring reads packed rows in rounds of eight entries and multiplies the slots past a row's end by
-            // a = 0: the pad behind the LAST row must hold finite values (0 * NaN would poison that row's score)
-            const size_t es = B->dtype == SG_F64 ? 16 : 8;
-            if (hipMemsetAsync((char *)p->d_fwd + (size_t)B->nnz * es, 0, 8 * es, ctx->stream) != hipSuccess) st = SG_ERR_HIP;
-        }
-        if (st == SG_OK && p->d_blk && B->n_rows > 0) {
-            const int64_t work = B->n_rows * (int64_t)(p->blk_bytes / 16);
-            const unsigned g3 = (unsigned)((work + 255) / 256);
-            if (B->dtype == SG_F64)
-                hipLaunchKernelGGL(row_blocks_kernel<double>, dim3(g3), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                                   (const double *)B->d_data, B->n_rows, (const uint32_t *)p->d_orig_of, p->blk_bytes, p->d_blk);
-            else
-                hipLaunchKernelGGL(row_blocks_kernel<float>, dim3(g3), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                                   (const float *)B->d_data, B->n_rows, (const uint32_t *)p->d_orig_of, p->blk_bytes, p->d_blk);
-            if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-        }
-        if (st == SG_OK && p->d_fwd_ptr && !fwd_done) {
-            const int64_t work = B->nnz > B->n_rows + 1 ? B->nnz : B->n_rows + 1;
-            const unsigned g2 = (unsigned)((work + 255) / 256);
-            if (B->dtype == SG_F64)
-                hipLaunchKernelGGL(fwd_pack<double>, dim3(g2), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                                   (const double *)B->d_data, B->n_rows, B->nnz, (const uint32_t *)p->d_orig_of, p->d_fwd_ptr, p->d_fwd);
-            else
-                hipLaunchKernelGGL(fwd_pack<float>, dim3(g2), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                                   (const float *)B->d_data, B->n_rows, B->nnz, (const uint32_t *)p->d_orig_of, p->d_fwd_ptr, p->d_fwd);
-            if (p->d_q8 && B->n_rows > 0) {
-                const unsigned g4 = (unsigned)((B->n_rows * 16 + 255) / 256);
-                if (B->dtype == SG_F64)
-                    hipLaunchKernelGGL(q8_pack_kernel<double>, dim3(g4), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                                       (const double *)B->d_data, B->n_rows, (const uint32_t *)p->d_orig_of, (uint4 *)p->d_q8, 1.0f / p->norm_up);
-                else
-                    hipLaunchKernelGGL(q8_pack_kernel<float>, dim3(g4), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                                       (const float *)B->d_data, B->n_rows, (const uint32_t *)p->d_orig_of, (uint4 *)p->d_q8, 1.0f / p->norm_up);
-            }
-            if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-        }
+    if (col) {
+        p->collapse = col;
+        p->caller_b_copy = borrowed(*B_in);
+        p->caller_b = &p->caller_b_copy;
+        p->n_right_caller = B_in->n_rows;
     }
-    if (st == SG_OK && p->d_filt && !aux_written) {
-        hipLaunchKernelGGL(null_postings_kernel, dim3(2), dim3(256), 0, ctx->stream, p->d_filt + B->nnz);
-        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-    }
-    if (st == SG_OK && p->d_fwd_ptr && !aux_written) {
-        st = ctx->alloc(256, (void **)&p->d_score_ctx);
-        if (st == SG_OK) {
-            SgScoreCtx sc;
-            sc.fwd_ptr = p->d_fwd_ptr;
-            sc.fwd = p->d_fwd;
-            sc.blk = p->d_blk;
-            sc.blk_bytes = p->blk_bytes;
-            sc.orig_of = p->d_orig_of;
-            sc.q8 = (const uint4 *)p->d_q8;
-            sc.q8_scale = p->d_q8 ? __builtin_nextafterf((float)(255.0 / (double)p->norm_up * (1.0 - 1e-6)), 0.f) : 0.f;
-            hipLaunchKernelGGL(score_ctx_kernel, dim3(1), dim3(1), 0, ctx->stream, sc, p->d_score_ctx);
-            if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-        }
-    }
-    if (st != SG_OK) {
-        sg_postings_free(p);
-        return st;
+    if (group) {
+        p->build_tile_cols = tile_cols;
+        p->build_flags = col ? flags : flags & 0xff;
     }
     *out = p;
     return SG_OK;
 }
 
-// The postings proper, when the build left them out (see sg_postings_build_flags): same two passes, values only.
+// The postings proper, when the build left them out (plan_build, lazy_full): same two passes, values only.
 int sg_postings_ensure_full(sg_ctx *ctx, const sg_postings *cp) {
     sg_postings *p = const_cast<sg_postings *>(cp);
     if (p->d_vals || p->nnz <= 0) return SG_OK;
     const sg_csr *B = &p->src;
-    const int64_t n_bins = p->n_terms * (int64_t)p->n_tiles;
-    const int32_t split = p->split > 0 ? p->split : 1;
-    int st = SG_OK;
-    if (B->dtype == SG_F64) st = sg_alloc(ctx, (size_t)B->nnz + 64, &p->d_rows);
-    if (st == SG_OK) st = ctx->alloc(((size_t)B->nnz + 64) * 8, &p->d_vals);
+    Scratch scratch(ctx);
     uint32_t *cnt = nullptr, *len_scratch = nullptr;
-    const int64_t wgs64 = (int64_t)p->n_tiles * split;
-    (void)n_bins;
+    if (B->dtype == SG_F64) SG_TRY(scratch.alloc((size_t)B->nnz + 64, &p->d_rows));
+    int st = scratch.alloc_bytes(((size_t)B->nnz + 64) * 8, &p->d_vals);
     if (st == SG_OK && !p->d_term_start) {
         sg_set_error("postings were built without the LDS path: nothing is lazy there");
         st = SG_ERR_BADARG;
     }
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)(wgs64 * B->n_cols) + 1, &cnt);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)B->n_cols + 2, &len_scratch);
-    if (st == SG_OK) {
-        const unsigned wgs = (unsigned)wgs64;
-        const size_t lds = (size_t)B->n_cols * 4 + ((size_t)(B->n_cols + 31) / 32) * 4;
-        hipLaunchKernelGGL(postings_count_lds, dim3(wgs), dim3(1024), (size_t)B->n_cols * 4, ctx->stream, B->d_indptr, B->d_indices,
-                           B->n_rows, p->tile_log2, (int32_t)B->n_cols, split, cnt);
-        hipLaunchKernelGGL(postings_colscan_kernel, dim3((unsigned)((B->n_cols + 63) / 64)), dim3(1024), 0, ctx->stream, cnt,
-                           (int32_t)wgs64, (int32_t)B->n_cols, 0u, len_scratch, (uint8_t *)nullptr);
-        if (B->dtype == SG_F64)
-            hipLaunchKernelGGL(postings_fill_lds<double>, dim3(wgs), dim3(1024), lds, ctx->stream, B->d_indptr, B->d_indices,
-                               (const double *)B->d_data, B->n_rows, p->tile_log2, (int32_t)B->n_cols, split, (const uint32_t *)cnt,
-                               (const uint32_t *)p->d_term_start, (const uint8_t *)nullptr, p->d_rows, (double *)p->d_vals,
-                               (uint32_t *)nullptr, 0.f, 0);
-        else
-            hipLaunchKernelGGL(postings_fill_lds<float>, dim3(wgs), dim3(1024), lds, ctx->stream, B->d_indptr, B->d_indices,
-                               (const float *)B->d_data, B->n_rows, p->tile_log2, (int32_t)B->n_cols, split, (const uint32_t *)cnt,
-                               (const uint32_t *)p->d_term_start, (const uint8_t *)nullptr, p->d_rows, (float *)p->d_vals,
-                               (uint32_t *)nullptr, 0.f, 0);
-        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-    }
-    ctx->release(cnt);
-    ctx->release(len_scratch);
-    if (st != SG_OK) {
-        ctx->release(p->d_vals);
-        ctx->release(p->d_rows);
+    const int32_t split = p->split > 0 ? p->split : 1;
+    if (st == SG_OK) st = scratch.alloc((size_t)((int64_t)p->n_tiles * split * B->n_cols) + 1, &cnt);
+    if (st == SG_OK) st = scratch.alloc((size_t)B->n_cols + 2, &len_scratch);
+    if (st == SG_OK) st = lds_count_scan_fill(ctx, p, cnt, len_scratch, nullptr, /*values_only=*/true, /*fill=*/true);
+    if (st != SG_OK) {     // (the scratch takes the two arrays back)
         p->d_vals = nullptr;
         p->d_rows = nullptr;
+        return st;
     }
-    return st;
+    scratch.keep(p->d_rows);
+    scratch.keep(p->d_vals);
+    return SG_OK;
 }
 
 extern "C" int sg_postings_free(sg_postings *p) {

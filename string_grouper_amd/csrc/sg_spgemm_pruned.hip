@@ -1862,41 +1862,7 @@ int sg_csr_props(sg_ctx *ctx, const sg_csr *m, bool *cosine_like, float *max_nor
 }
 
 // ------------------------------------------------------------------------------------------------
-// Host driver.  Two helpers of this file alone: scratch that goes back to the pool by itself, and the dtype dispatch.
-struct Scratch {   // blocks of the context's pool, released -- in the order they were taken -- when the scope ends
-    sg_ctx *ctx;
-    std::vector<void *> blocks;
-    explicit Scratch(sg_ctx *c) : ctx(c) {}
-    Scratch(const Scratch &) = delete;
-    ~Scratch() {
-        for (void *p : blocks) ctx->release(p);
-    }
-    int alloc_bytes(size_t bytes, void **out) {
-        const int st = ctx->alloc(bytes, out);
-        if (st == SG_OK) blocks.push_back(*out);
-        return st;
-    }
-    template <typename T>
-    int alloc(size_t count, T **out) {
-        void *p = nullptr;
-        const int st = alloc_bytes(count * sizeof(T), &p);
-        *out = (T *)p;
-        return st;
-    }
-    template <typename T>
-    T *keep(T *p) {   // the block outlives the scope: it is the caller's now
-        for (void *&b : blocks)
-            if (b == p) b = nullptr;
-        return p;
-    }
-    void release(void *p) { ctx->release(keep(p)); }   // ... or goes back early (stream-ordered, like every release)
-};
-
-template <typename F>
-static int by_dtype(int32_t dtype, F &&f) {   // f(double{}) or f(float{}): every launch below is written once
-    return dtype == SG_F64 ? f(double{}) : f(float{});
-}
-
+// Host driver.  (Scratch that goes back to the pool by itself, and the dtype dispatch: sg_internal.h.)
 struct PairList {   // symmetric mode: the mirrored pairs (i, j < i) above the threshold, in chunks of SG_PAIR_CHUNK entries
     SgPairSink sink;                           // the lists and their counters (sg_internal.h): what the exact kernel's launch is handed
     const SgPairSink *d_sink = nullptr;        // the same struct in device memory: what the pruned kernel is handed

@@ -579,17 +579,6 @@ __global__ void __launch_bounds__(64) topn_zip_kernel(const ZipPart<T> *__restri
 // ================================================================================================
 // host side
 // ================================================================================================
-// Dynamic LDS above the default 48 KiB has to be allowed for each kernel, once
-template <auto KERN>
-static int allow_dynamic_lds(size_t lds) {
-    static bool done = false;   // per instantiation
-    if (lds > 48 * 1024 && !done) {
-        SG_HIP_TRY(hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        done = true;
-    }
-    return SG_OK;
-}
-
 template <typename T, int TILE_LOG2>
 static int launch_spgemm(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t tile_begin, int32_t tile_end,
                          int32_t keep, int32_t pass_off, sg_topn *r, T thr, uint32_t *counter, unsigned grid,
