@@ -35,6 +35,7 @@
 //
 // Bound: HBM.  Algorithmic bytes = sum(len) + 8n (read strings) + nnz*(4+s) + 8(n+1) (write CSR)
 // + the key-space tables (4 * 2^(bits*n) for df and rank).
+#include <memory>
 #include <type_traits>
 
 #include "sg_internal.h"
@@ -902,13 +903,28 @@ __global__ void __launch_bounds__(256) weight_normalize_rows16_kernel(const int6
 // -------------------------------------------------------------------------------------------------
 static void free_cache(sg_ctx *ctx, TokenCache &c) {
     ctx->release(c.d_longs);
-    c.d_longs = nullptr;
     ctx->release(c.d_cnt);
     ctx->release(c.d_keys);
     ctx->release(c.d_tf);
     ctx->release(c.d_indptr);
     c = TokenCache();
 }
+
+struct OwnedTokens {   // a token cache that is freed when the scope ends, whichever way (what was moved out of it is empty here)
+    sg_ctx *ctx;
+    TokenCache c;
+    explicit OwnedTokens(sg_ctx *x) : ctx(x) {}
+    OwnedTokens(const OwnedTokens &) = delete;
+    ~OwnedTokens() { free_cache(ctx, c); }
+};
+
+template <auto FREE>
+struct FreeWith {      // the deleter of a half-built handle: every failure path frees it once
+    template <typename H>
+    void operator()(H *h) const { (void)FREE(h); }
+};
+using VocabPtr = std::unique_ptr<sg_vocab, FreeWith<sg_vocab_free>>;
+using CsrPtr = std::unique_ptr<sg_csr, FreeWith<sg_csr_free>>;
 
 static TokParams make_tok_params(const sg_vocab *v, const VocabImpl *im, const sg_strings *s) {
     TokParams tp;
@@ -922,89 +938,88 @@ static TokParams make_tok_params(const sg_vocab *v, const VocabImpl *im, const s
     return tp;
 }
 
+// The tokeniser kernels' two template parameters, chosen in one place: f(KeyT{}, std::bool_constant<SYMBOLS>{})
+template <typename F>
+static int by_key(bool sorted_mode, bool sym, F &&f) {
+    if (sorted_mode) return sym ? f(uint64_t{}, std::true_type{}) : f(uint64_t{}, std::false_type{});
+    return sym ? f(uint32_t{}, std::true_type{}) : f(uint32_t{}, std::false_type{});
+}
+
 // The strings of more than TOK_CAP n-grams that the wave-per-string kernels queued (c.d_longs): a workgroup per string, after
 // one host round trip for their sizes.
 template <typename KeyT, bool SYMBOLS>
 static int tokenize_longs_t(sg_ctx *ctx, const sg_strings *s, const TokParams &tp, int32_t *df_table, int32_t df_replicas,
                             int64_t df_stride, TokenCache &c, uint32_t n_long) {
     if (n_long == 0) return SG_OK;
-    uint32_t *longs = c.d_longs;
-    KeyT *keys = (KeyT *)c.d_keys;
+    const uint32_t *long_rows = c.d_longs + 1;
+    Scratch tmp(ctx);
     // sizes of the long strings -> scratch offsets (characters: the length; keys: the next power of two)
     int64_t *d_sizes = nullptr, *d_coff = nullptr, *d_koff = nullptr;
     std::vector<int64_t> sizes(n_long), coff(n_long + 1, 0), koff(n_long + 1, 0);
-    int st = sg_alloc(ctx, (size_t)n_long, &d_sizes);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_long + 1, &d_coff);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_long + 1, &d_koff);
-    hipError_t e = hipSuccess;
-    if (st == SG_OK) {
-        hipLaunchKernelGGL(long_sizes_kernel, dim3((n_long + 255) / 256), dim3(256), 0, ctx->stream, s->d_offsets,
-                           (const uint32_t *)(longs + 1), n_long, d_sizes);
-        e = hipMemcpyAsync(sizes.data(), d_sizes, sizeof(int64_t) * n_long, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    }
-    uint16_t *lchars = nullptr;
-    KeyT *lkeys = nullptr;
-    if (st == SG_OK && e == hipSuccess) {
+    SG_TRY(tmp.alloc((size_t)n_long, &d_sizes));
+    SG_TRY(tmp.alloc((size_t)n_long + 1, &d_coff));
+    SG_TRY(tmp.alloc((size_t)n_long + 1, &d_koff));
+    hipLaunchKernelGGL(long_sizes_kernel, dim3((n_long + 255) / 256), dim3(256), 0, ctx->stream, s->d_offsets, long_rows, n_long,
+                       d_sizes);
+    hipError_t e = hipMemcpyAsync(sizes.data(), d_sizes, sizeof(int64_t) * n_long, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) {
         for (uint32_t i = 0; i < n_long; ++i) {
             int64_t p2 = 64;
             while (p2 < sizes[i]) p2 <<= 1;
             coff[i + 1] = coff[i] + sizes[i] + 8;
             koff[i + 1] = koff[i] + p2;
         }
-        st = sg_alloc(ctx, (size_t)coff[n_long] + 8, &lchars);
-        if (st == SG_OK) st = sg_alloc(ctx, (size_t)koff[n_long] + 8, &lkeys);
-        if (st == SG_OK) {
-            e = hipMemcpyAsync(d_coff, coff.data(), sizeof(int64_t) * (n_long + 1), hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(d_koff, koff.data(), sizeof(int64_t) * (n_long + 1), hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL((tokenize_long_kernel<KeyT, SYMBOLS>), dim3(n_long), dim3(256), 0, ctx->stream,
-                                   (const void *)s->d_bytes, s->d_offsets, tp, (const uint32_t *)(longs + 1),
-                                   (const int64_t *)d_coff, (const int64_t *)d_koff, lchars, lkeys,
-                                   (const int64_t *)c.d_ub_ptr, c.d_cnt, keys, c.d_tf, df_table, df_replicas, df_stride);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // coff / koff are locals
+        uint16_t *lchars = nullptr;
+        KeyT *lkeys = nullptr;
+        SG_TRY(tmp.alloc((size_t)coff[n_long] + 8, &lchars));
+        SG_TRY(tmp.alloc((size_t)koff[n_long] + 8, &lkeys));
+        e = hipMemcpyAsync(d_coff, coff.data(), sizeof(int64_t) * (n_long + 1), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(d_koff, koff.data(), sizeof(int64_t) * (n_long + 1), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL((tokenize_long_kernel<KeyT, SYMBOLS>), dim3(n_long), dim3(256), 0, ctx->stream,
+                               (const void *)s->d_bytes, s->d_offsets, tp, long_rows, (const int64_t *)d_coff,
+                               (const int64_t *)d_koff, lchars, lkeys, (const int64_t *)c.d_ub_ptr, c.d_cnt, (KeyT *)c.d_keys,
+                               c.d_tf, df_table, df_replicas, df_stride);
+            e = hipGetLastError();
         }
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // coff / koff are locals
     }
-    ctx->release(d_sizes);
-    ctx->release(d_coff);
-    ctx->release(d_koff);
-    ctx->release(lchars);
-    ctx->release(lkeys);
-    if (st == SG_OK && e != hipSuccess) {
+    if (e != hipSuccess) {
         sg_set_error("tokenize_long_kernel: %s", hipGetErrorString(e));
-        st = SG_ERR_HIP;
+        return SG_ERR_HIP;
     }
-    return st;
+    return SG_OK;
 }
 
 // K1 over one string column: the one-wave-per-string kernel, then the workgroup-per-string kernel for the strings it
 // handed over (one small host round trip: how many there are and how long they are).
 // defer_longs (round 4): do NOT ask how many strings the last stage has to take -- the answer is "none" for any list of
 // names, and asking is a synchronisation per column and fit.  The caller asks together with its own next question
-// (sg_vec_fit_end: the size of the vocabulary) and tokenises the long strings then (resolve_longs), before anything
+// (read_fit_sizes: the size of the vocabulary) and tokenises the long strings then (resolve_longs), before anything
 // that depends on them is final.
 template <typename KeyT, bool SYMBOLS>
 static int tokenize_set_t(sg_ctx *ctx, const sg_strings *s, const TokParams &tp, int32_t *df_table, int32_t df_replicas,
                           int64_t df_stride, TokenCache *out, bool defer_longs) {
-    TokenCache c;
+    OwnedTokens own(ctx);        // (the caller's when this function succeeds)
+    TokenCache &c = own.c;
+    Scratch tmp(ctx);
     c.src = s;
     c.n = s->n;
     uint32_t *mids = nullptr;    // [0] count, then the rows of more than 64 characters
-    int st = sg_alloc(ctx, (size_t)s->n + 1, &c.d_cnt);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)s->n + 2, &c.d_longs);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)s->n + 2, &mids);
+    SG_TRY(sg_alloc(ctx, (size_t)s->n + 1, &c.d_cnt));
+    SG_TRY(sg_alloc(ctx, (size_t)s->n + 2, &c.d_longs));
+    SG_TRY(tmp.alloc((size_t)s->n + 2, &mids));
     c.d_ub_ptr = s->d_offsets;   // (no count, no scan: see TokenCache)
     // every row of L characters has at most L - n + 1 n-grams, so the total length bounds the padded size
     c.cap_total = s->total_bytes + 1;
     KeyT *keys = nullptr;
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)c.cap_total, &keys);
+    SG_TRY(sg_alloc(ctx, (size_t)c.cap_total, &keys));
     c.d_keys = keys;
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)c.cap_total, &c.d_tf);
+    SG_TRY(sg_alloc(ctx, (size_t)c.cap_total, &c.d_tf));
     uint32_t n_long = 0;
-    if (st == SG_OK && s->n > 0) {
+    if (s->n > 0) {
         // strings of up to 64 characters: tokenize_short_kernel; what it queues (mids): tokenize_kernel, launched on the
         // device-side count; what that one queues (longs, > TOK_CAP n-grams): tokenize_long_kernel after one host round trip
         uint32_t *longs = c.d_longs;
@@ -1027,32 +1042,26 @@ static int tokenize_set_t(sg_ctx *ctx, const sg_strings *s, const TokParams &tp,
         }
         if (e != hipSuccess) {
             sg_set_error("tokenize_kernel: %s", hipGetErrorString(e));
-            st = SG_ERR_HIP;
+            return SG_ERR_HIP;
         }
     }
-    if (st == SG_OK && !defer_longs) {
-        st = tokenize_longs_t<KeyT, SYMBOLS>(ctx, s, tp, df_table, df_replicas, df_stride, c, n_long);
+    if (!defer_longs) {
+        const int st = tokenize_longs_t<KeyT, SYMBOLS>(ctx, s, tp, df_table, df_replicas, df_stride, c, n_long);
         ctx->release(c.d_longs);
         c.d_longs = nullptr;
-    }
-    ctx->release(mids);
-    if (st != SG_OK) {
-        free_cache(ctx, c);
-        return st;
+        SG_TRY(st);
     }
     *out = c;
+    c = TokenCache();
     return SG_OK;
 }
 
 static int tokenize_set(sg_ctx *ctx, const sg_vocab *v, const sg_strings *s, int32_t *df_table, int32_t df_replicas,
                         int64_t df_stride, TokenCache *out, bool defer_longs = false) {
     const TokParams tp = make_tok_params(v, v->impl, s);
-    const bool sym = s->sym_width == 2;
-    if (v->sorted_mode)
-        return sym ? tokenize_set_t<uint64_t, true>(ctx, s, tp, df_table, df_replicas, df_stride, out, defer_longs)
-                   : tokenize_set_t<uint64_t, false>(ctx, s, tp, df_table, df_replicas, df_stride, out, defer_longs);
-    return sym ? tokenize_set_t<uint32_t, true>(ctx, s, tp, df_table, df_replicas, df_stride, out, defer_longs)
-               : tokenize_set_t<uint32_t, false>(ctx, s, tp, df_table, df_replicas, df_stride, out, defer_longs);
+    return by_key(v->sorted_mode, s->sym_width == 2, [&](auto key, auto sym) {
+        return tokenize_set_t<decltype(key), decltype(sym)::value>(ctx, s, tp, df_table, df_replicas, df_stride, out, defer_longs);
+    });
 }
 
 // the question tokenize_set_t(defer_longs) left open, answered: n_long strings of cache c go through the last stage
@@ -1060,14 +1069,9 @@ static int resolve_longs(sg_ctx *ctx, const sg_vocab *v, TokenCache &c, int32_t 
                          uint32_t n_long) {
     const sg_strings *s = c.src;
     const TokParams tp = make_tok_params(v, v->impl, s);
-    const bool sym = s->sym_width == 2;
-    int st;
-    if (v->sorted_mode)
-        st = sym ? tokenize_longs_t<uint64_t, true>(ctx, s, tp, df_table, df_replicas, df_stride, c, n_long)
-                 : tokenize_longs_t<uint64_t, false>(ctx, s, tp, df_table, df_replicas, df_stride, c, n_long);
-    else
-        st = sym ? tokenize_longs_t<uint32_t, true>(ctx, s, tp, df_table, df_replicas, df_stride, c, n_long)
-                 : tokenize_longs_t<uint32_t, false>(ctx, s, tp, df_table, df_replicas, df_stride, c, n_long);
+    const int st = by_key(v->sorted_mode, s->sym_width == 2, [&](auto key, auto sym) {
+        return tokenize_longs_t<decltype(key), decltype(sym)::value>(ctx, s, tp, df_table, df_replicas, df_stride, c, n_long);
+    });
     ctx->release(c.d_longs);
     c.d_longs = nullptr;
     return st;
@@ -1076,8 +1080,8 @@ static int resolve_longs(sg_ctx *ctx, const sg_vocab *v, TokenCache &c, int32_t 
 // fit = begin (tokenise, count document frequencies) + end (vocabulary).  The two halves are separate entry points so
 // that a multi-GPU caller can all-reduce the dense document-frequency table in between (one rank tokenises one block of
 // the strings; every rank then derives the SAME vocabulary and idf).
-static int fit_begin(sg_ctx *ctx, const sg_strings *const *sets, int32_t n_sets, const sg_vec_params *params, bool df_marks,
-                     sg_vocab **out) {
+// fit_begin is: check_fit_args, choose_coding, alloc_df_table, then K1 over every column (and the sum of the table's copies).
+static int check_fit_args(sg_ctx *ctx, const sg_strings *const *sets, int32_t n_sets, const sg_vec_params *params, sg_vocab **out) {
     SG_REQUIRE(ctx && sets && params && out && n_sets >= 1, "null argument");
     SG_REQUIRE(params->ngram_size >= 1 && params->ngram_size <= 64, "ngram_size must be in [1, 64]");
     SG_REQUIRE(params->dtype == SG_F32 || params->dtype == SG_F64, "dtype must be SG_F32 or SG_F64");
@@ -1086,19 +1090,14 @@ static int fit_begin(sg_ctx *ctx, const sg_strings *const *sets, int32_t n_sets,
         SG_REQUIRE(sets[i]->sym_width == sets[0]->sym_width && sets[i]->alphabet == sets[0]->alphabet,
                    "the string columns of one fit must be all byte columns or all symbol columns of one alphabet");
     }
-    sg_vocab *v = new (std::nothrow) sg_vocab();
-    VocabImpl *im = new (std::nothrow) VocabImpl();
-    if (!v || !im) {
-        delete v;
-        delete im;
-        return SG_ERR_OOM;
-    }
-    v->ctx = ctx;
-    v->params = *params;
-    v->impl = im;
-    int st = SG_OK;
-    const int n = params->ngram_size;
-    // ---- character coding
+    return SG_OK;
+}
+
+// How a character is coded in a key (raw 7 bits, ranks of the bytes that occur, or the host's symbols), and with it the
+// width of the keys: a dense table over the key space, or the sorted vocabulary.
+static int choose_coding(sg_ctx *ctx, sg_vocab *v, const sg_strings *const *sets, int32_t n_sets) {
+    VocabImpl *im = v->impl;
+    const int n = v->params.ngram_size;
     for (int c = 0; c < 128; ++c) {
         im->rank_of_byte[c] = (uint16_t)c;
         im->byte_of_rank[c] = (uint8_t)c;
@@ -1114,101 +1113,95 @@ static int fit_begin(sg_ctx *ctx, const sg_strings *const *sets, int32_t n_sets,
         im->local_alphabet = true;
     } else if (7 * n > 24) {
         // byte columns, long n-grams: ranks of the bytes that occur instead of the raw 7 bits
-        bool lower_any = false;
-        for (int i = 0; i < n_sets; ++i) lower_any |= params->ascii_lower && !sets[i]->prelowered;
+        Scratch tmp(ctx);
         uint32_t *d_present = nullptr;
-        st = sg_alloc(ctx, 4, &d_present);
+        SG_TRY(tmp.alloc(4, &d_present));
         uint32_t present[4] = {0, 0, 0, 0};
-        if (st == SG_OK) {
-            (void)hipMemsetAsync(d_present, 0, 16, ctx->stream);
-            for (int i = 0; i < n_sets; ++i)
-                if (sets[i]->total_bytes > 0) {
-                    const TokParams tp = make_tok_params(v, im, sets[i]);
-                    hipLaunchKernelGGL(alphabet_kernel, dim3(1024), dim3(256), 0, ctx->stream, sets[i]->d_bytes,
-                                       sets[i]->total_bytes, tp, d_present);
-                }
-            if (hipMemcpyAsync(present, d_present, 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess)
-                st = SG_ERR_HIP;
+        (void)hipMemsetAsync(d_present, 0, 16, ctx->stream);
+        for (int i = 0; i < n_sets; ++i)
+            if (sets[i]->total_bytes > 0) {
+                const TokParams tp = make_tok_params(v, im, sets[i]);
+                hipLaunchKernelGGL(alphabet_kernel, dim3(1024), dim3(256), 0, ctx->stream, sets[i]->d_bytes, sets[i]->total_bytes,
+                                   tp, d_present);
+            }
+        hipError_t e = hipMemcpyAsync(present, d_present, 16, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            sg_set_error("reading the alphabet of the fit failed: %s", hipGetErrorString(e));
+            return SG_ERR_HIP;
         }
-        (void)lower_any;
-        ctx->release(d_present);
-        if (st == SG_OK) {
-            // bytes that do not occur get the out-of-alphabet code: an n-gram containing one (only possible in a
-            // later transform() of strings that were not part of fit()) is not in the vocabulary and is skipped
-            for (int c = 0; c < 128; ++c) im->rank_of_byte[c] = SG_CHAR_ABSENT;
-            int sigma = 0;
-            for (int c = 0; c < 128; ++c)
-                if ((present[c >> 5] >> (c & 31)) & 1u) {
-                    im->rank_of_byte[c] = (uint16_t)sigma;
-                    im->byte_of_rank[sigma] = (uint8_t)c;
-                    ++sigma;
-                }
-            int bits = 1;
-            while ((1 << bits) < sigma) ++bits;
-            v->bits_per_char = bits;
-            im->local_alphabet = true;
-        }
+        // bytes that do not occur get the out-of-alphabet code: an n-gram containing one (only possible in a
+        // later transform() of strings that were not part of fit()) is not in the vocabulary and is skipped
+        for (int c = 0; c < 128; ++c) im->rank_of_byte[c] = SG_CHAR_ABSENT;
+        int sigma = 0;
+        for (int c = 0; c < 128; ++c)
+            if ((present[c >> 5] >> (c & 31)) & 1u) {
+                im->rank_of_byte[c] = (uint16_t)sigma;
+                im->byte_of_rank[sigma] = (uint8_t)c;
+                ++sigma;
+            }
+        int bits = 1;
+        while ((1 << bits) < sigma) ++bits;
+        v->bits_per_char = bits;
+        im->local_alphabet = true;
     }
-    if (st == SG_OK) {
-        const int key_bits = v->bits_per_char * n;
-        if (key_bits > 63) {
-            sg_set_error("n-grams of %d characters over an alphabet of 2^%d need %d-bit keys; the device vocabulary holds 63",
-                         n, v->bits_per_char, key_bits);
-            st = SG_ERR_UNSUPPORTED;
-        }
-        v->sorted_mode = key_bits > 30;
-        if (const char *e = ctx->opt("SG_VOCAB_SORTED"))      // test hook: the sorted vocabulary at any size
-            if (e[0] == '1') v->sorted_mode = true;
-        v->key_space = v->sorted_mode ? 0 : (int64_t)1 << key_bits;
+    const int key_bits = v->bits_per_char * n;
+    if (key_bits > 63) {
+        sg_set_error("n-grams of %d characters over an alphabet of 2^%d need %d-bit keys; the device vocabulary holds 63", n,
+                     v->bits_per_char, key_bits);
+        return SG_ERR_UNSUPPORTED;
     }
-    if (st != SG_OK) {
-        sg_vocab_free(v);
-        return st;
-    }
+    v->sorted_mode = key_bits > 30 || ctx->opt_is("SG_VOCAB_SORTED", '1');   // (the switch: a test hook, the sorted vocabulary at any size)
+    v->key_space = v->sorted_mode ? 0 : (int64_t)1 << key_bits;
+    return SG_OK;
+}
 
+// Dense mode's df table, cleared: counters in `replicas` copies (row mod replicas picks one) while they stay small, summed
+// afterwards -- or one copy of marks.  *replicas is what the tokeniser kernels take: 0 means "mark, do not count".
+static int alloc_df_table(sg_ctx *ctx, sg_vocab *v, bool df_marks, int32_t *replicas) {
+    VocabImpl *im = v->impl;
+    im->df_stride = v->key_space + 1;
+    *replicas = ctx->opt_int("SG_DF_REPLICAS", 8);
+    while (*replicas > 1 && im->df_stride * *replicas > ((int64_t)1 << 25)) *replicas >>= 1;   // <= 128 MiB of counters
+    if (*replicas < 1) *replicas = 1;
+    im->df_marks = df_marks && !ctx->opt_is("SG_DF_MARKS", '0');   // (the switch: A/B hook)
+    if (im->df_marks) *replicas = 0;
+    const size_t entries = (size_t)(im->df_stride * (im->df_marks ? 1 : *replicas));
+    SG_TRY(sg_alloc(ctx, entries, &im->d_df_table));
+    SG_TRY(sg_alloc(ctx, (size_t)v->key_space + 1, &v->d_key_to_col));
+    (void)hipMemsetAsync(im->d_df_table, 0, sizeof(int32_t) * entries, ctx->stream);
+    return SG_OK;
+}
+
+static int fit_begin(sg_ctx *ctx, const sg_strings *const *sets, int32_t n_sets, const sg_vec_params *params, bool df_marks,
+                     sg_vocab **out) {
+    SG_TRY(check_fit_args(ctx, sets, n_sets, params, out));
+    VocabPtr v(new (std::nothrow) sg_vocab());
+    if (!v) return SG_ERR_OOM;
+    v->ctx = ctx;
+    v->params = *params;
+    VocabImpl *im = v->impl = new (std::nothrow) VocabImpl();
+    if (!im) return SG_ERR_OOM;
+    SG_TRY(choose_coding(ctx, v.get(), sets, n_sets));
     {
         SgTimer timer(ctx, SG_K_TOKENIZE);
         int32_t replicas = 1;
-        int64_t df_stride = 0;
-        if (!v->sorted_mode) {
-            // df table: `replicas` copies (row mod replicas picks one) while they stay small, summed afterwards
-            df_stride = v->key_space + 1;
-            replicas = 8;
-            if (const char *e = ctx->opt("SG_DF_REPLICAS")) replicas = atoi(e);
-            while (replicas > 1 && df_stride * replicas > ((int64_t)1 << 25)) replicas >>= 1;   // <= 128 MiB of counters
-            if (replicas < 1) replicas = 1;
-            if (const char *e = ctx->opt("SG_DF_MARKS")) df_marks = df_marks && e[0] != '0';   // A/B hook
-            im->df_marks = df_marks;
-            const int64_t copies = df_marks ? 1 : replicas;
-            if (df_marks) replicas = 0;   // what the tokeniser kernels take as "mark, do not count"
-            st = sg_alloc(ctx, (size_t)(df_stride * copies), &im->d_df_table);
-            if (st == SG_OK) st = sg_alloc(ctx, (size_t)v->key_space + 1, &v->d_key_to_col);
-            if (st == SG_OK)
-                (void)hipMemsetAsync(im->d_df_table, 0, sizeof(int32_t) * (size_t)(df_stride * copies), ctx->stream);
-        }
-        for (int i = 0; i < n_sets && st == SG_OK; ++i) {
+        if (!v->sorted_mode) SG_TRY(alloc_df_table(ctx, v.get(), df_marks, &replicas));
+        for (int i = 0; i < n_sets; ++i) {
             TokenCache c;
             // (marks, dense table: the single-GPU fit, whose end asks for the long strings together with the vocabulary's size)
-            st = tokenize_set(ctx, v, sets[i], im->d_df_table, replicas, df_stride, &c, !v->sorted_mode && df_marks);
-            im->df_stride = df_stride;
-            if (st == SG_OK) {
-                im->caches.push_back(c);
-                v->n_docs += sets[i]->n;
-            }
+            SG_TRY(tokenize_set(ctx, v.get(), sets[i], im->d_df_table, replicas, im->df_stride, &c, im->df_marks));
+            im->caches.push_back(c);
+            v->n_docs += sets[i]->n;
         }
-        if (st == SG_OK && !v->sorted_mode && replicas > 1) {
+        if (!v->sorted_mode && replicas > 1) {
             const unsigned grid = (unsigned)((v->key_space + 255) / 256);
-            hipLaunchKernelGGL(df_reduce_kernel, dim3(grid), dim3(256), 0, ctx->stream, im->d_df_table, v->key_space,
-                               replicas, df_stride);
-            if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
+            hipLaunchKernelGGL(df_reduce_kernel, dim3(grid), dim3(256), 0, ctx->stream, im->d_df_table, v->key_space, replicas,
+                               im->df_stride);
+            if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
         }
     }
-    if (st != SG_OK) {
-        sg_vocab_free(v);
-        return st;
-    }
-    *out = v;
+    *out = v.release();
     return SG_OK;
 }
 
@@ -1232,46 +1225,43 @@ extern "C" int sg_vocab_df_table(sg_vocab *v, int32_t **d_table, int64_t *n_entr
 // sorted mode: vocabulary = sorted distinct keys of all columns of the fit, df = their run lengths
 static int finish_sorted_vocabulary(sg_ctx *ctx, sg_vocab *v) {
     VocabImpl *im = v->impl;
-    int64_t total = 0;
-    std::vector<int64_t *> dst_ptrs;
-    std::vector<int64_t> totals;
-    int st = SG_OK;
-    for (auto &c : im->caches) {   // where every row's keys go in the gathered array
-        int64_t *d = nullptr;
-        st = sg_alloc(ctx, (size_t)c.n + 1, &d);
-        if (st != SG_OK) break;
-        dst_ptrs.push_back(d);
-        int64_t t = 0;
-        if (c.n > 0) {
-            st = sg_exclusive_scan_i32_to_i64(ctx, c.d_cnt, d, c.n);
-            if (st == SG_OK && (hipMemcpyAsync(&t, d + c.n, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                                hipStreamSynchronize(ctx->stream) != hipSuccess))
-                st = SG_ERR_HIP;
-        }
-        if (st != SG_OK) break;
-        totals.push_back(t);
-        total += t;
-    }
-    uint64_t *all = nullptr;
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)total + 1, &all);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)total + 1, &v->d_keys);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)total + 1, &v->d_df);
-    int64_t at = 0;
-    for (size_t i = 0; i < im->caches.size() && st == SG_OK; ++i) {
-        const TokenCache &c = im->caches[i];
-        if (c.n > 0 && totals[i] > 0) {
-            hipLaunchKernelGGL(gather_keys_kernel, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, ctx->stream,
-                               (const int64_t *)c.d_ub_ptr, (const int32_t *)c.d_cnt, (const uint64_t *)c.d_keys,
-                               (const int64_t *)dst_ptrs[i], c.n, all + at);
-            if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-        }
-        at += totals[i];
-    }
     int64_t n_unique = 0;
-    if (st == SG_OK) st = sg_sort_unique_u64(ctx, all, total, v->d_keys, v->d_df, &n_unique);
-    for (int64_t *d : dst_ptrs) ctx->release(d);
-    ctx->release(all);
-    if (st != SG_OK) return st;
+    {
+        Scratch tmp(ctx);   // (goes back before the last read-back below)
+        int64_t total = 0;
+        std::vector<int64_t *> dst_ptrs;
+        std::vector<int64_t> totals;
+        for (auto &c : im->caches) {   // where every row's keys go in the gathered array
+            int64_t *d = nullptr;
+            SG_TRY(tmp.alloc((size_t)c.n + 1, &d));
+            dst_ptrs.push_back(d);
+            int64_t t = 0;
+            if (c.n > 0) {
+                SG_TRY(sg_exclusive_scan_i32_to_i64(ctx, c.d_cnt, d, c.n));
+                if (hipMemcpyAsync(&t, d + c.n, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                    hipStreamSynchronize(ctx->stream) != hipSuccess)
+                    return SG_ERR_HIP;
+            }
+            totals.push_back(t);
+            total += t;
+        }
+        uint64_t *all = nullptr;
+        SG_TRY(tmp.alloc((size_t)total + 1, &all));
+        SG_TRY(sg_alloc(ctx, (size_t)total + 1, &v->d_keys));
+        SG_TRY(sg_alloc(ctx, (size_t)total + 1, &v->d_df));
+        int64_t at = 0;
+        for (size_t i = 0; i < im->caches.size(); ++i) {
+            const TokenCache &c = im->caches[i];
+            if (c.n > 0 && totals[i] > 0) {
+                hipLaunchKernelGGL(gather_keys_kernel, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, ctx->stream,
+                                   (const int64_t *)c.d_ub_ptr, (const int32_t *)c.d_cnt, (const uint64_t *)c.d_keys,
+                                   (const int64_t *)dst_ptrs[i], c.n, all + at);
+                if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
+            }
+            at += totals[i];
+        }
+        SG_TRY(sg_sort_unique_u64(ctx, all, total, v->d_keys, v->d_df, &n_unique));
+    }
     // an out-of-alphabet key cannot occur at fit (the alphabet comes from these very strings), but a symbol column may
     // carry the code on purpose: it sorts last and is not a term
     if (n_unique > 0) {
@@ -1289,11 +1279,7 @@ static int finish_sorted_vocabulary(sg_ctx *ctx, sg_vocab *v) {
 static int count_df_by_column(sg_ctx *ctx, sg_vocab *v) {
     VocabImpl *im = v->impl;
     const int32_t max_cols = 30 * 1024;   // 120 KiB of LDS counters per pass over the tokens
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute((const void *)df_count_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_cols * 4);
-        attr_done = true;
-    }
+    SG_TRY(allow_dynamic_lds<df_count_lds_kernel>((size_t)max_cols * 4));
     std::vector<int32_t> wgs;
     int32_t n_partial = 0;
     for (const auto &c : im->caches) {
@@ -1302,11 +1288,11 @@ static int count_df_by_column(sg_ctx *ctx, sg_vocab *v) {
         wgs.push_back((int32_t)g);
         n_partial += (int32_t)g;
     }
+    Scratch tmp(ctx);
     uint32_t *partial = nullptr;
-    int st = sg_alloc(ctx, (size_t)((int64_t)(n_partial > 0 ? n_partial : 1) * v->n_terms), &partial);
-    if (st != SG_OK) return st;
+    SG_TRY(tmp.alloc((size_t)((int64_t)(n_partial > 0 ? n_partial : 1) * v->n_terms), &partial));
     int32_t at = 0;
-    const bool one_pass = v->n_terms <= max_cols && !(ctx->opt("SG_K2_COLUMNS") && ctx->opt("SG_K2_COLUMNS")[0] == '0');
+    const bool one_pass = v->n_terms <= max_cols && !ctx->opt_is("SG_K2_COLUMNS", '0');
     for (size_t i = 0; i < im->caches.size(); ++i) {
         TokenCache &c = im->caches[i];
         if (wgs[i] == 0) continue;
@@ -1322,108 +1308,105 @@ static int count_df_by_column(sg_ctx *ctx, sg_vocab *v) {
     }
     hipLaunchKernelGGL(df_sum_kernel, dim3((unsigned)((v->n_terms + 63) / 64)), dim3(256), 0, ctx->stream, (const uint32_t *)partial,
                        n_partial, v->n_terms, v->d_df);
-    if (hipGetLastError() != hipSuccess) {
-        sg_set_error("df_count_lds_kernel: %s", hipGetErrorString(hipGetLastError()));
-        st = SG_ERR_HIP;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        sg_set_error("df_count_lds_kernel: %s", hipGetErrorString(e));
+        return SG_ERR_HIP;
     }
-    ctx->release(partial);
-    return st;
+    return SG_OK;
+}
+
+// What the dense fit's end asks of the device, all of it in ONE synchronisation: the size of the vocabulary, and per column
+// -- the question fit_begin left open -- how many strings wait for the last tokeniser stage, and the non-zeros of the column's
+// matrix, whose row pointers are summed here and ride along (TokenCache).  The words land in the context's PINNED buffer: a
+// copy to a pageable address is staged and waited for on the spot -- three copies were three round trips, 20 - 40 us of idle
+// GPU each.  This is their layout, a head and then a record per column:
+struct FitSizesHead {
+    uint32_t n_terms, unused;
+};
+struct FitSizesColumn {
+    uint32_t n_long, unused;
+    int64_t nnz;
+};
+static int read_fit_sizes(sg_ctx *ctx, VocabImpl *im, const uint32_t *d_total, uint32_t *n_terms, std::vector<uint32_t> *n_long) {
+    const size_t n_cols = im->caches.size();
+    for (TokenCache &c : im->caches) {
+        if (c.n <= 0) continue;
+        if (!c.d_indptr) SG_TRY(sg_alloc(ctx, (size_t)c.n + 1, &c.d_indptr));
+        SG_TRY(sg_exclusive_scan_i32_to_i64(ctx, c.d_cnt, c.d_indptr, c.n));
+    }
+    // (a fit of more columns than the pinned buffer holds reads into pageable memory: the same words, a round trip each)
+    const size_t bytes = sizeof(FitSizesHead) + n_cols * sizeof(FitSizesColumn);
+    std::vector<uint64_t> pageable(bytes <= sizeof(uint32_t) * SG_H_FETCH_WORDS ? 0 : bytes / 8);
+    FitSizesHead *head = pageable.empty() ? (FitSizesHead *)ctx->h_fetch : (FitSizesHead *)pageable.data();
+    FitSizesColumn *col = (FitSizesColumn *)(head + 1);
+    hipError_t e = hipMemcpyAsync(&head->n_terms, d_total, 4, hipMemcpyDeviceToHost, ctx->stream);
+    for (size_t q = 0; q < n_cols && e == hipSuccess; ++q) {
+        const TokenCache &c = im->caches[q];
+        if (c.d_longs) e = hipMemcpyAsync(&col[q].n_long, c.d_longs, 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && c.d_indptr) e = hipMemcpyAsync(&col[q].nnz, c.d_indptr + c.n, 8, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    n_long->assign(n_cols, 0u);
+    for (size_t q = 0; q < n_cols; ++q) {
+        TokenCache &c = im->caches[q];
+        if (e == hipSuccess && c.d_longs) (*n_long)[q] = col[q].n_long;
+        c.nnz = e == hipSuccess && c.d_indptr ? col[q].nnz : -1;
+    }
+    if (e != hipSuccess) {
+        sg_set_error("reading the vocabulary size failed: %s", hipGetErrorString(e));
+        return SG_ERR_HIP;
+    }
+    *n_terms = head->n_terms;
+    return SG_OK;
+}
+
+// dense mode: vocabulary = keys with df > 0 (or a mark), column id = rank
+static int finish_dense_vocabulary(sg_ctx *ctx, sg_vocab *v) {
+    VocabImpl *im = v->impl;
+    uint32_t *key_rank = (uint32_t *)v->d_key_to_col;
+    Scratch tmp(ctx);
+    uint32_t *d_total = nullptr;
+    SG_TRY(tmp.alloc(4, &d_total));
+    // (the scan itself asks "does the key occur": no pass that writes 0 / 1 first)
+    SG_TRY(sg_exclusive_scan_positive_i32(ctx, im->d_df_table, key_rank, v->key_space, d_total));
+    uint32_t n_terms = 0;
+    std::vector<uint32_t> n_long;
+    SG_TRY(read_fit_sizes(ctx, im, d_total, &n_terms, &n_long));
+    bool any_long = false;
+    for (size_t q = 0; q < im->caches.size(); ++q) {
+        if (!im->caches[q].d_longs) continue;
+        any_long = any_long || n_long[q] > 0;
+        SG_TRY(resolve_longs(ctx, v, im->caches[q], im->d_df_table, 0, im->df_stride, n_long[q]));   // (marks: replicas 0)
+    }
+    if (any_long) {
+        // long strings have marked keys of their own: the vocabulary is taken again (and their rows' counts were not
+        // final when the row pointers were summed: they are summed and read again)
+        SG_TRY(sg_exclusive_scan_positive_i32(ctx, im->d_df_table, key_rank, v->key_space, d_total));
+        SG_TRY(read_fit_sizes(ctx, im, d_total, &n_terms, &n_long));
+    }
+    tmp.release(d_total);
+    v->n_terms = n_terms;
+    if (v->n_terms == 0) return SG_OK;
+    SG_TRY(sg_alloc(ctx, (size_t)v->n_terms + 1, &v->d_keys));
+    SG_TRY(sg_alloc(ctx, (size_t)v->n_terms + 1, &v->d_df));
+    hipLaunchKernelGGL(vocab_finalize_kernel, dim3((unsigned)((v->key_space + 255) / 256)), dim3(256), 0, ctx->stream,
+                       im->d_df_table, v->key_space, v->d_key_to_col, v->d_keys, v->d_df);
+    if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
+    return im->df_marks ? count_df_by_column(ctx, v) : SG_OK;
 }
 
 extern "C" int sg_vec_fit_end(sg_ctx *ctx, sg_vocab *v, int64_t n_docs_total) {
     SG_REQUIRE(ctx && v && v->impl, "null argument");
     SG_REQUIRE(v->n_terms == 0, "the vocabulary is already finished");
-    VocabImpl *im = v->impl;
     if (n_docs_total > 0) v->n_docs = n_docs_total;
-    int st = SG_OK;
-    {
-        SgTimer timer(ctx, SG_K_VOCAB);
-        if (v->sorted_mode) {
-            st = finish_sorted_vocabulary(ctx, v);
-        } else {
-            // ---- vocabulary = keys with df > 0, column id = rank
-            uint32_t *d_total = nullptr;
-            st = sg_alloc(ctx, 4, &d_total);
-            if (st == SG_OK) {
-                const unsigned grid = (unsigned)((v->key_space + 255) / 256);
-                (void)grid;   // (the scan itself asks "does the key occur": no pass that writes 0 / 1 first)
-                st = sg_exclusive_scan_positive_i32(ctx, im->d_df_table, (uint32_t *)v->d_key_to_col, v->key_space, d_total);
-            }
-            uint32_t n_terms = 0;
-            for (int attempt = 0; attempt < 2 && st == SG_OK; ++attempt) {
-                // the size of the vocabulary and -- the question fit_begin left open -- whether any column holds strings for the
-                // last tokeniser stage: ONE synchronisation; the row pointers of the columns' matrices ride along (TokenCache)
-                std::vector<uint32_t> n_long(im->caches.size(), 0u);
-                std::vector<int64_t> nnz_of(im->caches.size(), -1);
-                for (size_t q = 0; q < im->caches.size() && st == SG_OK; ++q) {
-                    TokenCache &c = im->caches[q];
-                    if (c.n <= 0) continue;
-                    if (!c.d_indptr) st = sg_alloc(ctx, (size_t)c.n + 1, &c.d_indptr);
-                    if (st == SG_OK) st = sg_exclusive_scan_i32_to_i64(ctx, c.d_cnt, c.d_indptr, c.n);
-                }
-                if (st != SG_OK) break;
-                // (into PINNED memory: a copy to a pageable address is staged and waited for on the spot -- three copies were three
-                //  round trips, 20 - 40 us of idle GPU each; layout: [0] vocabulary, then per column {strings for the last stage,
-                //  -, non-zeros: 64 bits})
-                uint32_t *hf = ctx->h_fetch;
-                const bool pinned = 4 * im->caches.size() + 4 <= SG_H_FETCH_WORDS;
-                hipError_t e = hipMemcpyAsync(pinned ? (void *)hf : (void *)&n_terms, d_total, 4, hipMemcpyDeviceToHost, ctx->stream);
-                for (size_t q = 0; q < im->caches.size() && e == hipSuccess; ++q) {
-                    if (im->caches[q].d_longs)
-                        e = hipMemcpyAsync(pinned ? (void *)(hf + 2 + 4 * q) : (void *)&n_long[q], im->caches[q].d_longs, 4, hipMemcpyDeviceToHost, ctx->stream);
-                    if (e == hipSuccess && im->caches[q].d_indptr)
-                        e = hipMemcpyAsync(pinned ? (void *)(hf + 4 + 4 * q) : (void *)&nnz_of[q], im->caches[q].d_indptr + im->caches[q].n, 8,
-                                           hipMemcpyDeviceToHost, ctx->stream);
-                }
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                if (pinned && e == hipSuccess) {
-                    n_terms = hf[0];
-                    for (size_t q = 0; q < im->caches.size(); ++q) {
-                        if (im->caches[q].d_longs) n_long[q] = hf[2 + 4 * q];
-                        if (im->caches[q].d_indptr) memcpy(&nnz_of[q], hf + 4 + 4 * q, 8);
-                    }
-                }
-                for (size_t q = 0; q < im->caches.size(); ++q) im->caches[q].nnz = nnz_of[q];
-                if (e != hipSuccess) {
-                    sg_set_error("reading the vocabulary size failed: %s", hipGetErrorString(e));
-                    st = SG_ERR_HIP;
-                    break;
-                }
-                bool any_long = false;
-                for (size_t q = 0; q < im->caches.size() && st == SG_OK; ++q) {
-                    if (!im->caches[q].d_longs) continue;
-                    any_long = any_long || n_long[q] > 0;
-                    st = resolve_longs(ctx, v, im->caches[q], im->d_df_table, 0, im->df_stride, n_long[q]);   // (marks: replicas 0)
-                }
-                if (!any_long || st != SG_OK) break;
-                // long strings have marked keys of their own: the vocabulary is taken again (and their rows' counts were not
-                // final when the row pointers were summed: the next attempt sums them again)
-                const unsigned grid = (unsigned)((v->key_space + 255) / 256);
-                (void)grid;
-                st = sg_exclusive_scan_positive_i32(ctx, im->d_df_table, (uint32_t *)v->d_key_to_col, v->key_space, d_total);
-            }
-            ctx->release(d_total);
-            if (st == SG_OK) {
-                v->n_terms = n_terms;
-                if (v->n_terms > 0) {
-                    st = sg_alloc(ctx, (size_t)v->n_terms + 1, &v->d_keys);
-                    if (st == SG_OK) st = sg_alloc(ctx, (size_t)v->n_terms + 1, &v->d_df);
-                    if (st == SG_OK) {
-                        const unsigned grid = (unsigned)((v->key_space + 255) / 256);
-                        hipLaunchKernelGGL(vocab_finalize_kernel, dim3(grid), dim3(256), 0, ctx->stream, im->d_df_table,
-                                           v->key_space, v->d_key_to_col, v->d_keys, v->d_df);
-                        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-                    }
-                    if (st == SG_OK && im->df_marks) st = count_df_by_column(ctx, v);
-                }
-            }
-        }
-        if (st == SG_OK && v->n_terms == 0) {
-            sg_set_error("empty vocabulary; perhaps the documents only contain stop words");
-            st = SG_ERR_BADARG;
-        }
+    SgTimer timer(ctx, SG_K_VOCAB);
+    SG_TRY(v->sorted_mode ? finish_sorted_vocabulary(ctx, v) : finish_dense_vocabulary(ctx, v));
+    if (v->n_terms == 0) {
+        sg_set_error("empty vocabulary; perhaps the documents only contain stop words");
+        return SG_ERR_BADARG;
     }
-    return st;
+    return SG_OK;
 }
 
 extern "C" int sg_vec_fit(sg_ctx *ctx, const sg_strings *const *sets, int32_t n_sets, const sg_vec_params *params,
@@ -1559,13 +1542,13 @@ extern "C" int sg_vocab_apply_idf_table(sg_ctx *ctx, sg_vocab *v, int32_t *appli
     if (!v->d_idf) SG_TRY(ctx->alloc(((size_t)v->n_terms + 1) * s, &v->d_idf));
     if (v->n_terms > 0) {
         const unsigned grid = (unsigned)((v->n_terms + 255) / 256);
-        if (v->params.dtype == SG_F64)
-            hipLaunchKernelGGL(idf_from_table_kernel<double>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)v->d_df, v->n_terms,
-                               (const double *)table, v->n_docs, (double *)v->d_idf);
-        else
-            hipLaunchKernelGGL(idf_from_table_kernel<float>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)v->d_df, v->n_terms,
-                               (const float *)table, v->n_docs, (float *)v->d_idf);
-        SG_HIP_TRY(hipGetLastError());
+        SG_TRY(by_dtype(v->params.dtype, [&](auto tag) -> int {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(idf_from_table_kernel<T>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)v->d_df, v->n_terms,
+                               (const T *)table, v->n_docs, (T *)v->d_idf);
+            SG_HIP_TRY(hipGetLastError());
+            return SG_OK;
+        }));
     }
     *applied = 1;
     return SG_OK;
@@ -1589,21 +1572,69 @@ extern "C" int sg_vocab_free(sg_vocab *v) {
     return SG_OK;
 }
 
-template <typename T, typename KeyT, typename Lookup>
-static void launch_weight(sg_ctx *ctx, const TokenCache *tc, Lookup lookup, const sg_vocab *v, int64_t n, const int64_t *indptr,
-                          int32_t *idx, void *val, uint32_t *props) {
-    const char *pe = ctx->opt("SG_K2_PLAIN");   // A/B and test hook: the thread-per-row statement of the arithmetic
-    const bool plain = pe && pe[0] == '1';
-    if (plain)
-        hipLaunchKernelGGL((weight_normalize_kernel<T, KeyT, Lookup>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const int64_t *)tc->d_ub_ptr, (const int32_t *)tc->d_cnt, (const KeyT *)tc->d_keys,
-                           (const int32_t *)tc->d_tf, lookup, (const T *)v->d_idf, n, indptr, idx, (T *)val, props);
-    else
-        hipLaunchKernelGGL((weight_normalize_rows16_kernel<T, KeyT, Lookup>), dim3((unsigned)((n + 15) / 16)), dim3(256), 0,
-                           ctx->stream, (const int64_t *)tc->d_ub_ptr, (const int32_t *)tc->d_cnt, (const KeyT *)tc->d_keys,
-                           (const int32_t *)tc->d_tf, lookup, (const T *)v->d_idf, n, indptr, idx, (T *)val, props);
+// K2 over the tokens of one column, written once: the dtype, and the thread-per-row statement of the arithmetic behind a switch
+template <typename KeyT, typename Lookup>
+static int launch_weight(sg_ctx *ctx, const TokenCache &tc, Lookup lookup, const sg_vocab *v, const sg_csr *m) {
+    const bool plain = ctx->opt_is("SG_K2_PLAIN", '1');   // A/B and test hook
+    return by_dtype(m->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if (plain)
+            hipLaunchKernelGGL((weight_normalize_kernel<T, KeyT, Lookup>), dim3((unsigned)((m->n_rows + 255) / 256)), dim3(256), 0,
+                               ctx->stream, (const int64_t *)tc.d_ub_ptr, (const int32_t *)tc.d_cnt, (const KeyT *)tc.d_keys,
+                               (const int32_t *)tc.d_tf, lookup, (const T *)v->d_idf, m->n_rows, m->d_indptr,
+                               (int32_t *)m->d_indices, (T *)m->d_data, m->d_props_words);
+        else
+            hipLaunchKernelGGL((weight_normalize_rows16_kernel<T, KeyT, Lookup>), dim3((unsigned)((m->n_rows + 15) / 16)), dim3(256),
+                               0, ctx->stream, (const int64_t *)tc.d_ub_ptr, (const int32_t *)tc.d_cnt, (const KeyT *)tc.d_keys,
+                               (const int32_t *)tc.d_tf, lookup, (const T *)v->d_idf, m->n_rows, m->d_indptr,
+                               (int32_t *)m->d_indices, (T *)m->d_data, m->d_props_words);
+        return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
+    });
 }
 
+// The row pointers of the matrix that a transform of the tokens `tc` returns, and its non-zeros.  `fitted`: the same cache
+// when the column was part of the fit (null otherwise).  `tmp` holds the kept counts until the caller's K2 is enqueued.
+struct RowPointers {
+    int64_t *indptr = nullptr;   // (the caller's: its matrix owns them)
+    int64_t nnz = 0;
+};
+static int row_pointers(sg_ctx *ctx, const sg_vocab *v, const TokenCache &tc, TokenCache *fitted, Scratch &tmp, RowPointers *out) {
+    const int64_t n = tc.n;
+    if (fitted && fitted->d_indptr && fitted->nnz >= 0 && n > 0) {   // summed and read by the fit's end
+        *out = {fitted->d_indptr, fitted->nnz};
+        fitted->d_indptr = nullptr;      // the matrix owns them now; a second transform of the column sums again
+        fitted->nnz = -1;
+        return SG_OK;
+    }
+    int32_t *kept = nullptr;
+    int64_t *indptr = nullptr;
+    if (!fitted) SG_TRY(tmp.alloc((size_t)n + 1, &kept));
+    SG_TRY(tmp.alloc((size_t)n + 1, &indptr));
+    if (n == 0) {
+        (void)hipMemsetAsync(indptr, 0, sizeof(int64_t), ctx->stream);
+    } else if (fitted) {
+        // the tokens of a column that was part of fit() are all in the vocabulary (min_df = 1): kept == distinct n-grams
+        SG_TRY(sg_exclusive_scan_i32_to_i64(ctx, tc.d_cnt, indptr, n));
+    } else {
+        const unsigned grid = (unsigned)((n + 255) / 256);
+        if (v->sorted_mode)
+            hipLaunchKernelGGL((kept_count_kernel<uint64_t, SortedLookup>), dim3(grid), dim3(256), 0, ctx->stream,
+                               (const int64_t *)tc.d_ub_ptr, (const int32_t *)tc.d_cnt, (const uint64_t *)tc.d_keys,
+                               SortedLookup{v->d_keys, v->n_terms}, n, kept);
+        else
+            hipLaunchKernelGGL((kept_count_kernel<uint32_t, DenseLookup>), dim3(grid), dim3(256), 0, ctx->stream,
+                               (const int64_t *)tc.d_ub_ptr, (const int32_t *)tc.d_cnt, (const uint32_t *)tc.d_keys,
+                               DenseLookup{v->d_key_to_col}, n, kept);
+        SG_TRY(sg_exclusive_scan_i32_to_i64(ctx, kept, indptr, n));
+    }
+    if (hipMemcpyAsync(&out->nnz, indptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return SG_ERR_HIP;
+    out->indptr = tmp.keep(indptr);
+    return SG_OK;
+}
+
+// transform = find or make the tokens; row_pointers; allocate the matrix's arrays; K2
 extern "C" int sg_vec_transform(sg_ctx *ctx, const sg_vocab *v, const sg_strings *strings, sg_csr **out) {
     SG_REQUIRE(ctx && v && strings && out, "null argument");
     SG_REQUIRE(v->d_idf != nullptr, "sg_vocab_set_idf has not been called");
@@ -1611,106 +1642,50 @@ extern "C" int sg_vec_transform(sg_ctx *ctx, const sg_vocab *v, const sg_strings
     SG_REQUIRE(im != nullptr, "unknown vocab");
     SG_REQUIRE((strings->sym_width == 2) == im->symbols && (!im->symbols || strings->alphabet == im->alphabet),
                "the strings are not of the kind (bytes / symbols of this alphabet) the vocabulary was fitted on");
-    // tokens: reuse the pass made by fit() when these strings were part of it
-    TokenCache local;
-    const TokenCache *tc = nullptr;
-    for (const auto &c : im->caches)
-        if (c.src == strings && c.n == strings->n) tc = &c;
-    int st = SG_OK;
-    if (!tc) {
-        SgTimer timer(ctx, SG_K_TOKENIZE);
-        st = tokenize_set(ctx, v, strings, nullptr, 1, 0, &local);
-        if (st != SG_OK) return st;
-        tc = &local;
-    }
-    const int64_t n = strings->n;
-    sg_csr *m = new (std::nothrow) sg_csr();
+    CsrPtr m(new (std::nothrow) sg_csr());
     if (!m) return SG_ERR_OOM;
     m->ctx = ctx;
-    m->n_rows = n;
+    m->n_rows = strings->n;
     m->n_cols = v->n_terms;
     m->dtype = v->params.dtype;
     m->owned = true;
-    int32_t *kept = nullptr;
-    int64_t *indptr = nullptr;
-    int64_t nnz = 0;
-    const DenseLookup dense{v->d_key_to_col};
-    const SortedLookup sorted{v->d_keys, v->n_terms};
-    {
-        SgTimer timer(ctx, SG_K_WEIGHT);
-        // the tokens of a column that was part of fit() are all in the vocabulary (min_df = 1): kept == distinct n-grams
-        const bool all_kept = tc != &local;
-        TokenCache *fitted = all_kept ? const_cast<TokenCache *>(tc) : nullptr;
-        const bool have_ptr = fitted && fitted->d_indptr && fitted->nnz >= 0 && n > 0;   // (summed and read by the fit's end)
-        if (have_ptr) {
-            indptr = fitted->d_indptr;
-            nnz = fitted->nnz;
-            fitted->d_indptr = nullptr;      // the matrix owns them now; a second transform of the column sums again
-            fitted->nnz = -1;
-        }
-        if (!all_kept) st = sg_alloc(ctx, (size_t)n + 1, &kept);
-        if (st == SG_OK && !have_ptr) st = sg_alloc(ctx, (size_t)n + 1, &indptr);
-        if (have_ptr) {
-            ;
-        } else if (st == SG_OK && n > 0) {
-            const unsigned grid = (unsigned)((n + 255) / 256);
-            if (all_kept)
-                ;
-            else if (v->sorted_mode)
-                hipLaunchKernelGGL((kept_count_kernel<uint64_t, SortedLookup>), dim3(grid), dim3(256), 0, ctx->stream,
-                                   (const int64_t *)tc->d_ub_ptr, (const int32_t *)tc->d_cnt, (const uint64_t *)tc->d_keys,
-                                   sorted, n, kept);
-            else
-                hipLaunchKernelGGL((kept_count_kernel<uint32_t, DenseLookup>), dim3(grid), dim3(256), 0, ctx->stream,
-                                   (const int64_t *)tc->d_ub_ptr, (const int32_t *)tc->d_cnt, (const uint32_t *)tc->d_keys,
-                                   dense, n, kept);
-            st = sg_exclusive_scan_i32_to_i64(ctx, all_kept ? tc->d_cnt : kept, indptr, n);
-        } else if (st == SG_OK) {
-            (void)hipMemsetAsync(indptr, 0, sizeof(int64_t), ctx->stream);
-        }
-        if (st == SG_OK && !have_ptr) {
-            if (hipMemcpyAsync(&nnz, indptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess)
-                st = SG_ERR_HIP;
-        }
-        int32_t *idx = nullptr;
-        void *val = nullptr;
-        const size_t s = m->dtype == SG_F64 ? 8 : 4;
-        if (st == SG_OK) st = sg_alloc(ctx, (size_t)nnz + 4, &idx);
-        if (st == SG_OK) st = ctx->alloc(((size_t)nnz + 4) * s, &val);
-        m->d_indptr = indptr;
-        m->d_indices = idx;
-        m->d_data = val;
-        m->nnz = nnz;
-        m->from_vectoriser = v->idf_trusted;
-        // (K2 can leave the largest row norm and the longest row behind; nothing reads them unless the opt-in row blocks
-        //  are built -- the matrix is cosine-like by construction, sg_csr_props)
-        if (st == SG_OK && ctx->opt("SG_ROW_BLOCKS") && ctx->opt("SG_ROW_BLOCKS")[0] == '1') {
-            st = sg_alloc(ctx, (size_t)4, &m->d_props_words);
-            if (st == SG_OK && hipMemsetAsync(m->d_props_words, 0, 16, ctx->stream) != hipSuccess) st = SG_ERR_HIP;
-        }
-        if (st == SG_OK && n > 0) {
-            uint32_t *props = m->d_props_words;
-            if (v->sorted_mode) {
-                if (m->dtype == SG_F64) launch_weight<double, uint64_t>(ctx, tc, sorted, v, n, indptr, idx, val, props);
-                else launch_weight<float, uint64_t>(ctx, tc, sorted, v, n, indptr, idx, val, props);
-            } else if (tc->keys_are_columns) {   // (the fit's df pass left the columns in place of the keys)
-                const ColumnsLookup cols{};
-                if (m->dtype == SG_F64) launch_weight<double, uint32_t>(ctx, tc, cols, v, n, indptr, idx, val, props);
-                else launch_weight<float, uint32_t>(ctx, tc, cols, v, n, indptr, idx, val, props);
-            } else {
-                if (m->dtype == SG_F64) launch_weight<double, uint32_t>(ctx, tc, dense, v, n, indptr, idx, val, props);
-                else launch_weight<float, uint32_t>(ctx, tc, dense, v, n, indptr, idx, val, props);
-            }
-            if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-        }
+    m->from_vectoriser = v->idf_trusted;
+    // tokens: reuse the pass made by fit() when these strings were part of it
+    OwnedTokens local(ctx);
+    Scratch tmp(ctx);
+    TokenCache *fitted = nullptr;
+    for (auto &c : im->caches)
+        if (c.src == strings && c.n == strings->n) fitted = &c;
+    if (!fitted) {
+        SgTimer timer(ctx, SG_K_TOKENIZE);
+        SG_TRY(tokenize_set(ctx, v, strings, nullptr, 1, 0, &local.c));
     }
-    ctx->release(kept);
-    if (tc == &local) free_cache(ctx, local);
-    if (st != SG_OK) {
-        sg_csr_free(m);
-        return st;
+    const TokenCache &tc = fitted ? *fitted : local.c;
+    SgTimer timer(ctx, SG_K_WEIGHT);
+    RowPointers rp;
+    SG_TRY(row_pointers(ctx, v, tc, fitted, tmp, &rp));
+    m->d_indptr = rp.indptr;
+    m->nnz = rp.nnz;
+    int32_t *idx = nullptr;
+    void *val = nullptr;
+    SG_TRY(sg_alloc(ctx, (size_t)m->nnz + 4, &idx));
+    m->d_indices = idx;
+    SG_TRY(ctx->alloc(((size_t)m->nnz + 4) * (m->dtype == SG_F64 ? 8 : 4), &val));
+    m->d_data = val;
+    // (K2 can leave the largest row norm and the longest row behind; nothing reads them unless the opt-in row blocks
+    //  are built -- the matrix is cosine-like by construction, sg_csr_props)
+    if (ctx->opt_is("SG_ROW_BLOCKS", '1')) {
+        SG_TRY(sg_alloc(ctx, (size_t)4, &m->d_props_words));
+        if (hipMemsetAsync(m->d_props_words, 0, 16, ctx->stream) != hipSuccess) return SG_ERR_HIP;
     }
-    *out = m;
+    if (m->n_rows > 0) {
+        if (v->sorted_mode)
+            SG_TRY(launch_weight<uint64_t>(ctx, tc, SortedLookup{v->d_keys, v->n_terms}, v, m.get()));
+        else if (tc.keys_are_columns)   // (the fit's df pass left the columns in place of the keys)
+            SG_TRY(launch_weight<uint32_t>(ctx, tc, ColumnsLookup{}, v, m.get()));
+        else
+            SG_TRY(launch_weight<uint32_t>(ctx, tc, DenseLookup{v->d_key_to_col}, v, m.get()));
+    }
+    *out = m.release();
     return SG_OK;
 }
