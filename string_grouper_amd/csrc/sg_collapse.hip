@@ -6,11 +6,12 @@
 // being one name took 391 ms (shape sweep) against 15 ms without it.  So the index (sg_postings.hip) is built
 // over ONE representative per group of identical rows, the multiply runs on groups, and its result is expanded:
 //
-//   * grouping: a 64-bit hash per row (sixteen lanes per row), a stable radix sort of (hash, row) (rocPRIM, like the
-//     wide-key vocabulary), a head flag where a sorted row differs from its predecessor -- compared entry by entry, the hash
-//     only brings candidates together; rows that collide without being equal stay separate groups -- and a scan;
-//     the representative of a group is its lowest row, groups are numbered by ascending representative, members listed
-//     ascending;
+//   * grouping: a 64-bit hash per row (sixteen lanes per row) brings candidates together, rows are compared entry by entry
+//     -- rows that collide without being equal stay separate groups --; the representative of a group is its lowest row,
+//     groups are numbered by ascending representative, members listed ascending.  Two paths to the same groups: by default
+//     an open-addressing table keyed by the hash (group_rows_kernel, round 4); for a list with more than SG_GROUP_LARGE_MAX
+//     groups of more than SG_GROUP_SORT_LDS rows, and under SG_GROUP_SORT=1, a stable radix sort of (hash, row) (rocPRIM,
+//     like the wide-key vocabulary), a head flag where a sorted row differs from its predecessor, and a scan (round 3);
 //   * multiply: A x U^T (one-sided) or U x U^T (self-join; all forms of the pruned multiply apply) with the caller's top_n:
 //     a row of the result over groups, ordered (score descending, group ascending), holds every group that can contribute
 //     to the row's top_n columns -- each group expands to at least one column, and the representative of a group among the
@@ -21,6 +22,9 @@
 //
 // Off when fewer than 3 % of the rows are repeats (the grouping costs ~0.3 ms at 663 k, the multiply grows with the
 // square of the rows): SG_COLLAPSE=0 / 1 force it.
+#include <cstddef>
+#include <memory>
+
 #include "sg_internal.h"
 #include "sg_scan.h"
 
@@ -465,14 +469,13 @@ int sg_collapse_materialize(sg_ctx *ctx, SgCollapse *c) {
     // (table path, round 6: the row pointers are pending too -- nothing on the way to the self-join's index reads them)
     if (c->d_rep_len) SG_TRY(sg_exclusive_scan_i32_to_i64(ctx, c->d_rep_len, (int64_t *)m->d_indptr, c->n_u));
     const unsigned gu = (unsigned)((c->n_u * 16 + 255) / 256);
-    if (B->dtype == SG_F64)
-        hipLaunchKernelGGL(unique_rows_kernel<double>, dim3(gu), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                           (const double *)B->d_data, (const uint32_t *)c->d_rep_rows, c->n_u, m->d_indptr, (int32_t *)m->d_indices,
-                           (double *)m->d_data);
-    else
-        hipLaunchKernelGGL(unique_rows_kernel<float>, dim3(gu), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                           (const float *)B->d_data, (const uint32_t *)c->d_rep_rows, c->n_u, m->d_indptr, (int32_t *)m->d_indices,
-                           (float *)m->d_data);
+    by_dtype(B->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(unique_rows_kernel<T>, dim3(gu), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
+                           (const T *)B->d_data, (const uint32_t *)c->d_rep_rows, c->n_u, m->d_indptr, (int32_t *)m->d_indices,
+                           (T *)m->d_data);
+        return SG_OK;
+    });
     SG_HIP_TRY(hipGetLastError());
     c->pending_src = nullptr;
     return SG_OK;
@@ -498,62 +501,61 @@ void sg_collapse_free(SgCollapse *c) {
     delete c;
 }
 
-static int collapse_groups(sg_ctx *ctx, const sg_csr *B, bool forced, bool by_table, bool defer_rows, SgCollapse **out);
+// ---- host driver: sg_collapse_build = wanted, then group_by_hash_table, then -- when that one reports more very large
+// groups than it lists -- group_by_sort.  (Scratch that goes back to the pool by itself, and the dtype dispatch: sg_internal.h.)
+struct CollapseFree {
+    void operator()(SgCollapse *c) const { sg_collapse_free(c); }
+};
+using CollapsePtr = std::unique_ptr<SgCollapse, CollapseFree>;   // half-built groups go back whole, whichever way a stage fails
 
-// *out stays null when collapsing is off, not worth it (fewer than 3 % repeats) or not possible.
-// left_side: the groups are those of a LEFT matrix of a one-sided product (sg_spgemm_topn): its own switch
-// (SG_COLLAPSE_LEFT=0 off, =1 from two rows on) and a higher bar by default -- the grouping is paid by the multiply that
-// asks for it, not by an index build that many multiplies share.
-int sg_collapse_build(sg_ctx *ctx, const sg_csr *B, SgCollapse **out, bool left_side, bool defer_rows) {
-    *out = nullptr;
-    const char *sw = ctx->opt("SG_COLLAPSE");
-    if ((sw && sw[0] == '0') || B->n_rows < 2 || B->nnz <= 0 || B->n_rows >= ((int64_t)1 << 31)) return SG_OK;
-    bool forced = sw && sw[0] == '1';
-    int64_t min_rows = 8192;
-    if (left_side) {
-        const char *ls = ctx->opt("SG_COLLAPSE_LEFT");
-        if (ls && ls[0] == '0') return SG_OK;
-        forced = ls && ls[0] == '1';
-        min_rows = 65536;
+static CollapsePtr new_groups(sg_ctx *ctx, int64_t n_rows) {
+    CollapsePtr c(new (std::nothrow) SgCollapse());
+    if (c) {
+        c->ctx = ctx;
+        c->n_orig = n_rows;
     }
-    if (!forced && B->n_rows < min_rows) return SG_OK;
-    const bool want_table = !(ctx->opt("SG_GROUP_SORT") && ctx->opt("SG_GROUP_SORT")[0] == '1');   // (=1: the sort-based path)
-    int st = collapse_groups(ctx, B, forced, want_table, defer_rows, out);
-    if (st == SG_OK && *out == nullptr && want_table && ctx->group_table_overflow) {
-        // a group of more than SG_GROUP_SORT_LDS members (a hub of identical names): the sort-based path lists any group
-        ctx->group_table_overflow = false;
-        st = collapse_groups(ctx, B, forced, false, defer_rows, out);
-    }
-    return st;
+    return c;
 }
 
-// the representatives' matrix of the groups `c` (n_u rows, nnz_u entries): arrays allocated, rows written unless deferred
-static int collapse_unique_matrix(sg_ctx *ctx, const sg_csr *B, SgCollapse *c, int64_t nnz_u, int64_t *ptr /* given: filled already */,
-                                  bool defer_rows) {
+// Asked for and possible?  left_side: the groups are those of a LEFT matrix of a one-sided product (sg_spgemm_topn): its own
+// switch (SG_COLLAPSE_LEFT=0 off, =1 from two rows on) and a higher bar by default -- the grouping is paid by the multiply
+// that asks for it, not by an index build that many multiplies share.
+static bool wanted(const sg_ctx *ctx, const sg_csr *B, bool left_side, bool *forced) {
+    *forced = false;
+    if (ctx->opt_is("SG_COLLAPSE", '0') || B->n_rows < 2 || B->nnz <= 0 || B->n_rows >= ((int64_t)1 << 31)) return false;
+    if (left_side && ctx->opt_is("SG_COLLAPSE_LEFT", '0')) return false;
+    *forced = ctx->opt_is(left_side ? "SG_COLLAPSE_LEFT" : "SG_COLLAPSE", '1');
+    return *forced || B->n_rows >= (left_side ? 65536 : 8192);
+}
+
+// Known once the groups are counted: some rows repeat at all, and -- unless forced -- at least 3 % of them do
+static bool worth_grouping(uint32_t n_groups, int64_t n, bool forced) {
+    return n_groups != 0 && (int64_t)n_groups != n && (forced || (double)n_groups <= 0.97 * (double)n);
+}
+
+// The representatives' matrix of the groups `c` (n_u rows, nnz_u entries): arrays allocated, rows written unless deferred.
+// `ptr`: its row pointers where they are filled already (null: allocated here, filled with the rows) -- this function's from
+// the moment it is called: the matrix's, or released.
+static int collapse_unique_matrix(sg_ctx *ctx, const sg_csr *B, SgCollapse *c, int64_t nnz_u, int64_t *ptr, bool defer_rows) {
     const int64_t n_u = c->n_u;
     int32_t *idx = nullptr;
     void *val = nullptr;
     const size_t vs = B->dtype == SG_F64 ? 8 : 4;
-    int st = SG_OK;
-    if (!ptr) st = sg_alloc(ctx, (size_t)n_u + 2, &ptr);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)nnz_u + 64, &idx);
-    if (st == SG_OK) st = ctx->alloc(((size_t)nnz_u + 64) * vs, &val);
-    sg_csr *m = st == SG_OK ? new (std::nothrow) sg_csr() : nullptr;
-    if (st == SG_OK && !m) st = SG_ERR_OOM;
-    if (st != SG_OK) {
-        ctx->release(ptr);
-        ctx->release(idx);
-        ctx->release(val);
-        return st;
-    }
+    Scratch arrays(ctx);   // (the matrix's once the matrix exists)
+    if (ptr) arrays.adopt(ptr);
+    else SG_TRY(arrays.alloc((size_t)n_u + 2, &ptr));
+    SG_TRY(arrays.alloc((size_t)nnz_u + 64, &idx));
+    SG_TRY(arrays.alloc_bytes(((size_t)nnz_u + 64) * vs, &val));
+    sg_csr *m = new (std::nothrow) sg_csr();
+    if (!m) return SG_ERR_OOM;
     m->ctx = ctx;
     m->n_rows = n_u;
     m->n_cols = B->n_cols;
     m->nnz = nnz_u;
     m->dtype = B->dtype;
-    m->d_indptr = ptr;
-    m->d_indices = idx;
-    m->d_data = val;
+    m->d_indptr = arrays.keep(ptr);
+    m->d_indices = arrays.keep(idx);
+    m->d_data = arrays.keep(val);
     m->owned = true;
     m->props_state = B->props_state;          // a subset of B's rows: cosine-like if B is; the maxima are upper bounds
     m->props_max_norm2 = B->props_max_norm2;
@@ -565,253 +567,260 @@ static int collapse_unique_matrix(sg_ctx *ctx, const sg_csr *B, SgCollapse *c, i
     return SG_OK;
 }
 
-// Grouping through the hash table (see group_rows_kernel).  ONE host round trip: the number of groups, the entries of
-// their representatives and what the member sort found arrive together, after everything has been queued on upper bounds
-// (n rows for n_u groups); rounds 4-5 stopped twice.  *out stays null when grouping is not worth it, or when a group is too
-// large for this path (ctx->group_table_overflow says so: the caller takes the sort-based one).
-static int collapse_groups_table(sg_ctx *ctx, const sg_csr *B, bool forced, bool defer_rows, SgCollapse **out) {
-    *out = nullptr;
-    ctx->group_table_overflow = false;
-    const int64_t n = B->n_rows;
+// What the table path reads back, in one copy.  The kernels leave it at three addresses of one block: the scan over "row r is
+// a representative" the number of groups, group_sort_small_kernel its words from `lds_queued` on, group_ids_kernel the entries
+// of the representatives in 32 partial sums, each on a 128-byte line of its own.
+struct GroupWords {
+    uint32_t n_groups;
+    uint32_t pad0_[3];
+    uint32_t lds_queued;                          // groups queued for the workgroup sort
+    uint32_t largest;                             // members of the largest group
+    uint32_t n_very_large;                        // groups of more than SG_GROUP_SORT_LDS members ...
+    uint32_t very_large[SG_GROUP_LARGE_MAX];      // ... and which, as far as they are listed
+    uint32_t pad1_[64 - 7 - SG_GROUP_LARGE_MAX];
+    struct {
+        unsigned long long entries;
+        uint32_t pad_[30];
+    } part[32];
+};
+static_assert(sizeof(GroupWords) == (64 + 32 * 32) * sizeof(uint32_t) && offsetof(GroupWords, lds_queued) == 4 * sizeof(uint32_t) &&
+                  offsetof(GroupWords, very_large) == 7 * sizeof(uint32_t) && offsetof(GroupWords, part) == 64 * sizeof(uint32_t) &&
+                  sizeof(GroupWords::part[0]) == 128,
+              "the layout the grouping's kernels write");
+static_assert(sizeof(GroupWords) <= SG_H_FETCH_WORDS * sizeof(uint32_t), "the pinned read-back buffer holds the grouping's words");
+
+struct TableWork {   // the table path's temporaries
     uint64_t table_size = 1024;
-    while (table_size < 2 * (uint64_t)n) table_size <<= 1;
     unsigned long long *table = nullptr;
     uint32_t *slot_of_row = nullptr, *rep_of_row = nullptr, *rep_excl = nullptr, *size = nullptr, *cursor = nullptr, *queue = nullptr;
-    uint32_t *totals = nullptr;   // [0] groups, [4 .. 36) the member sort's words, [64 .. 64 + 32 * 32) entries of the representatives (32 partial sums of 64 bits, 128 bytes apart)
-    SgCollapse *c = new (std::nothrow) SgCollapse();
-    if (!c) return SG_ERR_OOM;
-    c->ctx = ctx;
-    c->n_orig = n;
-    int st = sg_alloc(ctx, (size_t)table_size, &table);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &slot_of_row);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &rep_of_row);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &rep_excl);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 2, &size);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 2, &cursor);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 2, &queue);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)(64 + 32 * 32), &totals);
-    // (sized for n groups: the number is not known to the host while these are queued)
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &c->d_gid);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 2, &c->d_group_ptr);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &c->d_members);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &c->d_rep_rows);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 2, &c->d_rep_start);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 2, &c->d_rep_len);
-    auto cleanup = [&]() {
-        ctx->release(table);
-        ctx->release(slot_of_row);
-        ctx->release(rep_of_row);
-        ctx->release(rep_excl);
-        ctx->release(size);
-        ctx->release(cursor);
-        ctx->release(queue);
-        ctx->release(totals);
-    };
-    const unsigned g1 = (unsigned)((n + 255) / 256), g16 = (unsigned)((((n + SG_GROUP_ROWS - 1) / SG_GROUP_ROWS) * 16 + 255) / 256);
-    if (st == SG_OK)
-        st = SG_ZERO4(ctx, table, sizeof(unsigned long long) * (size_t)table_size, size, sizeof(uint32_t) * (size_t)(n + 2), cursor,
-                      sizeof(uint32_t) * (size_t)(n + 2), totals, (64 + 32 * 32) * sizeof(uint32_t));
-    if (st == SG_OK) {
-        if (B->dtype == SG_F64)
-            hipLaunchKernelGGL(group_rows_kernel<double>, dim3(g16), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                               (const double *)B->d_data, n, table, (uint32_t)(table_size - 1), slot_of_row);
-        else
-            hipLaunchKernelGGL(group_rows_kernel<float>, dim3(g16), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                               (const float *)B->d_data, n, table, (uint32_t)(table_size - 1), slot_of_row);
-        // representatives flagged and counted by the scan that needs the flags (totals[0] = number of groups)
-        st = sg_scan_launch<uint32_t>(ctx, GroupRepLoad{table, slot_of_row, rep_of_row}, SgScanStoreArray<uint32_t>{rep_excl}, n, totals);
-    }
-    if (st == SG_OK) {
-        hipLaunchKernelGGL(group_ids_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)rep_of_row, (const uint32_t *)rep_excl,
-                           (const uint32_t *)nullptr, n, c->d_gid, size, c->d_rep_rows, B->d_indptr, c->d_rep_start, c->d_rep_len,
-                           (unsigned long long *)(totals + 64));
-        // (over n + 1 sizes, zeros behind the last group: group_ptr[n_u] = n comes out by itself)
-        st = sg_exclusive_scan_u32(ctx, size, c->d_group_ptr, n + 1, nullptr);
-    }
-    if (st == SG_OK) {
-        hipLaunchKernelGGL(group_scatter_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_gid,
-                           (const uint32_t *)c->d_group_ptr, n, cursor, c->d_members);
-        hipLaunchKernelGGL(group_sort_small_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_group_ptr,
-                           (const uint32_t *)totals, c->d_members, totals + 4, queue);
-        hipLaunchKernelGGL(group_sort_lds_kernel, dim3(512), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_group_ptr, c->d_members,
-                           (const uint32_t *)(totals + 4), (const uint32_t *)queue);
-        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-    }
-    uint32_t h[64 + 32 * 32];
-    for (auto &w : h) w = 0;
-    static_assert(sizeof(h) <= SG_H_FETCH_WORDS * sizeof(uint32_t), "the pinned read-back buffer holds the grouping's words");
-    if (st == SG_OK) {   // (through pinned memory: see sg_ctx::h_fetch)
-        if (hipMemcpyAsync(ctx->h_fetch, totals, sizeof(h), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess)
-            st = SG_ERR_HIP;
-        else memcpy(h, ctx->h_fetch, sizeof(h));
-    }
-    const uint32_t n_groups = h[0];
-    int64_t nnz_u = 0;
-    for (int q = 0; q < 32; ++q) nnz_u += (int64_t)(((uint64_t)h[64 + 32 * q + 1] << 32) | (uint64_t)h[64 + 32 * q]);
-    const uint32_t *h_words = h + 4;      // [0] groups queued for the LDS sort, [1] the largest group, [2] very large groups, [3 ..] which
-    if (st != SG_OK || n_groups == 0 || (!forced && (double)n_groups > 0.97 * (double)n) || (int64_t)n_groups == n) {
-        cleanup();
-        sg_collapse_free(c);
-        return st;
-    }
-    if (h_words[2] > SG_GROUP_LARGE_MAX) {
-        // dozens of very large groups: the sort-based path lists any number of them in one go -- the caller takes it
-        ctx->group_table_overflow = true;
-        cleanup();
-        sg_collapse_free(c);
-        return SG_OK;
-    }
-    c->n_u = n_groups;
-    for (uint32_t q = 0; q < h_words[2] && st == SG_OK; ++q) {
-        // a group too large for the workgroup sort: flag / prefix sum / scatter of its own (size and rep_excl have served)
-        const uint32_t g = h_words[3 + q];
-        hipLaunchKernelGGL(large_group_flag_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_gid, n, g, size);
-        st = sg_exclusive_scan_u32(ctx, size, rep_excl, n, nullptr);
-        if (st == SG_OK) {
-            hipLaunchKernelGGL(large_group_fill_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_gid,
-                               (const uint32_t *)rep_excl, n, g, (const uint32_t *)c->d_group_ptr, c->d_members);
-            if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-        }
-    }
-    cleanup();
-    if (st == SG_OK) st = collapse_unique_matrix(ctx, B, c, nnz_u, nullptr, defer_rows);
-    if (st != SG_OK) {
-        sg_collapse_free(c);
-        return st;
-    }
-    *out = c;
+    GroupWords *words = nullptr;
+};
+
+// (the groups' arrays sized for n groups: the number is not known to the host while the work on them is queued)
+static int table_alloc(Scratch &scratch, int64_t n, TableWork *w, SgCollapse *c) {
+    sg_ctx *ctx = scratch.ctx;
+    while (w->table_size < 2 * (uint64_t)n) w->table_size <<= 1;
+    SG_TRY(scratch.alloc((size_t)w->table_size, &w->table));
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->slot_of_row));
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->rep_of_row));
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->rep_excl));
+    SG_TRY(scratch.alloc((size_t)n + 2, &w->size));
+    SG_TRY(scratch.alloc((size_t)n + 2, &w->cursor));
+    SG_TRY(scratch.alloc((size_t)n + 2, &w->queue));
+    SG_TRY(scratch.alloc((size_t)1, &w->words));
+    SG_TRY(sg_alloc(ctx, (size_t)n + 1, &c->d_gid));
+    SG_TRY(sg_alloc(ctx, (size_t)n + 2, &c->d_group_ptr));
+    SG_TRY(sg_alloc(ctx, (size_t)n + 1, &c->d_members));
+    SG_TRY(sg_alloc(ctx, (size_t)n + 1, &c->d_rep_rows));
+    SG_TRY(sg_alloc(ctx, (size_t)n + 2, &c->d_rep_start));
+    SG_TRY(sg_alloc(ctx, (size_t)n + 2, &c->d_rep_len));
     return SG_OK;
 }
 
-// The sort-based way to the groups (lists with dozens of very large groups; SG_GROUP_SORT=1); *out stays null when grouping
-// is not worth it.
-static int collapse_groups(sg_ctx *ctx, const sg_csr *B, bool forced, bool by_table, bool defer_rows, SgCollapse **out) {
-    if (by_table) return collapse_groups_table(ctx, B, forced, defer_rows, out);
-    *out = nullptr;
-    ctx->group_table_overflow = false;
+// everything up to the sorted member lists of all groups but the very large ones, on upper bounds
+static int table_queue(sg_ctx *ctx, const sg_csr *B, const TableWork &w, SgCollapse *c) {
     const int64_t n = B->n_rows;
+    const unsigned g1 = (unsigned)((n + 255) / 256), g16 = (unsigned)((((n + SG_GROUP_ROWS - 1) / SG_GROUP_ROWS) * 16 + 255) / 256);
+    SG_TRY(SG_ZERO4(ctx, w.table, sizeof(unsigned long long) * (size_t)w.table_size, w.size, sizeof(uint32_t) * (size_t)(n + 2),
+                    w.cursor, sizeof(uint32_t) * (size_t)(n + 2), w.words, sizeof(GroupWords)));
+    by_dtype(B->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(group_rows_kernel<T>, dim3(g16), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices, (const T *)B->d_data,
+                           n, w.table, (uint32_t)(w.table_size - 1), w.slot_of_row);
+        return SG_OK;
+    });
+    // representatives flagged and counted by the scan that needs the flags
+    SG_TRY(sg_scan_launch<uint32_t>(ctx, GroupRepLoad{w.table, w.slot_of_row, w.rep_of_row}, SgScanStoreArray<uint32_t>{w.rep_excl}, n,
+                                    &w.words->n_groups));
+    hipLaunchKernelGGL(group_ids_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)w.rep_of_row, (const uint32_t *)w.rep_excl,
+                       (const uint32_t *)nullptr, n, c->d_gid, w.size, c->d_rep_rows, B->d_indptr, c->d_rep_start, c->d_rep_len,
+                       &w.words->part[0].entries);
+    // (over n + 1 sizes, zeros behind the last group: group_ptr[n_u] = n comes out by itself)
+    SG_TRY(sg_exclusive_scan_u32(ctx, w.size, c->d_group_ptr, n + 1, nullptr));
+    hipLaunchKernelGGL(group_scatter_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_gid,
+                       (const uint32_t *)c->d_group_ptr, n, w.cursor, c->d_members);
+    hipLaunchKernelGGL(group_sort_small_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_group_ptr,
+                       (const uint32_t *)&w.words->n_groups, c->d_members, &w.words->lds_queued, w.queue);
+    hipLaunchKernelGGL(group_sort_lds_kernel, dim3(512), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_group_ptr, c->d_members,
+                       (const uint32_t *)&w.words->lds_queued, (const uint32_t *)w.queue);
+    SG_HIP_TRY(hipGetLastError());
+    return SG_OK;
+}
+
+static int fetch_words(sg_ctx *ctx, const GroupWords *d_words, GroupWords *h) {   // (through pinned memory: see sg_ctx::h_fetch)
+    SG_HIP_TRY(hipMemcpyAsync(ctx->h_fetch, d_words, sizeof(GroupWords), hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(h, ctx->h_fetch, sizeof(GroupWords));
+    return SG_OK;
+}
+
+// a group too large for the workgroup sort: flag / prefix sum / scatter of its own (size and rep_excl have served)
+static int list_very_large(sg_ctx *ctx, int64_t n, const GroupWords &h, const TableWork &w, SgCollapse *c) {
+    const unsigned g1 = (unsigned)((n + 255) / 256);
+    for (uint32_t q = 0; q < h.n_very_large; ++q) {
+        const uint32_t g = h.very_large[q];
+        hipLaunchKernelGGL(large_group_flag_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_gid, n, g, w.size);
+        SG_TRY(sg_exclusive_scan_u32(ctx, w.size, w.rep_excl, n, nullptr));
+        hipLaunchKernelGGL(large_group_fill_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_gid,
+                           (const uint32_t *)w.rep_excl, n, g, (const uint32_t *)c->d_group_ptr, c->d_members);
+        SG_HIP_TRY(hipGetLastError());
+    }
+    return SG_OK;
+}
+
+// Grouping through the hash table (see group_rows_kernel).  ONE host round trip: the number of groups, the entries of
+// their representatives and what the member sort found arrive together, after everything has been queued on upper bounds
+// (n rows for n_u groups); rounds 4-5 stopped twice.  *out stays null when grouping is not worth it, or when there are more
+// very large groups than this path lists: *too_many_large says so, and the caller takes the sort-based path.
+static int group_by_hash_table(sg_ctx *ctx, const sg_csr *B, bool forced, bool defer_rows, SgCollapse **out, bool *too_many_large) {
+    *out = nullptr;
+    *too_many_large = false;
+    const int64_t n = B->n_rows;
+    CollapsePtr c = new_groups(ctx, n);
+    if (!c) return SG_ERR_OOM;
+    int64_t nnz_u = 0;
+    {
+        Scratch scratch(ctx);   // (back in the pool before the representatives' matrix is allocated: it takes these blocks)
+        TableWork w;
+        SG_TRY(table_alloc(scratch, n, &w, c.get()));
+        SG_TRY(table_queue(ctx, B, w, c.get()));
+        GroupWords h;
+        SG_TRY(fetch_words(ctx, w.words, &h));
+        if (!worth_grouping(h.n_groups, n, forced)) return SG_OK;
+        // dozens of very large groups: the sort-based path lists any number of them in one go
+        if (h.n_very_large > SG_GROUP_LARGE_MAX) {
+            *too_many_large = true;
+            return SG_OK;
+        }
+        c->n_u = h.n_groups;
+        for (const auto &p : h.part) nnz_u += (int64_t)p.entries;
+        SG_TRY(list_very_large(ctx, n, h, w, c.get()));
+    }
+    SG_TRY(collapse_unique_matrix(ctx, B, c.get(), nnz_u, nullptr, defer_rows));
+    *out = c.release();
+    return SG_OK;
+}
+
+struct SortWork {   // the sort-based path's temporaries
     uint64_t *hash = nullptr, *hash_sorted = nullptr;
     uint32_t *row_id = nullptr, *row_sorted = nullptr, *head = nullptr, *run_excl = nullptr, *head_pos = nullptr;
     uint32_t *rep_of_row = nullptr, *rank_of_row = nullptr, *is_rep = nullptr, *rep_excl = nullptr, *size = nullptr;
     uint32_t *totals = nullptr;
-    SgCollapse *c = nullptr;
-    int st = sg_alloc(ctx, (size_t)n + 1, &hash);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)40, &totals);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &hash_sorted);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &row_id);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &row_sorted);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &head);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &run_excl);
-    auto cleanup = [&]() {
-        ctx->release(hash);
-        ctx->release(hash_sorted);
-        ctx->release(row_id);
-        ctx->release(row_sorted);
-        ctx->release(head);
-        ctx->release(run_excl);
-        ctx->release(head_pos);
-        ctx->release(rep_of_row);
-        ctx->release(rank_of_row);
-        ctx->release(is_rep);
-        ctx->release(rep_excl);
-        ctx->release(size);
-        ctx->release(totals);
-    };
+};
+
+// rows sorted by hash, a head flag where a sorted row differs from its predecessor, the heads counted: *n_groups
+static int sort_and_count(Scratch &scratch, const sg_csr *B, SortWork *w, uint32_t *n_groups) {
+    sg_ctx *ctx = scratch.ctx;
+    const int64_t n = B->n_rows;
     const unsigned g1 = (unsigned)((n + 255) / 256), g16 = (unsigned)((n * 16 + 255) / 256);
-    if (st == SG_OK) {
-        if (B->dtype == SG_F64)
-            hipLaunchKernelGGL(row_hash_kernel<double>, dim3(g16), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                               (const double *)B->d_data, n, hash, row_id);
-        else
-            hipLaunchKernelGGL(row_hash_kernel<float>, dim3(g16), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                               (const float *)B->d_data, n, hash, row_id);
-        st = sg_sort_pairs_u64_u32(ctx, hash, row_id, n, hash_sorted, row_sorted);
-    }
-    if (st == SG_OK) {
-        if (B->dtype == SG_F64)
-            hipLaunchKernelGGL(group_heads_kernel<double>, dim3(g1), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                               (const double *)B->d_data, n, (const uint64_t *)hash_sorted, (const uint32_t *)row_sorted, head);
-        else
-            hipLaunchKernelGGL(group_heads_kernel<float>, dim3(g1), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                               (const float *)B->d_data, n, (const uint64_t *)hash_sorted, (const uint32_t *)row_sorted, head);
-        st = sg_exclusive_scan_u32(ctx, head, run_excl, n, totals);   // totals[0] = number of groups
-    }
-    uint32_t n_groups = 0;
-    if (st == SG_OK) {
-        if (hipMemcpyAsync(&n_groups, totals, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess)
-            st = SG_ERR_HIP;
-    }
-    if (st != SG_OK || n_groups == 0 || (!forced && (double)n_groups > 0.97 * (double)n) || (int64_t)n_groups == n) {
-        cleanup();
-        return st;
-    }
-    const int64_t n_u = n_groups;
-    c = new (std::nothrow) SgCollapse();
-    if (!c) {
-        cleanup();
-        return SG_ERR_OOM;
-    }
-    c->ctx = ctx;
-    c->n_orig = n;
-    c->n_u = n_u;
-    st = sg_alloc(ctx, (size_t)n_u + 1, &size);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &c->d_gid);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_u + 2, &c->d_group_ptr);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &c->d_members);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_u + 1, &c->d_rep_rows);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_u + 1, &head_pos);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &rep_of_row);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &rank_of_row);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &is_rep);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &rep_excl);
-    if (st == SG_OK) st = SG_ZERO2(ctx, is_rep, sizeof(uint32_t) * (size_t)(n + 1), size, sizeof(uint32_t) * (size_t)(n_u + 1));
-    if (st == SG_OK) {
-        hipLaunchKernelGGL(head_pos_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)head, (const uint32_t *)run_excl, n,
-                           head_pos);
-        hipLaunchKernelGGL(group_members_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)head,
-                           (const uint32_t *)run_excl, (const uint32_t *)head_pos, (const uint32_t *)row_sorted, n, rep_of_row,
-                           rank_of_row, is_rep);
-        st = sg_exclusive_scan_u32(ctx, is_rep, rep_excl, n, nullptr);
-    }
-    if (st == SG_OK) {
-        hipLaunchKernelGGL(group_ids_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)rep_of_row,
-                           (const uint32_t *)rep_excl, (const uint32_t *)is_rep, n, c->d_gid, size, c->d_rep_rows,
-                           (const int64_t *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr, (unsigned long long *)nullptr);
-        st = sg_exclusive_scan_u32(ctx, size, c->d_group_ptr, n_u, c->d_group_ptr + n_u);
-    }
-    if (st == SG_OK) {
-        hipLaunchKernelGGL(group_fill_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_gid,
-                           (const uint32_t *)rank_of_row, (const uint32_t *)c->d_group_ptr, n, c->d_members);
-        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-    }
-    // the matrix of the representatives: its row pointers here (one more round trip for the number of entries)
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->hash));
+    SG_TRY(scratch.alloc((size_t)40, &w->totals));
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->hash_sorted));
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->row_id));
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->row_sorted));
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->head));
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->run_excl));
+    by_dtype(B->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(row_hash_kernel<T>, dim3(g16), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices, (const T *)B->d_data, n,
+                           w->hash, w->row_id);
+        return SG_OK;
+    });
+    SG_TRY(sg_sort_pairs_u64_u32(ctx, w->hash, w->row_id, n, w->hash_sorted, w->row_sorted));
+    by_dtype(B->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(group_heads_kernel<T>, dim3(g1), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices, (const T *)B->d_data, n,
+                           (const uint64_t *)w->hash_sorted, (const uint32_t *)w->row_sorted, w->head);
+        return SG_OK;
+    });
+    SG_TRY(sg_exclusive_scan_u32(ctx, w->head, w->run_excl, n, w->totals));   // totals[0] = number of groups
+    SG_HIP_TRY(hipMemcpyAsync(n_groups, w->totals, 4, hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SG_OK;
+}
+
+// per row its representative and its rank among the group's members; the groups' ids, sizes and member lists
+static int sorted_members(Scratch &scratch, int64_t n, SortWork *w, SgCollapse *c) {
+    sg_ctx *ctx = scratch.ctx;
+    const int64_t n_u = c->n_u;
+    const unsigned g1 = (unsigned)((n + 255) / 256);
+    SG_TRY(scratch.alloc((size_t)n_u + 1, &w->size));
+    SG_TRY(sg_alloc(ctx, (size_t)n + 1, &c->d_gid));
+    SG_TRY(sg_alloc(ctx, (size_t)n_u + 2, &c->d_group_ptr));
+    SG_TRY(sg_alloc(ctx, (size_t)n + 1, &c->d_members));
+    SG_TRY(sg_alloc(ctx, (size_t)n_u + 1, &c->d_rep_rows));
+    SG_TRY(scratch.alloc((size_t)n_u + 1, &w->head_pos));
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->rep_of_row));
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->rank_of_row));
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->is_rep));
+    SG_TRY(scratch.alloc((size_t)n + 1, &w->rep_excl));
+    SG_TRY(SG_ZERO2(ctx, w->is_rep, sizeof(uint32_t) * (size_t)(n + 1), w->size, sizeof(uint32_t) * (size_t)(n_u + 1)));
+    hipLaunchKernelGGL(head_pos_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)w->head, (const uint32_t *)w->run_excl, n,
+                       w->head_pos);
+    hipLaunchKernelGGL(group_members_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)w->head,
+                       (const uint32_t *)w->run_excl, (const uint32_t *)w->head_pos, (const uint32_t *)w->row_sorted, n, w->rep_of_row,
+                       w->rank_of_row, w->is_rep);
+    SG_TRY(sg_exclusive_scan_u32(ctx, w->is_rep, w->rep_excl, n, nullptr));
+    hipLaunchKernelGGL(group_ids_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)w->rep_of_row,
+                       (const uint32_t *)w->rep_excl, (const uint32_t *)w->is_rep, n, c->d_gid, w->size, c->d_rep_rows,
+                       (const int64_t *)nullptr, (int64_t *)nullptr, (int32_t *)nullptr, (unsigned long long *)nullptr);
+    SG_TRY(sg_exclusive_scan_u32(ctx, w->size, c->d_group_ptr, n_u, c->d_group_ptr + n_u));
+    hipLaunchKernelGGL(group_fill_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_gid,
+                       (const uint32_t *)w->rank_of_row, (const uint32_t *)c->d_group_ptr, n, c->d_members);
+    SG_HIP_TRY(hipGetLastError());
+    return SG_OK;
+}
+
+// the row pointers of the representatives' matrix (one more round trip for the number of entries): *ptr is the caller's
+static int unique_row_pointers(Scratch &scratch, const sg_csr *B, const SgCollapse *c, int64_t **ptr, int64_t *nnz_u) {
+    sg_ctx *ctx = scratch.ctx;
+    const int64_t n_u = c->n_u;
     int32_t *len = nullptr;
+    SG_TRY(scratch.alloc((size_t)n_u + 1, &len));
+    SG_TRY(scratch.alloc((size_t)n_u + 2, ptr));
+    hipLaunchKernelGGL(unique_len_kernel, dim3((unsigned)((n_u + 255) / 256)), dim3(256), 0, ctx->stream, B->d_indptr,
+                       (const uint32_t *)c->d_rep_rows, n_u, len);
+    SG_TRY(sg_exclusive_scan_i32_to_i64(ctx, len, *ptr, n_u));
+    SG_HIP_TRY(hipMemcpyAsync(nnz_u, *ptr + n_u, 8, hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    scratch.keep(*ptr);
+    return SG_OK;
+}
+
+// The sort-based way to the groups (lists with dozens of very large groups; SG_GROUP_SORT=1): a stable radix sort of
+// (hash, row) brings candidates together, neighbours are compared entry by entry, the sort's stability gives every row its
+// rank among its group's members.  *out stays null when grouping is not worth it.
+static int group_by_sort(sg_ctx *ctx, const sg_csr *B, bool forced, bool defer_rows, SgCollapse **out) {
+    *out = nullptr;
+    const int64_t n = B->n_rows;
+    CollapsePtr c;
     int64_t *ptr = nullptr;
     int64_t nnz_u = 0;
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_u + 1, &len);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_u + 2, &ptr);
-    if (st == SG_OK) {
-        hipLaunchKernelGGL(unique_len_kernel, dim3((unsigned)((n_u + 255) / 256)), dim3(256), 0, ctx->stream, B->d_indptr,
-                           (const uint32_t *)c->d_rep_rows, n_u, len);
-        st = sg_exclusive_scan_i32_to_i64(ctx, len, ptr, n_u);
+    {
+        Scratch scratch(ctx);   // (back in the pool before the representatives' matrix is allocated: it takes these blocks)
+        SortWork w;
+        uint32_t n_groups = 0;
+        SG_TRY(sort_and_count(scratch, B, &w, &n_groups));
+        if (!worth_grouping(n_groups, n, forced)) return SG_OK;
+        c = new_groups(ctx, n);
+        if (!c) return SG_ERR_OOM;
+        c->n_u = n_groups;
+        SG_TRY(sorted_members(scratch, n, &w, c.get()));
+        SG_TRY(unique_row_pointers(scratch, B, c.get(), &ptr, &nnz_u));
     }
-    if (st == SG_OK && (hipMemcpyAsync(&nnz_u, ptr + n_u, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                        hipStreamSynchronize(ctx->stream) != hipSuccess))
-        st = SG_ERR_HIP;
-    ctx->release(len);
-    cleanup();
-    if (st == SG_OK) {
-        st = collapse_unique_matrix(ctx, B, c, nnz_u, ptr, defer_rows);
-        ptr = nullptr;    // (the matrix's, or released by collapse_unique_matrix)
-    }
-    ctx->release(ptr);
-    if (st != SG_OK) {
-        sg_collapse_free(c);
-        return st;
-    }
-    *out = c;
+    SG_TRY(collapse_unique_matrix(ctx, B, c.get(), nnz_u, ptr, defer_rows));
+    *out = c.release();
+    return SG_OK;
+}
+
+// *out stays null when collapsing is off, not worth it (fewer than 3 % repeats) or not possible.
+int sg_collapse_build(sg_ctx *ctx, const sg_csr *B, SgCollapse **out, bool left_side, bool defer_rows) {
+    *out = nullptr;
+    bool forced = false;
+    if (!wanted(ctx, B, left_side, &forced)) return SG_OK;
+    bool by_sort = ctx->opt_is("SG_GROUP_SORT", '1');   // (the switch: the sort-based path at once)
+    if (!by_sort) SG_TRY(group_by_hash_table(ctx, B, forced, defer_rows, out, &by_sort));
+    if (by_sort) SG_TRY(group_by_sort(ctx, B, forced, defer_rows, out));
     return SG_OK;
 }
 
@@ -948,36 +957,27 @@ int sg_collapse_expand(sg_ctx *ctx, const SgCollapse *c, const sg_topn *ru, bool
                        const int32_t *row_list) {
     const int64_t n_out = out->n_rows;
     if (n_out <= 0) return SG_OK;
-    uint32_t *slow = nullptr;
-    SG_TRY(sg_alloc(ctx, (size_t)n_out + 4, &slow));
+    Scratch scratch(ctx);
+    uint32_t *slow = nullptr;   // [0] rows queued for the wave-per-row kernel, [4 ..) which
+    SG_TRY(scratch.alloc((size_t)n_out + 4, &slow));
     // (the output's counts and the slow-row queue's head in one launch; the callers do not clear the counts themselves)
-    int st = SG_ZERO2(ctx, out->d_counts, sizeof(int32_t) * (size_t)(n_out + 1), slow, 16);
-    if (st == SG_OK) {
-        // (tried in round 6: sixteen lanes per output row, contiguous reads and writes -- 0.82 instead of 0.64 ms at 5 M: a
-        //  chain of four dependent loads per row with one row per sixteen lanes in flight; a thread per row keeps ten going)
-        const unsigned g1 = (unsigned)((n_out + 255) / 256);
-        const uint32_t *gid = rows_are_groups ? c->d_gid : nullptr;
-        if (out->dtype == SG_F64) {
-            hipLaunchKernelGGL(expand_simple_kernel<double>, dim3(g1), dim3(256), 0, ctx->stream, (const int32_t *)ru->d_cols,
-                               (const double *)ru->d_vals, (const int32_t *)ru->d_counts, ru->stride, gid, row_list,
-                               (const uint32_t *)c->d_group_ptr, (const uint32_t *)c->d_members, n_out, out->stride, out->d_cols,
-                               (double *)out->d_vals, out->d_counts, slow, slow + 4);
-            hipLaunchKernelGGL(expand_merge_kernel<double>, dim3(2048), dim3(64), 0, ctx->stream, (const int32_t *)ru->d_cols,
-                               (const double *)ru->d_vals, (const int32_t *)ru->d_counts, ru->stride, gid, row_list,
-                               (const uint32_t *)c->d_group_ptr, (const uint32_t *)c->d_members, out->stride, out->d_cols,
-                               (double *)out->d_vals, out->d_counts, (const uint32_t *)slow, (const uint32_t *)(slow + 4));
-        } else {
-            hipLaunchKernelGGL(expand_simple_kernel<float>, dim3(g1), dim3(256), 0, ctx->stream, (const int32_t *)ru->d_cols,
-                               (const float *)ru->d_vals, (const int32_t *)ru->d_counts, ru->stride, gid, row_list,
-                               (const uint32_t *)c->d_group_ptr, (const uint32_t *)c->d_members, n_out, out->stride, out->d_cols,
-                               (float *)out->d_vals, out->d_counts, slow, slow + 4);
-            hipLaunchKernelGGL(expand_merge_kernel<float>, dim3(2048), dim3(64), 0, ctx->stream, (const int32_t *)ru->d_cols,
-                               (const float *)ru->d_vals, (const int32_t *)ru->d_counts, ru->stride, gid, row_list,
-                               (const uint32_t *)c->d_group_ptr, (const uint32_t *)c->d_members, out->stride, out->d_cols,
-                               (float *)out->d_vals, out->d_counts, (const uint32_t *)slow, (const uint32_t *)(slow + 4));
-        }
-        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-    }
-    ctx->release(slow);
-    return st;
+    SG_TRY(SG_ZERO2(ctx, out->d_counts, sizeof(int32_t) * (size_t)(n_out + 1), slow, 16));
+    // (tried in round 6: sixteen lanes per output row, contiguous reads and writes -- 0.82 instead of 0.64 ms at 5 M: a
+    //  chain of four dependent loads per row with one row per sixteen lanes in flight; a thread per row keeps ten going)
+    const unsigned g1 = (unsigned)((n_out + 255) / 256);
+    const uint32_t *gid = rows_are_groups ? c->d_gid : nullptr;
+    by_dtype(out->dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(expand_simple_kernel<T>, dim3(g1), dim3(256), 0, ctx->stream, (const int32_t *)ru->d_cols,
+                           (const T *)ru->d_vals, (const int32_t *)ru->d_counts, ru->stride, gid, row_list,
+                           (const uint32_t *)c->d_group_ptr, (const uint32_t *)c->d_members, n_out, out->stride, out->d_cols,
+                           (T *)out->d_vals, out->d_counts, slow, slow + 4);
+        hipLaunchKernelGGL(expand_merge_kernel<T>, dim3(2048), dim3(64), 0, ctx->stream, (const int32_t *)ru->d_cols,
+                           (const T *)ru->d_vals, (const int32_t *)ru->d_counts, ru->stride, gid, row_list,
+                           (const uint32_t *)c->d_group_ptr, (const uint32_t *)c->d_members, out->stride, out->d_cols,
+                           (T *)out->d_vals, out->d_counts, (const uint32_t *)slow, (const uint32_t *)(slow + 4));
+        return SG_OK;
+    });
+    SG_HIP_TRY(hipGetLastError());
+    return SG_OK;
 }

@@ -108,7 +108,6 @@ struct sg_ctx {
     };
     std::vector<IdfTable> idf_tables;
     int inner_multiply_depth = 0;                // > 0: sg_spgemm_topn runs for a wrapper (groups of identical rows) that counts the kept entries itself
-    bool group_table_overflow = false;           // sg_collapse.hip: the table path met a group too large for it
 
     int alloc(size_t bytes, void **out);         // pooled hipMalloc
     void release(void *p);                       // back to the pool
@@ -161,6 +160,7 @@ struct Scratch {   // blocks of the context's pool, released -- in the order the
         return p;
     }
     void release(void *p) { ctx->release(keep(p)); }   // ... or goes back early (stream-ordered, like every release)
+    void adopt(void *p) { blocks.push_back(p); }       // a block taken elsewhere: this scope's from here on
 };
 
 template <typename F>

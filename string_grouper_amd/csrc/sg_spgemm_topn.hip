@@ -1079,6 +1079,12 @@ static int run_plan(sg_ctx *ctx, const sg_csr *A, const SgPlan &plan, sg_topn *r
     return st;
 }
 
+struct InnerMultiply {   // while it lives, sg_spgemm_topn runs for a wrapper that counts the kept entries itself
+    sg_ctx *ctx;
+    explicit InnerMultiply(sg_ctx *c) : ctx(c) { ++ctx->inner_multiply_depth; }
+    ~InnerMultiply() { --ctx->inner_multiply_depth; }
+};
+
 // The index was built over one representative per group of identical right-hand rows (sg_collapse.hip): multiply on the
 // groups, expand to the caller's columns (and, in a self-join, to the caller's rows).
 static int spgemm_topn_collapsed(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t top_n, double threshold,
@@ -1100,10 +1106,10 @@ static int spgemm_topn_collapsed(sg_ctx *ctx, const sg_csr *A, const sg_postings
     view.plain = nullptr;
     view.view_of = Bt;
     sg_topn *groups = nullptr;
-    ++ctx->inner_multiply_depth;
-    const int st_inner = sg_spgemm_topn(ctx, self ? c->unique : A, &view, top_n, threshold, 1, &groups);
-    --ctx->inner_multiply_depth;
-    SG_TRY(st_inner);
+    {
+        const InnerMultiply inner(ctx);
+        SG_TRY(sg_spgemm_topn(ctx, self ? c->unique : A, &view, top_n, threshold, 1, &groups));
+    }
     const TopnPtr ru(groups);
     TopnPtr r;
     SG_TRY(topn_alloc(ctx, A->n_rows, c->n_orig, (int32_t)stride64, A->dtype, &r));
@@ -1164,10 +1170,10 @@ static int spgemm_topn_left_groups(sg_ctx *ctx, const sg_csr *A, const sg_postin
     const SgCollapse *g = A->left_groups;
     sg_topn *groups = nullptr;
     g->unique->left_state = 1;                      // (representatives are distinct)
-    ++ctx->inner_multiply_depth;
-    const int st_inner = sg_spgemm_topn(ctx, g->unique, Bt, top_n, threshold, sort, &groups);
-    --ctx->inner_multiply_depth;
-    SG_TRY(st_inner);
+    {
+        const InnerMultiply inner(ctx);
+        SG_TRY(sg_spgemm_topn(ctx, g->unique, Bt, top_n, threshold, sort, &groups));
+    }
     const TopnPtr ru(groups);
     TopnPtr r;
     SG_TRY(topn_alloc(ctx, A->n_rows, ru->n_cols, ru->stride, ru->dtype, &r));
@@ -1175,14 +1181,13 @@ static int spgemm_topn_left_groups(sg_ctx *ctx, const sg_csr *A, const sg_postin
         SgTimer timer(ctx, SG_K_ZIP);
         const int64_t cells = A->n_rows * (int64_t)ru->stride;
         const unsigned grid = (unsigned)((cells + 255) / 256);
-        if (ru->dtype == SG_F64)
-            hipLaunchKernelGGL(expand_left_rows_kernel<double>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)ru->d_cols,
-                               (const double *)ru->d_vals, (const int32_t *)ru->d_counts, (const uint32_t *)g->d_gid, A->n_rows,
-                               ru->stride, r->d_cols, (double *)r->d_vals, r->d_counts);
-        else
-            hipLaunchKernelGGL(expand_left_rows_kernel<float>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)ru->d_cols,
-                               (const float *)ru->d_vals, (const int32_t *)ru->d_counts, (const uint32_t *)g->d_gid, A->n_rows,
-                               ru->stride, r->d_cols, (float *)r->d_vals, r->d_counts);
+        by_dtype(ru->dtype, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(expand_left_rows_kernel<T>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)ru->d_cols,
+                               (const T *)ru->d_vals, (const int32_t *)ru->d_counts, (const uint32_t *)g->d_gid, A->n_rows,
+                               ru->stride, r->d_cols, (T *)r->d_vals, r->d_counts);
+            return SG_OK;
+        });
         // entries kept: counted on all rows (word [1] is still zero: the inner multiplies clear it and do not count)
         hipLaunchKernelGGL(sum_counts_kernel, dim3(256), dim3(256), 0, ctx->stream, r->d_counts, A->n_rows,
                            (unsigned long long *)(ctx->d_stat_words + 1));
@@ -1387,36 +1392,30 @@ extern "C" int sg_topn_expand_range(sg_ctx *ctx, const sg_postings *Bt, const sg
     *d_rows = nullptr;
     *n_rows = 0;
     const int64_t n = c->n_orig;
-    uint32_t *flag = nullptr, *at = nullptr, *total = nullptr;
+    Scratch mine(ctx);   // the rows' numbers: the caller's once the result exists
     int32_t *rows = nullptr;
-    int st = sg_alloc(ctx, (size_t)n + 1, &flag);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &at);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)4, &total);
     uint32_t n_mine = 0;
-    if (st == SG_OK && n > 0) {
-        const unsigned g1 = (unsigned)((n + 255) / 256);
-        hipLaunchKernelGGL(rows_of_range_flag_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_gid,
-                           (const uint32_t *)Bt->d_pos_of, n, (uint32_t)pos_lo, (uint32_t)pos_hi, (uint32_t)pos_step, flag);
-        st = sg_exclusive_scan_u32(ctx, flag, at, n, total);
-        if (st == SG_OK && (hipMemcpyAsync(&n_mine, total, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                            hipStreamSynchronize(ctx->stream) != hipSuccess))
-            st = SG_ERR_HIP;
-        if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_mine + 1, &rows);
-        if (st == SG_OK) {
+    {
+        Scratch scratch(ctx);
+        uint32_t *flag = nullptr, *at = nullptr, *total = nullptr;
+        SG_TRY(scratch.alloc((size_t)n + 1, &flag));
+        SG_TRY(scratch.alloc((size_t)n + 1, &at));
+        SG_TRY(scratch.alloc((size_t)4, &total));
+        if (n > 0) {
+            const unsigned g1 = (unsigned)((n + 255) / 256);
+            hipLaunchKernelGGL(rows_of_range_flag_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_gid,
+                               (const uint32_t *)Bt->d_pos_of, n, (uint32_t)pos_lo, (uint32_t)pos_hi, (uint32_t)pos_step, flag);
+            SG_TRY(sg_exclusive_scan_u32(ctx, flag, at, n, total));
+            SG_HIP_TRY(hipMemcpyAsync(&n_mine, total, 4, hipMemcpyDeviceToHost, ctx->stream));
+            SG_HIP_TRY(hipStreamSynchronize(ctx->stream));
+            SG_TRY(mine.alloc((size_t)n_mine + 1, &rows));
             hipLaunchKernelGGL(rows_of_range_fill_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const uint32_t *)flag,
                                (const uint32_t *)at, n, rows);
-            if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
+            SG_HIP_TRY(hipGetLastError());
         }
     }
-    ctx->release(flag);
-    ctx->release(at);
-    ctx->release(total);
-    if (st == SG_OK) st = sg_topn_expand_groups(ctx, Bt, groups, rows, (int64_t)n_mine, out);
-    if (st != SG_OK) {
-        ctx->release(rows);
-        return st;
-    }
-    *d_rows = rows;
+    SG_TRY(sg_topn_expand_groups(ctx, Bt, groups, rows, (int64_t)n_mine, out));
+    *d_rows = mine.keep(rows);
     *n_rows = (int64_t)n_mine;
     return SG_OK;
 }
