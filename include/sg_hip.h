@@ -195,7 +195,16 @@ int sg_csr_rowwise_dot(sg_ctx *ctx, const sg_csr *A, const sg_csr *B, void *out_
  * tile j / tile_cols.  tile_cols must be a power of two supported by the multiply (0 = default).
  * The postings keep a reference to B's arrays (the multiply re-scores candidates against B's rows, and an index over
  * all rows is built from them on demand when a multiply asks for more than 64 columns per row of an index over groups of
- * identical rows): B MUST stay alive -- and unchanged -- until the postings are freed. */
+ * identical rows): B MUST stay alive -- and unchanged -- until the postings are freed.
+ * What B may hold.  Every row of B must name a column ONCE: a row with the same column in two entries is refused with
+ * SG_ERR_BADARG (scipy keeps such entries; sum them first, sum_duplicates()) -- in the index they would be two postings of
+ * one row in one segment, and the exact multiply adds a segment's products without looking for that.  The call sees it
+ * where it scans B anyway, and in a row that is not in ascending column order by a second look at such rows.  Nothing
+ * else is a precondition: values of any sign, zeros, NaN and inf, rows in any column order and of any norm are accepted,
+ * and decide only WHICH kernel multiplies -- the pruned kernels take a matrix whose values are all >= 0 (-0.0 and
+ * denormals included; NaN is not), whose rows are in strictly ascending column order and whose largest squared row norm
+ * is <= 1.0001; any other matrix, on either side of the product, takes the exact kernel.  The result is the same bits
+ * either way. */
 int sg_postings_build(sg_ctx *ctx, const sg_csr *B, int32_t tile_cols, sg_postings **out);
 /* The same with options.  SG_POSTINGS_NO_PERMUTATION: by default the index is built over a fixed permutation of B's rows
  * (a sorted name list has its similar names side by side, which piles a row's candidates into a few column tiles: the
@@ -207,7 +216,13 @@ int sg_postings_build_flags(sg_ctx *ctx, const sg_csr *B, int32_t tile_cols, int
 int sg_postings_free(sg_postings *p);
 
 /* C = topn_rowwise(A . B^T restricted to > threshold).  A: n_left x V, postings of B: n_right x V.
- * Row i of the result holds counts[i] <= top_n entries at [i*top_n, i*top_n + counts[i]). */
+ * Row i of the result holds counts[i] <= top_n entries at [i*top_n, i*top_n + counts[i]).
+ * On every A and every index sg_postings_build accepted the result is, bit for bit, what sparse_dot_topn's row-wise
+ * product gives on the same arrays with A's rows in ascending column order: products and sums rounded separately in the
+ * matrices' type, a pair kept when its score is > (type)threshold -- a NaN score never is, an inf score is and sorts
+ * first --, score descending, then column ascending.  A may name a column twice in a row (both entries are multiplied,
+ * as scipy would), hold values of any sign, NaN and inf, and rows of any norm; none of it is refused, and none of it
+ * changes the numbers: it decides between the pruned and the exact kernel (sg_postings_build). */
 int sg_spgemm_topn(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t top_n, double threshold,
                    int32_t sort, sg_topn **out);
 int sg_topn_dims(const sg_topn *r, int64_t *n_rows, int32_t *stride, int32_t *dtype, int64_t *n_cols);

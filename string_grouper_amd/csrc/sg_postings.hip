@@ -1226,6 +1226,7 @@ static int build_permuted(sg_ctx *ctx, const sg_csr *B, int64_t tile_cols, sg_po
     m->props_state = B->props_state;         // same rows: same properties
     m->props_max_norm2 = B->props_max_norm2;
     m->props_max_nnz = B->props_max_nnz;
+    m->props_repeated_column = B->props_repeated_column;
     p->permuted = m;
     p->d_orig_of = scratch.keep(orig_of);
     p->d_pos_of = scratch.keep(pos_of);
@@ -1479,6 +1480,11 @@ static int build_index(sg_ctx *ctx, const sg_csr *B_in, int32_t tile_cols, int32
     bool cosine_like = false;
     float max_norm2 = 0.f;
     SG_TRY(sg_csr_props(ctx, B_in, &cosine_like, &max_norm2));
+    // a posting segment (term k, tile t) must name every row once: the exact kernel adds a segment's products with a plain
+    // read-add-write per lane (sg_spgemm_topn.hip), and of two entries (j, k) of one row one product would be lost
+    SG_REQUIRE(!B_in->props_repeated_column,
+               "the right-hand matrix has a row that names a column twice: the columns of a row must be distinct (sum the "
+               "repeated entries first, e.g. scipy's sum_duplicates())");
     BuildPlan plan;
     SG_TRY(plan_build(ctx, B_in, tile_cols, flags, cosine_like, max_norm2, &plan));
     if (!timer) timer.emplace(ctx, SG_K_POSTINGS);   // the whole build, the permuted copy included

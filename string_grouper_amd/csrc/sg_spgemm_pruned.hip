@@ -1777,6 +1777,10 @@ __global__ void __launch_bounds__(64) pairs_select_kernel(const uint32_t *__rest
 // ------------------------------------------------------------------------------------------------
 // Properties a matrix must have for the pruned kernel: values >= 0 (no NaN), column indices strictly
 // ascending within every row, row norms <= 1 (+ rounding).  One thread per row.
+// out[0]: bit 0 = some violation, bit 1 = a row names a column twice in adjacent entries, bit 2 = a row has a descending
+// pair.  A column named twice matters beyond the pruned kernel: as a RIGHT-hand matrix such a row puts the same j twice
+// into one posting segment, where the exact kernel's read-add-write keeps one of the two products (sg_spgemm_topn.hip) --
+// sg_postings_build refuses it.
 template <typename T>
 __global__ void __launch_bounds__(256) csr_props_kernel(const int64_t *__restrict__ indptr,
                                                         const int32_t *__restrict__ indices,
@@ -1792,8 +1796,8 @@ __global__ void __launch_bounds__(256) csr_props_kernel(const int64_t *__restric
         for (int64_t p = indptr[i]; p < indptr[i + 1]; ++p) {
             const T v = data[p];
             const int k = indices[p];
-            if (!(v >= (T)0)) bad = 1;
-            if (k <= prev) bad = 1;
+            if (!(v >= (T)0)) bad |= 1u;
+            if (k <= prev) bad |= k == prev ? 3u : 5u;
             prev = k;
             s += (double)v * (double)v;
         }
@@ -1807,9 +1811,29 @@ __global__ void __launch_bounds__(256) csr_props_kernel(const int64_t *__restric
         bad |= (uint32_t)__shfl_xor((int)bad, d, 64);
     }
     if ((threadIdx.x & 63) == 0) {
-        if (bad) atomicOr(out, 1u);
+        if (bad) atomicOr(out, bad);
         atomicMax(out + 1, nb);
         atomicMax(out + 2, len);
+    }
+}
+
+// The rows that are not in ascending order, where a column named twice need not sit in adjacent entries: every pair of a
+// row's entries is compared.  Only launched for a matrix with a descending pair; a row in ascending order costs one walk.
+__global__ void __launch_bounds__(256) csr_repeated_column_kernel(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                                  int64_t n_rows, uint32_t *out /* [0] |= 2 */) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const int64_t lo = indptr[i], hi = indptr[i + 1];
+    bool ascending = true;
+    for (int64_t p = lo + 1; p < hi; ++p) ascending = ascending && indices[p] > indices[p - 1];
+    if (ascending) return;
+    for (int64_t p = lo + 1; p < hi; ++p) {
+        const int k = indices[p];
+        for (int64_t q = lo; q < p; ++q)
+            if (indices[q] == k) {
+                atomicOr(out, 2u);
+                return;
+            }
     }
 }
 
@@ -1842,8 +1866,16 @@ int sg_csr_props(sg_ctx *ctx, const sg_csr *m, bool *cosine_like, float *max_nor
                                    m->d_indices, (const float *)m->d_data, m->n_rows, d);
             e = hipGetLastError();
         }
+        const bool scanned = e == hipSuccess && !m->d_props_words && m->n_rows > 0;
         if (e == hipSuccess) e = hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess && scanned && (h[0] & 4u) && !(h[0] & 2u)) {   // unsorted rows: is a column named twice further apart?
+            hipLaunchKernelGGL(csr_repeated_column_kernel, dim3((unsigned)((m->n_rows + 255) / 256)), dim3(256), 0, ctx->stream,
+                               m->d_indptr, m->d_indices, m->n_rows, d);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(h, d, 4, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        }
         ctx->release(d);
         if (e != hipSuccess) {
             sg_set_error("sg_csr_props: %s", hipGetErrorString(e));
@@ -1853,6 +1885,7 @@ int sg_csr_props(sg_ctx *ctx, const sg_csr *m, bool *cosine_like, float *max_nor
         memcpy(&n2, &h[1], 4);
         if (!m->props_by_construction) m->props_max_norm2 = n2;     // (a bound already in use stays: the index may be built on it)
         m->props_max_nnz = h[2];
+        m->props_repeated_column = (h[0] & 2u) != 0;
         m->props_state = (h[0] == 0 && n2 <= 1.0001f) ? 1 : 2;
     }
     *cosine_like = m->props_state == 1;

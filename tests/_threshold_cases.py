@@ -70,16 +70,18 @@ def _distinct_draws(rng, lo, hi, n, k):
 
 
 @functools.lru_cache(maxsize=None)
-def _ladder_rows(seed=LADDER_SEED):
+def _ladder_rows(seed=LADDER_SEED, anchors=LADDER_ANCHORS, candidates=LADDER_CANDIDATES, filler_rows=LADDER_FILLER_ROWS):
+    """(columns, values) of the ladder's rows, 16 a row; the defaults are ``ladder()``'s, tests/_offnorm_cases.py asks for a
+    smaller one."""
     rng = np.random.default_rng(seed)
     k = len(LADDER_VALUES)
-    n_anchor_cols = LADDER_ANCHORS * k
+    n_anchor_cols = anchors * k
     # anchors on disjoint column blocks, their values in a random order over the block
-    anchor_cols = rng.permutation(n_anchor_cols).reshape(LADDER_ANCHORS, k)
-    anchor_vals = np.stack([rng.permutation(LADDER_VALUES) for _ in range(LADDER_ANCHORS)])
+    anchor_cols = rng.permutation(n_anchor_cols).reshape(anchors, k)
+    anchor_vals = np.stack([rng.permutation(LADDER_VALUES) for _ in range(anchors)])
     cols, vals = [anchor_cols], [anchor_vals]
-    for a in range(LADDER_ANCHORS):
-        for c in range(LADDER_CANDIDATES):
+    for a in range(anchors):
+        for c in range(candidates):
             # 6 .. 16 of the anchor's columns; every third anchor is a tight family (13 .. 16, values in place for three of
             # four members) so that rows have more than 129 matches at 0.75 too
             tight = a % 3 == 0
@@ -94,8 +96,8 @@ def _ladder_rows(seed=LADDER_SEED):
                 row_vals = np.concatenate([anchor_vals[a, keep], rng.permutation(rest)])
             cols.append(row_cols[None, :])
             vals.append(row_vals[None, :])
-    filler_cols = _distinct_draws(rng, n_anchor_cols, LADDER_COLS, LADDER_FILLER_ROWS, k)
-    filler_vals = np.stack([rng.permutation(LADDER_VALUES) for _ in range(LADDER_FILLER_ROWS)])
+    filler_cols = _distinct_draws(rng, n_anchor_cols, LADDER_COLS, filler_rows, k)
+    filler_vals = np.stack([rng.permutation(LADDER_VALUES) for _ in range(filler_rows)])
     cols = np.concatenate(cols + [filler_cols])
     vals = np.concatenate(vals + [filler_vals])
     shuffle = rng.permutation(len(cols))                  # the members of a tie lie in different tiles

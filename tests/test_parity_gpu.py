@@ -1616,7 +1616,9 @@ def test_pruned_multiply_with_hubs_of_duplicates(ctx, monkeypatch):
 
 
 def test_matrices_that_are_not_cosine_like_take_the_exact_kernel(ctx, mats, monkeypatch):
-    """Row norms above 1, negative values or unsorted rows: no pruning (its bounds would not hold)."""
+    """Row norms above 1 (every value times 1.5) or negative values (every seventh): no pruning (its bounds would not hold).
+    Gross violations only; one bad entry at a time, unsorted rows and the band of norms the gate lets through are
+    tests/test_cosine_gate_gpu.py's."""
     monkeypatch.delenv("SG_PRUNE", raising=False)
     A = mats[np.float32][:4000].copy()
     scaled = A * np.float32(1.5)

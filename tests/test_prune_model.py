@@ -71,30 +71,71 @@ def survivors_of_row(a_idx, a_val, Bt_indptr, Bt_rows, bq_t, fq, thr, delta, nor
     return surv, streamed
 
 
-@pytest.mark.parametrize("thr,delta,freq", [(0.8, 0.2, 0.003), (0.8, 0.05, 0.0), (0.5, 0.2, 0.01), (0.95, 0.3, 0.05),
-                                            (0.8, 0.1, 0.003)])
-def test_survivors_cover_every_oracle_match(thr, delta, freq):
-    names = synth_names(3000, 77)
-    (m,), _, _ = O.tfidf_sklearn(names, [names], dtype=np.float32)
+# Off the unit norm (tests/_offnorm_cases.py has the matrices the GPU multiplies): the 3 000 names' matrix times `scale`, so that
+# norm_up is ~0.75, ~0.5 or ~1.00004 -- K3 divides every quantised bound by it, K4p multiplies by it, and at 1.000001 the two
+# cannot disagree visibly.  (scale, threshold): the threshold is the same cosine, ~0.8, at every scale.
+OFF_NORM = ((0.75, 0.45), (0.5, 0.2), (1.00004, 0.8))
+
+
+def _scaled_names(seed, scale, dtype=np.float32, n=3000, names=None):
+    """(m, m.T) in CSR with sorted rows, every value times `scale` in the matrix type (None: as the vectoriser made it)."""
+    names = synth_names(n, seed) if names is None else names
+    (m,), _, _ = O.tfidf_sklearn(names, [names], dtype=dtype)
     m = m.tocsr()
+    if scale is not None:
+        m = m * dtype(scale)
+        assert m.dtype == dtype
     m.sort_indices()
     mt = m.T.tocsr()
     mt.sort_indices()
+    return m, mt
+
+
+def _survivor_coverage(m, mt, thr, delta, freq, norm_up_k3=None):
+    """-> (oracle matches the survivors do not cover, postings streamed, postings in all).  norm_up_k3: what K3 quantises
+    against when it is NOT the norm_up the multiply uses (the mismatch the off-norm cases are there to catch)."""
     C = O.sp_matmul_topn(m, m.T.tocsr(), 10_000, thr, sort=True)   # uncapped: every pair above thr
-    norm_up = np.nextafter(f32(np.sqrt(f32(np.asarray(m.multiply(m).sum(axis=1)).max())) * f32(1.000001)), f32(2))
+    norm_up = _norm_up(m)
     freq_min = max(1, int(freq * m.shape[0]))
-    fq, bq_t = quantise_right(m, mt, freq_min, norm_up)
-    total_streamed = total_full = total_surv = 0
+    fq, bq_t = quantise_right(m, mt, freq_min, norm_up if norm_up_k3 is None else norm_up_k3)
+    lost = []
+    total_streamed = total_full = 0
     for i in range(0, m.shape[0], 7):
         lo, hi = m.indptr[i], m.indptr[i + 1]
         surv, streamed = survivors_of_row(m.indices[lo:hi], m.data[lo:hi], mt.indptr, mt.indices, bq_t, fq, thr, delta,
                                           norm_up, freq_min)
         want = C.indices[C.indptr[i]:C.indptr[i + 1]]
-        assert set(want) <= set(surv), (i, sorted(set(want) - set(surv)))
+        lost += [(i, int(j)) for j in sorted(set(want) - set(surv))]
         total_streamed += streamed
-        total_surv += len(surv)
         total_full += int((mt.indptr[m.indices[lo:hi] + 1] - mt.indptr[m.indices[lo:hi]]).sum())
+    return lost, total_streamed, total_full
+
+
+def _with_scales(old_sets, new_sets):
+    """The parameter sets a test had before it knew about scales, under the ids they had, and the new ones."""
+    return ([pytest.param(*ps, None, id="-".join(str(x) for x in ps)) for ps in old_sets] +
+            [pytest.param(*ps, id="-".join(str(x) for x in ps[:-1]) + f"-scale{ps[-1]}") for ps in new_sets])
+
+
+@pytest.mark.parametrize("thr,delta,freq,scale", _with_scales(
+    [(0.8, 0.2, 0.003), (0.8, 0.05, 0.0), (0.5, 0.2, 0.01), (0.95, 0.3, 0.05), (0.8, 0.1, 0.003)],
+    [(t, 0.05, 0.003, sc) for sc, t in OFF_NORM]))
+def test_survivors_cover_every_oracle_match(thr, delta, freq, scale):
+    m, mt = _scaled_names(77, scale)
+    lost, total_streamed, total_full = _survivor_coverage(m, mt, thr, delta, freq)
+    assert not lost, lost[:10]
     assert total_streamed < total_full   # the filter does prune
+
+
+@pytest.mark.parametrize("scale,thr", OFF_NORM[:2])
+def test_survivors_lose_matches_when_the_index_is_quantised_against_another_norm(scale, thr):
+    """The mistake the off-norm inputs exist to catch: K3 quantises against 1 while the multiply scales by the true norm_up.
+    Every bq is then too small by the factor norm_up and matches fall below the survivor bar -- the model with the right
+    formulas (above) loses none at the same scale, so a kernel that loses one has this mismatch or one like it."""
+    m, mt = _scaled_names(77, scale)
+    assert abs(float(_norm_up(m)) - scale) < 1e-4
+    lost, _, _ = _survivor_coverage(m, mt, thr, 0.05, 0.003, norm_up_k3=f32(1.0))
+    assert len(lost) >= 1
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -212,18 +253,16 @@ def records_of_row_stream(a_idx, a_val, Bt_indptr, Bt_rows, bq_t, fq, postings, 
     return np.array(rec, dtype=np.int64), len(cols)
 
 
-@pytest.mark.parametrize("thr,delta,freq,tile", [(0.8, 0.05, 0.005, 4096), (0.8, 0.05, 0.0045, 16), (0.5, 0.2, 0.01, 16),
-                                                 (0.95, 0.3, 0.05, 64), (0.6, 0.02, 0.0, 16), (0.8, 0.03, 0.005, 4096)])
-def test_stream_form_records_cover_every_oracle_match(thr, delta, freq, tile):
-    """`tile` much smaller than the kernel's 4096 folds 3000 columns as heavily as 663 k columns fold in the kernel."""
-    names = synth_names(3000, 78)
-    (m,), _, _ = O.tfidf_sklearn(names, [names], dtype=np.float32)
-    m = m.tocsr()
-    m.sort_indices()
-    mt = m.T.tocsr()
-    mt.sort_indices()
+@pytest.mark.parametrize("thr,delta,freq,tile,scale", _with_scales(
+    [(0.8, 0.05, 0.005, 4096), (0.8, 0.05, 0.0045, 16), (0.5, 0.2, 0.01, 16), (0.95, 0.3, 0.05, 64), (0.6, 0.02, 0.0, 16),
+     (0.8, 0.03, 0.005, 4096)],
+    [(t, 0.05, 0.005, tile, sc) for sc, t in OFF_NORM for tile in (4096, 16)]))
+def test_stream_form_records_cover_every_oracle_match(thr, delta, freq, tile, scale):
+    """`tile` much smaller than the kernel's 4096 folds 3000 columns as heavily as 663 k columns fold in the kernel.
+    `scale`: the matrix off the unit norm (OFF_NORM)."""
+    m, mt = _scaled_names(78, scale)
     C = O.sp_matmul_topn(m, m.T.tocsr(), 10_000, thr, sort=True)
-    norm_up = np.nextafter(f32(np.sqrt(f32(np.asarray(m.multiply(m).sum(axis=1)).max())) * f32(1.000001)), f32(2))
+    norm_up = _norm_up(m)
     freq_min = max(1, int(freq * m.shape[0]))
     fq, bq_t, postings = quantise_right_stream(m, mt, freq_min, norm_up, tile=tile)
     n_true = 0
@@ -313,17 +352,20 @@ def _norm_up(m):
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
-@pytest.mark.parametrize("thr", [0.5, 0.8, 0.95])
-def test_second_filter_passes_every_pair_above_the_threshold(dtype, thr):
+@pytest.mark.parametrize("thr,scale", [pytest.param(0.5, None, id="0.5"), pytest.param(0.8, None, id="0.8"),
+                                       pytest.param(0.95, None, id="0.95")] +
+                         [pytest.param(t, sc, id=f"{t}-scale{sc}") for sc, t in OFF_NORM])
+def test_second_filter_passes_every_pair_above_the_threshold(dtype, thr, scale):
     """Every match the oracle keeps -- hubs of identical and near-identical names included -- passes the 8-bit bound, and
-    the bound rejects most of what is far below the threshold (it is a filter, not a formality)."""
+    the bound rejects most of what is far below the threshold (it is a filter, not a formality).  `scale`: the matrix off
+    the unit norm (OFF_NORM) -- bq is quantised relative to norm_up and the bar scaled by 255 / norm_up."""
     names = list(synth_names(4000, 321))
     for k in range(60):                                   # a hub: identical rows and one-character variants
         names[50 * k] = "NORTHERN LIGHTS HOLDING CO" + ("" if k % 3 else " " + "ABC"[k % 3])
-    (m,), _, _ = O.tfidf_sklearn(names, [names], dtype=dtype)
-    m = m.tocsr()
-    m.sort_indices()
+    m, _ = _scaled_names(None, scale, dtype, names=names)
     norm_up = _norm_up(m)
+    if scale is not None:
+        assert abs(float(norm_up) - scale) < 1e-4
     C = O.sp_matmul_topn(m, m.T.tocsr(), 100000, thr, sort=True)
     rng = np.random.default_rng(7)
     rows = np.unique(np.concatenate([rng.integers(0, m.shape[0], 500), np.arange(0, 3000, 50)]))
