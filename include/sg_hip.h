@@ -75,7 +75,9 @@ int sg_ctx_trim(sg_ctx *ctx);
  * of the environment ONCE, in sg_ctx_create; afterwards only these calls change them (value NULL: unset), and nothing
  * inside an API call looks at the environment.  sg_ctx_options writes the active set as NAME=VALUE lines into buf and
  * returns the bytes needed (0-terminated); sg_ctx_reset_options re-reads the environment (test hook).  Not to be
- * called while another thread has a call in flight on the same context. */
+ * called while another thread has a call in flight on the same context.
+ * Among the switches that select an earlier form of a kernel: SG_DEAL=floor -- the pruned multiply
+ * deals a wave's lanes to a row's prefix terms with the remainders dropped, as it did before the largest-remainder rule. */
 int sg_ctx_set_option(sg_ctx *ctx, const char *name, const char *value);
 int sg_ctx_reset_options(sg_ctx *ctx);
 int sg_ctx_options(sg_ctx *ctx, char *buf, int64_t len);

@@ -167,6 +167,69 @@ struct Post<double> {
 };
 
 
+// ---- Dealing the 64 lanes of a wave to the np prefix terms of a row (pruned multiply), in proportion to their list
+// lengths df.  THE RULE, for the kernel and for the host restatement the tests drive (sg_debug_deal_lanes):
+//     every term gets one lane; the 64 - np spare ones go by largest remainder --
+//     spare * df_t = q_t * dsum + rem_t  (0 <= rem_t < dsum, dsum = sum of the df),   G_t = 1 + q_t,   R = spare - sum q_t
+//     and the R terms with the largest rem_t get one lane more; equal remainders: the term that comes first.
+// In integers, hence exact: sum G = 64 whenever 1 <= np <= 64 and dsum > 0 (sum rem_t = R * dsum, so R <= np - 1 terms have
+// a remainder to be chosen by), and a longer list never has fewer lanes than a shorter one (a larger df has the larger
+// (q, rem) pair).  The rule before it, G_t = 1 + floor(spare * 0.999 * df_t / dsum) in floats, threw the remainders away:
+// 4.6 of the 64 lanes read postings that add nothing for the whole row at 663 k, while the longest lane stream sets the
+// rounds of every visit (scripts/k4p_deal_model.py).  It is kept behind SG_DEAL=floor.
+//
+// U = uint64_t on the host (any df below 2^32).  U = uint32_t on the wave: dsum < 2^30 there -- the lists are disjoint
+// pieces of one posting array whose byte offsets fit 32 bits -- and the quotient (at most 63) comes from a float estimate
+// that is off by one at most (three roundings of 2^-24 and a reciprocal of one ulp on a number below 64), set right by the
+// remainder, which is computed modulo 2^32: the true one lies in (-dsum, 2 dsum).  No integer division on the GPU.
+template <typename U>
+__host__ __device__ __forceinline__ void sg_deal_share(U df, U dsum, uint32_t spare, uint32_t &q, U &rem) {
+    if constexpr (sizeof(U) == 8) {
+        const U num = (U)spare * df;
+        q = (uint32_t)(num / dsum);
+        rem = num % dsum;
+    } else {
+#ifdef __HIP_DEVICE_COMPILE__
+        const float inv = __builtin_amdgcn_rcpf((float)dsum);
+#else
+        const float inv = 1.0f / (float)dsum;
+#endif
+        q = (uint32_t)((float)spare * (float)df * inv);
+        int32_t r = (int32_t)(spare * df - q * dsum);
+        if (r < 0) {
+            --q;
+            r += (int32_t)dsum;
+        } else if (r >= (int32_t)dsum) {
+            ++q;
+            r -= (int32_t)dsum;
+        }
+        rem = (U)r;
+    }
+}
+// The remainder from which a term gets one of the R >= 1 lanes left over: the largest c with at_least(c) >= R, where
+// at_least(c) counts the prefix terms whose remainder is c or more (on the wave: one compare and a population count of its
+// mask per probe).  Terms above c get a lane, the first R - at_least(c + 1) of those at c the rest.  Found bit by bit from
+// the top bit of dsum - 1 down -- and no further than the first c that exactly R terms reach: they are the R largest, and
+// with a handful of remainders spread over [0, dsum) that is a few probes, not log2(dsum).
+template <typename U, typename AtLeast>
+__host__ __device__ __forceinline__ U sg_deal_cut(U dsum, uint32_t R, AtLeast at_least) {
+    U cut = 0;   // at_least(0) >= R: every term counts
+    if (dsum < 2) return cut;
+    const int top = (sizeof(U) == 8 ? 63 - __builtin_clzll((unsigned long long)(dsum - 1)) : 31 - __builtin_clz((unsigned)(dsum - 1)));
+    for (U bit = (U)1 << top; bit; bit >>= 1) {
+        const uint32_t n = at_least(cut | bit);
+        if (n >= R) {
+            cut |= bit;
+            if (n == R) break;
+        }
+    }
+    return cut;
+}
+// The rule before: remainders dropped (dsum as a float; np <= 64).
+__host__ __device__ __forceinline__ uint32_t sg_deal_floor_rule(uint32_t df, float dsum, int np) {
+    return 1u + (uint32_t)((float)(64 - np) * 0.999f * ((float)df / dsum));
+}
+
 // Next left row for this wave: one global atomic by lane 0, broadcast.  The result is made
 // explicitly wave-uniform so that everything derived from it stays in SGPRs / uniform branches.
 __device__ __forceinline__ uint32_t next_row(uint32_t *row_counter, int lane) {

@@ -705,7 +705,7 @@ spgemm_topn_pruned_kernel(const int64_t *__restrict__ a_indptr, const int32_t *_
                           uint32_t null_off /* stream form: byte offset of 256 filter postings that add nothing, four per lane */,
                           uint32_t n_right /* right-hand rows (columns of the result) */,
                           uint32_t *heavy_count, uint32_t *heavy_rows /* stream + self-join form: rows set aside for the launch over parts */,
-                          uint32_t sym_step,
+                          uint32_t sym_step, uint32_t deal_floor /* SG_DEAL=floor: the lanes dealt by the earlier rule, remainders dropped */,
                           uint32_t part_cfg /* 0: every row whole; < 2^31: rows of at least this many rounds (bits [0, 28)) are set aside, and a row that has scored rounds << bits [28, 31) candidates hands its remaining visits on;
                                                bit 31: this IS the launch over parts (rows in row_list, SG_ROW_PARTS items each) */) {
     constexpr int TILE = 1 << TILE_LOG2;
@@ -796,46 +796,73 @@ spgemm_topn_pruned_kernel(const int64_t *__restrict__ a_indptr, const int32_t *_
         }
         if (nnz == 0) continue;   // out_cnt is zero-initialised
         int k[SLOTS];
-        T a[SLOTS];
-        uint32_t df[SLOTS], lo_e[SLOTS];
+        T a[SLOTS], a2[SLOTS];
+        uint32_t df[SLOTS], lo_e[SLOTS], key[SLOTS];
         float w[SLOTS], cum[SLOTS];
+        uint64_t fm[SLOTS];   // the row's frequent terms: the only ones that can join the suffix
 #pragma unroll
         for (int sl = 0; sl < SLOTS; ++sl) {
             k[sl] = 0;
             a[sl] = (T)0;
             df[sl] = lo_e[sl] = 0;
-            if (lane + 64 * sl < nnz) {
+            const bool have = lane + 64 * sl < nnz;
+            if (have) {
                 k[sl] = a_indices[rlo + lane + 64 * sl];
                 a[sl] = a_data[rlo + lane + 64 * sl];
                 const uint32_t *sp = seg + (int64_t)k[sl] * n_tiles;
                 lo_e[sl] = sp[0];
                 df[sl] = sp[n_tiles] - lo_e[sl];
             }
+            a2[sl] = mul_rn<T>(a[sl], a[sl]);   // (the diagonal's addend, below; in float also the first product of w)
             // rounded up: covers the float sums below
-            w[sl] = lane + 64 * sl < nnz ? (float)a[sl] * (float)a[sl] * 1.00001f : 0.f;
+            w[sl] = have ? (sizeof(T) == 4 ? (float)a2[sl] : (float)a[sl] * (float)a[sl]) * 1.00001f : 0.f;
             cum[sl] = 0.f;
+            // the order of the ranking as ONE number: list length descending, then position ascending.  Lists of 2^25 entries
+            // and more count as equally long (the key has 25 bits for the length): among them the position decides, which is
+            // still one total order, so cum stays a running sum along it and the suffix a valid one -- but on an index
+            // with several such lists in a row cum is no longer the number the three compares gave
+            key[sl] = (min(df[sl], (1u << 25) - 1u) << 7) | (127u - (uint32_t)(lane + 64 * sl));
+            fm[sl] = ballot64(have && df[sl] >= freq_min);
         }
         // ---- suffix S: the most frequent terms while the bound on ||a_S|| holds.  cum = sum of squares of
-        // the terms ordered before this one (list length descending, position ascending), inclusive.
-        for (int q = 0; q < nnz; ++q) {
-            uint32_t dq;
-            float wq;
-            if (SLOTS == 1 || q < 64) {
-                dq = wave_read<uint32_t>(df[0], q);
-                wq = wave_read<float>(w[0], q);
-            } else {
-                dq = wave_read<uint32_t>(df[SLOTS - 1], q - 64);
-                wq = wave_read<float>(w[SLOTS - 1], q - 64);
-            }
+        // the terms ordered before this one (list length descending, position ascending), inclusive -- added in ascending
+        // position.  Only a frequent term can join the suffix and only frequent terms come before one: the others neither
+        // need their sum nor add to anybody's (what they added was 0).
+        // Self-join, stream form: the same trip over the row sums the row's match with ITSELF -- see `own` below.
+        const bool sum_own = SYM && FOLD_LOG2 > 0 && !part_mode;
+        T own = (T)0;
+        auto rank_step = [&](int sl_q, int f) {   // entry f of slot sl_q (wave-uniform) against every lane's
+            const uint32_t kq = wave_read<uint32_t>(key[sl_q], f);
+            const float wq = wave_read<float>(w[sl_q], f);
 #pragma unroll
-            for (int sl = 0; sl < SLOTS; ++sl) {
-                const bool before = dq > df[sl] || (dq == df[sl] && q <= lane + 64 * sl);
-                cum[sl] += before ? wq : 0.f;
+            for (int sl = 0; sl < SLOTS; ++sl) cum[sl] += kq >= key[sl] ? wq : 0.f;
+        };
+        if (sum_own) {
+#pragma unroll
+            for (int sl_q = 0; sl_q < SLOTS; ++sl_q) {
+                const int n_q = min(nnz - 64 * sl_q, 64);
+                for (int f = 0; f < n_q; ++f) {
+                    own = add_rn<T>(own, wave_read<T>(a2[sl_q], f));
+                    if ((fm[sl_q] >> f) & 1ull) rank_step(sl_q, f);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int sl_q = 0; sl_q < SLOTS; ++sl_q) {
+                uint64_t m = fm[sl_q];
+                SG_WD_DECL(wd_r);
+                while (m) {
+                    SG_WD(wd_r, 70, 18)
+                    const int f = __builtin_ctzll(m);
+                    m &= m - 1;
+                    rank_step(sl_q, f);
+                }
             }
         }
         bool in_p[SLOTS];
         uint64_t pm[SLOTS];
-        float bs2 = 0.f, dsum = 0.f;
+        float bs2 = 0.f;
+        uint32_t dsum_i = 0;   // (an integer: the dealing below is exact; the lists are pieces of one array of < 2^30 entries)
         int np = 0;
 #pragma unroll
         for (int sl = 0; sl < SLOTS; ++sl) {
@@ -845,7 +872,7 @@ spgemm_topn_pruned_kernel(const int64_t *__restrict__ a_indptr, const int32_t *_
             pm[sl] = __ballot(in_p[sl]);
             np += __popcll(pm[sl]);
             bs2 = fmaxf(bs2, in_s ? cum[sl] : 0.f);
-            dsum += in_p[sl] ? (float)df[sl] : 0.f;
+            dsum_i += in_p[sl] ? df[sl] : 0u;
         }
         if (np == 0) continue;   // ||a|| * max ||b|| <= beta < threshold: no match possible
         if (np > 64) {           // (wide rows only) more prefix terms than lanes: exact kernel
@@ -860,11 +887,11 @@ spgemm_topn_pruned_kernel(const int64_t *__restrict__ a_indptr, const int32_t *_
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) {
             bs2 = fmaxf(bs2, __shfl_xor(bs2, d, 64));
-            dsum += __shfl_xor(dsum, d, 64);
+            dsum_i += __shfl_xor(dsum_i, d, 64);
         }
         bs2 = wave_read<float>(bs2, 0);     // explicitly wave-uniform: the branches below must not diverge
-        dsum = wave_read<float>(dsum, 0);
-        if (!(dsum > 0.f)) continue;   // every list of P is empty
+        dsum_i = wave_read<uint32_t>(dsum_i, 0);
+        if (dsum_i == 0u) continue;   // every list of P is empty
         // ---- survivor test in fixed point (scale 2^15).  q_ij accumulates UPPER bounds of the products, so
         //      p_ij * 2^15 <= q_ij; the exact kernel's float score obeys  score~ <= score + 1e-5  and
         //      score <= p_ij + ||a_S|| f_j  with  f_j <= fq_j / 255 * norm_b.  Column j survives when
@@ -888,23 +915,65 @@ spgemm_topn_pruned_kernel(const int64_t *__restrict__ a_indptr, const int32_t *_
         }
         const int32_t T0m = T0 - 256;    // (T0m - C1 * fq) >> 8 == tq - 1 >= 0
 
-        // ---- deal the 64 lanes to the terms of P in proportion to their list lengths
-        uint32_t G[SLOTS], start[SLOTS];
-        uint32_t before_slot = 0;
+        // ---- deal the 64 lanes to the terms of P in proportion to their list lengths (the rule: sg_k4_device.h)
+        uint32_t G[SLOTS], rem[SLOTS];
 #pragma unroll
         for (int sl = 0; sl < SLOTS; ++sl) {
-            G[sl] = in_p[sl] ? 1u + (uint32_t)((float)(64 - np) * 0.999f * ((float)df[sl] / dsum)) : 0u;
-            uint32_t inc = G[sl];   // inclusive scan, made exclusive below
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t o = __shfl_up(inc, d, 64);
-                if (lane >= d) inc += o;
+            rem[sl] = 0u;
+            if (deal_floor) {
+                // (dsum: the exact sum rounded once, where the rule used to add floats across the wave -- the same number
+                //  below 2^24 entries, the nearest float above)
+                G[sl] = in_p[sl] ? sg_deal_floor_rule(df[sl], (float)dsum_i, np) : 0u;
+            } else {
+                uint32_t q = 0;
+                // (a lane outside P shares nothing: its list may be far longer than dsum, a quotient beyond 32 bits)
+                sg_deal_share<uint32_t>(in_p[sl] ? df[sl] : 0u, dsum_i, (uint32_t)(64 - np), q, rem[sl]);
+                G[sl] = in_p[sl] ? 1u + q : 0u;
             }
-            start[sl] = before_slot + inc - G[sl];
-            before_slot += wave_read<uint32_t>(inc, 63);
         }
+        if (!deal_floor) {
+            // the lanes given so far, added up term by term in scalar registers (a handful of terms: cheaper than a
+            // reduction across the wave, which is six exchanges through the LDS crossbar and their waits)
+            uint32_t given = 0;
+#pragma unroll
+            for (int sl = 0; sl < SLOTS; ++sl) {
+                uint64_t m = pm[sl];
+                SG_WD_DECL(wd_g);
+                while (m) {
+                    SG_WD(wd_g, 70, 19)
+                    given += wave_read<uint32_t>(G[sl], __builtin_ctzll(m));
+                    m &= m - 1;
+                }
+            }
+            if (given < 64u) {   // the lanes left over: to the largest remainders, the first of equal ones
+                const uint32_t R = 64u - given;
+                const uint32_t cut = sg_deal_cut<uint32_t>(dsum_i, R, [&](uint32_t c) {
+                    uint32_t n = 0;
+#pragma unroll
+                    for (int sl = 0; sl < SLOTS; ++sl) n += (uint32_t)__popcll(ballot64(rem[sl] >= c));
+                    return n;
+                });
+                // (a lane's rank in a mask from mbcnt on the scalar mask: the vector copy of `lanes_below` costs the kernels
+                //  at the register limit two registers across the set-up)
+                auto below = [](uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); };
+                uint32_t n_above = 0;
+#pragma unroll
+                for (int sl = 0; sl < SLOTS; ++sl) n_above += (uint32_t)__popcll(ballot64(rem[sl] > cut));
+                uint32_t at_before = 0;
+#pragma unroll
+                for (int sl = 0; sl < SLOTS; ++sl) {
+                    const bool at = in_p[sl] && rem[sl] == cut;
+                    const uint64_t am = ballot64(at);
+                    G[sl] += (rem[sl] > cut || (at && at_before + below(am) < R - n_above)) ? 1u : 0u;
+                    at_before += (uint32_t)__popcll(am);
+                }
+            }
+        }
+        // lane -> (term, u of its G lanes): the terms of P one after the other, each taking the next G lanes -- the first lane
+        // of a term is a running sum in a scalar register (it was an exclusive scan of G across the wave: six exchanges)
         int src = 0, src_slot = 0;
         uint32_t u = 0, g = 0;
+        uint32_t first_lane = 0;
 #pragma unroll
         for (int sl = 0; sl < SLOTS; ++sl) {
             uint64_t m = pm[sl];
@@ -913,14 +982,15 @@ spgemm_topn_pruned_kernel(const int64_t *__restrict__ a_indptr, const int32_t *_
                 SG_WD(wd_a, 70, 12)
                 const int f = __builtin_ctzll(m);
                 m &= m - 1;
-                const uint32_t sf = wave_read<uint32_t>(start[sl], f), gf = wave_read<uint32_t>(G[sl], f);
-                const uint32_t d = (uint32_t)lane - sf;
+                const uint32_t gf = wave_read<uint32_t>(G[sl], f);
+                const uint32_t d = (uint32_t)lane - first_lane;
                 if (d < gf) {
                     src = f;
                     src_slot = sl;
                     u = d;
                     g = gf;
                 }
+                first_lane += gf;
             }
         }
         int my_k = wave_shfl<int>(k[0], src);
@@ -991,12 +1061,7 @@ spgemm_topn_pruned_kernel(const int64_t *__restrict__ a_indptr, const int32_t *_
         // keep the old way (the part that holds the row's own tile scores it); a row that hands its last visits to the
         // parts has the pair twice in the pair list's merge, which drops repeats (pairs_select_kernel).
         uint32_t row_arg = row | ((SYM && keep > SG_TOPN_LANES) ? 0x40000000u : 0u);   // (bit 30: see drain_survivors)
-        if (SYM && FOLD_LOG2 > 0 && !part_mode) {
-            T own = (T)0;
-            for (int q = 0; q < nnz; ++q) {
-                const T aq = (SLOTS == 1 || q < 64) ? wave_read<T>(a[0], q) : wave_read<T>(a[SLOTS - 1], q - 64);
-                own = add_rn<T>(own, mul_rn<T>(aq, aq));
-            }
+        if (sum_own) {   // (summed with the ranking, in the row's set-up)
             if (own > thr) top.insert(own, (int)row_out, lane);
             row_arg |= 0x80000000u;
         }
@@ -1553,6 +1618,56 @@ spgemm_topn_pruned_kernel(const int64_t *__restrict__ a_indptr, const int32_t *_
 #endif
 }
 
+// The dealing rule on the host, for tests (tests/test_lane_dealing_cpu.py) and models (scripts/k4p_deal_model.py): G_out[t] =
+// lanes of prefix term t of a row whose np prefix terms have lists of df[t] entries, by the kernel's rule (sg_k4_device.h)
+// or, floor_rule != 0, by the earlier one.  Like the other sg_debug_* hooks neither in the header nor in the binding.
+// Returns 0; 1 for arguments the kernel never sees (np outside 1 .. 64, every list empty); 2 if the 32-bit evaluation the
+// wave uses (sums below 2^30) disagrees with the 64-bit one -- a bug.
+extern "C" int sg_debug_deal_lanes(const uint32_t *df, int np, uint32_t *G_out, int floor_rule) {
+    if (np < 1 || np > 64 || !df || !G_out) return 1;
+    uint64_t dsum = 0;
+    for (int t = 0; t < np; ++t) dsum += df[t];
+    if (dsum == 0) return 1;
+    if (floor_rule) {
+        for (int t = 0; t < np; ++t) G_out[t] = sg_deal_floor_rule(df[t], (float)dsum, np);
+        return 0;
+    }
+    const uint32_t spare = (uint32_t)(64 - np);
+    uint64_t rem[64];
+    uint32_t given = 0;
+    for (int t = 0; t < np; ++t) {
+        uint32_t q = 0;
+        sg_deal_share<uint64_t>(df[t], dsum, spare, q, rem[t]);
+        if (dsum < (1ull << 30)) {
+            uint32_t q32 = 0, rem32 = 0;
+            sg_deal_share<uint32_t>(df[t], (uint32_t)dsum, spare, q32, rem32);
+            if (q32 != q || rem32 != rem[t]) return 2;
+        }
+        G_out[t] = 1u + q;
+        given += G_out[t];
+    }
+    if (given < 64u) {
+        const uint32_t R = 64u - given;
+        const uint64_t cut = sg_deal_cut<uint64_t>(dsum, R, [&](uint64_t c) {
+            uint32_t n = 0;
+            for (int t = 0; t < np; ++t) n += rem[t] >= c ? 1u : 0u;
+            return n;
+        });
+        uint32_t left = R;
+        for (int t = 0; t < np; ++t)
+            if (rem[t] > cut) {
+                ++G_out[t];
+                --left;
+            }
+        for (int t = 0; t < np && left; ++t)
+            if (rem[t] == cut) {
+                ++G_out[t];
+                --left;
+            }
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Symmetric mode, second pass: the pair list (i, j < i, s) -> for every row j the list of the rows i > j that match it
 // -> merged with the row's own top list (its matches <= j, written by pass 1) -> top-n.
@@ -1992,7 +2107,7 @@ static int launch_pruned(const PrunedJob &job, const PrunedLaunch &l) {
                        (T *)r->d_vals,
                        r->d_counts, l.row_counter, l.out_count, l.out_rows, job.stats, pl.d_sink, pl.sink.chunks, pl.row_lo, pl.row_hi,
                        l.in_rows, l.in_len, (const uint32_t *)Bt->d_ends8, Bt->nv_pad, (uint32_t)(Bt->nnz * 4), (uint32_t)Bt->n_right,
-                       l.heavy_count, l.heavy_rows, pl.row_step, l.part_cfg);
+                       l.heavy_count, l.heavy_rows, pl.row_step, ctx->opt_is("SG_DEAL", 'f') ? 1u : 0u, l.part_cfg);
     SG_HIP_TRY(hipGetLastError());
     return SG_OK;
 }
