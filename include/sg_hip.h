@@ -59,9 +59,10 @@ typedef struct sg_topn sg_topn;         /* device-resident fixed-stride top-n re
 const char *sg_last_error(void);
 /* Bumped whenever a signature or a struct of this header changes (round 4: 2 -- row_step arguments of round 3, sg_stats
  * grew; round 5: 3 -- sg_stats.prune_scored; 4 -- sg_topn_transpose_select; 5 -- sg_csr_concat; 6 -- sg_csr_select_rows,
- * sg_topn_drop_columns, sg_device_upload); a binding compares it with the value it was written for right after loading the
- * library. */
-#define SG_ABI_VERSION 6
+ * sg_topn_drop_columns, sg_device_upload; 7 -- sg_topn_concat_rows, sg_topn_forget, sg_topn_put_rows, sg_csr_take_rows,
+ * sg_device_download); a
+ * binding compares it with the value it was written for right after loading the library. */
+#define SG_ABI_VERSION 7
 int sg_abi_version(void);
 int sg_device_count(int *count);
 /* hip_stream: a hipStream_t to launch on (e.g. torch.cuda.current_stream().cuda_stream), or NULL
@@ -183,6 +184,15 @@ int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_parts, sg_c
  * of sg_csr_concat.  A matrix made by sg_vec_transform stays one (cosine-like by construction); the words the vectoriser
  * left are carried over and are then UPPER bounds: the largest norm and the longest row may have been dropped. */
 int sg_csr_select_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d_drop_sorted, int64_t n_drop, sg_csr **out);
+/* The rows d_rows[0 .. n_rows) of m, in that order, in a new matrix that owns its arrays: scipy's m[rows] (what a caller who
+ * has to multiply a few rows of master_matrix again does to it on the host; the reference has no such operation, it multiplies
+ * every row again).  d_rows: DEVICE memory, row numbers of m in any order, a row may be named more than once; a number outside
+ * [0, m's rows) is SG_ERR_BADARG, seen on the device before anything is copied.  m may be a row-block view and may have rows
+ * without entries; n_rows == 0 is a matrix without rows.  Every taken row is a part of sg_csr_concat's copy, which runs at its
+ * usual width.  One synchronisation: the number of entries comes back to size the result.  m is only read and may be freed
+ * after the call.  A matrix made by sg_vec_transform stays one, as in sg_csr_select_rows, and the words the vectoriser left
+ * are carried over as UPPER bounds. */
+int sg_csr_take_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d_rows, int64_t n_rows, sg_csr **out);
 int sg_csr_free(sg_csr *m);
 
 /* Row-wise similarity of two matrices of the same shape (StringGrouper.dot / compute_pairwise_similarities,
@@ -344,6 +354,9 @@ int sg_device_free(sg_ctx *ctx, void *d_ptr);
  * a small list to sg_csr_select_rows / sg_topn_drop_columns and keeps it resident between calls.  The host memory may be
  * reused once the call returns. */
 int sg_device_upload(sg_ctx *ctx, const void *host, int64_t bytes, void **d_out);
+/* ... and back: bytes of device memory of the library (a list a call returned, e.g. sg_topn_forget's rows) copied to the
+ * host, behind everything the context's stream holds.  A synchronisation. */
+int sg_device_download(sg_ctx *ctx, const void *d_ptr, int64_t bytes, void *host);
 
 /* ------------------------------------------------------------------ resident corpus: the reverse path */
 /* A corpus whose index stays on the device answers match_strings(corpus, new) / match_most_similar(corpus, new) -- the
@@ -371,6 +384,33 @@ int sg_topn_transpose_select(sg_ctx *ctx, const sg_topn *pairs, int64_t n_rows_o
  * are dead.  No synchronisation. */
 int sg_topn_drop_columns(sg_ctx *ctx, const sg_topn *r, const int32_t *d_dead_sorted, int32_t n_dead, int32_t top_n,
                          sg_topn **out);
+
+/* ------------------------------------------------------------------ resident corpus: a self-join that is kept */
+/* A corpus may keep the result of its own self-join -- sp_matmul_topn(M, M.T, top_n, threshold), string_grouper.py:725-729 --
+ * on the device and edit it when rows join or leave instead of multiplying again.  Three operations on
+ * whole rows of fixed-stride results do the editing; none of them looks at a score.
+ *
+ * sg_topn_concat_rows: the rows of parts[0], then parts[1], ... in one new result: scipy's vstack of result blocks
+ * (string_grouper.py:750) without the trip through the host.  Every part has the same n_cols and dtype (SG_ERR_BADARG
+ * otherwise); the strides may differ, *out has the largest; a part may have no rows; one part makes a copy.  The parts are only
+ * read.  No synchronisation. */
+int sg_topn_concat_rows(sg_ctx *ctx, const sg_topn *const *parts, int32_t n_parts, sg_topn **out);
+/* sg_topn_forget: scipy's C[keep][:, keep] on a SQUARE result (rows and columns number the same strings; anything else is
+ * SG_ERR_BADARG), keep the complement of d_dead_sorted[0 .. n_dead) (DEVICE memory, ascending and distinct, each in [0, rows)
+ * -- the caller's responsibility as for sg_topn_drop_columns, whose filter of a row this call shares): the dead rows are left
+ * out, the dead columns are dropped from every other row, rows and columns are lowered by the dead ones below them, the order
+ * inside a row is kept; *out has r's stride.  A list longer than the 2 048 entries the kernel keeps in LDS is searched where it
+ * lies.  *d_short_rows (device memory of the library, sg_device_free) holds, ascending and in the NEW numbering, the *n_short_rows
+ * surviving rows that held top_n entries and hold fewer now: the only rows whose top_n over the surviving columns may hold
+ * a pair that the cut had dropped -- a row with fewer than top_n entries held every pair above the threshold, and a full row
+ * that named no dead column still holds its top_n.  One synchronisation: *n_short_rows comes back. */
+int sg_topn_forget(sg_ctx *ctx, const sg_topn *r, const int32_t *d_dead_sorted, int32_t n_dead, int32_t top_n, sg_topn **out,
+                   int32_t **d_short_rows, int64_t *n_short_rows);
+/* sg_topn_put_rows: IN PLACE, row d_rows[k] of r becomes row k of src, k in [0, n_rows) with n_rows = src's rows (scipy:
+ * C[rows] = S on a lil_matrix).  d_rows: DEVICE memory, distinct rows of r (the caller's responsibility; a number outside r is
+ * passed over, nothing is read back).  src has r's n_cols and dtype and a stride not above r's, otherwise SG_ERR_BADARG.
+ * No synchronisation. */
+int sg_topn_put_rows(sg_ctx *ctx, sg_topn *r, const int32_t *d_rows, int64_t n_rows, const sg_topn *src);
 
 /* ------------------------------------------------------------------ measurement */
 enum { SG_K_TOKENIZE = 0, SG_K_WEIGHT = 1, SG_K_POSTINGS = 2, SG_K_SPGEMM = 3 /* the multiply's whole launch group */,

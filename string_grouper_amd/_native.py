@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SG_HIP_LIB") or os.path.join(_HERE, "libsg_hip.so")
 
 SG_OK, SG_ERR_BADARG, SG_ERR_OOM, SG_ERR_OVERFLOW, SG_ERR_HIP, SG_ERR_NODEVICE, SG_ERR_UNSUPPORTED = range(7)
 SG_F32, SG_F64 = 0, 1
-ABI_VERSION = 6          # include/sg_hip.h: SG_ABI_VERSION
+ABI_VERSION = 7          # include/sg_hip.h: SG_ABI_VERSION
 SG_K_TOKENIZE, SG_K_WEIGHT, SG_K_POSTINGS, SG_K_SPGEMM, SG_K_ZIP, SG_K_VOCAB, SG_K_SPGEMM_KERNEL, SG_K_COUNT = range(8)
 KERNEL_NAMES = ("tokenize", "weight", "postings", "spgemm_topn", "zip", "vocab", "spgemm_kernel")
 
@@ -108,8 +108,13 @@ ABI = {
     "sg_topn_expand_range": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _PP, _PP, _P, C.c_int64]),
     "sg_device_free": (C.c_int, [_P, _P]),
     "sg_device_upload": (C.c_int, [_P, _P, C.c_int64, _PP]),
+    "sg_device_download": (C.c_int, [_P, _P, C.c_int64, _P]),
     "sg_topn_transpose_select": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _PP]),
     "sg_topn_drop_columns": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _PP]),
+    "sg_topn_concat_rows": (C.c_int, [_P, _PP, C.c_int32, _PP]),
+    "sg_topn_forget": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _PP, _PP, C.POINTER(C.c_int64)]),
+    "sg_topn_put_rows": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
+    "sg_csr_take_rows": (C.c_int, [_P, _P, _P, C.c_int64, _PP]),
     "sg_csr_rowwise_dot": (C.c_int, [_P, _P, _P, _P]),
     "sg_ctx_stats": (C.c_int, [_P, C.POINTER(SgStats)]),
 }
@@ -321,14 +326,18 @@ class MatchList(_Handle):
 
 
 class DeviceInts:
-    """A sorted list of distinct int32 numbers kept in device memory (sg_device_upload), with its host copy."""
+    """A list of int32 numbers kept in device memory (sg_device_upload), with its host copy: ascending and distinct, unless
+    ``any_order`` (the rows of ``csr_take_rows``, which the device checks against its matrix)."""
 
-    def __init__(self, ctx: "Context", values):
+    def __init__(self, ctx: "Context", values, any_order: bool = False):
         host = np.asarray(values)
         if host.ndim != 1 or (host.size and host.dtype.kind not in "iu"):
             raise ValueError("a one-dimensional array of integers is expected")
         host = np.ascontiguousarray(host, dtype=np.int64)
-        if host.size and (host[0] < 0 or host[-1] > np.iinfo(np.int32).max or np.any(host[1:] <= host[:-1])):
+        if any_order:
+            if host.size and (host.min() < np.iinfo(np.int32).min or host.max() > np.iinfo(np.int32).max):
+                raise ValueError("bad argument: the list must hold 32-bit row numbers")
+        elif host.size and (host[0] < 0 or host[-1] > np.iinfo(np.int32).max or np.any(host[1:] <= host[:-1])):
             raise ValueError("bad argument: the list must be ascending, distinct and hold row numbers (0 .. 2^31 - 1)")
         self.host = host.astype(np.int32)
         self.ctx = ctx
@@ -542,6 +551,17 @@ class Context:
         check(lib().sg_csr_select_rows(self.h, m.h, C.c_void_p(drop.ptr), len(drop), C.byref(out)))
         return Csr(self, out)
 
+    def csr_take_rows(self, m: Csr, rows: "DeviceInts") -> Csr:
+        """The rows ``rows`` of ``m`` -- any order, repeats allowed -- in a new owned matrix (include/sg_hip.h:
+        sg_csr_take_rows; scipy's m[rows]).  A row outside ``m``: ValueError."""
+        out = C.c_void_p()
+        check(lib().sg_csr_take_rows(self.h, m.h, C.c_void_p(rows.ptr), len(rows), C.byref(out)))
+        return Csr(self, out)
+
+    def upload_ints(self, values) -> "DeviceInts":
+        """A list of row numbers in any order in device memory, for ``csr_take_rows``."""
+        return DeviceInts(self, values, any_order=True)
+
     def upload_sorted_ints(self, values) -> "DeviceInts":
         """An ascending list of distinct non-negative row / column numbers in device memory, for ``csr_select_rows`` and
         ``topn_drop_columns``.  Anything else: ValueError (checked here, on the host copy, where it costs nothing)."""
@@ -676,6 +696,35 @@ class Context:
         out = C.c_void_p()
         check(lib().sg_topn_drop_columns(self.h, res.h, C.c_void_p(dead.ptr), len(dead), int(top_n), C.byref(out)))
         return TopN(self, out)
+
+    def topn_concat_rows(self, parts) -> TopN:
+        """The rows of ``parts`` one after the other in a new result of the largest stride; one part: a copy
+        (include/sg_hip.h: sg_topn_concat_rows)."""
+        parts = list(parts)
+        arr = (C.c_void_p * max(len(parts), 1))(*[p.h for p in parts])
+        out = C.c_void_p()
+        check(lib().sg_topn_concat_rows(self.h, arr, len(parts), C.byref(out)))
+        return TopN(self, out)
+
+    def topn_forget(self, res: TopN, dead: "DeviceInts", top_n: int):
+        """(``res`` without the rows and the columns of ``dead``, renumbered; device pointer of the surviving rows that were
+        full and are not any more -- ascending int32, ``device_free`` it --, how many) (include/sg_hip.h: sg_topn_forget)."""
+        out, rows, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        check(lib().sg_topn_forget(self.h, res.h, C.c_void_p(dead.ptr), len(dead), int(top_n), C.byref(out), C.byref(rows),
+                                   C.byref(n)))
+        return TopN(self, out), rows.value or 0, n.value
+
+    def topn_put_rows(self, res: TopN, d_rows: int, n_rows: int, src: TopN) -> None:
+        """In place: row ``d_rows[k]`` (device int32, distinct) of ``res`` becomes row k of ``src`` (include/sg_hip.h:
+        sg_topn_put_rows)."""
+        check(lib().sg_topn_put_rows(self.h, res.h, C.c_void_p(d_rows) if d_rows else None, int(n_rows), src.h))
+
+    def download_ints(self, d_ptr: int, n: int) -> np.ndarray:
+        """``n`` int32 numbers of device memory (a list the library made, e.g. ``topn_forget``'s) on the host."""
+        out = np.empty(max(int(n), 1), np.int32)
+        if n:
+            check(lib().sg_device_download(self.h, C.c_void_p(d_ptr), int(n) * 4, _ptr(out)))
+        return out[:n]
 
     def topn_zip(self, parts, col_offsets, top_n: int) -> TopN:
         arr = (C.c_void_p * len(parts))(*[p.h for p in parts])

@@ -13,6 +13,10 @@ idf (nothing is refitted, no score between two old rows changes), ``corpus.maste
 forget: ``corpus.remove(rows)`` takes rows out, ``corpus.master`` is then the shorter Series and row numbers count through
 it; vocabulary and idf stay what the original list gave.
 
+A service that asks after every change which group each record belongs to now -- ``corpus.group_similar_strings(corpus.master)``
+-- may have the corpus keep that self-join on the device: ``corpus.keep_self_join()``.  ``append`` and ``remove`` then edit the
+kept result with work that follows the change, and the call is served from it, bit for bit what the whole multiply gives.
+
 Every Series a method receives is transformed with the corpus's vocabulary and idf (an n-gram the corpus never had is
 dropped, as sklearn's transform drops it); everything after that is what ``StringGrouper.fit()`` and its frames do with the
 two matrices.  The methods have the signatures of the module-level functions (string_grouper.py:55-153).
@@ -159,7 +163,8 @@ class Corpus:
 
     # ------------------------------------------------------------------ resources
     def close(self) -> None:
-        """Free everything the corpus holds on the device (vocabulary, idf, its rows and indexes, segment by segment)."""
+        """Free everything the corpus holds on the device (vocabulary, idf, its rows and indexes, segment by segment, a kept
+        self-join)."""
         if self._state is not None:
             self._engine.corpus_free(self._state)
             self._state = None
@@ -299,6 +304,39 @@ class Corpus:
         if hasattr(self._engine, "corpus_compact"):
             self._engine.corpus_compact(state)
 
+    # ------------------------------------------------------------------ a self-join that is kept
+    def keep_self_join(self, **kwargs) -> None:
+        """Keep the result of the corpus's self-join on the device and keep it current across ``append`` and ``remove``.
+        ``min_similarity`` and ``max_n_matches`` only (defaults: the corpus's own options); ``max_n_matches=None`` is refused,
+        because the cut would move with every append.  From now on a self-join of the CURRENT ``corpus.master`` --
+        ``match_strings(corpus.master)`` or ``group_similar_strings(corpus.master)``, whatever ``group_rep``,
+        ``force_symmetries`` and ``ignore_index`` -- whose effective ``min_similarity`` and ``max_n_matches`` equal the kept
+        ones is served from the kept result; every other call runs as it always did.  The result is multiplied when a call
+        first needs it, once (``stats['self_join_full']``); an append then costs the new rows against the corpus and the
+        corpus rows against the new ones, a remove the rows that were cut at ``max_n_matches`` and named a removed row
+        (``stats['self_join_rows_refilled']``).  Calling it again with other values replaces the kept result."""
+        state = self._live()
+        self._same_engine()
+        unknown = sorted(set(kwargs) - {"min_similarity", "max_n_matches"})
+        if unknown:
+            raise TypeError(f"keep_self_join() takes min_similarity and max_n_matches only, not {', '.join(unknown)}")
+        if not hasattr(self._engine, "corpus_keep_self_join"):
+            raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} keeps no self-join")
+        options = self._options(kwargs)
+        if options["max_n_matches"] is None:
+            raise ValueError("max_n_matches=None cannot be kept: the cut would move with every append")
+        top_n = options["max_n_matches"]
+        if isinstance(top_n, (bool, np.bool_)) or not isinstance(top_n, (int, np.integer)) or top_n < 1:
+            raise ValueError(f"max_n_matches={top_n!r} cannot be kept: a whole number of at least 1 is expected")
+        self._engine.corpus_keep_self_join(state, int(top_n), float(options["min_similarity"]))
+
+    def drop_self_join(self) -> None:
+        """Free the kept self-join; every call runs the whole multiply again.  Nothing to do when none is kept."""
+        state = self._live()
+        self._same_engine()
+        if hasattr(self._engine, "corpus_drop_self_join"):
+            self._engine.corpus_drop_self_join(state)
+
     def _same_engine(self) -> None:
         if _engine_mod.get_engine() is not self._engine:
             raise RuntimeError("the engine has changed since the corpus was built (engine.set_engine / enable_distributed): "
@@ -317,7 +355,10 @@ class Corpus:
         ``compactions``, ``segments`` (1, or 2 while appended rows wait in their own segment) and ``base_index_builds``
         (builds of the first segment's index: 1 + compactions at most, whatever the number of appends; ``index_builds``
         counts every build, the second segment's included); ``removals`` / ``rows_removed`` and ``dead_rows`` (removed rows
-        that still lie in the segments, until the next compaction)."""
+        that still lie in the segments, until the next compaction); for a kept self-join (``keep_self_join``)
+        ``self_join_full`` (whole multiplies made for it), ``self_join_served`` (calls answered from it),
+        ``self_join_append_updates`` / ``self_join_remove_updates`` (changes it followed without a whole multiply) and
+        ``self_join_rows_refilled`` (rows a remove had to multiply again)."""
         return dict(self._live().stats)
 
     def _rows_of(self, series, made):

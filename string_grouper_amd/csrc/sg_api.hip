@@ -574,3 +574,11 @@ extern "C" int sg_device_upload(sg_ctx *ctx, const void *host, int64_t bytes, vo
     *d_out = d;
     return SG_OK;
 }
+
+extern "C" int sg_device_download(sg_ctx *ctx, const void *d_ptr, int64_t bytes, void *host) {
+    SG_REQUIRE(ctx && bytes >= 0 && (bytes == 0 || (d_ptr != nullptr && host != nullptr)), "null argument or negative size");
+    if (bytes == 0) return SG_OK;
+    SG_HIP_TRY(hipMemcpyAsync(host, d_ptr, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SG_OK;
+}

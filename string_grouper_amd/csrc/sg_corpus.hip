@@ -26,6 +26,17 @@
 // uncut product, then the cut).
 //   drop_columns_kernel  a wave per result row, 64 entries a round: a binary search per lane in the sorted dead list (in
 //                        LDS up to DROP_LDS_MAX columns), the survivors' positions by ballot + popcount on a running base
+//
+// And the editing of a KEPT self-join ("A self-join that is kept"): the corpus's own top-n result stays on
+// the device and follows every append and remove, so whole rows of fixed-stride results are stacked (scipy's vstack of result
+// blocks, string_grouper.py:750), taken out together with their columns (C[keep][:, keep]) and written back one by one.
+//   topn_copy_rows_kernel  a wave per row: the row's first counts[r] entries to row row_off + r (sg_topn_concat_rows) or to
+//                          row rows[r] (sg_topn_put_rows) of a result of another stride; 16 bytes a lane where both strides
+//                          are multiples of four entries, an entry a lane otherwise
+//   forget_kernel          a wave per SURVIVING row: where it lay (a binary search in dead[i] - i), then drop_columns_kernel's
+//                          filter of its entries; a row that was full and is not any more is flagged
+//   (prefix sum)           positions of the flagged rows, sg_exclusive_scan_positive_i32
+//   short_rows_kernel      their numbers, ascending
 #include "sg_internal.h"
 
 #include <algorithm>
@@ -259,6 +270,39 @@ __global__ void __launch_bounds__(TSEL_BLOCK) tsel_block_kernel(const uint32_t *
 // ---- sg_topn_drop_columns
 constexpr int DROP_LDS_MAX = 2048;            // dead columns kept in LDS (8 KiB); a longer list is searched where it lies
 
+// One result row through the filter, by the wave that owns it: the row's first c entries without those whose column is in
+// dead[0 .. n_dead), the others renumbered, at most stride_out of them written in their old order.  Returns the survivors
+// (wave-uniform, cut or not).  `dead` is the list where the kernel keeps it: LDS, or global memory for a long one.
+template <typename T>
+__device__ inline int32_t drop_dead_of_row(const int32_t *__restrict__ row_cols, const T *__restrict__ row_vals, int32_t c,
+                                           const int32_t *dead, int32_t n_dead, int32_t stride_out,
+                                           int32_t *__restrict__ out_cols, T *__restrict__ out_vals, int lane) {
+    const uint64_t below = (1ull << lane) - 1ull;                // the lanes before this one
+    int32_t base = 0;                                            // survivors so far (wave-uniform, as are the loop's bounds)
+    for (int32_t j0 = 0; j0 < c && base < stride_out; j0 += SG_WAVE) {
+        const int32_t j = j0 + lane;
+        const bool mine = j < c;
+        const int32_t col = mine ? row_cols[j] : 0;
+        const T v = mine ? row_vals[j] : T(0);
+        int32_t lo = 0, hi = n_dead;                             // lo: dead columns below col
+        while (lo < hi) {
+            const int32_t mid = (lo + hi) >> 1;
+            if (dead[mid] < col) lo = mid + 1;
+            else hi = mid;
+        }
+        const bool gone = lo < n_dead && dead[lo] == col;
+        const bool keep = mine && !gone;
+        const uint64_t kept = __ballot(keep);
+        const int32_t pos = base + (int32_t)__popcll(kept & below);
+        if (keep && pos < stride_out) {
+            out_cols[pos] = col - lo;
+            out_vals[pos] = v;
+        }
+        base += (int32_t)__popcll(kept);
+    }
+    return base;
+}
+
 template <typename T, bool IN_LDS>
 __global__ void __launch_bounds__(TSEL_BLOCK) drop_columns_kernel(const int32_t *__restrict__ cols,
                                                                   const T *__restrict__ vals,
@@ -273,37 +317,169 @@ __global__ void __launch_bounds__(TSEL_BLOCK) drop_columns_kernel(const int32_t 
         __syncthreads();
     }
     const int lane = threadIdx.x & (SG_WAVE - 1);
-    const uint64_t below = (1ull << lane) - 1ull;                // the lanes before this one
     const int64_t step = (int64_t)gridDim.x * TSEL_WAVES;
     for (int64_t r = (int64_t)blockIdx.x * TSEL_WAVES + threadIdx.x / SG_WAVE; r < n_rows; r += step) {
         const int32_t c = min(max(counts[r], 0), stride_in);
-        const int32_t *row_cols = cols + r * (int64_t)stride_in;
-        const T *row_vals = vals + r * (int64_t)stride_in;
-        int32_t base = 0;                                        // survivors so far (wave-uniform, as are the loop's bounds)
-        for (int32_t j0 = 0; j0 < c && base < stride_out; j0 += SG_WAVE) {
-            const int32_t j = j0 + lane;
-            const bool mine = j < c;
-            const int32_t col = mine ? row_cols[j] : 0;
-            const T v = mine ? row_vals[j] : T(0);
-            int32_t lo = 0, hi = n_dead;                         // lo: dead columns below col
-            while (lo < hi) {
-                const int32_t mid = (lo + hi) >> 1;
-                const int32_t d = IN_LDS ? lds_dead[mid] : dead[mid];
-                if (d < col) lo = mid + 1;
-                else hi = mid;
-            }
-            const bool gone = lo < n_dead && (IN_LDS ? lds_dead[lo] : dead[lo]) == col;
-            const bool keep = mine && !gone;
-            const uint64_t kept = __ballot(keep);
-            const int32_t pos = base + (int32_t)__popcll(kept & below);
-            if (keep && pos < stride_out) {
-                out_cols[r * (int64_t)stride_out + pos] = col - lo;
-                out_vals[r * (int64_t)stride_out + pos] = v;
-            }
-            base += (int32_t)__popcll(kept);
-        }
-        if (lane == 0) out_counts[r] = min(base, stride_out);
+        const int32_t left = drop_dead_of_row<T>(cols + r * (int64_t)stride_in, vals + r * (int64_t)stride_in, c,
+                                                 IN_LDS ? lds_dead : dead, n_dead, stride_out,
+                                                 out_cols + r * (int64_t)stride_out, out_vals + r * (int64_t)stride_out, lane);
+        if (lane == 0) out_counts[r] = min(left, stride_out);
     }
+}
+
+// ---- sg_topn_concat_rows, sg_topn_put_rows: whole rows from one fixed-stride result into another
+// The first c entries of a row by the wave that owns it.  VEC: both rows start on a 16-byte boundary in both arrays (the
+// strides are multiples of four entries), a lane moves four entries; the slots between c and the end of its last unit lie
+// inside both rows and hold nothing anybody reads.
+template <typename T, bool VEC>
+__device__ inline void copy_row(const int32_t *__restrict__ src_cols, const T *__restrict__ src_vals, int32_t c,
+                                int32_t *__restrict__ dst_cols, T *__restrict__ dst_vals, int lane) {
+    if (VEC) {
+        const uint4 *sc = reinterpret_cast<const uint4 *>(src_cols);
+        const uint4 *sv = reinterpret_cast<const uint4 *>(src_vals);
+        uint4 *dc = reinterpret_cast<uint4 *>(dst_cols);
+        uint4 *dv = reinterpret_cast<uint4 *>(dst_vals);
+        for (int32_t u = lane; u < (c + 3) >> 2; u += SG_WAVE) {
+            dc[u] = sc[u];
+            if (sizeof(T) == 4) {
+                dv[u] = sv[u];
+            } else {
+                const uint4 v0 = sv[2 * u], v1 = sv[2 * u + 1];
+                dv[2 * u] = v0;
+                dv[2 * u + 1] = v1;
+            }
+        }
+    } else {
+        for (int32_t j = lane; j < c; j += SG_WAVE) {
+            dst_cols[j] = src_cols[j];
+            dst_vals[j] = src_vals[j];
+        }
+    }
+}
+
+// row k of the source becomes row rows[k] of the destination (rows == null: row row_off + k); a row number outside the
+// destination is passed over
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(TSEL_BLOCK) topn_copy_rows_kernel(const int32_t *__restrict__ cols,
+                                                                    const T *__restrict__ vals,
+                                                                    const int32_t *__restrict__ counts, int64_t n_rows,
+                                                                    int32_t stride_in, const int32_t *__restrict__ rows,
+                                                                    int64_t row_off, int64_t n_rows_out, int32_t stride_out,
+                                                                    int32_t *__restrict__ out_cols, T *__restrict__ out_vals,
+                                                                    int32_t *__restrict__ out_counts) {
+    const int lane = threadIdx.x & (SG_WAVE - 1);
+    const int64_t step = (int64_t)gridDim.x * TSEL_WAVES;
+    for (int64_t k = (int64_t)blockIdx.x * TSEL_WAVES + threadIdx.x / SG_WAVE; k < n_rows; k += step) {
+        const int64_t to = rows != nullptr ? (int64_t)rows[k] : row_off + k;
+        if (to < 0 || to >= n_rows_out) continue;                // (wave-uniform)
+        const int32_t c = min(min(max(counts[k], 0), stride_in), stride_out);
+        copy_row<T, VEC>(cols + k * (int64_t)stride_in, vals + k * (int64_t)stride_in, c, out_cols + to * (int64_t)stride_out,
+                         out_vals + to * (int64_t)stride_out, lane);
+        if (lane == 0) out_counts[to] = c;
+    }
+}
+
+template <typename T>
+int copy_rows(sg_ctx *ctx, const sg_topn *src, const int32_t *d_rows, int64_t row_off, sg_topn *dst) {
+    if (src->n_rows == 0) return SG_OK;
+    const int grid = (int)std::min<int64_t>((src->n_rows + TSEL_WAVES - 1) / TSEL_WAVES, (int64_t)ctx->num_cu * 16);
+    if (src->stride % 4 == 0 && dst->stride % 4 == 0)
+        hipLaunchKernelGGL((topn_copy_rows_kernel<T, true>), dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream,
+                           (const int32_t *)src->d_cols, (const T *)src->d_vals, (const int32_t *)src->d_counts, src->n_rows,
+                           src->stride, d_rows, row_off, dst->n_rows, dst->stride, dst->d_cols, (T *)dst->d_vals,
+                           dst->d_counts);
+    else
+        hipLaunchKernelGGL((topn_copy_rows_kernel<T, false>), dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream,
+                           (const int32_t *)src->d_cols, (const T *)src->d_vals, (const int32_t *)src->d_counts, src->n_rows,
+                           src->stride, d_rows, row_off, dst->n_rows, dst->stride, dst->d_cols, (T *)dst->d_vals,
+                           dst->d_counts);
+    SG_HIP_TRY(hipGetLastError());
+    return SG_OK;
+}
+
+// ---- sg_topn_forget: a square result without the rows AND the columns of the dead list.  short_flag has one entry per
+// surviving row and a zero behind the last, so that its prefix sum ends with the number of flagged rows.
+template <typename T, bool IN_LDS>
+__global__ void __launch_bounds__(TSEL_BLOCK) forget_kernel(const int32_t *__restrict__ cols, const T *__restrict__ vals,
+                                                            const int32_t *__restrict__ counts, int64_t n_rows_in,
+                                                            int64_t n_rows_out, int32_t stride_in,
+                                                            const int32_t *__restrict__ dead, int32_t n_dead, int32_t top_n,
+                                                            int32_t stride_out, int32_t *__restrict__ out_cols,
+                                                            T *__restrict__ out_vals, int32_t *__restrict__ out_counts,
+                                                            int32_t *__restrict__ short_flag) {
+    __shared__ int32_t lds_dead[IN_LDS ? DROP_LDS_MAX : 1];
+    if (IN_LDS) {
+        for (int i = threadIdx.x; i < n_dead; i += TSEL_BLOCK) lds_dead[i] = dead[i];
+        __syncthreads();
+    }
+    const int32_t *dl = IN_LDS ? lds_dead : dead;
+    const int lane = threadIdx.x & (SG_WAVE - 1);
+    const int64_t step = (int64_t)gridDim.x * TSEL_WAVES;
+    if (blockIdx.x == 0 && threadIdx.x == 0) short_flag[n_rows_out] = 0;
+    for (int64_t k = (int64_t)blockIdx.x * TSEL_WAVES + threadIdx.x / SG_WAVE; k < n_rows_out; k += step) {
+        // surviving row k lay at k + the dead rows before it: dead row i has dead[i] - i survivors before it
+        int32_t lo = 0, hi = n_dead;
+        while (lo < hi) {
+            const int32_t mid = (lo + hi) >> 1;
+            if ((int64_t)dl[mid] - mid <= k) lo = mid + 1;
+            else hi = mid;
+        }
+        const int64_t r = k + lo;
+        int32_t c = 0, left = 0;
+        if (r < n_rows_in) {                                     // (a list that is what the header asks for never fails this)
+            c = min(max(counts[r], 0), stride_in);
+            left = drop_dead_of_row<T>(cols + r * (int64_t)stride_in, vals + r * (int64_t)stride_in, c, dl, n_dead, stride_out,
+                                       out_cols + k * (int64_t)stride_out, out_vals + k * (int64_t)stride_out, lane);
+            left = min(left, stride_out);
+        }
+        if (lane == 0) {
+            out_counts[k] = left;
+            short_flag[k] = (c >= top_n && left < top_n) ? 1 : 0;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(TSEL_BLOCK) short_rows_kernel(const int32_t *__restrict__ short_flag,
+                                                                const uint32_t *__restrict__ pos, int64_t n_rows,
+                                                                int64_t n_short, int32_t *__restrict__ rows) {
+    const int64_t step = (int64_t)gridDim.x * TSEL_BLOCK;
+    for (int64_t k = (int64_t)blockIdx.x * TSEL_BLOCK + threadIdx.x; k < n_rows; k += step)
+        if (short_flag[k] > 0 && (int64_t)pos[k] < n_short) rows[pos[k]] = (int32_t)k;
+}
+
+template <typename T>
+int forget(sg_ctx *ctx, const sg_topn *in, const int32_t *d_dead, int32_t n_dead, int32_t top_n, sg_topn *r,
+           int32_t *short_flag) {
+    const int64_t waves = r->n_rows > 0 ? r->n_rows : 1;
+    const int grid = (int)std::min<int64_t>((waves + TSEL_WAVES - 1) / TSEL_WAVES, (int64_t)ctx->num_cu * 16);
+    if (n_dead <= DROP_LDS_MAX)
+        hipLaunchKernelGGL((forget_kernel<T, true>), dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream, (const int32_t *)in->d_cols,
+                           (const T *)in->d_vals, (const int32_t *)in->d_counts, in->n_rows, r->n_rows, in->stride, d_dead,
+                           n_dead, top_n, r->stride, r->d_cols, (T *)r->d_vals, r->d_counts, short_flag);
+    else
+        hipLaunchKernelGGL((forget_kernel<T, false>), dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream, (const int32_t *)in->d_cols,
+                           (const T *)in->d_vals, (const int32_t *)in->d_counts, in->n_rows, r->n_rows, in->stride, d_dead,
+                           n_dead, top_n, r->stride, r->d_cols, (T *)r->d_vals, r->d_counts, short_flag);
+    SG_HIP_TRY(hipGetLastError());
+    return SG_OK;
+}
+
+// an empty result of the given shape (rows, columns, stride): the three arrays, nothing written
+int topn_new(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, int32_t stride, int32_t dtype,
+             std::unique_ptr<sg_topn, int (*)(sg_topn *)> *out) {
+    sg_topn *r = new (std::nothrow) sg_topn();
+    if (!r) return SG_ERR_OOM;
+    out->reset(r);
+    r->ctx = ctx;
+    r->n_rows = n_rows;
+    r->n_cols = n_cols;
+    r->stride = stride;
+    r->dtype = dtype;
+    const size_t cells = (size_t)n_rows * (size_t)stride + 64;
+    SG_TRY(sg_alloc(ctx, cells, &r->d_cols));
+    SG_TRY(ctx->alloc(cells * (dtype == SG_F64 ? 8 : 4), &r->d_vals));
+    SG_TRY(sg_alloc(ctx, (size_t)n_rows + 64, &r->d_counts));
+    return SG_OK;
 }
 
 template <typename T>
@@ -437,5 +613,77 @@ extern "C" int sg_topn_drop_columns(sg_ctx *ctx, const sg_topn *r_in, const int3
     SG_TRY(r->dtype == SG_F64 ? drop_columns<double>(ctx, r_in, d_dead_sorted, n_dead, r)
                               : drop_columns<float>(ctx, r_in, d_dead_sorted, n_dead, r));
     *out = guard.release();
+    return SG_OK;
+}
+
+extern "C" int sg_topn_concat_rows(sg_ctx *ctx, const sg_topn *const *parts, int32_t n_parts, sg_topn **out) {
+    SG_REQUIRE(ctx && parts && out && n_parts >= 1, "null argument or no parts");
+    int64_t n_rows = 0;
+    int32_t stride = 1;
+    for (int p = 0; p < n_parts; ++p) {
+        SG_REQUIRE(parts[p] != nullptr, "a part is null");
+        SG_REQUIRE(parts[p]->n_cols == parts[0]->n_cols && parts[p]->dtype == parts[0]->dtype,
+                   "parts disagree in columns or dtype");
+        n_rows += parts[p]->n_rows;
+        stride = std::max(stride, parts[p]->stride);
+    }
+    if ((double)n_rows * (double)stride > 2.0e9) {
+        sg_set_error("result of %lld rows x stride %d does not fit the 32-bit result index", (long long)n_rows, stride);
+        return SG_ERR_OVERFLOW;
+    }
+    std::unique_ptr<sg_topn, int (*)(sg_topn *)> r(nullptr, sg_topn_free);
+    SG_TRY(topn_new(ctx, n_rows, parts[0]->n_cols, stride, parts[0]->dtype, &r));
+    int64_t row_off = 0;
+    for (int p = 0; p < n_parts; ++p) {
+        SG_TRY(r->dtype == SG_F64 ? copy_rows<double>(ctx, parts[p], nullptr, row_off, r.get())
+                                  : copy_rows<float>(ctx, parts[p], nullptr, row_off, r.get()));
+        row_off += parts[p]->n_rows;
+    }
+    *out = r.release();
+    return SG_OK;
+}
+
+extern "C" int sg_topn_put_rows(sg_ctx *ctx, sg_topn *r, const int32_t *d_rows, int64_t n_rows, const sg_topn *src) {
+    SG_REQUIRE(ctx && r && src, "null argument");
+    SG_REQUIRE(n_rows == src->n_rows, "as many row numbers as src has rows are expected");
+    SG_REQUIRE(n_rows == 0 || d_rows != nullptr, "the list of rows is null");
+    SG_REQUIRE(src->n_cols == r->n_cols && src->dtype == r->dtype, "src and r disagree in columns or dtype");
+    SG_REQUIRE(src->stride <= r->stride, "src has the longer rows");
+    SG_REQUIRE(n_rows <= r->n_rows, "more rows than r has");
+    return r->dtype == SG_F64 ? copy_rows<double>(ctx, src, d_rows, 0, r) : copy_rows<float>(ctx, src, d_rows, 0, r);
+}
+
+extern "C" int sg_topn_forget(sg_ctx *ctx, const sg_topn *r_in, const int32_t *d_dead_sorted, int32_t n_dead, int32_t top_n,
+                              sg_topn **out, int32_t **d_short_rows, int64_t *n_short_rows) {
+    SG_REQUIRE(ctx && r_in && out && d_short_rows && n_short_rows, "null argument");
+    SG_REQUIRE(top_n >= 1, "top_n must be at least 1");
+    SG_REQUIRE(r_in->n_rows == r_in->n_cols, "the result is not square");
+    SG_REQUIRE(n_dead >= 0 && (int64_t)n_dead <= r_in->n_rows, "more dead rows than the result has rows");
+    SG_REQUIRE(n_dead == 0 || d_dead_sorted != nullptr, "the list of dead rows is null");
+    const int64_t n_out = r_in->n_rows - n_dead;
+    std::unique_ptr<sg_topn, int (*)(sg_topn *)> r(nullptr, sg_topn_free);
+    SG_TRY(topn_new(ctx, n_out, n_out, r_in->stride, r_in->dtype, &r));
+    Scratch scratch(ctx);
+    int32_t *short_flag = nullptr, *rows = nullptr;
+    uint32_t *pos = nullptr;
+    SG_TRY(scratch.alloc((size_t)n_out + 1, &short_flag));
+    SG_TRY(scratch.alloc((size_t)n_out + 1, &pos));
+    SG_TRY(r->dtype == SG_F64 ? forget<double>(ctx, r_in, d_dead_sorted, n_dead, top_n, r.get(), short_flag)
+                              : forget<float>(ctx, r_in, d_dead_sorted, n_dead, top_n, r.get(), short_flag));
+    // (the flag behind the last row is zero: pos[n_out] = the number of flagged rows, the one thing that comes back)
+    SG_TRY(sg_exclusive_scan_positive_i32(ctx, short_flag, pos, n_out + 1, nullptr));
+    SG_HIP_TRY(hipMemcpyAsync(ctx->h_fetch, pos + n_out, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const int64_t n_short = (int64_t)ctx->h_fetch[0];
+    SG_TRY(scratch.alloc((size_t)std::max<int64_t>(n_short, 4), &rows));
+    if (n_short > 0) {
+        const int grid = (int)std::min<int64_t>((n_out + TSEL_BLOCK - 1) / TSEL_BLOCK, (int64_t)ctx->num_cu * 16);
+        hipLaunchKernelGGL(short_rows_kernel, dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream, (const int32_t *)short_flag,
+                           (const uint32_t *)pos, n_out, n_short, rows);
+        SG_HIP_TRY(hipGetLastError());
+    }
+    *d_short_rows = scratch.keep(rows);
+    *n_short_rows = n_short;
+    *out = r.release();
     return SG_OK;
 }

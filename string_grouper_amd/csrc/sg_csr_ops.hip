@@ -25,6 +25,13 @@
 //                            reads from the source's row pointers) -- and the totals, the only thing read back: they size
 //                            the result;
 //   csr_select_kernel        (a) and (b) above over those descriptors; the vectoriser's words are the source's own.
+//
+// sg_csr_take_rows is scipy's m[rows] for a list in any order ("A self-join that is kept": the rows whose kept
+// result has to be computed again).  A taken row is a part of one row:
+//   csr_take_parts_kernel    one workgroup: checks the list (every row inside the matrix) and writes a part descriptor per
+//                            taken row -- its row pointer, its place k and the entries before it (the same scan, over the rows'
+//                            sizes) -- and the total, the only thing read back;
+//   csr_select_kernel        as above.
 #include "sg_internal.h"
 
 #include <memory>
@@ -144,6 +151,24 @@ __global__ void __launch_bounds__(CONCAT_BLOCK) csr_concat_kernel(const ConcatPa
     }
 }
 
+// One round of the descriptors' scan, by every thread of the one workgroup: the sizes of the CONCAT_BLOCK parts of this round
+// summed in LDS; returns the entries before this thread's part (the rounds before in *carry, which moves on by the round's sum)
+__device__ inline int64_t sizes_before(int64_t *scan, int64_t *carry, int tid, int64_t len) {
+    scan[tid] = len;
+    __syncthreads();
+    for (int off = 1; off < CONCAT_BLOCK; off <<= 1) {
+        const int64_t v = tid >= off ? scan[tid - off] : 0;
+        __syncthreads();
+        scan[tid] += v;
+        __syncthreads();
+    }
+    const int64_t before = *carry + scan[tid] - len;
+    __syncthreads();
+    if (tid == CONCAT_BLOCK - 1) *carry += scan[tid];
+    __syncthreads();
+    return before;
+}
+
 // ---- sg_csr_select_rows: the gaps between the dropped rows as parts of a concatenation.  info[0] = kept entries,
 // info[1] != 0: the drop list is not ascending, not distinct or names a row outside the matrix (nothing else is written).
 __global__ void __launch_bounds__(CONCAT_BLOCK) csr_select_gaps_kernel(const int64_t *__restrict__ indptr,
@@ -183,22 +208,51 @@ __global__ void __launch_bounds__(CONCAT_BLOCK) csr_select_gaps_kernel(const int
             const int64_t end = g < n_drop ? (int64_t)drop[g] : n_rows;
             len = indptr[end] - indptr[first];
         }
-        scan[tid] = len;
-        __syncthreads();
-        for (int off = 1; off < CONCAT_BLOCK; off <<= 1) {
-            const int64_t v = tid >= off ? scan[tid - off] : 0;
-            __syncthreads();
-            scan[tid] += v;
-            __syncthreads();
-        }
-        const int64_t before = carry + scan[tid] - len;
+        const int64_t before = sizes_before(scan, &carry, tid, len);
         if (g < n_gaps) parts[g] = ConcatPart{indptr + first, indices, data, nullptr, first - g, before};
-        __syncthreads();
-        if (tid == CONCAT_BLOCK - 1) carry += scan[tid];
-        __syncthreads();
     }
     if (tid == 0) {
         parts[n_gaps] = ConcatPart{nullptr, nullptr, nullptr, nullptr, n_rows - n_drop, carry};
+        info[0] = carry;
+        info[1] = 0;
+    }
+}
+
+// ---- sg_csr_take_rows: every taken row as a part of a concatenation.  info as above; info[1] != 0: a row outside the matrix.
+__global__ void __launch_bounds__(CONCAT_BLOCK) csr_take_parts_kernel(const int64_t *__restrict__ indptr,
+                                                                      const int32_t *__restrict__ indices,
+                                                                      const void *__restrict__ data, int64_t n_rows,
+                                                                      const int32_t *__restrict__ rows, int64_t n_take,
+                                                                      ConcatPart *__restrict__ parts,
+                                                                      int64_t *__restrict__ info) {
+    __shared__ int64_t scan[CONCAT_BLOCK];
+    __shared__ int64_t carry;
+    __shared__ int bad;
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        carry = 0;
+        bad = 0;
+    }
+    __syncthreads();
+    for (int64_t k = tid; k < n_take; k += CONCAT_BLOCK)
+        if (rows[k] < 0 || (int64_t)rows[k] >= n_rows) atomicOr(&bad, 1);
+    __syncthreads();
+    if (bad) {                                 // (uniform: read after the barrier)
+        if (tid == 0) {
+            info[0] = 0;
+            info[1] = 1;
+        }
+        return;
+    }
+    for (int64_t k0 = 0; k0 < n_take; k0 += CONCAT_BLOCK) {
+        const int64_t k = k0 + tid;
+        const int64_t row = k < n_take ? (int64_t)rows[k] : 0;
+        const int64_t len = k < n_take ? indptr[row + 1] - indptr[row] : 0;
+        const int64_t before = sizes_before(scan, &carry, tid, len);
+        if (k < n_take) parts[k] = ConcatPart{indptr + row, indices, data, nullptr, k, before};
+    }
+    if (tid == 0) {
+        parts[n_take] = ConcatPart{nullptr, nullptr, nullptr, nullptr, n_take, carry};
         info[0] = carry;
         info[1] = 0;
     }
@@ -376,6 +430,40 @@ extern "C" int sg_csr_select_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d
     ctx->release(d_info);
     ctx->release(d_desc);          // (stream-ordered pool: a later taker of the block runs behind the kernel)
     if (st != SG_OK) return st;
+    *out = r.release();
+    return SG_OK;
+}
+
+extern "C" int sg_csr_take_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d_rows, int64_t n_rows, sg_csr **out) {
+    SG_REQUIRE(ctx && m && out, "null argument");
+    SG_REQUIRE(n_rows >= 0 && n_rows < INT32_MAX, "the number of rows to take is negative or exceeds int32");
+    SG_REQUIRE(n_rows == 0 || d_rows != nullptr, "the list of rows is null");
+    if (m->rows_of) SG_TRY(sg_csr_ensure_rows(ctx, m));
+    std::unique_ptr<sg_csr, CsrDeleter> r(new (std::nothrow) sg_csr());
+    if (!r) return SG_ERR_OOM;
+    r->ctx = ctx;
+    r->n_rows = n_rows;
+    r->n_cols = m->n_cols;
+    r->dtype = m->dtype;
+    r->owned = true;
+    r->from_vectoriser = m->from_vectoriser;
+    // a descriptor per taken row and the totals; the totals are the one thing that comes back: they size the result
+    Scratch scratch(ctx);
+    ConcatPart *d_desc = nullptr;
+    int64_t *d_info = nullptr;
+    SG_TRY(scratch.alloc((size_t)n_rows + 1, &d_desc));
+    SG_TRY(scratch.alloc((size_t)2, &d_info));
+    hipLaunchKernelGGL(csr_take_parts_kernel, dim3(1), dim3(CONCAT_BLOCK), 0, ctx->stream, m->d_indptr, m->d_indices, m->d_data,
+                       m->n_rows, d_rows, n_rows, d_desc, d_info);
+    SG_HIP_TRY(hipGetLastError());
+    int64_t info[2] = {0, 0};
+    SG_HIP_TRY(hipMemcpyAsync(ctx->h_fetch, d_info, sizeof(info), hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(info, ctx->h_fetch, sizeof(info));
+    SG_REQUIRE(info[1] == 0, "a row to take lies outside the matrix");
+    r->nnz = info[0];
+    SG_TRY(m->dtype == SG_F64 ? select_rows<double>(ctx, m, d_desc, n_rows, n_rows, r->nnz, r.get())
+                              : select_rows<float>(ctx, m, d_desc, n_rows, n_rows, r->nnz, r.get()));
     *out = r.release();
     return SG_OK;
 }

@@ -91,7 +91,12 @@ class CorpusState:
     Removed rows stay in their segment until the next compaction: ``dead`` is the sorted list of their PHYSICAL numbers
     (counting through base, then delta), ``dead_dev`` its copy on the device.  A live row's physical number is its own plus
     the dead rows up to it (``physical_rows``); the calls against the indexes filter the dead columns out
-    (HipEngine._corpus_topn), every call that reads the rows as one matrix compacts first (``rows``)."""
+    (HipEngine._corpus_topn), every call that reads the rows as one matrix compacts first (``rows``).
+
+    A self-join that is kept (``Corpus.keep_self_join``): ``kept_opts`` is the (max_n_matches,
+    min_similarity) it is kept for, ``kept`` the result over the LIVE rows -- None until the first call needs it, and again
+    whenever an update could not follow a change (it is then multiplied anew on next need).  It is numbered by live rows, so a
+    compaction does not touch it."""
 
     def __init__(self, vec: HipTfidfVectorizer, column, base: Optional["N.Csr"] = None, engine: Optional["HipEngine"] = None):
         self.vec = vec
@@ -105,9 +110,13 @@ class CorpusState:
         self.matrix: Optional["CorpusMatrix"] = None
         self.index_overflow = False           # the corpus does not fit its indexes: every call takes today's blocked path
         self.placeholder: Optional[int] = None
+        self.kept: Optional["N.TopN"] = None
+        self.kept_opts: Optional[Tuple[int, float]] = None
         self.stats = {"tokenisations": 1, "index_builds": 0, "transforms": 0, "resident_index": 0, "forward": 0,
                       "reverse": 0, "reverse_fallbacks": 0, "appends": 0, "rows_appended": 0, "compactions": 0,
-                      "segments": 1, "base_index_builds": 0, "removals": 0, "rows_removed": 0, "dead_rows": 0}
+                      "segments": 1, "base_index_builds": 0, "removals": 0, "rows_removed": 0, "dead_rows": 0,
+                      "self_join_full": 0, "self_join_served": 0, "self_join_append_updates": 0,
+                      "self_join_remove_updates": 0, "self_join_rows_refilled": 0}
         if base is not None:
             self.set_segments(CorpusSegment(base), None)
 
@@ -170,6 +179,12 @@ class CorpusState:
         if self.whole is not None:
             self.whole.free()
             self.whole = None
+
+    def drop_kept(self) -> None:
+        """The kept self-join is stale (or no longer wanted): freed, multiplied anew when a call next needs it."""
+        if self.kept is not None:
+            self.kept.free()
+            self.kept = None
 
 
 class CorpusMatrix(DeviceMatrix):
@@ -339,6 +354,7 @@ class HipEngine:
         if n_new == 0:
             return
         new = self._corpus_rows_of(state, strings)
+        old_rows = self._kept_old_rows_against(state, new)          # (None: no self-join is kept)
         state.drop_whole()
         if state.delta is None:
             delta = CorpusSegment(new)
@@ -351,6 +367,8 @@ class HipEngine:
         state.stats["rows_appended"] += n_new
         if delta.n_rows > self.CORPUS_COMPACT_SHARE * state.base.n_rows:
             self.corpus_compact(state)
+        if old_rows is not None:
+            self._kept_add_new_rows(state, old_rows, n_new)
 
     def corpus_remove(self, state: CorpusState, positions) -> None:
         """The rows ``positions`` (sorted, distinct, numbered as the corpus's live rows are now) leave the corpus.  Nothing on
@@ -366,11 +384,14 @@ class HipEngine:
             raise IndexError(f"positions must be ascending, distinct and inside [0, {n_live})")
         if len(positions) == n_live:
             raise ValueError("every row of the corpus would be removed: build a new corpus instead")
+        short = self._kept_forget(state, positions)                 # (None: no self-join is kept)
         state.set_dead(np.union1d(state.dead, state.physical_rows(positions)))
         state.stats["removals"] += 1
         state.stats["rows_removed"] += len(positions)
         if len(state.dead) > self.CORPUS_MAX_DEAD:
             self.corpus_compact(state)
+        if short is not None:
+            self._kept_refill(state, *short)
 
     def corpus_compact(self, state: CorpusState) -> None:
         """Fold the delta segment into the base and drop the dead rows: one matrix of the live rows (sg_csr_concat, then
@@ -420,6 +441,8 @@ class HipEngine:
 
     def corpus_free(self, state: CorpusState) -> None:
         state.drop_whole()
+        state.drop_kept()
+        state.kept_opts = None
         if state.dead_dev is not None:
             state.dead_dev.free()
         state.dead_dev, state.dead = None, np.zeros(0, np.int64)
@@ -445,19 +468,9 @@ class HipEngine:
         the reverse path (the new rows against the corpus index, turned round by sg_topn_transpose_select)."""
         if isinstance(B, CorpusMatrix):
             state = B.corpus
-            if isinstance(A, CorpusMatrix) and len(state.dead):
-                self.corpus_compact(state)    # a self-join reads the rows as one matrix: no dead rows in it
-            segs = self.corpus_indexes(state)
-            if segs is None:
-                return None
-            state.stats["resident_index"] += 1
-            # dead rows are still in the indexes: at most that many of a row's first top_n + dead entries are dead, so the
-            # first top_n live ones of the longer list are the top_n over the live rows (DESIGN.md section 9)
-            n_dead = len(state.dead)
-            ask = top_n + n_dead
-            parts = [self.ctx.spgemm_topn(A.csr, idx, ask, threshold, True) for idx, _, _ in segs]
-            res = self._zip_segments(parts, segs, ask)
-            return self._drop_dead(state, res, top_n) if n_dead else res
+            if A is B and B is state.matrix and state.kept_opts == (int(top_n), float(threshold)):
+                return self._kept_copy(state)
+            return self._corpus_against_indexes(state, A, top_n, threshold)
         state = A.corpus
         mode = self._corpus_reverse_mode()
         if mode is None:
@@ -470,6 +483,143 @@ class HipEngine:
             state.stats["reverse_fallbacks"] += 1
         state.stats["forward"] += 1
         return None
+
+    def _corpus_against_indexes(self, state: CorpusState, A: DeviceMatrix, top_n: int, threshold: float) -> Optional["N.TopN"]:
+        """The rows of ``A`` (the corpus itself: a self-join) against the corpus's own indexes, in live numbering; None when
+        the corpus does not fit its indexes."""
+        if isinstance(A, CorpusMatrix) and len(state.dead):
+            self.corpus_compact(state)    # a self-join reads the rows as one matrix: no dead rows in it
+        segs = self.corpus_indexes(state)
+        if segs is None:
+            return None
+        state.stats["resident_index"] += 1
+        # dead rows are still in the indexes: at most that many of a row's first top_n + dead entries are dead, so the
+        # first top_n live ones of the longer list are the top_n over the live rows (DESIGN.md section 9)
+        n_dead = len(state.dead)
+        ask = top_n + n_dead
+        parts = [self.ctx.spgemm_topn(A.csr, idx, ask, threshold, True) for idx, _, _ in segs]
+        res = self._zip_segments(parts, segs, ask)
+        return self._drop_dead(state, res, top_n) if n_dead else res
+
+    # ------------------------------------------------------------------ a self-join that is kept (DESIGN.md section 9)
+    def corpus_keep_self_join(self, state: CorpusState, top_n: int, threshold: float) -> None:
+        """From now on the self-join of the corpus with these two options is kept on the device and follows every append and
+        remove; it is multiplied when a call first needs it.  Other values than the ones kept so far replace the result."""
+        opts = (int(top_n), float(threshold))
+        if state.kept_opts != opts:
+            state.drop_kept()
+        state.kept_opts = opts
+
+    def corpus_drop_self_join(self, state: CorpusState) -> None:
+        state.drop_kept()
+        state.kept_opts = None
+
+    def _kept_result(self, state: CorpusState) -> Optional["N.TopN"]:
+        """The kept self-join, multiplied now if it is not there: the multiply a self-join of the corpus takes anyway."""
+        if state.kept is None:
+            top_n, threshold = state.kept_opts
+            state.kept = self._corpus_against_indexes(state, state.matrix, top_n, threshold)
+            if state.kept is not None:
+                state.stats["self_join_full"] += 1
+        return state.kept
+
+    def _kept_copy(self, state: CorpusState) -> Optional["N.TopN"]:
+        """What a served call gets: a copy it may free (callers free what _topn_device returns), never the kept object."""
+        kept = self._kept_result(state)
+        if kept is None:
+            return None
+        state.stats["self_join_served"] += 1
+        return self.ctx.topn_concat_rows([kept])
+
+    def _kept_old_rows_against(self, state: CorpusState, new: "N.Csr") -> Optional["N.TopN"]:
+        """First half of an append's update, before the rows join: every old row's kept top-n merged (K5) with its top-n over
+        the NEW rows -- the product of match_strings(master, new), by the same reverse-or-forward rule.  A row's top-n over a
+        union of column sets is the merge of its top-n over each, and the new columns carry the highest numbers, so the order
+        of equal scores (column ascending) holds across the boundary."""
+        if state.kept is None:
+            return None
+        top_n, threshold = state.kept_opts
+        n_old = state.matrix.shape[0]
+        try:
+            over_new = self._topn_device(state.matrix, DeviceMatrix(new), top_n, threshold)
+            try:
+                return self.ctx.topn_zip([state.kept, over_new], np.array([0, n_old], dtype=np.int64), top_n)
+            finally:
+                over_new.free()
+        except Exception:
+            state.drop_kept()
+            raise
+
+    def _kept_add_new_rows(self, state: CorpusState, old_rows: "N.TopN", n_new: int) -> None:
+        """Second half, after the rows have joined: the new rows -- the last ones of the last segment -- against the grown
+        corpus, stacked under the old rows."""
+        top_n, threshold = state.kept_opts
+        state.drop_kept()
+        view = new_rows = None
+        try:
+            last = state.segments[-1]
+            view = last.csr.row_block(last.n_rows - n_new, last.n_rows)
+            new_rows = self._corpus_against_indexes(state, DeviceMatrix(view), top_n, threshold)
+            if new_rows is not None:                  # (None: the corpus has outgrown its indexes; stale)
+                state.kept = self.ctx.topn_concat_rows([old_rows, new_rows])
+                state.stats["self_join_append_updates"] += 1
+        finally:
+            for h in (new_rows, view, old_rows):
+                if h is not None:
+                    h.free()
+
+    def _kept_forget(self, state: CorpusState, positions: np.ndarray):
+        """First half of a remove's update: the kept result without the rows and columns ``positions`` (live numbering), and
+        the rows that were full and are not any more -- (device pointer, how many) -- the only ones the cut may have hidden
+        a candidate from."""
+        if state.kept is None:
+            return None
+        gone = self.ctx.upload_sorted_ints(positions)
+        try:
+            left, d_short, n_short = self.ctx.topn_forget(state.kept, gone, state.kept_opts[0])
+        except Exception:
+            state.drop_kept()
+            raise
+        finally:
+            gone.free()
+        state.drop_kept()
+        state.kept = left
+        return d_short, n_short
+
+    def _kept_refill(self, state: CorpusState, d_short: int, n_short: int) -> None:
+        """Second half, with the rows gone from the corpus: the short rows are taken from their segments, multiplied against
+        the corpus's indexes (which over-ask for the dead rows and answer in live numbering) and written back."""
+        top_n, threshold = state.kept_opts
+        made = []
+        try:
+            if n_short:
+                where = state.physical_rows(self.ctx.download_ints(d_short, n_short).astype(np.int64))
+                first = 0
+                for seg in state.segments:
+                    mine = where[(where >= first) & (where < first + seg.n_rows)] - first
+                    if len(mine):
+                        rows = self.ctx.upload_ints(mine)
+                        made.append(self.ctx.csr_take_rows(seg.csr, rows))
+                        rows.free()
+                    first += seg.n_rows
+                if len(made) > 1:
+                    made.append(self.ctx.csr_concat(made))
+                again = self._corpus_against_indexes(state, DeviceMatrix(made[-1]), top_n, threshold)
+                if again is None or again.dims()[1] > state.kept.dims()[1]:
+                    state.drop_kept()                 # (the corpus has outgrown its indexes; stale)
+                else:
+                    self.ctx.topn_put_rows(state.kept, d_short, n_short, again)
+                    state.stats["self_join_rows_refilled"] += n_short
+                if again is not None:
+                    again.free()
+            state.stats["self_join_remove_updates"] += 1
+        except Exception:
+            state.drop_kept()
+            raise
+        finally:
+            self.ctx.device_free(d_short)
+            for h in reversed(made):
+                h.free()
 
     def _zip_segments(self, parts: List["N.TopN"], segs, top_n: int) -> "N.TopN":
         """The results against the segments' indexes as one over the corpus's rows: columns offset by the segment's first
