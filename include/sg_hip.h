@@ -365,7 +365,9 @@ int sg_device_download(sg_ctx *ctx, const void *d_ptr, int64_t bytes, void *host
  * index (sg_spgemm_topn with a cap that no row filled, so that it holds EVERY pair above the threshold).
  * sg_topn_transpose_select turns such a pair list into the result over the corpus rows: row m of *out holds the at most
  * top_n pairs (r, m) of `pairs` -- r a row of `pairs` -- ordered by score descending, then r ascending, as sg_spgemm_topn
- * orders and cuts a row; *out has n_rows_out rows, pairs->n_rows columns and the stride min(top_n, columns).  The rows of
+ * orders and cuts a row (scores compare by VALUE: zeros of either sign are equal, as in the multiply, and the lower r goes
+ * first; what is written out is the pair's own bits, the sign of a zero included); *out has n_rows_out rows,
+ * pairs->n_rows columns and the stride min(top_n, columns).  The rows of
  * `pairs` must not name one column twice and its columns must lie in [0, n_rows_out).  top_n <= 2048 (larger:
  * SG_ERR_BADARG).  The result feeds sg_matchlist_build and sg_matchlist_best_master like a multiply's.  Bit for bit the
  * forward product's rows: a score is the sum of the separately rounded products of the shared terms in ascending term

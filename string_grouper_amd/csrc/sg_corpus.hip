@@ -50,14 +50,17 @@ constexpr uint32_t TSEL_WAVE_MAX = 1024;      // candidates a wave ranks by itse
 constexpr int TSEL_MAX_TOPN = 2048;           // LDS of the workgroup kernel's selected set (16 bytes an entry)
 constexpr int TSEL_BIG_GRID = 512;
 
-// A score as an unsigned key with the order of the value (finite values of either sign), zero-extended to 64 bits so that
-// both value types share one comparison
+// A score as an unsigned key with the order of the value (values of either sign, +inf included; -0.0 gets the key of +0.0:
+// the multiply compares values, to which the two are equal), zero-extended to 64 bits so that both value types share one
+// comparison
 __device__ inline uint64_t score_key(float v) {
     const uint32_t b = __float_as_uint(v);
+    if ((b << 1) == 0) return 0x80000000ull;
     return (uint64_t)((b & 0x80000000u) ? ~b : (b | 0x80000000u));
 }
 __device__ inline uint64_t score_key(double v) {
     const uint64_t b = (uint64_t)__double_as_longlong(v);
+    if ((b << 1) == 0) return 0x8000000000000000ull;
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
