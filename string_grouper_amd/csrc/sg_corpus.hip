@@ -40,7 +40,6 @@
 #include "sg_internal.h"
 
 #include <algorithm>
-#include <memory>
 
 namespace {
 
@@ -455,33 +454,11 @@ int forget(sg_ctx *ctx, const sg_topn *in, const int32_t *d_dead, int32_t n_dead
            int32_t *short_flag) {
     const int64_t waves = r->n_rows > 0 ? r->n_rows : 1;
     const int grid = (int)std::min<int64_t>((waves + TSEL_WAVES - 1) / TSEL_WAVES, (int64_t)ctx->num_cu * 16);
-    if (n_dead <= DROP_LDS_MAX)
-        hipLaunchKernelGGL((forget_kernel<T, true>), dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream, (const int32_t *)in->d_cols,
-                           (const T *)in->d_vals, (const int32_t *)in->d_counts, in->n_rows, r->n_rows, in->stride, d_dead,
-                           n_dead, top_n, r->stride, r->d_cols, (T *)r->d_vals, r->d_counts, short_flag);
-    else
-        hipLaunchKernelGGL((forget_kernel<T, false>), dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream, (const int32_t *)in->d_cols,
-                           (const T *)in->d_vals, (const int32_t *)in->d_counts, in->n_rows, r->n_rows, in->stride, d_dead,
-                           n_dead, top_n, r->stride, r->d_cols, (T *)r->d_vals, r->d_counts, short_flag);
+    const auto kernel = n_dead <= DROP_LDS_MAX ? forget_kernel<T, true> : forget_kernel<T, false>;   // the list in LDS, or where it lies
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream, (const int32_t *)in->d_cols, (const T *)in->d_vals,
+                       (const int32_t *)in->d_counts, in->n_rows, r->n_rows, in->stride, d_dead, n_dead, top_n, r->stride,
+                       r->d_cols, (T *)r->d_vals, r->d_counts, short_flag);
     SG_HIP_TRY(hipGetLastError());
-    return SG_OK;
-}
-
-// an empty result of the given shape (rows, columns, stride): the three arrays, nothing written
-int topn_new(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, int32_t stride, int32_t dtype,
-             std::unique_ptr<sg_topn, int (*)(sg_topn *)> *out) {
-    sg_topn *r = new (std::nothrow) sg_topn();
-    if (!r) return SG_ERR_OOM;
-    out->reset(r);
-    r->ctx = ctx;
-    r->n_rows = n_rows;
-    r->n_cols = n_cols;
-    r->stride = stride;
-    r->dtype = dtype;
-    const size_t cells = (size_t)n_rows * (size_t)stride + 64;
-    SG_TRY(sg_alloc(ctx, cells, &r->d_cols));
-    SG_TRY(ctx->alloc(cells * (dtype == SG_F64 ? 8 : 4), &r->d_vals));
-    SG_TRY(sg_alloc(ctx, (size_t)n_rows + 64, &r->d_counts));
     return SG_OK;
 }
 
@@ -489,14 +466,10 @@ template <typename T>
 int drop_columns(sg_ctx *ctx, const sg_topn *in, const int32_t *d_dead, int32_t n_dead, sg_topn *r) {
     const int64_t waves = in->n_rows > 0 ? in->n_rows : 1;
     const int grid = (int)std::min<int64_t>((waves + TSEL_WAVES - 1) / TSEL_WAVES, (int64_t)ctx->num_cu * 16);
-    if (n_dead <= DROP_LDS_MAX)
-        hipLaunchKernelGGL((drop_columns_kernel<T, true>), dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream,
-                           (const int32_t *)in->d_cols, (const T *)in->d_vals, (const int32_t *)in->d_counts, in->n_rows,
-                           in->stride, d_dead, n_dead, r->stride, r->d_cols, (T *)r->d_vals, r->d_counts);
-    else
-        hipLaunchKernelGGL((drop_columns_kernel<T, false>), dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream,
-                           (const int32_t *)in->d_cols, (const T *)in->d_vals, (const int32_t *)in->d_counts, in->n_rows,
-                           in->stride, d_dead, n_dead, r->stride, r->d_cols, (T *)r->d_vals, r->d_counts);
+    const auto kernel = n_dead <= DROP_LDS_MAX ? drop_columns_kernel<T, true> : drop_columns_kernel<T, false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(TSEL_BLOCK), 0, ctx->stream, (const int32_t *)in->d_cols, (const T *)in->d_vals,
+                       (const int32_t *)in->d_counts, in->n_rows, in->stride, d_dead, n_dead, r->stride, r->d_cols,
+                       (T *)r->d_vals, r->d_counts);
     SG_HIP_TRY(hipGetLastError());
     return SG_OK;
 }
@@ -524,8 +497,7 @@ int transpose_select(sg_ctx *ctx, const sg_topn *pairs, int64_t n_out, int32_t t
                        (const uint32_t *)big_rows, flags);
     SG_HIP_TRY(hipGetLastError());
     uint32_t h_flags[2] = {0, 0};
-    SG_HIP_TRY(hipMemcpyAsync(ctx->h_fetch, flags, sizeof(h_flags), hipMemcpyDeviceToHost, ctx->stream));
-    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    SG_TRY(sg_fetch(ctx, ctx->h_fetch, flags, sizeof(h_flags)));
     memcpy(h_flags, ctx->h_fetch, sizeof(h_flags));
     if (h_flags[0] & 1u) {
         sg_set_error("bad argument: a pair names a row outside [0, n_rows_out)");
@@ -548,50 +520,29 @@ extern "C" int sg_topn_transpose_select(sg_ctx *ctx, const sg_topn *pairs, int64
     SG_REQUIRE((double)pairs->n_rows * (double)pairs->stride < 4.0e9, "more than 2^32 pair slots");
     SG_REQUIRE(n_rows_out < (int64_t)UINT32_MAX, "too many result rows");
     const int64_t n_cols = pairs->n_rows;          // the result's columns are the pair list's rows
-    const int32_t stride = (int32_t)(top_n < n_cols ? top_n : (n_cols > 0 ? n_cols : 1));
-    if ((double)n_rows_out * (double)stride > 2.0e9) {
-        sg_set_error("result of %lld rows x top_n %d does not fit the 32-bit result index", (long long)n_rows_out, stride);
-        return SG_ERR_OVERFLOW;
-    }
-    sg_topn *r = new (std::nothrow) sg_topn();
-    if (!r) return SG_ERR_OOM;
-    std::unique_ptr<sg_topn, int (*)(sg_topn *)> guard(r, sg_topn_free);
-    r->ctx = ctx;
-    r->n_rows = n_rows_out;
-    r->n_cols = n_cols;
-    r->stride = stride;
-    r->dtype = pairs->dtype;
-    const size_t cells = (size_t)n_rows_out * (size_t)stride + 64;
-    const size_t vsize = pairs->dtype == SG_F64 ? 8 : 4;
-    SG_TRY(sg_alloc(ctx, cells, &r->d_cols));
-    SG_TRY(ctx->alloc(cells * vsize, &r->d_vals));
-    SG_TRY(sg_alloc(ctx, (size_t)n_rows_out + 64, &r->d_counts));
+    int32_t stride = 0;
+    if (!result_stride(n_rows_out, top_n, n_cols, &stride)) return result_overflow(n_rows_out, stride, "");
+    TopnPtr r;
+    SG_TRY(topn_alloc(ctx, n_rows_out, n_cols, stride, pairs->dtype, &r));
     // scratch: counters (n_out + 1), offsets (n_out + 1), flags {error bits, queued rows}, the queue, the buckets (at most
     // one entry per slot of the pair list)
     const size_t slots = (size_t)pairs->n_rows * (size_t)pairs->stride + 1;
+    Scratch scratch(ctx);
     uint32_t *cnt = nullptr, *off = nullptr, *flags = nullptr, *big_rows = nullptr;
     int32_t *b_rows = nullptr;
     void *b_vals = nullptr;
-    int st = sg_alloc(ctx, (size_t)n_rows_out + 1, &cnt);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_rows_out + 1, &off);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)64, &flags);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_rows_out + 1, &big_rows);
-    if (st == SG_OK) st = sg_alloc(ctx, slots, &b_rows);
-    if (st == SG_OK) st = ctx->alloc(slots * vsize, &b_vals);
-    if (st == SG_OK) st = SG_ZERO2(ctx, cnt, ((size_t)n_rows_out + 1) * 4, flags, 64 * 4);
-    if (st == SG_OK) {
-        st = pairs->dtype == SG_F64
-                 ? transpose_select<double>(ctx, pairs, n_rows_out, top_n, r, cnt, off, flags, big_rows, b_rows, (double *)b_vals)
-                 : transpose_select<float>(ctx, pairs, n_rows_out, top_n, r, cnt, off, flags, big_rows, b_rows, (float *)b_vals);
-    }
-    ctx->release(cnt);
-    ctx->release(off);
-    ctx->release(flags);
-    ctx->release(big_rows);
-    ctx->release(b_rows);
-    ctx->release(b_vals);
-    if (st != SG_OK) return st;
-    *out = guard.release();
+    SG_TRY(scratch.alloc((size_t)n_rows_out + 1, &cnt));
+    SG_TRY(scratch.alloc((size_t)n_rows_out + 1, &off));
+    SG_TRY(scratch.alloc((size_t)64, &flags));
+    SG_TRY(scratch.alloc((size_t)n_rows_out + 1, &big_rows));
+    SG_TRY(scratch.alloc(slots, &b_rows));
+    SG_TRY(scratch.alloc_bytes(slots * (pairs->dtype == SG_F64 ? 8 : 4), &b_vals));
+    SG_TRY(SG_ZERO2(ctx, cnt, ((size_t)n_rows_out + 1) * 4, flags, 64 * 4));
+    SG_TRY(by_dtype(pairs->dtype, [&](auto t) {
+        using T = decltype(t);
+        return transpose_select<T>(ctx, pairs, n_rows_out, top_n, r.get(), cnt, off, flags, big_rows, b_rows, (T *)b_vals);
+    }));
+    *out = r.release();
     return SG_OK;
 }
 
@@ -601,21 +552,11 @@ extern "C" int sg_topn_drop_columns(sg_ctx *ctx, const sg_topn *r_in, const int3
     SG_REQUIRE(top_n >= 1, "top_n must be at least 1");
     SG_REQUIRE(n_dead >= 0 && (int64_t)n_dead <= r_in->n_cols, "more dead columns than the result has columns");
     SG_REQUIRE(n_dead == 0 || d_dead_sorted != nullptr, "the list of dead columns is null");
-    sg_topn *r = new (std::nothrow) sg_topn();
-    if (!r) return SG_ERR_OOM;
-    std::unique_ptr<sg_topn, int (*)(sg_topn *)> guard(r, sg_topn_free);
-    r->ctx = ctx;
-    r->n_rows = r_in->n_rows;
-    r->n_cols = r_in->n_cols - n_dead;
-    r->stride = std::max<int32_t>(std::min<int32_t>(top_n, r_in->stride), 1);
-    r->dtype = r_in->dtype;
-    const size_t cells = (size_t)r->n_rows * (size_t)r->stride + 64;
-    SG_TRY(sg_alloc(ctx, cells, &r->d_cols));
-    SG_TRY(ctx->alloc(cells * (r->dtype == SG_F64 ? 8 : 4), &r->d_vals));
-    SG_TRY(sg_alloc(ctx, (size_t)r->n_rows + 64, &r->d_counts));
-    SG_TRY(r->dtype == SG_F64 ? drop_columns<double>(ctx, r_in, d_dead_sorted, n_dead, r)
-                              : drop_columns<float>(ctx, r_in, d_dead_sorted, n_dead, r));
-    *out = guard.release();
+    TopnPtr r;
+    SG_TRY(topn_alloc(ctx, r_in->n_rows, r_in->n_cols - n_dead, std::max<int32_t>(std::min<int32_t>(top_n, r_in->stride), 1),
+                      r_in->dtype, &r));
+    SG_TRY(by_dtype(r->dtype, [&](auto t) { return drop_columns<decltype(t)>(ctx, r_in, d_dead_sorted, n_dead, r.get()); }));
+    *out = r.release();
     return SG_OK;
 }
 
@@ -634,8 +575,8 @@ extern "C" int sg_topn_concat_rows(sg_ctx *ctx, const sg_topn *const *parts, int
         sg_set_error("result of %lld rows x stride %d does not fit the 32-bit result index", (long long)n_rows, stride);
         return SG_ERR_OVERFLOW;
     }
-    std::unique_ptr<sg_topn, int (*)(sg_topn *)> r(nullptr, sg_topn_free);
-    SG_TRY(topn_new(ctx, n_rows, parts[0]->n_cols, stride, parts[0]->dtype, &r));
+    TopnPtr r;
+    SG_TRY(topn_alloc(ctx, n_rows, parts[0]->n_cols, stride, parts[0]->dtype, &r));
     int64_t row_off = 0;
     for (int p = 0; p < n_parts; ++p) {
         SG_TRY(r->dtype == SG_F64 ? copy_rows<double>(ctx, parts[p], nullptr, row_off, r.get())
@@ -664,8 +605,8 @@ extern "C" int sg_topn_forget(sg_ctx *ctx, const sg_topn *r_in, const int32_t *d
     SG_REQUIRE(n_dead >= 0 && (int64_t)n_dead <= r_in->n_rows, "more dead rows than the result has rows");
     SG_REQUIRE(n_dead == 0 || d_dead_sorted != nullptr, "the list of dead rows is null");
     const int64_t n_out = r_in->n_rows - n_dead;
-    std::unique_ptr<sg_topn, int (*)(sg_topn *)> r(nullptr, sg_topn_free);
-    SG_TRY(topn_new(ctx, n_out, n_out, r_in->stride, r_in->dtype, &r));
+    TopnPtr r;
+    SG_TRY(topn_alloc(ctx, n_out, n_out, r_in->stride, r_in->dtype, &r));
     Scratch scratch(ctx);
     int32_t *short_flag = nullptr, *rows = nullptr;
     uint32_t *pos = nullptr;

@@ -334,27 +334,22 @@ extern "C" int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_
         nnz_off += parts[p]->nnz;
     }
     desc[n_parts] = ConcatPart{nullptr, nullptr, nullptr, nullptr, row_off, nnz_off};
-    void *d_desc = nullptr;
-    SG_TRY(ctx->alloc(desc.size() * sizeof(ConcatPart), &d_desc));
-    hipError_t e = hipMemcpyAsync(d_desc, desc.data(), desc.size() * sizeof(ConcatPart), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // desc is a local
-    if (e == hipSuccess) {
-        const int64_t work = std::max<int64_t>(std::max<int64_t>((nnz + CONCAT_UNIT - 1) / CONCAT_UNIT, n_rows), 1);
-        const int64_t want = (work + CONCAT_BLOCK - 1) / CONCAT_BLOCK;
-        const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)ctx->num_cu * 32);
-        if (dtype == SG_F64)
-            hipLaunchKernelGGL(csr_concat_kernel<double>, dim3(grid), dim3(CONCAT_BLOCK), 0, ctx->stream,
-                               (const ConcatPart *)d_desc, (int)n_parts, dp, di, (double *)dd, m->d_props_words);
-        else
-            hipLaunchKernelGGL(csr_concat_kernel<float>, dim3(grid), dim3(CONCAT_BLOCK), 0, ctx->stream,
-                               (const ConcatPart *)d_desc, (int)n_parts, dp, di, (float *)dd, m->d_props_words);
-        e = hipGetLastError();
-    }
-    ctx->release(d_desc);          // (stream-ordered pool: a later taker of the block runs behind the kernel)
-    if (e != hipSuccess) {
-        sg_set_error("sg_csr_concat: %s", hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? SG_ERR_OOM : SG_ERR_HIP;
-    }
+    Scratch scratch(ctx);
+    ConcatPart *d_desc = nullptr;
+    SG_TRY(scratch.alloc(desc.size(), &d_desc));
+    SG_HIP_TRY(hipMemcpyAsync(d_desc, desc.data(), desc.size() * sizeof(ConcatPart), hipMemcpyHostToDevice, ctx->stream));
+    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));      // desc is a local
+    const int64_t work = std::max<int64_t>(std::max<int64_t>((nnz + CONCAT_UNIT - 1) / CONCAT_UNIT, n_rows), 1);
+    const int64_t want = (work + CONCAT_BLOCK - 1) / CONCAT_BLOCK;
+    const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)ctx->num_cu * 32);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(csr_concat_kernel<T>, dim3(grid), dim3(CONCAT_BLOCK), 0, ctx->stream, (const ConcatPart *)d_desc,
+                           (int)n_parts, dp, di, (T *)dd, m->d_props_words);
+        return SG_OK;
+    });
+    scratch.release(d_desc);       // (stream-ordered pool: a later taker of the block runs behind the kernel)
+    SG_HIP_TRY(hipGetLastError());
     *out = m.release();
     return SG_OK;
 }
@@ -400,36 +395,23 @@ extern "C" int sg_csr_select_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d
     r->owned = true;
     r->from_vectoriser = m->from_vectoriser;
     // the gaps' descriptors and the totals; the totals are the one thing that comes back: they size the result
+    Scratch scratch(ctx);
     ConcatPart *d_desc = nullptr;
     int64_t *d_info = nullptr;
-    SG_TRY(sg_alloc(ctx, (size_t)n_gaps + 1, &d_desc));
-    int st = sg_alloc(ctx, (size_t)2, &d_info);
+    SG_TRY(scratch.alloc((size_t)n_gaps + 1, &d_desc));
+    SG_TRY(scratch.alloc((size_t)2, &d_info));
+    hipLaunchKernelGGL(csr_select_gaps_kernel, dim3(1), dim3(CONCAT_BLOCK), 0, ctx->stream, m->d_indptr, m->d_indices, m->d_data,
+                       m->n_rows, d_drop_sorted, n_drop, d_desc, d_info);
+    SG_HIP_TRY(hipGetLastError());
     int64_t info[2] = {0, 0};
-    if (st == SG_OK) {
-        hipLaunchKernelGGL(csr_select_gaps_kernel, dim3(1), dim3(CONCAT_BLOCK), 0, ctx->stream, m->d_indptr, m->d_indices,
-                           m->d_data, m->n_rows, d_drop_sorted, n_drop, d_desc, d_info);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_fetch, d_info, sizeof(info), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            sg_set_error("sg_csr_select_rows: %s", hipGetErrorString(e));
-            st = SG_ERR_HIP;
-        } else {
-            memcpy(info, ctx->h_fetch, sizeof(info));
-        }
-    }
-    if (st == SG_OK && info[1] != 0) {
-        sg_set_error("bad argument: the rows to drop must be ascending, distinct and inside the matrix");
-        st = SG_ERR_BADARG;
-    }
-    if (st == SG_OK) {
-        r->nnz = info[0];
-        st = m->dtype == SG_F64 ? select_rows<double>(ctx, m, d_desc, n_gaps, r->n_rows, r->nnz, r.get())
-                                : select_rows<float>(ctx, m, d_desc, n_gaps, r->n_rows, r->nnz, r.get());
-    }
-    ctx->release(d_info);
-    ctx->release(d_desc);          // (stream-ordered pool: a later taker of the block runs behind the kernel)
-    if (st != SG_OK) return st;
+    SG_TRY(sg_fetch(ctx, ctx->h_fetch, d_info, sizeof(info)));
+    memcpy(info, ctx->h_fetch, sizeof(info));
+    SG_REQUIRE(info[1] == 0, "the rows to drop must be ascending, distinct and inside the matrix");
+    r->nnz = info[0];
+    SG_TRY(by_dtype(m->dtype, [&](auto t) {
+        return select_rows<decltype(t)>(ctx, m, d_desc, n_gaps, r->n_rows, r->nnz, r.get());
+    }));
+    scratch.release(d_info);       // (the totals' block goes back first, then the descriptors': the pool's order of old)
     *out = r.release();
     return SG_OK;
 }

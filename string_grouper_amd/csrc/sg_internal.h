@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -166,6 +167,13 @@ struct Scratch {   // blocks of the context's pool, released -- in the order the
 template <typename F>
 static int by_dtype(int32_t dtype, F &&f) {   // f(double{}) or f(float{}): every launch below is written once
     return dtype == SG_F64 ? f(double{}) : f(float{});
+}
+
+// n bytes of device memory to the host, and the wait for them: the small read-backs that size what a driver does next
+static inline int sg_fetch(sg_ctx *ctx, void *dst, const void *d_src, size_t bytes) {
+    SG_HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return SG_OK;
 }
 
 // Dynamic LDS above the default 48 KiB has to be allowed for each kernel, once
@@ -365,6 +373,17 @@ struct sg_topn {
     void *d_vals = nullptr;
     int32_t *d_counts = nullptr;
 };
+
+// sg_topn.hip: a result under construction (freed on every early return), an empty one of a given shape, and the rule of a
+// multiply's result -- top_n cut at the columns there are; rows x stride must fit 2 * 10^9 -- with its refusal
+struct TopnFree {
+    void operator()(sg_topn *r) const { sg_topn_free(r); }
+};
+using TopnPtr = std::unique_ptr<sg_topn, TopnFree>;
+int topn_alloc(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, int32_t stride, int32_t dtype, TopnPtr *out);
+bool result_stride(int64_t n_rows, int64_t top_n, int64_t n_cols, int32_t *stride);
+int result_overflow(int64_t n_rows, int32_t stride, const char *advice);
+int sort_rows_by_column(sg_ctx *ctx, sg_topn *r);   // every row of an unsorted result (sort == 0) by ascending column
 
 struct sg_vocab {
     sg_ctx *ctx = nullptr;

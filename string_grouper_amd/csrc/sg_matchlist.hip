@@ -152,110 +152,103 @@ extern "C" int sg_matchlist_free(sg_matchlist *ml) {
     return SG_OK;
 }
 
+struct MatchlistFree {
+    void operator()(sg_matchlist *ml) const { sg_matchlist_free(ml); }
+};
+using MatchlistPtr = std::unique_ptr<sg_matchlist, MatchlistFree>;   // a list under construction: freed on every early return
+
+static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// Stage 1: the entries of every row -- own[r] those it keeps itself, extra[r] the mirrors of other rows' entries that it
+// receives (the self-join post-processing; a two-series result keeps its counts and receives none)
+static int count_row_entries(sg_ctx *ctx, const sg_topn *r, int32_t fix_diagonal, int32_t symmetrize, int32_t *own,
+                             int32_t *extra) {
+    const int64_t n = r->n_rows;
+    if (n == 0) return SG_OK;
+    SG_HIP_TRY(hipMemsetAsync(extra, 0, sizeof(int32_t) * (size_t)(n + 1), ctx->stream));
+    if (fix_diagonal || symmetrize)
+        hipLaunchKernelGGL(ml_count_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, (const int32_t *)r->d_cols,
+                           (const int32_t *)r->d_counts, r->stride, n, fix_diagonal, symmetrize, own, extra);
+    else
+        SG_HIP_TRY(hipMemcpyAsync(own, r->d_counts, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+    return SG_OK;
+}
+
+// Stage 2: the row pointers (prefix sum of own + extra) and their last one, the number of entries, which sizes the list:
+// the build's one read-back
+static int make_row_pointers(sg_ctx *ctx, int64_t n, const int32_t *own, const int32_t *extra, int32_t *total,
+                             int64_t *row_ptr, int64_t *n_entries) {
+    if (n > 0) {
+        hipLaunchKernelGGL(ml_add_kernel, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, own, extra, total, n);
+        SG_TRY(sg_exclusive_scan_i32_to_i64(ctx, total, row_ptr, n));
+    } else {
+        SG_HIP_TRY(hipMemsetAsync(row_ptr, 0, sizeof(int64_t), ctx->stream));
+    }
+    return sg_fetch(ctx, n_entries, row_ptr + n, sizeof(int64_t));
+}
+
+// Stage 3: the entries.  A self-join's rows are filled with their mirrors (`cursor`: where the next mirror of a row goes,
+// behind its own entries), a two-series result is compacted; rows that are to be ordered by column go to the temporaries
+// first and the per-row sort takes them from there.
+static int fill_rows(sg_ctx *ctx, const sg_topn *r, int32_t fix_diagonal, int32_t symmetrize, bool sorted, const int32_t *own,
+                     int32_t *cursor, int32_t *tmp_cols, void *tmp_vals, sg_matchlist *ml) {
+    const int64_t n = r->n_rows;
+    if (n == 0) return SG_OK;
+    const bool self = fix_diagonal || symmetrize;
+    if (self) SG_HIP_TRY(hipMemsetAsync(cursor, 0, sizeof(int32_t) * (size_t)(n + 1), ctx->stream));
+    const unsigned grid = blocks_for(n), sgrid = (unsigned)(n < 256 * 64 ? n : 256 * 64);
+    return by_dtype(r->dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        int32_t *c_out = sorted ? tmp_cols : ml->d_cols;
+        T *v_out = (T *)(sorted ? tmp_vals : ml->d_vals);
+        if (self)
+            hipLaunchKernelGGL(ml_fill_kernel<T>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)r->d_cols,
+                               (const T *)r->d_vals, (const int32_t *)r->d_counts, r->stride, n, fix_diagonal, symmetrize,
+                               (const int64_t *)ml->d_row_ptr, own, cursor, c_out, v_out);
+        else
+            hipLaunchKernelGGL(ml_compact_kernel<T>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)r->d_cols,
+                               (const T *)r->d_vals, (const int32_t *)r->d_counts, r->stride, n,
+                               (const int64_t *)ml->d_row_ptr, c_out, v_out);
+        if (sorted)
+            hipLaunchKernelGGL(ml_sort_rows_kernel<T>, dim3(sgrid), dim3(64), 0, ctx->stream, (const int64_t *)ml->d_row_ptr, n,
+                               (const int32_t *)tmp_cols, (const T *)tmp_vals, ml->d_cols, (T *)ml->d_vals);
+        SG_HIP_TRY(hipGetLastError());
+        return SG_OK;
+    });
+}
+
 extern "C" int sg_matchlist_build(sg_ctx *ctx, const sg_topn *r, int32_t fix_diagonal, int32_t symmetrize,
                                   int32_t sort_by_column, sg_matchlist **out) {
     SG_REQUIRE(ctx && r && out, "null argument");
     if (fix_diagonal || symmetrize) SG_REQUIRE(r->n_rows == r->n_cols, "self-join post-processing needs a square result");
     const int64_t n = r->n_rows;
-    sg_matchlist *ml = new (std::nothrow) sg_matchlist();
+    MatchlistPtr ml(new (std::nothrow) sg_matchlist());
     if (!ml) return SG_ERR_OOM;
     ml->ctx = ctx;
     ml->n_rows = n;
     ml->n_cols = r->n_cols;
     ml->dtype = r->dtype;
     const size_t s = r->dtype == SG_F64 ? 8 : 4;
+    Scratch scratch(ctx);
     int32_t *own = nullptr, *extra = nullptr, *total = nullptr, *tmp_cols = nullptr;
     void *tmp_vals = nullptr;
-    int st = sg_alloc(ctx, (size_t)n + 1, &own);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &extra);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 1, &total);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n + 2, &ml->d_row_ptr);
-    const unsigned grid = (unsigned)((n + 255) / 256);
-    const bool self = fix_diagonal || symmetrize;
-    if (st == SG_OK && n > 0) {
-        (void)hipMemsetAsync(extra, 0, sizeof(int32_t) * (size_t)(n + 1), ctx->stream);
-        if (self) {
-            hipLaunchKernelGGL(ml_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)r->d_cols,
-                               (const int32_t *)r->d_counts, r->stride, n, fix_diagonal, symmetrize, own, extra);
-        } else {
-            (void)hipMemcpyAsync(own, r->d_counts, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream);
-        }
-    }
-    if (st == SG_OK && n > 0) {
-        hipLaunchKernelGGL(ml_add_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)own,
-                           (const int32_t *)extra, total, n);
-        st = sg_exclusive_scan_i32_to_i64(ctx, total, ml->d_row_ptr, n);
-    } else if (st == SG_OK) {
-        (void)hipMemsetAsync(ml->d_row_ptr, 0, sizeof(int64_t), ctx->stream);
-    }
+    SG_TRY(scratch.alloc((size_t)n + 1, &own));
+    SG_TRY(scratch.alloc((size_t)n + 1, &extra));
+    SG_TRY(scratch.alloc((size_t)n + 1, &total));
+    SG_TRY(sg_alloc(ctx, (size_t)n + 2, &ml->d_row_ptr));
+    SG_TRY(count_row_entries(ctx, r, fix_diagonal, symmetrize, own, extra));
     int64_t n_entries = 0;
-    if (st == SG_OK) {
-        if (hipMemcpyAsync(&n_entries, ml->d_row_ptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess)
-            st = SG_ERR_HIP;
-    }
+    SG_TRY(make_row_pointers(ctx, n, own, extra, total, ml->d_row_ptr, &n_entries));
     ml->n_entries = n_entries;
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_entries + 4, &ml->d_cols);
-    if (st == SG_OK) st = ctx->alloc(((size_t)n_entries + 4) * s, &ml->d_vals);
-    const bool sorted = self || sort_by_column;
-    if (st == SG_OK && sorted) st = sg_alloc(ctx, (size_t)n_entries + 4, &tmp_cols);
-    if (st == SG_OK && sorted) st = ctx->alloc(((size_t)n_entries + 4) * s, &tmp_vals);
-    if (st == SG_OK && n > 0) {
-        if (self) {
-            (void)hipMemsetAsync(extra, 0, sizeof(int32_t) * (size_t)(n + 1), ctx->stream);   // now the mirror cursors
-            const unsigned sgrid = (unsigned)(n < 256 * 64 ? n : 256 * 64);
-            if (r->dtype == SG_F64) {
-                hipLaunchKernelGGL(ml_fill_kernel<double>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)r->d_cols,
-                                   (const double *)r->d_vals, (const int32_t *)r->d_counts, r->stride, n, fix_diagonal,
-                                   symmetrize, (const int64_t *)ml->d_row_ptr, (const int32_t *)own, extra, tmp_cols,
-                                   (double *)tmp_vals);
-                hipLaunchKernelGGL(ml_sort_rows_kernel<double>, dim3(sgrid), dim3(64), 0, ctx->stream,
-                                   (const int64_t *)ml->d_row_ptr, n, (const int32_t *)tmp_cols, (const double *)tmp_vals,
-                                   ml->d_cols, (double *)ml->d_vals);
-            } else {
-                hipLaunchKernelGGL(ml_fill_kernel<float>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t *)r->d_cols,
-                                   (const float *)r->d_vals, (const int32_t *)r->d_counts, r->stride, n, fix_diagonal,
-                                   symmetrize, (const int64_t *)ml->d_row_ptr, (const int32_t *)own, extra, tmp_cols,
-                                   (float *)tmp_vals);
-                hipLaunchKernelGGL(ml_sort_rows_kernel<float>, dim3(sgrid), dim3(64), 0, ctx->stream,
-                                   (const int64_t *)ml->d_row_ptr, n, (const int32_t *)tmp_cols, (const float *)tmp_vals,
-                                   ml->d_cols, (float *)ml->d_vals);
-            }
-        } else {
-            // plain compaction; optionally followed by the per-row column sort
-            int32_t *c_out = sort_by_column ? tmp_cols : ml->d_cols;
-            void *v_out = sort_by_column ? tmp_vals : ml->d_vals;
-            const unsigned sgrid = (unsigned)(n < 256 * 64 ? n : 256 * 64);
-            if (r->dtype == SG_F64) {
-                hipLaunchKernelGGL(ml_compact_kernel<double>, dim3(grid), dim3(256), 0, ctx->stream,
-                                   (const int32_t *)r->d_cols, (const double *)r->d_vals, (const int32_t *)r->d_counts,
-                                   r->stride, n, (const int64_t *)ml->d_row_ptr, c_out, (double *)v_out);
-                if (sort_by_column)
-                    hipLaunchKernelGGL(ml_sort_rows_kernel<double>, dim3(sgrid), dim3(64), 0, ctx->stream,
-                                       (const int64_t *)ml->d_row_ptr, n, (const int32_t *)tmp_cols,
-                                       (const double *)tmp_vals, ml->d_cols, (double *)ml->d_vals);
-            } else {
-                hipLaunchKernelGGL(ml_compact_kernel<float>, dim3(grid), dim3(256), 0, ctx->stream,
-                                   (const int32_t *)r->d_cols, (const float *)r->d_vals, (const int32_t *)r->d_counts,
-                                   r->stride, n, (const int64_t *)ml->d_row_ptr, c_out, (float *)v_out);
-                if (sort_by_column)
-                    hipLaunchKernelGGL(ml_sort_rows_kernel<float>, dim3(sgrid), dim3(64), 0, ctx->stream,
-                                       (const int64_t *)ml->d_row_ptr, n, (const int32_t *)tmp_cols,
-                                       (const float *)tmp_vals, ml->d_cols, (float *)ml->d_vals);
-            }
-        }
-        if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
+    SG_TRY(sg_alloc(ctx, (size_t)n_entries + 4, &ml->d_cols));
+    SG_TRY(ctx->alloc(((size_t)n_entries + 4) * s, &ml->d_vals));
+    const bool sorted = fix_diagonal || symmetrize || sort_by_column;
+    if (sorted) {
+        SG_TRY(scratch.alloc((size_t)n_entries + 4, &tmp_cols));
+        SG_TRY(scratch.alloc_bytes(((size_t)n_entries + 4) * s, &tmp_vals));
     }
-    ctx->release(own);
-    ctx->release(extra);
-    ctx->release(total);
-    ctx->release(tmp_cols);
-    ctx->release(tmp_vals);
-    if (st != SG_OK) {
-        sg_matchlist_free(ml);
-        return st;
-    }
-    *out = ml;
+    SG_TRY(fill_rows(ctx, r, fix_diagonal, symmetrize, sorted, own, extra, tmp_cols, tmp_vals, ml.get()));
+    *out = ml.release();
     return SG_OK;
 }
 

@@ -212,41 +212,65 @@ extern "C" int sg_matchlist_best_master(sg_ctx *ctx, const sg_matchlist *ml, int
     SG_TRY(sg_matchlist_device_view(ml, &n_rows, &n_cols, &n_entries, &dtype, &row_ptr, &cols, &vals));
     if (n_cols == 0) return SG_OK;
     const size_t bs = dtype == SG_F64 ? 8 : 4;
+    Scratch scratch(ctx);
     void *col_max = nullptr;
     int32_t *best = nullptr;
-    int st = ctx->alloc((size_t)n_cols * bs, &col_max);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)n_cols, &best);
-    hipError_t e = hipSuccess;
-    if (st == SG_OK) e = hipMemsetAsync(col_max, 0, (size_t)n_cols * bs, ctx->stream);
-    if (st == SG_OK && e == hipSuccess) {
-        e = hipMemsetD32Async((hipDeviceptr_t)best, INT32_MAX, (size_t)n_cols, ctx->stream);
-        if (e == hipSuccess && n_rows > 0) {
-            if (dtype == SG_F64) {
-                hipLaunchKernelGGL(best_max_kernel<double>, dim3(blocks_for(n_rows)), dim3(256), 0, ctx->stream, row_ptr, cols,
-                                   (const double *)vals, n_rows, (unsigned long long *)col_max);
-                hipLaunchKernelGGL(best_row_kernel<double>, dim3(blocks_for(n_rows)), dim3(256), 0, ctx->stream, row_ptr, cols,
-                                   (const double *)vals, n_rows, (const unsigned long long *)col_max, best);
-            } else {
-                hipLaunchKernelGGL(best_max_kernel<float>, dim3(blocks_for(n_rows)), dim3(256), 0, ctx->stream, row_ptr, cols,
-                                   (const float *)vals, n_rows, (unsigned int *)col_max);
-                hipLaunchKernelGGL(best_row_kernel<float>, dim3(blocks_for(n_rows)), dim3(256), 0, ctx->stream, row_ptr, cols,
-                                   (const float *)vals, n_rows, (const unsigned int *)col_max, best);
-            }
+    SG_TRY(scratch.alloc_bytes((size_t)n_cols * bs, &col_max));
+    SG_TRY(scratch.alloc((size_t)n_cols, &best));
+    SG_HIP_TRY(hipMemsetAsync(col_max, 0, (size_t)n_cols * bs, ctx->stream));
+    SG_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)best, INT32_MAX, (size_t)n_cols, ctx->stream));
+    if (n_rows > 0)
+        by_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            using B = typename Bits<T>::type;
+            hipLaunchKernelGGL(best_max_kernel<T>, dim3(blocks_for(n_rows)), dim3(256), 0, ctx->stream, row_ptr, cols,
+                               (const T *)vals, n_rows, (B *)col_max);
+            hipLaunchKernelGGL(best_row_kernel<T>, dim3(blocks_for(n_rows)), dim3(256), 0, ctx->stream, row_ptr, cols,
+                               (const T *)vals, n_rows, (const B *)col_max, best);
+            return SG_OK;
+        });
+    hipLaunchKernelGGL(best_finish_kernel, dim3(blocks_for(n_cols)), dim3(256), 0, ctx->stream, best, n_cols);
+    SG_HIP_TRY(hipGetLastError());
+    return sg_fetch(ctx, out_best, best, (size_t)n_cols * 4);
+}
+
+// K8, first half: label[i] = the lowest index of i's component.  Rounds of hooking and pointer jumping until one changes
+// nothing; `flag` is the device's word for "changed", read back after every round.
+static int connected_components(sg_ctx *ctx, const int64_t *row_ptr, const int32_t *cols, int64_t n, int32_t *label,
+                                int32_t *flag) {
+    const unsigned grid = blocks_for(n);
+    hipLaunchKernelGGL(cc_init_kernel, dim3(grid), dim3(256), 0, ctx->stream, label, n);
+    int32_t changed = 1;
+    for (int rounds = 1; changed; ++rounds) {
+        if (rounds > 100000) {
+            sg_set_error("connected components did not converge");
+            return SG_ERR_HIP;
         }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(best_finish_kernel, dim3(blocks_for(n_cols)), dim3(256), 0, ctx->stream, best, n_cols);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out_best, best, (size_t)n_cols * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        SG_HIP_TRY(hipMemsetAsync(flag, 0, 4, ctx->stream));
+        hipLaunchKernelGGL(cc_hook_kernel, dim3(grid), dim3(256), 0, ctx->stream, row_ptr, cols, n, label, flag);
+        hipLaunchKernelGGL(cc_jump_kernel, dim3(grid), dim3(256), 0, ctx->stream, label, n, flag);
+        SG_TRY(sg_fetch(ctx, &changed, flag, 4));
     }
-    ctx->release(col_max);
-    ctx->release(best);
-    if (st != SG_OK) return st;
-    if (e != hipSuccess) {
-        sg_set_error("sg_matchlist_best_master: %s", hipGetErrorString(e));
-        return SG_ERR_HIP;
-    }
+    return SG_OK;
+}
+
+// K8, second half (group_rep='centroid'): out[i] = the member of i's component with the largest row sum of similarities,
+// the lowest index among equals
+static int pick_centroids(sg_ctx *ctx, const int64_t *row_ptr, const void *vals, int32_t dtype, int64_t n, const int32_t *label,
+                          double *weight, unsigned long long *gmax, int32_t *rep, int32_t *out) {
+    const unsigned grid = blocks_for(n);
+    SG_HIP_TRY(hipMemsetAsync(gmax, 0, (size_t)n * 8, ctx->stream));
+    SG_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)rep, INT32_MAX, (size_t)n, ctx->stream));
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(row_weight_kernel<T>, dim3(grid), dim3(256), 0, ctx->stream, row_ptr, (const T *)vals, n, weight);
+        return SG_OK;
+    });
+    hipLaunchKernelGGL(rep_max_kernel<double>, dim3(grid), dim3(256), 0, ctx->stream, label, (const double *)weight, n, gmax);
+    hipLaunchKernelGGL(rep_pick_kernel<double>, dim3(grid), dim3(256), 0, ctx->stream, label, (const double *)weight, n,
+                       (const unsigned long long *)gmax, rep);
+    hipLaunchKernelGGL(rep_gather_kernel, dim3(grid), dim3(256), 0, ctx->stream, label, (const int32_t *)rep, n, out);
+    SG_HIP_TRY(hipGetLastError());
     return SG_OK;
 }
 
@@ -260,66 +284,22 @@ extern "C" int sg_matchlist_group_reps(sg_ctx *ctx, const sg_matchlist *ml, int3
     SG_TRY(sg_matchlist_device_view(ml, &n, &n_cols, &n_entries, &dtype, &row_ptr, &cols, &vals));
     SG_REQUIRE(n == n_cols, "group representatives need a square match list (a self-join)");
     if (n == 0) return SG_OK;
+    Scratch scratch(ctx);
     int32_t *label = nullptr, *flag = nullptr, *rep = nullptr, *out = nullptr;
-    void *weight = nullptr, *gmax = nullptr;
-    int st = sg_alloc(ctx, (size_t)n, &label);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)16, &flag);
-    if (st == SG_OK && centroid) {
-        st = sg_alloc(ctx, (size_t)n, &rep);
-        if (st == SG_OK) st = sg_alloc(ctx, (size_t)n, &out);
-        if (st == SG_OK) st = ctx->alloc((size_t)n * 8, &weight);
-        if (st == SG_OK) st = ctx->alloc((size_t)n * 8, &gmax);
+    double *weight = nullptr;
+    unsigned long long *gmax = nullptr;
+    SG_TRY(scratch.alloc((size_t)n, &label));
+    SG_TRY(scratch.alloc((size_t)16, &flag));
+    if (centroid) {
+        SG_TRY(scratch.alloc((size_t)n, &rep));
+        SG_TRY(scratch.alloc((size_t)n, &out));
+        SG_TRY(scratch.alloc((size_t)n, &weight));
+        SG_TRY(scratch.alloc((size_t)n, &gmax));
     }
-    hipError_t e = hipSuccess;
-    const unsigned grid = blocks_for(n);
-    if (st == SG_OK) {
-        hipLaunchKernelGGL(cc_init_kernel, dim3(grid), dim3(256), 0, ctx->stream, label, n);
-        int32_t changed = 1;
-        int rounds = 0;
-        while (changed && e == hipSuccess) {
-            if (++rounds > 100000) {
-                sg_set_error("connected components did not converge");
-                st = SG_ERR_HIP;
-                break;
-            }
-            e = hipMemsetAsync(flag, 0, 4, ctx->stream);
-            hipLaunchKernelGGL(cc_hook_kernel, dim3(grid), dim3(256), 0, ctx->stream, row_ptr, cols, n, label, flag);
-            hipLaunchKernelGGL(cc_jump_kernel, dim3(grid), dim3(256), 0, ctx->stream, label, n, flag);
-            if (e == hipSuccess) e = hipMemcpyAsync(&changed, flag, 4, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        }
-    }
-    const int32_t *result = label;   // 'first': the label is the lowest index of the component
-    if (st == SG_OK && e == hipSuccess && centroid) {
-        e = hipMemsetAsync(gmax, 0, (size_t)n * 8, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)rep, INT32_MAX, (size_t)n, ctx->stream);
-        if (e == hipSuccess) {
-            if (dtype == SG_F64)
-                hipLaunchKernelGGL(row_weight_kernel<double>, dim3(grid), dim3(256), 0, ctx->stream, row_ptr, (const double *)vals, n,
-                                   (double *)weight);
-            else
-                hipLaunchKernelGGL(row_weight_kernel<float>, dim3(grid), dim3(256), 0, ctx->stream, row_ptr, (const float *)vals, n,
-                                   (double *)weight);
-            hipLaunchKernelGGL(rep_max_kernel<double>, dim3(grid), dim3(256), 0, ctx->stream, label, (const double *)weight, n,
-                               (unsigned long long *)gmax);
-            hipLaunchKernelGGL(rep_pick_kernel<double>, dim3(grid), dim3(256), 0, ctx->stream, label, (const double *)weight, n,
-                               (const unsigned long long *)gmax, rep);
-            hipLaunchKernelGGL(rep_gather_kernel, dim3(grid), dim3(256), 0, ctx->stream, label, rep, n, out);
-            e = hipGetLastError();
-            result = out;
-        }
-    }
-    if (st == SG_OK && e == hipSuccess) {
-        e = hipMemcpyAsync(out_rep, result, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    }
-    for (void *p : {(void *)label, (void *)flag, (void *)rep, (void *)out, weight, gmax}) ctx->release(p);
-    if (st != SG_OK) return st;
-    if (e != hipSuccess) {
-        sg_set_error("sg_matchlist_group_reps: %s", hipGetErrorString(e));
-        return SG_ERR_HIP;
-    }
-    return SG_OK;
+    SG_TRY(connected_components(ctx, row_ptr, cols, n, label, flag));
+    if (centroid) SG_TRY(pick_centroids(ctx, row_ptr, vals, dtype, n, label, weight, gmax, rep, out));
+    // 'first': the label is the lowest index of the component
+    return sg_fetch(ctx, out_rep, centroid ? out : label, (size_t)n * 4);
 }
 
 extern "C" int sg_csr_rowwise_dot(sg_ctx *ctx, const sg_csr *A, const sg_csr *B, void *out_host) {
@@ -329,29 +309,16 @@ extern "C" int sg_csr_rowwise_dot(sg_ctx *ctx, const sg_csr *A, const sg_csr *B,
     const int64_t n = A->n_rows;
     if (n == 0) return SG_OK;
     const size_t s = A->dtype == SG_F64 ? 8 : 4;
+    Scratch tmp(ctx);
     void *scratch = nullptr, *out = nullptr;
-    int st = ctx->alloc(((size_t)A->nnz + 1) * s, &scratch);
-    if (st == SG_OK) st = ctx->alloc((size_t)n * s, &out);
-    hipError_t e = hipSuccess;
-    if (st == SG_OK) {
-        if (A->dtype == SG_F64)
-            hipLaunchKernelGGL(rowwise_dot_kernel<double>, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, A->d_indptr, A->d_indices,
-                               (const double *)A->d_data, B->d_indptr, B->d_indices, (const double *)B->d_data, n,
-                               (double *)scratch, (double *)out);
-        else
-            hipLaunchKernelGGL(rowwise_dot_kernel<float>, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, A->d_indptr, A->d_indices,
-                               (const float *)A->d_data, B->d_indptr, B->d_indices, (const float *)B->d_data, n,
-                               (float *)scratch, (float *)out);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(out_host, out, (size_t)n * s, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    }
-    ctx->release(scratch);
-    ctx->release(out);
-    if (st != SG_OK) return st;
-    if (e != hipSuccess) {
-        sg_set_error("sg_csr_rowwise_dot: %s", hipGetErrorString(e));
-        return SG_ERR_HIP;
-    }
-    return SG_OK;
+    SG_TRY(tmp.alloc_bytes(((size_t)A->nnz + 1) * s, &scratch));
+    SG_TRY(tmp.alloc_bytes((size_t)n * s, &out));
+    by_dtype(A->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(rowwise_dot_kernel<T>, dim3(blocks_for(n)), dim3(256), 0, ctx->stream, A->d_indptr, A->d_indices,
+                           (const T *)A->d_data, B->d_indptr, B->d_indices, (const T *)B->d_data, n, (T *)scratch, (T *)out);
+        return SG_OK;
+    });
+    SG_HIP_TRY(hipGetLastError());
+    return sg_fetch(ctx, out_host, out, (size_t)n * s);
 }

@@ -1,8 +1,8 @@
 // K4 -- thresholded sparse top-n multiply  C = topn_rowwise(A . B^T restricted to > threshold)
-// K5 -- top-n merge of column-block results (zip)
+// (K5, the top-n merge of column-block results, and the result handle itself: sg_topn.hip)
 //
-// Replaces sparse_dot_topn.sp_matmul_topn / zip_sp_matmul_topn as called from
-// string_grouper/string_grouper.py:725-732, :737-743 and :746 of the reference.
+// Replaces sparse_dot_topn.sp_matmul_topn as called from string_grouper/string_grouper.py:725-732 and :737-743 of the
+// reference.
 //
 // Algorithm (row-wise Gustavson product, MI355X shape).  One 64-lane wave owns one left row i at a
 // time and a private accumulator tile of TILE = 2^TILE_LOG2 values in LDS (single-wave workgroups:
@@ -488,94 +488,6 @@ __global__ void __launch_bounds__(256) sum_counts_kernel(const int32_t *__restri
     block_add_u64(local, out);
 }
 
-// Re-order every row of a fixed-stride result by ascending column (sort == 0).  One wave per row;
-// dynamic LDS: stride * (4 + sizeof(T)) bytes.
-template <typename T>
-__global__ void __launch_bounds__(64) topn_sort_by_col_kernel(int32_t *cols, T *vals, const int32_t *cnt,
-                                                              int64_t n_rows, int32_t stride) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    T *sv = reinterpret_cast<T *>(smem);
-    int32_t *sc = reinterpret_cast<int32_t *>(smem + sizeof(T) * (size_t)stride);
-    const int lane = threadIdx.x;
-    for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
-        const int n = cnt[row];
-        int32_t *rc = cols + (size_t)row * stride;
-        T *rv = vals + (size_t)row * stride;
-        for (int i = lane; i < n; i += 64) {   // rank by counting; columns of one row are distinct
-            const int myc = rc[i];
-            int rank = 0;
-            for (int q = 0; q < n; ++q) rank += (rc[q] < myc);
-            sc[rank] = myc;
-            sv[rank] = rv[i];
-        }
-        __syncthreads();
-        for (int i = lane; i < n; i += 64) {
-            rc[i] = sc[i];
-            rv[i] = sv[i];
-        }
-        __syncthreads();
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// K5: merge of column-block results (zip_sp_matmul_topn).  One wave per row, register top-n.
-template <typename T>
-struct ZipPart {
-    const int32_t *cols;
-    const T *vals;
-    const int32_t *cnt;
-    int32_t stride;
-    int32_t col_offset;
-};
-
-template <typename T>
-__global__ void __launch_bounds__(64) topn_zip_kernel(const ZipPart<T> *__restrict__ parts, int32_t n_parts,
-                                                      int64_t n_rows, int32_t keep, int32_t pass_off,
-                                                      int32_t out_stride, int32_t *out_cols, T *out_vals,
-                                                      int32_t *out_cnt) {
-    const int lane = threadIdx.x;
-    for (int64_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
-        const size_t obase = (size_t)row * out_stride + pass_off;
-        TopList<T> top;
-        top.clear();
-        T floor_s = INFINITY;
-        int floor_c = -1;
-        if (pass_off > 0) {
-            if (out_cnt[row] < pass_off) continue;
-            floor_s = out_vals[obase - 1];
-            floor_c = out_cols[obase - 1];
-        }
-        for (int b = 0; b < n_parts; ++b) {
-            const ZipPart<T> part = parts[b];
-            const int n = part.cnt[row];
-            for (int base = 0; base < n; base += 64) {
-                T v = (T)0;
-                int c = 0;
-                const bool ok = base + lane < n;
-                if (ok) {
-                    v = part.vals[(size_t)row * part.stride + base + lane];
-                    c = part.cols[(size_t)row * part.stride + base + lane] + part.col_offset;
-                }
-                uint64_t m = __ballot(ok);
-                while (m) {
-                    const int src = __builtin_ctzll(m);
-                    m &= m - 1;
-                    const T ns = wave_read<T>(v, src);
-                    const int nc = wave_read<int>(c, src);
-                    if (ns < floor_s || (ns == floor_s && nc > floor_c)) top.insert(ns, nc, lane);
-                }
-            }
-        }
-        int cnt = __popcll(__ballot(top.c != INT32_MAX));
-        if (cnt > keep) cnt = keep;
-        if (lane < cnt) {
-            out_vals[obase + lane] = top.s;
-            out_cols[obase + lane] = top.c;
-        }
-        if (lane == 0) out_cnt[row] = pass_off + cnt;
-    }
-}
-
 // ================================================================================================
 // host side
 // ================================================================================================
@@ -658,58 +570,6 @@ int sg_spgemm_exact_selfjoin_rows(sg_ctx *ctx, const sg_csr *A, const sg_posting
     return dispatch_selfjoin_rows<float>(ctx, A, Bt, keep, r, (float)threshold, row_counter, row_list, row_list_len, sink, all_rows);
 }
 
-struct TopnFree {
-    void operator()(sg_topn *r) const { sg_topn_free(r); }
-};
-using TopnPtr = std::unique_ptr<sg_topn, TopnFree>;   // a result under construction: freed on every early return
-
-static int topn_alloc(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, int32_t stride, int32_t dtype, TopnPtr *out) {
-    TopnPtr r(new (std::nothrow) sg_topn());
-    if (!r) return SG_ERR_OOM;
-    r->ctx = ctx;
-    r->n_rows = n_rows;
-    r->n_cols = n_cols;
-    r->stride = stride;
-    r->dtype = dtype;
-    const size_t cells = (size_t)n_rows * (size_t)stride + 64;
-    SG_TRY(sg_alloc(ctx, cells, &r->d_cols));
-    SG_TRY(ctx->alloc(cells * (dtype == SG_F64 ? 8 : 4), &r->d_vals));
-    SG_TRY(sg_alloc(ctx, (size_t)n_rows + 64, &r->d_counts));
-    *out = std::move(r);
-    return SG_OK;
-}
-
-// The result's stride -- top_n, cut at the n_cols columns there are (at least one) -- and whether n_rows rows of it fit the
-// 32-bit result index
-static bool result_stride(int64_t n_rows, int64_t top_n, int64_t n_cols, int32_t *stride) {
-    *stride = (int32_t)(top_n < n_cols ? top_n : (n_cols > 0 ? n_cols : 1));
-    return (double)n_rows * (double)*stride <= 2.0e9;
-}
-
-static int result_overflow(int64_t n_rows, int32_t stride, const char *advice) {
-    sg_set_error("result of %lld rows x top_n %lld does not fit the 32-bit result index%s", (long long)n_rows, (long long)stride,
-                 advice);
-    return SG_ERR_OVERFLOW;
-}
-
-// Every row of an unsorted result (sort == 0) re-ordered by ascending column
-static int sort_rows_by_column(sg_ctx *ctx, sg_topn *r) {
-    if (r->n_rows <= 0) return SG_OK;
-    const unsigned grid = (unsigned)(r->n_rows < 65535 * 16 ? r->n_rows : 65535 * 16);
-    const size_t lds = (size_t)r->stride * (4 + (r->dtype == SG_F64 ? 8 : 4));
-    if (lds > 64 * 1024) {
-        sg_set_error("sort=0 with top_n=%d is not supported", r->stride);
-        return SG_ERR_UNSUPPORTED;
-    }
-    if (r->dtype == SG_F64)
-        hipLaunchKernelGGL(topn_sort_by_col_kernel<double>, dim3(grid), dim3(64), lds, ctx->stream, r->d_cols, (double *)r->d_vals,
-                           r->d_counts, r->n_rows, r->stride);
-    else
-        hipLaunchKernelGGL(topn_sort_by_col_kernel<float>, dim3(grid), dim3(64), lds, ctx->stream, r->d_cols, (float *)r->d_vals,
-                           r->d_counts, r->n_rows, r->stride);
-    return SG_OK;
-}
-
 // Algorithmic bytes of the multiply (stream model): macs*(4+s) + nnz(A)*(4+s) + (nL+V+2)*4 + out*(4+s); the MAC and
 // output terms are added in sg_ctx_stats once the device counters are read
 static void record_bytes(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, double threshold) {
@@ -731,39 +591,28 @@ static int prune_pilot(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int3
     const int64_t block = 512;
     TopnPtr scratch;
     SG_TRY(topn_alloc(ctx, block, Bt->n_right, stride, A->dtype, &scratch));
+    Scratch tmp(ctx);
     uint32_t *words = nullptr;            // [0] row counter [1] flagged count, then flagged rows
     unsigned long long *d_stats = nullptr;   // [0] rows [1] postings [2] survivors [3] MACs of the whole multiply [4] pairs scored exactly (the kernel's; eight words like sg_spgemm_pruned_symmetric)
-    int st = sg_alloc(ctx, (size_t)block + 8, &words);
-    if (st == SG_OK) st = sg_alloc(ctx, (size_t)8, &d_stats);
-    hipError_t e = hipSuccess;
-    if (st == SG_OK) e = hipMemsetAsync(d_stats, 0, 8 * sizeof(unsigned long long), ctx->stream);
+    SG_TRY(tmp.alloc((size_t)block + 8, &words));
+    SG_TRY(tmp.alloc((size_t)8, &d_stats));
+    SG_HIP_TRY(hipMemsetAsync(d_stats, 0, 8 * sizeof(unsigned long long), ctx->stream));
     const int64_t starts[3] = {0, (A->n_rows - block) / 2, A->n_rows - block};
-    for (int b = 0; b < 3 && st == SG_OK && e == hipSuccess; ++b) {
+    for (int b = 0; b < 3; ++b) {
         sg_csr view = *A;
         view.n_rows = block;
         view.d_indptr = A->d_indptr + starts[b];
         view.owned = false;
-        e = hipMemsetAsync(words, 0, 8 * sizeof(uint32_t), ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(scratch->d_counts, 0, sizeof(int32_t) * (size_t)block, ctx->stream);
-        if (e == hipSuccess)
-            st = sg_spgemm_pruned_launch(ctx, &view, Bt, stride < SG_TOPN_LANES ? stride : SG_TOPN_LANES, scratch.get(), threshold,
-                                         delta, words, words + 1, words + 8, d_stats);
+        SG_HIP_TRY(hipMemsetAsync(words, 0, 8 * sizeof(uint32_t), ctx->stream));
+        SG_HIP_TRY(hipMemsetAsync(scratch->d_counts, 0, sizeof(int32_t) * (size_t)block, ctx->stream));
+        SG_TRY(sg_spgemm_pruned_launch(ctx, &view, Bt, stride < SG_TOPN_LANES ? stride : SG_TOPN_LANES, scratch.get(), threshold,
+                                       delta, words, words + 1, words + 8, d_stats));
     }
-    if (st == SG_OK && e == hipSuccess) {
-        hipLaunchKernelGGL(count_macs_kernel, dim3(512), dim3(256), 0, ctx->stream, A->d_indptr, A->d_indices, A->n_rows,
-                           (const uint32_t *)Bt->d_term_len, d_stats + 3);
-        e = hipGetLastError();
-    }
+    hipLaunchKernelGGL(count_macs_kernel, dim3(512), dim3(256), 0, ctx->stream, A->d_indptr, A->d_indices, A->n_rows,
+                       (const uint32_t *)Bt->d_term_len, d_stats + 3);
+    SG_HIP_TRY(hipGetLastError());
     unsigned long long h[4] = {0, 0, 0, 0};
-    if (st == SG_OK && e == hipSuccess) e = hipMemcpyAsync(h, d_stats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream);
-    if (st == SG_OK && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    ctx->release(words);
-    ctx->release(d_stats);
-    if (st != SG_OK) return st;
-    if (e != hipSuccess) {
-        sg_set_error("pruning pilot: %s", hipGetErrorString(e));
-        return SG_ERR_HIP;
-    }
+    SG_TRY(sg_fetch(ctx, h, d_stats, sizeof(h)));
     const double s = A->dtype == SG_F64 ? 8.0 : 4.0;
     const double rows = (double)A->n_rows, sampled = h[0] > 0 ? (double)h[0] : 1.0;
     const double candidates = (double)h[2] * rows / sampled;
@@ -1437,183 +1286,12 @@ extern "C" int sg_row_costs(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt,
     SG_REQUIRE(ctx && A && Bt && out_cost, "null argument");
     SG_REQUIRE(A->n_cols == Bt->n_terms, "A and B have different numbers of columns");
     if (A->n_rows == 0) return SG_OK;
+    Scratch tmp(ctx);
     int64_t *d = nullptr;
-    SG_TRY(sg_alloc(ctx, (size_t)A->n_rows, &d));
+    SG_TRY(tmp.alloc((size_t)A->n_rows, &d));
     hipLaunchKernelGGL(row_cost_kernel, dim3((unsigned)((A->n_rows + 255) / 256)), dim3(256), 0, ctx->stream,
                        A->d_indptr, A->d_indices, A->n_rows, (const uint32_t *)Bt->d_term_len, d);
-    hipError_t e = hipMemcpyAsync(out_cost, d, sizeof(int64_t) * (size_t)A->n_rows, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    ctx->release(d);
-    if (e != hipSuccess) {
-        sg_set_error("sg_row_costs: %s", hipGetErrorString(e));
-        return SG_ERR_HIP;
-    }
-    return SG_OK;
-}
-
-extern "C" int sg_topn_dims(const sg_topn *r, int64_t *n_rows, int32_t *stride, int32_t *dtype, int64_t *n_cols) {
-    SG_REQUIRE(r != nullptr, "result is null");
-    if (n_rows) *n_rows = r->n_rows;
-    if (stride) *stride = r->stride;
-    if (dtype) *dtype = r->dtype;
-    if (n_cols) *n_cols = r->n_cols;
-    return SG_OK;
-}
-
-extern "C" int sg_topn_device_ptrs(const sg_topn *r, const int32_t **d_cols, const void **d_vals,
-                                   const int32_t **d_counts) {
-    SG_REQUIRE(r != nullptr, "result is null");
-    if (d_cols) *d_cols = r->d_cols;
-    if (d_vals) *d_vals = r->d_vals;
-    if (d_counts) *d_counts = r->d_counts;
-    return SG_OK;
-}
-
-extern "C" int sg_topn_to_host(sg_ctx *ctx, const sg_topn *r, int32_t *cols, void *vals, int32_t *counts) {
-    SG_REQUIRE(ctx && r && counts, "null argument");
-    const size_t cells = (size_t)r->n_rows * (size_t)r->stride;
-    const size_t s = r->dtype == SG_F64 ? 8 : 4;
-    if (cells > 0) {
-        SG_REQUIRE(cols && vals, "null output");
-        SG_HIP_TRY(hipMemcpyAsync(cols, r->d_cols, cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-        SG_HIP_TRY(hipMemcpyAsync(vals, r->d_vals, cells * s, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (r->n_rows > 0)
-        SG_HIP_TRY(hipMemcpyAsync(counts, r->d_counts, (size_t)r->n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return SG_OK;
-}
-
-extern "C" int sg_topn_counts_to_host(sg_ctx *ctx, const sg_topn *r, int32_t *counts) {
-    SG_REQUIRE(ctx && r && counts, "null argument");
-    if (r->n_rows > 0)
-        SG_HIP_TRY(hipMemcpyAsync(counts, r->d_counts, (size_t)r->n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return SG_OK;
-}
-
-extern "C" int sg_topn_from_host(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, int32_t stride, int32_t dtype,
-                                 const int32_t *cols, const void *vals, const int32_t *counts, sg_topn **out) {
-    SG_REQUIRE(ctx && counts && out && n_rows >= 0 && stride >= 1, "bad argument");
-    SG_REQUIRE(dtype == SG_F32 || dtype == SG_F64, "dtype must be SG_F32 or SG_F64");
-    TopnPtr r;
-    SG_TRY(topn_alloc(ctx, n_rows, n_cols, stride, dtype, &r));
-    const size_t cells = (size_t)n_rows * (size_t)stride;
-    const size_t s = dtype == SG_F64 ? 8 : 4;
-    hipError_t e = hipSuccess;
-    if (cells > 0) {
-        e = hipMemcpyAsync(r->d_cols, cols, cells * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(r->d_vals, vals, cells * s, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(r->d_counts, counts, (size_t)n_rows * 4, hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        sg_set_error("sg_topn_from_host: %s", hipGetErrorString(e));
-        return SG_ERR_HIP;
-    }
-    *out = r.release();
-    return SG_OK;
-}
-
-extern "C" int sg_topn_from_device(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, int32_t stride, int32_t dtype,
-                                   const int32_t *d_cols, const void *d_vals, const int32_t *d_counts, sg_topn **out) {
-    SG_REQUIRE(ctx && d_counts && out && n_rows >= 0 && stride >= 1, "bad argument");
-    SG_REQUIRE(dtype == SG_F32 || dtype == SG_F64, "dtype must be SG_F32 or SG_F64");
-    TopnPtr r;
-    SG_TRY(topn_alloc(ctx, n_rows, n_cols, stride, dtype, &r));
-    const size_t cells = (size_t)n_rows * (size_t)stride;
-    const size_t s = dtype == SG_F64 ? 8 : 4;
-    hipError_t e = hipSuccess;
-    if (cells > 0) {
-        e = hipMemcpyAsync(r->d_cols, d_cols, cells * 4, hipMemcpyDeviceToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(r->d_vals, d_vals, cells * s, hipMemcpyDeviceToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(r->d_counts, d_counts, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, ctx->stream);
-    }
-    if (e != hipSuccess) {
-        sg_set_error("sg_topn_from_device: %s", hipGetErrorString(e));
-        return SG_ERR_HIP;
-    }
-    *out = r.release();
-    return SG_OK;
-}
-
-extern "C" int sg_topn_free(sg_topn *r) {
-    if (!r) return SG_OK;
-    r->ctx->release(r->d_cols);
-    r->ctx->release(r->d_vals);
-    r->ctx->release(r->d_counts);
-    delete r;
-    return SG_OK;
-}
-
-extern "C" int sg_topn_zip(sg_ctx *ctx, const sg_topn *const *parts, const int64_t *col_offsets, int32_t n_parts,
-                           int32_t top_n, sg_topn **out) {
-    SG_REQUIRE(ctx && parts && col_offsets && out && n_parts >= 1 && top_n >= 1, "bad argument");
-    const int64_t n_rows = parts[0]->n_rows;
-    const int32_t dtype = parts[0]->dtype;
-    int64_t total_cols = 0, total_stride = 0;
-    for (int b = 0; b < n_parts; ++b) {
-        SG_REQUIRE(parts[b] && parts[b]->n_rows == n_rows && parts[b]->dtype == dtype, "parts disagree in shape/dtype");
-        const int64_t end = col_offsets[b] + parts[b]->n_cols;
-        if (end > total_cols) total_cols = end;
-        total_stride += parts[b]->stride;
-    }
-    if (total_cols > INT32_MAX) {
-        sg_set_error("zipped column count exceeds int32");
-        return SG_ERR_OVERFLOW;
-    }
-    int64_t stride64 = top_n < total_stride ? top_n : total_stride;
-    if (stride64 < 1) stride64 = 1;
-    const int32_t stride = (int32_t)stride64;
-    TopnPtr r;
-    SG_TRY(topn_alloc(ctx, n_rows, total_cols, stride, dtype, &r));
-    const size_t s = dtype == SG_F64 ? 8 : 4;
-    // part descriptors: host-pinned scratch would add a dependency; a tiny pooled device buffer + sync copy
-    std::vector<unsigned char> host_desc((size_t)n_parts * (dtype == SG_F64 ? sizeof(ZipPart<double>) : sizeof(ZipPart<float>)));
-    for (int b = 0; b < n_parts; ++b) {
-        if (dtype == SG_F64) {
-            ZipPart<double> d{parts[b]->d_cols, (const double *)parts[b]->d_vals, parts[b]->d_counts, parts[b]->stride,
-                              (int32_t)col_offsets[b]};
-            memcpy(host_desc.data() + (size_t)b * sizeof(d), &d, sizeof(d));
-        } else {
-            ZipPart<float> d{parts[b]->d_cols, (const float *)parts[b]->d_vals, parts[b]->d_counts, parts[b]->stride,
-                             (int32_t)col_offsets[b]};
-            memcpy(host_desc.data() + (size_t)b * sizeof(d), &d, sizeof(d));
-        }
-    }
-    void *d_desc = nullptr;
-    SG_TRY(ctx->alloc(host_desc.size(), &d_desc));
-    (void)s;
-    hipError_t he = hipMemcpyAsync(d_desc, host_desc.data(), host_desc.size(), hipMemcpyHostToDevice, ctx->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);   // host_desc is a local
-    if (he == hipSuccess) he = hipMemsetAsync(r->d_counts, 0, sizeof(int32_t) * (size_t)n_rows, ctx->stream);
-    if (he != hipSuccess) {
-        sg_set_error("sg_topn_zip: %s", hipGetErrorString(he));
-        ctx->release(d_desc);
-        return he == hipErrorOutOfMemory ? SG_ERR_OOM : SG_ERR_HIP;
-    }
-    {
-        SgTimer timer(ctx, SG_K_ZIP);
-        const int n_pass = (stride + SG_TOPN_LANES - 1) / SG_TOPN_LANES;
-        unsigned grid = (unsigned)(n_rows < 256 * 32 ? (n_rows > 0 ? n_rows : 1) : 256 * 32);
-        for (int pass = 0; pass < n_pass && n_rows > 0; ++pass) {
-            const int pass_off = pass * SG_TOPN_LANES;
-            const int keep = stride - pass_off < SG_TOPN_LANES ? stride - pass_off : SG_TOPN_LANES;
-            if (dtype == SG_F64)
-                hipLaunchKernelGGL(topn_zip_kernel<double>, dim3(grid), dim3(64), 0, ctx->stream,
-                                   (const ZipPart<double> *)d_desc, n_parts, n_rows, keep, pass_off, stride, r->d_cols,
-                                   (double *)r->d_vals, r->d_counts);
-            else
-                hipLaunchKernelGGL(topn_zip_kernel<float>, dim3(grid), dim3(64), 0, ctx->stream,
-                                   (const ZipPart<float> *)d_desc, n_parts, n_rows, keep, pass_off, stride, r->d_cols,
-                                   (float *)r->d_vals, r->d_counts);
-        }
-    }
-    const int st = hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
-    ctx->release(d_desc);
-    SG_TRY(st);
-    *out = r.release();
-    return SG_OK;
+    return sg_fetch(ctx, out_cost, d, sizeof(int64_t) * (size_t)A->n_rows);
 }
 
 extern "C" int sg_sp_matmul_topn_host(sg_ctx *ctx, int64_t n_left, int64_t n_right, int64_t n_cols,
@@ -1621,9 +1299,6 @@ extern "C" int sg_sp_matmul_topn_host(sg_ctx *ctx, int64_t n_left, int64_t n_rig
                                       const int64_t *b_indptr, const int32_t *b_indices, const void *b_data,
                                       int32_t dtype, int32_t top_n, double threshold, int32_t sort,
                                       int32_t *out_cols, void *out_vals, int32_t *out_counts) {
-    sg_csr *A = nullptr, *B = nullptr;
-    sg_postings *P = nullptr;
-    sg_topn *R = nullptr;
     SG_REQUIRE(ctx && a_indptr && b_indptr && out_cols && out_vals && out_counts, "null argument");
     SG_REQUIRE(n_left >= 0 && n_right >= 0 && n_cols >= 0, "negative size");
     SG_REQUIRE(dtype == SG_F32 || dtype == SG_F64, "dtype must be SG_F32 or SG_F64");
@@ -1638,15 +1313,23 @@ extern "C" int sg_sp_matmul_topn_host(sg_ctx *ctx, int64_t n_left, int64_t n_rig
                (nnz == 0 || (std::memcmp(a_indices, b_indices, sizeof(int32_t) * nnz) == 0 &&
                              std::memcmp(a_data, b_data, (dtype == SG_F64 ? 8 : 4) * nnz) == 0));
     }
-    int st = sg_csr_from_host(ctx, n_left, n_cols, a_indptr, a_indices, a_data, dtype, &A);
-    if (same) B = A;
-    else if (st == SG_OK) st = sg_csr_from_host(ctx, n_right, n_cols, b_indptr, b_indices, b_data, dtype, &B);
-    if (st == SG_OK) st = sg_postings_build(ctx, B, 0, &P);
-    if (st == SG_OK) st = sg_spgemm_topn(ctx, A, P, top_n, threshold, sort, &R);
-    if (st == SG_OK) st = sg_topn_to_host(ctx, R, out_cols, out_vals, out_counts);
-    sg_topn_free(R);
-    sg_postings_free(P);
-    if (!same) sg_csr_free(B);
-    sg_csr_free(A);
-    return st;
+    // the four handles, freed in reverse -- the result, the index, B (unless it is A), A -- whichever way the call ends
+    using CsrPtr = std::unique_ptr<sg_csr, int (*)(sg_csr *)>;
+    CsrPtr A(nullptr, sg_csr_free), B(nullptr, sg_csr_free);
+    std::unique_ptr<sg_postings, int (*)(sg_postings *)> P(nullptr, sg_postings_free);
+    TopnPtr R;
+    sg_csr *m = nullptr;
+    SG_TRY(sg_csr_from_host(ctx, n_left, n_cols, a_indptr, a_indices, a_data, dtype, &m));
+    A.reset(m);
+    if (!same) {
+        SG_TRY(sg_csr_from_host(ctx, n_right, n_cols, b_indptr, b_indices, b_data, dtype, &m));
+        B.reset(m);
+    }
+    sg_postings *p = nullptr;
+    SG_TRY(sg_postings_build(ctx, same ? A.get() : B.get(), 0, &p));
+    P.reset(p);
+    sg_topn *r = nullptr;
+    SG_TRY(sg_spgemm_topn(ctx, A.get(), P.get(), top_n, threshold, sort, &r));
+    R.reset(r);
+    return sg_topn_to_host(ctx, R.get(), out_cols, out_vals, out_counts);
 }
