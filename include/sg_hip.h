@@ -60,9 +60,9 @@ const char *sg_last_error(void);
 /* Bumped whenever a signature or a struct of this header changes (round 4: 2 -- row_step arguments of round 3, sg_stats
  * grew; round 5: 3 -- sg_stats.prune_scored; 4 -- sg_topn_transpose_select; 5 -- sg_csr_concat; 6 -- sg_csr_select_rows,
  * sg_topn_drop_columns, sg_device_upload; 7 -- sg_topn_concat_rows, sg_topn_forget, sg_topn_put_rows, sg_csr_take_rows,
- * sg_device_download); a
+ * sg_device_download; 8 -- sg_csr_row_norms, sg_csr_vectoriser_words, sg_csr_column_counts, sg_vec_reweigh); a
  * binding compares it with the value it was written for right after loading the library. */
-#define SG_ABI_VERSION 7
+#define SG_ABI_VERSION 8
 int sg_abi_version(void);
 int sg_device_count(int *count);
 /* hip_stream: a hipStream_t to launch on (e.g. torch.cuda.current_stream().cuda_stream), or NULL
@@ -146,8 +146,29 @@ int sg_vocab_set_idf(sg_ctx *ctx, sg_vocab *v, const void *idf, int32_t dtype);
 int sg_ctx_put_idf_table(sg_ctx *ctx, int64_t n_docs, int32_t dtype, const void *table);
 int sg_vocab_apply_idf_table(sg_ctx *ctx, sg_vocab *v, int32_t *applied);
 int sg_vocab_free(sg_vocab *v);
-/* TfidfVectorizer.transform(strings): counts -> *idf -> row L2 normalise, CSR with sorted indices. */
+/* TfidfVectorizer.transform(strings): counts -> *idf -> row L2 normalise, CSR with sorted indices.  The matrix also keeps,
+ * per row, the norm it was divided by (sg_csr_row_norms): with it the whole count behind an entry can be recovered, which is
+ * what sg_vec_reweigh needs. */
 int sg_vec_transform(sg_ctx *ctx, const sg_vocab *v, const sg_strings *strings, sg_csr **out);
+/* The idf refreshed from resident rows, no string read again: what TfidfVectorizer(vocabulary=<v's n-grams>, ...).fit(docs)
+ * .transform(docs) gives when m holds the rows of docs under v's CURRENT idf.  The caller counts the documents per column
+ * (sg_csr_column_counts of m: K2 names a column once per row), derives the idf from them with its own numpy (as for
+ * sg_vocab_set_idf, so that log() stays sklearn's) and hands both over: df_host and idf_host hold one entry per column of the
+ * vocabulary, n_docs is the number of rows behind them (rows without entries count, as sklearn counts them), dtype the type
+ * of idf_host.  *out is a NEW matrix that owns its arrays -- its own copy of row pointers and indices, made by the
+ * vectoriser, with row norms -- in which every entry is (count * idf_new[col]) / the row's new norm, rounded as
+ * sg_vec_transform rounds; m is only read (indexes borrow its arrays) and may be a row-block view.  On success df, n_docs and
+ * the idf of v are the new ones: sg_vocab_to_host reports them and later transforms weight with them.
+ * The count behind an entry is recovered as rint(v * norm / idf_old[col]) and CHECKED: made again from the count it must
+ * give the entry's bits.  One synchronisation (the number of entries that failed the check comes back).
+ * Refusals install nothing and leave v as it was:
+ *   SG_ERR_BADARG       m carries no row norms (it is no sg_vec_transform / sg_vec_reweigh matrix, nor a concatenation or row
+ *                       selection of such); m's columns are not v's; dtype is not v's and m's; an idf entry that is not
+ *                       positive and finite;
+ *   SG_ERR_UNSUPPORTED  an entry failed the check (m was made under another idf than v holds now): silently different
+ *                       numbers are never an outcome. */
+int sg_vec_reweigh(sg_ctx *ctx, sg_vocab *v, const sg_csr *m, const int32_t *df_host, int64_t n_docs, const void *idf_host,
+                   int32_t dtype, sg_csr **out);
 
 /* ------------------------------------------------------------------ CSR objects */
 int sg_csr_from_host(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, const int64_t *indptr,
@@ -161,6 +182,17 @@ int sg_csr_dims(const sg_csr *m, int64_t *n_rows, int64_t *n_cols, int64_t *nnz,
 int sg_csr_device_ptrs(const sg_csr *m, const int64_t **d_indptr, const int32_t **d_indices,
                        const void **d_data);
 int sg_csr_to_host(sg_ctx *ctx, const sg_csr *m, int64_t *indptr, int32_t *indices, void *data);
+/* *d_norms: DEVICE array of m's rows doubles, the norm each row was divided by when sg_vec_transform (or sg_vec_reweigh) made
+ * it, 0.0 for a row without entries; owned by m (a row-block view points into its parent's).  NULL when the matrix carries
+ * none: sg_csr_from_host / sg_csr_from_device matrices, a concatenation with such a part, sg_csr_take_rows' result. */
+int sg_csr_row_norms(const sg_csr *m, const double **d_norms);
+/* The three words the vectoriser may leave with a matrix (violations = 0, the largest squared row norm rounded up as float
+ * bits, the longest row) on the host; *present == 0: the matrix carries none (words = 0).  A synchronisation. */
+int sg_csr_vectoriser_words(sg_ctx *ctx, const sg_csr *m, uint32_t *words /* 3 */, int32_t *present);
+/* counts_host[c] = entries of m that name column c, for c in [0, n_cols): the number of rows that hold the column when no row
+ * names a column twice (what sg_vec_transform guarantees).  Any CSR, a row-block view and a caller-made matrix included
+ * (entries whose column lies outside [0, n_cols) are passed over).  One pass over the column indices, one synchronisation. */
+int sg_csr_column_counts(sg_ctx *ctx, const sg_csr *m, int32_t *counts_host /* n_cols */);
 /* Rows [r0, r1) as a view (no copy); the parent must outlive the view.  (A view derives its own groups of identical
  * rows when it is multiplied; it never shares the parent's.) */
 int sg_csr_row_block(sg_ctx *ctx, const sg_csr *m, int64_t r0, int64_t r1, sg_csr **out);
@@ -171,7 +203,8 @@ int sg_csr_row_block(sg_ctx *ctx, const sg_csr *m, int64_t r0, int64_t r1, sg_cs
  * freed once the call has returned and the context's stream has passed it (sg_csr_free after the call is safe: the pool
  * is stream-ordered).  One pass on the device, nothing is read back.  When every part was made by sg_vec_transform the
  * result counts as made by it too (cosine-like by construction: the pruned multiply needs no scan of it), and the words
- * the vectoriser left with the parts are merged.  More than INT32_MAX rows: SG_ERR_OVERFLOW. */
+ * the vectoriser left with the parts are merged; when every part carries row norms (sg_csr_row_norms) so does the result.
+ * More than INT32_MAX rows: SG_ERR_OVERFLOW. */
 int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_parts, sg_csr **out);
 /* m without the rows d_drop_sorted[0 .. n_drop) in a new matrix that owns its arrays: scipy's m[keep] with keep the
  * complement of the list (what a master list that forgets rows does to master_matrix on the host; the reference has no such
@@ -182,7 +215,8 @@ int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_parts, sg_c
  * sg_csr_concat's over the gaps: one pass at the width of that kernel however the dropped rows lie.  One synchronisation:
  * the number of kept entries comes back to size the result.  m is only read and may be freed after the call, as the parts
  * of sg_csr_concat.  A matrix made by sg_vec_transform stays one (cosine-like by construction); the words the vectoriser
- * left are carried over and are then UPPER bounds: the largest norm and the longest row may have been dropped. */
+ * left are carried over and are then UPPER bounds: the largest norm and the longest row may have been dropped.  The kept
+ * rows' norms (sg_csr_row_norms) are carried over as well. */
 int sg_csr_select_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d_drop_sorted, int64_t n_drop, sg_csr **out);
 /* The rows d_rows[0 .. n_rows) of m, in that order, in a new matrix that owns its arrays: scipy's m[rows] (what a caller who
  * has to multiply a few rows of master_matrix again does to it on the host; the reference has no such operation, it multiplies
@@ -191,7 +225,7 @@ int sg_csr_select_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d_drop_sorte
  * without entries; n_rows == 0 is a matrix without rows.  Every taken row is a part of sg_csr_concat's copy, which runs at its
  * usual width.  One synchronisation: the number of entries comes back to size the result.  m is only read and may be freed
  * after the call.  A matrix made by sg_vec_transform stays one, as in sg_csr_select_rows, and the words the vectoriser left
- * are carried over as UPPER bounds. */
+ * are carried over as UPPER bounds.  Row norms (sg_csr_row_norms) are NOT carried: the result has none. */
 int sg_csr_take_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d_rows, int64_t n_rows, sg_csr **out);
 int sg_csr_free(sg_csr *m);
 

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SG_HIP_LIB") or os.path.join(_HERE, "libsg_hip.so")
 
 SG_OK, SG_ERR_BADARG, SG_ERR_OOM, SG_ERR_OVERFLOW, SG_ERR_HIP, SG_ERR_NODEVICE, SG_ERR_UNSUPPORTED = range(7)
 SG_F32, SG_F64 = 0, 1
-ABI_VERSION = 7          # include/sg_hip.h: SG_ABI_VERSION
+ABI_VERSION = 8          # include/sg_hip.h: SG_ABI_VERSION
 SG_K_TOKENIZE, SG_K_WEIGHT, SG_K_POSTINGS, SG_K_SPGEMM, SG_K_ZIP, SG_K_VOCAB, SG_K_SPGEMM_KERNEL, SG_K_COUNT = range(8)
 KERNEL_NAMES = ("tokenize", "weight", "postings", "spgemm_topn", "zip", "vocab", "spgemm_kernel")
 
@@ -116,6 +116,10 @@ ABI = {
     "sg_topn_put_rows": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "sg_csr_take_rows": (C.c_int, [_P, _P, _P, C.c_int64, _PP]),
     "sg_csr_rowwise_dot": (C.c_int, [_P, _P, _P, _P]),
+    "sg_csr_row_norms": (C.c_int, [_P, _PP]),
+    "sg_csr_vectoriser_words": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int32)]),
+    "sg_csr_column_counts": (C.c_int, [_P, _P, _P]),
+    "sg_vec_reweigh": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int32, _PP]),
     "sg_ctx_stats": (C.c_int, [_P, C.POINTER(SgStats)]),
 }
 
@@ -247,6 +251,34 @@ class Csr(_Handle):
         m = sp.csr_matrix((data[:nnz], indices[:nnz], indptr.astype(idx_dtype)), shape=(r, c))
         m.has_sorted_indices = True
         return m
+
+    def row_norms(self) -> Optional[np.ndarray]:
+        """The norm every row was divided by when the vectoriser made it (0.0: a row without entries), or None when the
+        matrix carries none (include/sg_hip.h: sg_csr_row_norms)."""
+        p = C.c_void_p()
+        check(lib().sg_csr_row_norms(self.h, C.byref(p)))
+        if not p.value:
+            return None
+        n = self.dims()[0]
+        out = np.zeros(max(n, 1), np.float64)
+        if n:
+            check(lib().sg_device_download(self.ctx.h, p, n * 8, _ptr(out)))
+        return out[:n]
+
+    def vectoriser_words(self) -> Optional[tuple]:
+        """(violations, largest squared row norm rounded up, longest row) as the vectoriser left them, or None."""
+        words, present = np.zeros(3, np.uint32), C.c_int32()
+        check(lib().sg_csr_vectoriser_words(self.ctx.h, self.h, _ptr(words), C.byref(present)))
+        if not present.value:
+            return None
+        return int(words[0]), float(words[1:2].view(np.float32)[0]), int(words[2])
+
+    def column_counts(self) -> np.ndarray:
+        """Entries per column: the document count of every column for a matrix of the vectoriser (sg_csr_column_counts)."""
+        n_cols = self.dims()[1]
+        out = np.zeros(max(n_cols, 1), np.int32)
+        check(lib().sg_csr_column_counts(self.ctx.h, self.h, _ptr(out)))
+        return out[:n_cols]
 
     def row_block(self, r0: int, r1: int) -> "Csr":
         out = C.c_void_p()
@@ -520,6 +552,19 @@ class Context:
     def vec_transform(self, v: Vocab, s: Strings) -> Csr:
         out = C.c_void_p()
         check(lib().sg_vec_transform(self.h, v.h, s.h, C.byref(out)))
+        return Csr(self, out)
+
+    def vec_reweigh(self, v: Vocab, m: Csr, df: np.ndarray, n_docs: int, idf: np.ndarray) -> Csr:
+        """The rows of ``m`` weighted with ``idf`` instead of the vocabulary's own, in a new matrix; ``df``, ``n_docs`` and
+        ``idf`` become the vocabulary's (include/sg_hip.h: sg_vec_reweigh).  A matrix made under another idf than the
+        vocabulary holds: NotImplementedError, and nothing has changed."""
+        df = np.ascontiguousarray(df, dtype=np.int32)
+        idf = np.ascontiguousarray(idf)
+        n_terms = self.vocab_size(v)[0]
+        if df.shape != (n_terms,) or idf.shape != (n_terms,):
+            raise ValueError(f"bad argument: df and idf must hold one entry for each of the vocabulary's {n_terms} columns")
+        out = C.c_void_p()
+        check(lib().sg_vec_reweigh(self.h, v.h, m.h, _ptr(df), int(n_docs), _ptr(idf), np_dtype_code(idf.dtype), C.byref(out)))
         return Csr(self, out)
 
     # ---- CSR

@@ -11,7 +11,9 @@ the fixed-corpus form:
 A corpus may grow: ``corpus.append(new_strings)`` puts new rows behind the last one, transformed with the SAME vocabulary and
 idf (nothing is refitted, no score between two old rows changes), ``corpus.master`` is then the longer Series.  And it may
 forget: ``corpus.remove(rows)`` takes rows out, ``corpus.master`` is then the shorter Series and row numbers count through
-it; vocabulary and idf stay what the original list gave.
+it; vocabulary and idf stay what the original list gave -- until ``corpus.refit_idf()``, which makes the idf follow the
+CURRENT list on the device without reading a string again (the vocabulary is still the original's; only a new ``Corpus`` learns
+new n-grams).
 
 A service that asks after every change which group each record belongs to now -- ``corpus.group_similar_strings(corpus.master)``
 -- may have the corpus keep that self-join on the device: ``corpus.keep_self_join()``.  ``append`` and ``remove`` then edit the
@@ -216,7 +218,8 @@ class Corpus:
         never had are dropped; a string with none it knows is an empty row that still matches itself in a self-join), and
         every result afterwards is what ``TfidfVectorizer.fit(original master).transform(all strings)`` gives, row numbers
         counting through the concatenated list.  The idf therefore drifts from what a refit on the grown list would give;
-        ``Corpus(corpus.master, corpus.master_id)`` is the refit.  The cost follows the batch, not the corpus: the new rows
+        ``refit_idf()`` brings the idf up to the current list (the vocabulary stays), ``Corpus(corpus.master,
+        corpus.master_id)`` is the whole refit, new n-grams included.  The cost follows the batch, not the corpus: the new rows
         wait in a second segment with an index of its own, which is folded into the first once it exceeds
         ``engine.HipEngine.CORPUS_COMPACT_SHARE`` of it (or by ``compact()``).  ``remove`` takes rows out again."""
         state = self._live()
@@ -273,7 +276,8 @@ class Corpus:
 
         The vocabulary and the idf do NOT change (nor the number of documents behind the idf): every result afterwards is
         what ``TfidfVectorizer.fit(original master).transform(remaining strings)`` gives, and an n-gram whose last row went
-        away keeps its column.  ``Corpus(corpus.master, corpus.master_id)`` is the refit.  On the device a removed row stays
+        away keeps its column.  ``refit_idf()`` brings the idf up to the remaining list, ``Corpus(corpus.master,
+        corpus.master_id)`` is the whole refit.  On the device a removed row stays
         where it is until the next compaction (more than ``engine.HipEngine.CORPUS_MAX_DEAD`` of them, an append's share
         rule, ``compact()``, or a call that needs all rows in one matrix); on the host the Series is copied without it,
         which costs what the list costs."""
@@ -303,6 +307,28 @@ class Corpus:
         self._same_engine()
         if hasattr(self._engine, "corpus_compact"):
             self._engine.corpus_compact(state)
+
+    # ------------------------------------------------------------------ an idf that follows the list
+    def refit_idf(self) -> None:
+        """Refit the idf on the CURRENT ``corpus.master``; the vocabulary stays the original list's.  Afterwards every result is,
+        bit for bit, what sklearn's vectoriser gives when it is fitted on the current list with
+        ``vocabulary=corpus.vectorizer.vocabulary_``: the document count is the number of rows now in the corpus (a string with
+        no known n-gram counts, as sklearn counts it), a column's document frequency is the number of those rows that hold
+        it, a column whose last row was removed keeps its place with frequency 0 and a finite idf that no row uses, and an
+        n-gram the original list never had is still dropped -- ``Corpus(corpus.master, corpus.master_id)`` remains the only way
+        to a new vocabulary.  Batches transformed afterwards are weighted with the new idf; ``corpus.vectorizer.idf_`` reports
+        it.
+
+        No string is read again (``stats['tokenisations']`` stays 1, ``stats['idf_refits']`` counts the calls): the rows on the
+        device are counted by column and weighted anew from the whole counts they were made of.  Removed
+        rows still pending are dropped first (a compaction).  A kept self-join (``keep_self_join``) is dropped and multiplied
+        anew when next needed -- every score has changed -- with its options kept.  On a corpus that was never appended to
+        nor removed from, nothing changes, to the bit."""
+        state = self._live()
+        self._same_engine()
+        if not hasattr(self._engine, "corpus_refit_idf"):
+            raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} refits no idf")
+        self._engine.corpus_refit_idf(state)
 
     # ------------------------------------------------------------------ a self-join that is kept
     def keep_self_join(self, **kwargs) -> None:
@@ -358,7 +384,7 @@ class Corpus:
         that still lie in the segments, until the next compaction); for a kept self-join (``keep_self_join``)
         ``self_join_full`` (whole multiplies made for it), ``self_join_served`` (calls answered from it),
         ``self_join_append_updates`` / ``self_join_remove_updates`` (changes it followed without a whole multiply) and
-        ``self_join_rows_refilled`` (rows a remove had to multiply again)."""
+        ``self_join_rows_refilled`` (rows a remove had to multiply again); ``idf_refits`` (calls of ``refit_idf``)."""
         return dict(self._live().stats)
 
     def _rows_of(self, series, made):

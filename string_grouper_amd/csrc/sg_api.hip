@@ -430,6 +430,23 @@ extern "C" int sg_csr_device_ptrs(const sg_csr *m, const int64_t **d_indptr, con
     return SG_OK;
 }
 
+extern "C" int sg_csr_row_norms(const sg_csr *m, const double **d_norms) {
+    SG_REQUIRE(m && d_norms, "null argument");
+    *d_norms = m->d_row_norm;
+    return SG_OK;
+}
+
+extern "C" int sg_csr_vectoriser_words(sg_ctx *ctx, const sg_csr *m, uint32_t *words, int32_t *present) {
+    SG_REQUIRE(ctx && m && words && present, "null argument");
+    *present = m->d_props_words != nullptr;
+    words[0] = words[1] = words[2] = 0;
+    if (m->d_props_words) {
+        SG_TRY(sg_fetch(ctx, ctx->h_fetch, m->d_props_words, 12));
+        memcpy(words, ctx->h_fetch, 12);
+    }
+    return SG_OK;
+}
+
 extern "C" int sg_csr_to_host(sg_ctx *ctx, const sg_csr *m, int64_t *indptr, int32_t *indices, void *data) {
     SG_REQUIRE(ctx && m && indptr, "null argument");
     SG_HIP_TRY(hipMemcpyAsync(indptr, m->d_indptr, sizeof(int64_t) * (size_t)(m->n_rows + 1), hipMemcpyDeviceToHost,
@@ -464,6 +481,7 @@ extern "C" int sg_csr_row_block(sg_ctx *ctx, const sg_csr *m, int64_t r0, int64_
     v->left_state = 0;
     v->n_rows = r1 - r0;
     v->d_indptr = m->d_indptr + r0;
+    if (m->d_row_norm) v->d_row_norm = m->d_row_norm + r0;   // (the parent's array: a view frees nothing)
     int64_t ends[2] = {0, 0};
     SG_HIP_TRY(hipMemcpyAsync(&ends[0], m->d_indptr + r0, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     SG_HIP_TRY(hipMemcpyAsync(&ends[1], m->d_indptr + r1, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -481,6 +499,7 @@ extern "C" int sg_csr_free(sg_csr *m) {
         m->ctx->release((void *)m->d_indices);
         m->ctx->release((void *)m->d_data);
         m->ctx->release(m->d_props_words);
+        m->ctx->release(m->d_row_norm);
     }
     delete m;
     return SG_OK;

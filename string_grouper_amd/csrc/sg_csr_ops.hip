@@ -32,6 +32,11 @@
 //                            taken row -- its row pointer, its place k and the entries before it (the same scan, over the rows'
 //                            sizes) -- and the total, the only thing read back;
 //   csr_select_kernel        as above.
+//
+// The norms K2 divided the rows by (sg_csr::d_row_norm) travel with the rows BESIDE these kernels, which stay as they are: a
+// concatenation copies every part's array device to device on the context's stream (a row-block view's pointer is the parent's,
+// shifted by the view's first row), sg_csr_select_rows gathers them past the dropped rows with one small kernel over the gaps'
+// descriptors (gather_row_norms_kernel).  A result carries norms only when every source row had one; sg_csr_take_rows' never does.
 #include "sg_internal.h"
 
 #include <memory>
@@ -278,6 +283,20 @@ __global__ void __launch_bounds__(CONCAT_BLOCK) csr_select_kernel(const ConcatPa
     }
 }
 
+// The kept rows' norms: output row r lies in gap p, whose descriptor holds the source's row pointers from the gap's first row on
+// -- so the row's place in the source is that pointer's distance from the source's, plus r's place in the gap.
+__global__ void __launch_bounds__(CONCAT_BLOCK) gather_row_norms_kernel(const ConcatPart *__restrict__ parts, int n_parts,
+                                                                        const int64_t *__restrict__ src_indptr,
+                                                                        const double *__restrict__ src_norm,
+                                                                        double *__restrict__ out_norm) {
+    const int64_t n_rows = parts[n_parts].row_off;
+    const int64_t step = (int64_t)gridDim.x * CONCAT_BLOCK;
+    for (int64_t r = (int64_t)blockIdx.x * CONCAT_BLOCK + threadIdx.x; r < n_rows; r += step) {
+        const int p = part_of<true>(parts, n_parts, r);
+        out_norm[r] = src_norm[(parts[p].indptr - src_indptr) + (r - parts[p].row_off)];
+    }
+}
+
 struct CsrDeleter {
     void operator()(sg_csr *m) const { sg_csr_free(m); }
 };
@@ -287,7 +306,7 @@ struct CsrDeleter {
 extern "C" int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_parts, sg_csr **out) {
     SG_REQUIRE(ctx && parts && out && n_parts >= 1, "null argument or no parts");
     int64_t n_rows = 0, nnz = 0;
-    bool all_vec = true, all_words = true;
+    bool all_vec = true, all_words = true, all_norms = true;
     for (int p = 0; p < n_parts; ++p) {
         SG_REQUIRE(parts[p] != nullptr, "a part is null");
         SG_REQUIRE(parts[p]->n_cols == parts[0]->n_cols && parts[p]->dtype == parts[0]->dtype,
@@ -298,6 +317,7 @@ extern "C" int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_
         nnz += parts[p]->nnz;
         all_vec = all_vec && parts[p]->from_vectoriser;
         all_words = all_words && parts[p]->d_props_words != nullptr;
+        all_norms = all_norms && parts[p]->d_row_norm != nullptr;
     }
     if (n_rows > INT32_MAX) {
         sg_set_error("sg_csr_concat: %lld rows exceed int32 indices", (long long)n_rows);
@@ -324,6 +344,7 @@ extern "C" int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_
     SG_TRY(ctx->alloc(((size_t)nnz + 4) * s, &dd));
     m->d_data = dd;
     if (all_vec && all_words) SG_TRY(sg_alloc(ctx, (size_t)4, &m->d_props_words));
+    if (all_norms) SG_TRY(sg_alloc(ctx, (size_t)n_rows + 1, &m->d_row_norm));
 
     std::vector<ConcatPart> desc((size_t)n_parts + 1);
     int64_t row_off = 0, nnz_off = 0;
@@ -350,6 +371,15 @@ extern "C" int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_
     });
     scratch.release(d_desc);       // (stream-ordered pool: a later taker of the block runs behind the kernel)
     SG_HIP_TRY(hipGetLastError());
+    if (all_norms) {               // the rows' norms, part by part (a view's pointer starts at its first row)
+        int64_t at = 0;
+        for (int p = 0; p < n_parts; ++p) {
+            if (parts[p]->n_rows > 0)
+                SG_HIP_TRY(hipMemcpyAsync(m->d_row_norm + at, parts[p]->d_row_norm, sizeof(double) * (size_t)parts[p]->n_rows,
+                                          hipMemcpyDeviceToDevice, ctx->stream));
+            at += parts[p]->n_rows;
+        }
+    }
     *out = m.release();
     return SG_OK;
 }
@@ -411,6 +441,16 @@ extern "C" int sg_csr_select_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d
     SG_TRY(by_dtype(m->dtype, [&](auto t) {
         return select_rows<decltype(t)>(ctx, m, d_desc, n_gaps, r->n_rows, r->nnz, r.get());
     }));
+    if (m->d_row_norm) {           // the kept rows' norms, gathered past the dropped rows
+        SG_TRY(sg_alloc(ctx, (size_t)r->n_rows + 1, &r->d_row_norm));
+        if (r->n_rows > 0) {
+            const int64_t want = (r->n_rows + CONCAT_BLOCK - 1) / CONCAT_BLOCK;
+            hipLaunchKernelGGL(gather_row_norms_kernel, dim3((unsigned)std::min<int64_t>(want, (int64_t)ctx->num_cu * 32)),
+                               dim3(CONCAT_BLOCK), 0, ctx->stream, (const ConcatPart *)d_desc, (int)n_gaps, m->d_indptr,
+                               (const double *)m->d_row_norm, r->d_row_norm);
+            SG_HIP_TRY(hipGetLastError());
+        }
+    }
     scratch.release(d_info);       // (the totals' block goes back first, then the descriptors': the pool's order of old)
     *out = r.release();
     return SG_OK;

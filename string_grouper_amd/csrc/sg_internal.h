@@ -220,6 +220,11 @@ struct sg_csr {
     // a matrix made by the vectoriser is cosine-like by construction; K2 leaves [0] violations (= 0), [1] max ||row||^2 as
     // float bits, [2] longest row here and sg_csr_props reads them instead of scanning the matrix again (owned)
     uint32_t *d_props_words = nullptr;
+    // ||row|| as K2 divided by it, one double per row (0.0: the row got no entry): with it the integer count behind an entry
+    // is tf = rint(v * norm / idf[col]), which is what sg_vec_reweigh needs to weight the rows with another idf.  Only
+    // matrices made by sg_vec_transform / sg_vec_reweigh carry it, and what sg_csr_concat and sg_csr_select_rows make of
+    // them (owned; a row-block view holds the parent's pointer shifted by its first row); null otherwise.
+    double *d_row_norm = nullptr;
     // groups of identical rows of a LEFT matrix (sg_spgemm_topn, one-sided products: round 4), made on first use and kept
     // for the multiplies that follow with the same matrix (column blocks of the right-hand side): 0 not looked at yet,
     // 1 looked at and not worth it / not possible, 2 `left_groups` holds them (owned, also by views)

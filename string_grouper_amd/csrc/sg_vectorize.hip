@@ -24,7 +24,10 @@
 // exclusive scan over (df > 0).
 // K2: a thread per row: col = rank[key], w = (T)tf * idf[col] (one rounding), acc(double) += (T)(w*w)
 // sequentially in column order, w = (T)((double)w / sqrt(acc)); rows with acc == 0 are left alone.
-// This op order reproduces sklearn bit for bit (tests/test_parity_gpu.py).
+// This op order reproduces sklearn bit for bit (tests/test_parity_gpu.py).  The norm sqrt(acc) stays with the row
+// (sg_csr::d_row_norm): from it, the entry and the idf the whole count tf is recovered when the idf of a resident matrix is
+// refreshed without its strings -- sg_csr_column_counts (the df of the rows that are there) and sg_vec_reweigh (K2's second
+// half again, fed by the matrix), at the end of this file.
 //
 // Domain (round 2).  Strings of any length: one wave sorts up to 1024 n-grams in LDS, longer strings go to a
 // workgroup-per-string kernel with its keys in global scratch.  Keys of up to 30 bits index a dense table (3-grams over
@@ -741,7 +744,8 @@ __global__ void __launch_bounds__(256) weight_normalize_kernel(const int64_t *__
                                                                const T *__restrict__ idf, int64_t n,
                                                                const int64_t *__restrict__ indptr,
                                                                int32_t *__restrict__ out_idx, T *__restrict__ out_val,
-                                                               uint32_t *props /* [1] max ||row||^2 (float bits) [2] longest row */) {
+                                                               uint32_t *props /* [1] max ||row||^2 (float bits) [2] longest row */,
+                                                               double *__restrict__ row_norm /* the norm each row is divided by */) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     float n2 = 0.f;
     uint32_t len = 0;
@@ -761,8 +765,9 @@ __global__ void __launch_bounds__(256) weight_normalize_kernel(const int64_t *__
             ++o;
         }
         len = (uint32_t)(o - o0);
+        const double nrm = acc != 0.0 ? __dsqrt_rn(acc) : 0.0;
+        if (row_norm) row_norm[i] = nrm;   // (0.0: the row got no entry)
         if (acc != 0.0) {
-            const double nrm = __dsqrt_rn(acc);
             double s2 = 0.0;   // norm^2 of the row as stored (what sg_csr_props would compute by scanning the matrix)
             for (int64_t q = o0; q < o; ++q) {
                 const T v = (T)__ddiv_rn((double)out_val[q], nrm);
@@ -816,7 +821,7 @@ __global__ void __launch_bounds__(256) weight_normalize_rows16_kernel(const int6
                                                                       const T *__restrict__ idf, int64_t n,
                                                                       const int64_t *__restrict__ indptr,
                                                                       int32_t *__restrict__ out_idx, T *__restrict__ out_val,
-                                                                      uint32_t *props) {
+                                                                      uint32_t *props, double *__restrict__ row_norm) {
     const int lane = threadIdx.x & 63, sub = lane & 15, grp_shift = lane & 48;
     const int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const bool valid = row < n;
@@ -855,8 +860,10 @@ __global__ void __launch_bounds__(256) weight_normalize_rows16_kernel(const int6
     }
     float n2 = 0.f;
     uint32_t len = 0;
+    const double nrm = carry != 0.0 ? __dsqrt_rn(carry) : 0.0;
+    // the norm stays with the row (sg_csr::d_row_norm): one 8-byte store a row, 0.0 for a row that gets no entry
+    if (valid && sub == 0 && row_norm) row_norm[row] = nrm;
     if (carry != 0.0) {
-        const double nrm = __dsqrt_rn(carry);
         double s2 = 0.0;
         int kept_before = 0;
         for (int base = 0; base < cmax; base += 16) {
@@ -894,6 +901,164 @@ __global__ void __launch_bounds__(256) weight_normalize_rows16_kernel(const int6
     }
     // one counter takes ~12 ns per atomic whoever sends it: look first (a stale value is lower, never higher)
     if (lane == 0 && props) {
+        const volatile uint32_t *seen = props;
+        if (nb > seen[1]) atomicMax(props + 1, nb);
+        if (len > seen[2]) atomicMax(props + 2, len);
+    }
+}
+
+// ---- sg_vec_reweigh / sg_csr_column_counts: the idf of a resident matrix refreshed without its strings
+// How many entries of a CSR name each column: a flat pass over indices[indptr[0] .. indptr[n]) -- no row structure -- in
+// df_count_lds_kernel's idiom: an LDS histogram over [col0, col0 + n_cols), at most one workgroup per CU, one row of `partial`
+// per workgroup, summed by df_sum_kernel.  The range is cut where its ADDRESS is 16-byte aligned (the first entry of a
+// row-block view is not): workgroup 0 takes the up to three entries of the head and of the tail one by one, the body between
+// them is dealt to the workgroups in contiguous runs of 16-byte units.
+__global__ void __launch_bounds__(1024) column_count_lds_kernel(const int64_t *__restrict__ indptr, int64_t n_rows,
+                                                                const int32_t *__restrict__ indices, int32_t col0,
+                                                                int32_t n_cols, int64_t n_terms,
+                                                                uint32_t *__restrict__ partial) {
+    extern __shared__ uint32_t df_hist[];
+    for (int k = threadIdx.x; k < n_cols; k += blockDim.x) df_hist[k] = 0;
+    __syncthreads();
+    const int32_t *p = indices + indptr[0];
+    const int64_t total = indptr[n_rows] - indptr[0];
+    int64_t head = (int64_t)((0u - (uint32_t)((uintptr_t)p >> 2)) & 3u);   // entries in front of the first aligned unit
+    if (head > total) head = total;
+    const int64_t units = (total - head) >> 2;
+    const int64_t tail0 = head + units * 4;
+    const int4 *body = reinterpret_cast<const int4 *>(p + head);
+    const int64_t per_wg = (units + gridDim.x - 1) / gridDim.x;
+    const int64_t u0 = (int64_t)blockIdx.x * per_wg;
+    int64_t u1 = u0 + per_wg;
+    if (u1 > units) u1 = units;
+    const uint32_t nc = (uint32_t)n_cols;
+    for (int64_t u = u0 + threadIdx.x; u < u1; u += blockDim.x) {
+        const int4 c = body[u];
+        const uint32_t c0 = (uint32_t)(c.x - col0), c1 = (uint32_t)(c.y - col0), c2 = (uint32_t)(c.z - col0),
+                       c3 = (uint32_t)(c.w - col0);
+        if (c0 < nc) atomicAdd(&df_hist[c0], 1u);
+        if (c1 < nc) atomicAdd(&df_hist[c1], 1u);
+        if (c2 < nc) atomicAdd(&df_hist[c2], 1u);
+        if (c3 < nc) atomicAdd(&df_hist[c3], 1u);
+    }
+    if (blockIdx.x == 0) {
+        const int64_t e = (int64_t)threadIdx.x < head ? (int64_t)threadIdx.x : tail0 + ((int64_t)threadIdx.x - head);
+        if (e < total) {                       // (head + the tail's entries: six at the most)
+            const uint32_t c = (uint32_t)(p[e] - col0);
+            if (c < nc) atomicAdd(&df_hist[c], 1u);
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < n_cols; k += blockDim.x) partial[(int64_t)blockIdx.x * n_terms + col0 + k] = df_hist[k];
+}
+
+// The rows of a matrix K2 made, weighted with another idf: K2's shape (sixteen lanes a row, four rows a wave, the sum of
+// squares down the row_shr:1 chain in column order, the first 32 entries kept in registers between the passes), fed by the
+// matrix itself instead of the tokens.  An entry is v = (T)((double)((T)tf * idf_old[col]) / nrm_old), so the count behind it is
+// tf = rint(v * nrm_old / idf_old[col]): three roundings of 2^-24 (fp32) each on a whole number far below 2^21 (DESIGN.md
+// section 9).  The recovery is CHECKED all the same: the entry is made again from tf the way K2 made it and must give v's bits;
+// an entry that does not is counted in *mismatch (one atomic per such entry, none otherwise) and the host refuses the result.
+template <typename T>
+struct ReweighEntry {
+    int32_t col;
+    T w;         // (T)tf * idf_new[col]
+    bool bad;    // the entry is not what K2 makes of a whole count under idf_old and nrm_old
+};
+template <typename T>
+__device__ __forceinline__ ReweighEntry<T> reweigh_entry(int32_t col, T v, double nrm_old, const T *__restrict__ idf_old,
+                                                         const T *__restrict__ idf_new) {
+    const T io = idf_old[col];
+    const T tf = (T)rint(__ddiv_rn(__dmul_rn((double)v, nrm_old), (double)io));
+    const T again = (T)__ddiv_rn((double)tmul<T>(tf, io), nrm_old);
+    bool same;
+    if (sizeof(T) == 4) same = __float_as_uint((float)again) == __float_as_uint((float)v);
+    else same = __double_as_longlong((double)again) == __double_as_longlong((double)v);
+    return ReweighEntry<T>{col, tmul<T>(tf, idf_new[col]), !same};
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) reweigh_rows16_kernel(const int64_t *__restrict__ indptr,
+                                                             const int32_t *__restrict__ in_idx, const T *__restrict__ in_val,
+                                                             const double *__restrict__ in_norm, const T *__restrict__ idf_old,
+                                                             const T *__restrict__ idf_new, int64_t n,
+                                                             int64_t *__restrict__ out_indptr, int32_t *__restrict__ out_idx,
+                                                             T *__restrict__ out_val, double *__restrict__ out_norm,
+                                                             uint32_t *props, uint32_t *mismatch) {
+    const int lane = threadIdx.x & 63, sub = lane & 15;
+    const int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const bool valid = row < n;
+    const int64_t first = indptr[0];            // (a row-block view holds absolute offsets: the new matrix starts at 0)
+    const int64_t b = valid ? indptr[row] : first;
+    const int c = valid ? (int)(indptr[row + 1] - b) : 0;
+    const int64_t o0 = b - first;
+    const double nrm_old = valid ? in_norm[row] : 0.0;
+    if (valid && sub == 0) {
+        out_indptr[row] = o0;
+        if (row == n - 1) out_indptr[n] = o0 + c;
+    }
+    int cmax = c;   // the wave walks its four rows together
+    cmax = max(cmax, __shfl_xor(cmax, 16, 64));
+    cmax = max(cmax, __shfl_xor(cmax, 32, 64));
+    double carry = 0.0;
+    int32_t col_keep[2] = {-1, -1};
+    T w_keep[2] = {(T)0, (T)0};
+    for (int base = 0; base < cmax; base += 16) {
+        const int q = base + sub;
+        double w2 = 0.0;
+        if (q < c) {
+            const ReweighEntry<T> e = reweigh_entry<T>(in_idx[b + q], in_val[b + q], nrm_old, idf_old, idf_new);
+            if (e.bad) atomicAdd(mismatch, 1u);
+            w2 = (double)tmul<T>(e.w, e.w);
+            if (base == 0) {
+                col_keep[0] = e.col;
+                w_keep[0] = e.w;
+            } else if (base == 16) {
+                col_keep[1] = e.col;
+                w_keep[1] = e.w;
+            }
+        }
+        double acc = w2;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) acc = __dadd_rn(dpp_from_lower_lane(acc, carry), w2);
+        carry = shfl_double(acc, lane | 15);
+    }
+    float n2 = 0.f;
+    uint32_t len = 0;
+    const double nrm = carry != 0.0 ? __dsqrt_rn(carry) : 0.0;
+    if (valid && sub == 0) out_norm[row] = nrm;
+    if (carry != 0.0) {
+        double s2 = 0.0;
+        for (int base = 0; base < cmax; base += 16) {
+            const int q = base + sub;
+            if (q >= c) continue;
+            int32_t col;
+            T w;
+            if (base < 32) {          // (kept by the first pass)
+                col = base == 0 ? col_keep[0] : col_keep[1];
+                w = base == 0 ? w_keep[0] : w_keep[1];
+            } else {
+                const ReweighEntry<T> e = reweigh_entry<T>(in_idx[b + q], in_val[b + q], nrm_old, idf_old, idf_new);
+                col = e.col;
+                w = e.w;
+            }
+            const T v = (T)__ddiv_rn((double)w, nrm);
+            out_idx[o0 + q] = col;
+            out_val[o0 + q] = v;
+            s2 += (double)v * (double)v;
+        }
+        len = (uint32_t)c;
+#pragma unroll
+        for (int d = 8; d > 0; d >>= 1) s2 += shfl_double(s2, lane ^ d);
+        // an upper bound of the norm^2 of the row as stored, whatever the order of the additions
+        n2 = __double2float_ru(s2 * (1.0 + 1e-12));
+    }
+    uint32_t nb = __float_as_uint(n2);   // non-negative floats order like unsigned integers
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        nb = max(nb, (uint32_t)__shfl_xor((int)nb, d, 64));
+        len = max(len, (uint32_t)__shfl_xor((int)len, d, 64));
+    }
+    if (lane == 0) {
         const volatile uint32_t *seen = props;
         if (nb > seen[1]) atomicMax(props + 1, nb);
         if (len > seen[2]) atomicMax(props + 2, len);
@@ -1582,12 +1747,12 @@ static int launch_weight(sg_ctx *ctx, const TokenCache &tc, Lookup lookup, const
             hipLaunchKernelGGL((weight_normalize_kernel<T, KeyT, Lookup>), dim3((unsigned)((m->n_rows + 255) / 256)), dim3(256), 0,
                                ctx->stream, (const int64_t *)tc.d_ub_ptr, (const int32_t *)tc.d_cnt, (const KeyT *)tc.d_keys,
                                (const int32_t *)tc.d_tf, lookup, (const T *)v->d_idf, m->n_rows, m->d_indptr,
-                               (int32_t *)m->d_indices, (T *)m->d_data, m->d_props_words);
+                               (int32_t *)m->d_indices, (T *)m->d_data, m->d_props_words, m->d_row_norm);
         else
             hipLaunchKernelGGL((weight_normalize_rows16_kernel<T, KeyT, Lookup>), dim3((unsigned)((m->n_rows + 15) / 16)), dim3(256),
                                0, ctx->stream, (const int64_t *)tc.d_ub_ptr, (const int32_t *)tc.d_cnt, (const KeyT *)tc.d_keys,
                                (const int32_t *)tc.d_tf, lookup, (const T *)v->d_idf, m->n_rows, m->d_indptr,
-                               (int32_t *)m->d_indices, (T *)m->d_data, m->d_props_words);
+                               (int32_t *)m->d_indices, (T *)m->d_data, m->d_props_words, m->d_row_norm);
         return hipGetLastError() == hipSuccess ? SG_OK : SG_ERR_HIP;
     });
 }
@@ -1678,6 +1843,8 @@ extern "C" int sg_vec_transform(sg_ctx *ctx, const sg_vocab *v, const sg_strings
         SG_TRY(sg_alloc(ctx, (size_t)4, &m->d_props_words));
         if (hipMemsetAsync(m->d_props_words, 0, 16, ctx->stream) != hipSuccess) return SG_ERR_HIP;
     }
+    // the norm K2 divides each row by stays with the matrix: what sg_vec_reweigh recovers the counts with
+    SG_TRY(sg_alloc(ctx, (size_t)m->n_rows + 1, &m->d_row_norm));
     if (m->n_rows > 0) {
         if (v->sorted_mode)
             SG_TRY(launch_weight<uint64_t>(ctx, tc, SortedLookup{v->d_keys, v->n_terms}, v, m.get()));
@@ -1687,5 +1854,107 @@ extern "C" int sg_vec_transform(sg_ctx *ctx, const sg_vocab *v, const sg_strings
             SG_TRY(launch_weight<uint32_t>(ctx, tc, DenseLookup{v->d_key_to_col}, v, m.get()));
     }
     *out = m.release();
+    return SG_OK;
+}
+
+// ---- the idf refreshed from a resident matrix ("An idf that follows the list")
+// counts[col] = entries of m that name col, on the device: LDS histograms of at most 30 * 1024 counters a pass, summed and
+// WRITTEN by df_sum_kernel (count_df_by_column's idiom)
+static int column_counts_device(sg_ctx *ctx, const sg_csr *m, int32_t *d_counts) {
+    const int32_t max_cols = 30 * 1024;   // 120 KiB of LDS counters per pass over the entries
+    SG_TRY(allow_dynamic_lds<column_count_lds_kernel>((size_t)max_cols * 4));
+    int64_t g = (m->nnz + 16383) / 16384;   // >= 16 entries per thread, at most one workgroup per CU
+    g = std::max<int64_t>(1, std::min<int64_t>(g, ctx->num_cu));
+    Scratch tmp(ctx);
+    uint32_t *partial = nullptr;
+    SG_TRY(tmp.alloc((size_t)(g * m->n_cols), &partial));
+    for (int64_t col0 = 0; col0 < m->n_cols; col0 += max_cols) {
+        const int32_t n_cols = (int32_t)std::min<int64_t>(m->n_cols - col0, max_cols);
+        hipLaunchKernelGGL(column_count_lds_kernel, dim3((unsigned)g), dim3(1024), (size_t)n_cols * 4, ctx->stream, m->d_indptr,
+                           m->n_rows, m->d_indices, (int32_t)col0, n_cols, m->n_cols, partial);
+    }
+    hipLaunchKernelGGL(df_sum_kernel, dim3((unsigned)((m->n_cols + 63) / 64)), dim3(256), 0, ctx->stream, (const uint32_t *)partial,
+                       (int32_t)g, m->n_cols, d_counts);
+    SG_HIP_TRY(hipGetLastError());
+    return SG_OK;
+}
+
+extern "C" int sg_csr_column_counts(sg_ctx *ctx, const sg_csr *m, int32_t *counts_host) {
+    SG_REQUIRE(ctx && m, "null argument");
+    if (m->n_cols == 0) return SG_OK;
+    SG_REQUIRE(counts_host != nullptr, "the counts' array is null");
+    if (m->rows_of) SG_TRY(sg_csr_ensure_rows(ctx, m));
+    Scratch tmp(ctx);
+    int32_t *d_counts = nullptr;
+    SG_TRY(tmp.alloc((size_t)m->n_cols, &d_counts));
+    SG_TRY(column_counts_device(ctx, m, d_counts));
+    return sg_fetch(ctx, counts_host, d_counts, sizeof(int32_t) * (size_t)m->n_cols);
+}
+
+extern "C" int sg_vec_reweigh(sg_ctx *ctx, sg_vocab *v, const sg_csr *m, const int32_t *df_host, int64_t n_docs,
+                              const void *idf_host, int32_t dtype, sg_csr **out) {
+    SG_REQUIRE(ctx && v && m && df_host && idf_host && out, "null argument");
+    SG_REQUIRE(v->d_idf != nullptr && v->d_df != nullptr, "the vocabulary has no idf yet (sg_vocab_set_idf)");
+    SG_REQUIRE(m->d_row_norm != nullptr, "the matrix carries no row norms: only what sg_vec_transform made can be weighted anew");
+    SG_REQUIRE(m->n_cols == v->n_terms, "the matrix's columns are not the vocabulary's");
+    SG_REQUIRE(dtype == v->params.dtype && dtype == m->dtype, "dtype differs from the vectoriser's or the matrix's");
+    SG_REQUIRE(n_docs >= 0, "negative number of documents");
+    SG_REQUIRE(weights_positive_and_finite(idf_host, v->n_terms, dtype), "an idf that is not positive and finite");
+    const size_t s = dtype == SG_F64 ? 8 : 4;
+    CsrPtr r(new (std::nothrow) sg_csr());
+    if (!r) return SG_ERR_OOM;
+    r->ctx = ctx;
+    r->n_rows = m->n_rows;
+    r->n_cols = m->n_cols;
+    r->nnz = m->nnz;
+    r->dtype = dtype;
+    r->owned = true;
+    r->from_vectoriser = true;               // (counts times positive weights, every row divided by its norm)
+    int64_t *dp = nullptr;
+    int32_t *di = nullptr;
+    void *dd = nullptr;
+    SG_TRY(sg_alloc(ctx, (size_t)r->n_rows + 1, &dp));
+    r->d_indptr = dp;
+    SG_TRY(sg_alloc(ctx, (size_t)r->nnz + 4, &di));
+    r->d_indices = di;
+    SG_TRY(ctx->alloc(((size_t)r->nnz + 4) * s, &dd));
+    r->d_data = dd;
+    SG_TRY(sg_alloc(ctx, (size_t)r->n_rows + 1, &r->d_row_norm));
+    SG_TRY(sg_alloc(ctx, (size_t)4, &r->d_props_words));
+    Scratch tmp(ctx);
+    void *d_idf_new = nullptr;
+    uint32_t *d_mismatch = nullptr;
+    SG_TRY(tmp.alloc_bytes(((size_t)v->n_terms + 1) * s, &d_idf_new));
+    SG_TRY(tmp.alloc((size_t)4, &d_mismatch));
+    SG_TRY(SG_ZERO2(ctx, r->d_props_words, 16, d_mismatch, 16));
+    SG_HIP_TRY(hipMemcpyAsync(d_idf_new, idf_host, s * (size_t)v->n_terms, hipMemcpyHostToDevice, ctx->stream));
+    if (r->n_rows == 0) {
+        SG_HIP_TRY(hipMemsetAsync(dp, 0, sizeof(int64_t), ctx->stream));
+    } else {
+        SgTimer timer(ctx, SG_K_WEIGHT);
+        SG_TRY(by_dtype(dtype, [&](auto tag) -> int {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(reweigh_rows16_kernel<T>, dim3((unsigned)((r->n_rows + 15) / 16)), dim3(256), 0, ctx->stream,
+                               m->d_indptr, m->d_indices, (const T *)m->d_data, (const double *)m->d_row_norm,
+                               (const T *)v->d_idf, (const T *)d_idf_new, r->n_rows, dp, di, (T *)dd, r->d_row_norm,
+                               r->d_props_words, d_mismatch);
+            SG_HIP_TRY(hipGetLastError());
+            return SG_OK;
+        }));
+    }
+    uint32_t mismatch = 0;
+    SG_TRY(sg_fetch(ctx, ctx->h_fetch, d_mismatch, sizeof(uint32_t)));
+    memcpy(&mismatch, ctx->h_fetch, sizeof(uint32_t));
+    if (mismatch != 0) {                      // nothing is installed: vocabulary and matrix are what they were
+        sg_set_error("sg_vec_reweigh: %u entries are not a whole count times the vocabulary's idf over the row's norm -- was the "
+                     "matrix made under another idf?", mismatch);
+        return SG_ERR_UNSUPPORTED;
+    }
+    SG_HIP_TRY(hipMemcpyAsync(v->d_idf, d_idf_new, s * (size_t)v->n_terms, hipMemcpyDeviceToDevice, ctx->stream));
+    SG_HIP_TRY(hipMemcpyAsync(v->d_df, df_host, sizeof(int32_t) * (size_t)v->n_terms, hipMemcpyHostToDevice, ctx->stream));
+    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));   // (df_host is the caller's)
+    v->n_docs = n_docs;
+    v->idf_trusted = true;
+    *out = r.release();
     return SG_OK;
 }

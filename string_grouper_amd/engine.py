@@ -116,7 +116,7 @@ class CorpusState:
                       "reverse": 0, "reverse_fallbacks": 0, "appends": 0, "rows_appended": 0, "compactions": 0,
                       "segments": 1, "base_index_builds": 0, "removals": 0, "rows_removed": 0, "dead_rows": 0,
                       "self_join_full": 0, "self_join_served": 0, "self_join_append_updates": 0,
-                      "self_join_remove_updates": 0, "self_join_rows_refilled": 0}
+                      "self_join_remove_updates": 0, "self_join_rows_refilled": 0, "idf_refits": 0}
         if base is not None:
             self.set_segments(CorpusSegment(base), None)
 
@@ -411,6 +411,26 @@ class HipEngine:
         for seg in old:
             seg.free()
         state.stats["compactions"] += 1
+
+    def corpus_refit_idf(self, state: CorpusState) -> None:
+        """The idf follows the CURRENT list, the vocabulary stays the original's: what sklearn's vectoriser gives when it is
+        fitted on the live strings with ``vocabulary=`` fixed.  No string is read (``stats['tokenisations']`` stays 1): the live
+        rows in one matrix (a compaction when rows are dead), their column counts, numpy's idf of those, and one pass that
+        weights the rows anew (HipTfidfVectorizer.refit_idf_prepared) into a NEW base segment; then the old segments go, index
+        first, and with them the cached concatenation and a kept self-join -- every score has changed, so it is multiplied
+        anew when next needed (its options stay).  A refusal of the device leaves the corpus as it was."""
+        t0 = time.perf_counter()
+        rows = state.rows()
+        t1 = time.perf_counter()
+        new = state.vec.refit_idf_prepared(rows)
+        old = state.segments
+        state.set_segments(CorpusSegment(new), None)
+        for seg in old:
+            seg.free()
+        state.drop_whole()
+        state.drop_kept()
+        state.stats["idf_refits"] += 1
+        self.timings = dict(refit_rows_s=t1 - t0, **{f"refit_{k}_s": v for k, v in state.vec.last_refit_s.items()})
 
     def _segment_index(self, state: CorpusState, seg: CorpusSegment) -> Optional["N.Postings"]:
         if seg.index is None and not state.index_overflow:

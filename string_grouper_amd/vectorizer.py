@@ -17,6 +17,7 @@ that fit -- so that the packed keys still sort like sklearn's vocabulary).
 """
 from __future__ import annotations
 
+import time
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -234,6 +235,28 @@ class HipTfidfVectorizer:
                     "was fitted on ASCII-only strings: fit on a corpus that contains the characters, as StringGrouper "
                     "does (it fits on master + duplicates)")
         return self.ctx.vec_transform(self._vocab, dev.dev)
+
+    def refit_idf_prepared(self, m: N.Csr) -> N.Csr:
+        """The idf refitted on the documents whose rows ``m`` holds (a matrix this vectoriser made, under its current idf),
+        the vocabulary staying what it is: ``TfidfVectorizer(vocabulary=self.vocabulary_, ...).fit(docs)``.  Returns
+        ``.transform(docs)`` under the new idf as a new matrix; ``m`` is only read.  No string is read: the document counts
+        are the column counts of ``m`` (a row names a column once), the number of documents is its rows (empty ones count, as
+        sklearn counts them), the idf is ``idf_from_df`` of the two -- numpy's log -- and the device recovers every entry's
+        count from its value and its row's norm (include/sg_hip.h: sg_vec_reweigh).  ``idf_`` and the counts
+        ``sg_vocab_to_host`` reports are the new ones afterwards, and later transforms use them.  ``last_refit_s`` holds the
+        seconds of the three steps."""
+        if self._vocab is None:
+            raise RuntimeError("vectoriser is not fitted")
+        t0 = time.perf_counter()
+        df = m.column_counts().astype(np.int64)
+        n_docs = m.dims()[0]
+        t1 = time.perf_counter()
+        idf = idf_from_df(df, n_docs, self.dtype)
+        t2 = time.perf_counter()
+        out = self.ctx.vec_reweigh(self._vocab, m, df, n_docs, idf)
+        self.last_refit_s = {"counts": t1 - t0, "host_idf": t2 - t1, "reweigh": time.perf_counter() - t2}
+        self._df, self._idf, self._n_docs = df, idf, n_docs
+        return out
 
     # ------------------------------------------------------------------ sklearn-shaped API (seam b1)
     def fit(self, raw_documents, y=None):
