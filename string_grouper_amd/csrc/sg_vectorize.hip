@@ -774,7 +774,9 @@ __global__ void __launch_bounds__(256) weight_normalize_kernel(const int64_t *__
                 out_val[q] = v;
                 s2 += (double)v * (double)v;
             }
-            n2 = __double2float_ru(s2);
+            // an upper bound whatever the order of the additions, as in the form that runs: a row of a thousand entries summed
+            // one after the other can come out a few units in the last place BELOW the exactly rounded sum
+            n2 = __double2float_ru(s2 * (1.0 + 1e-12));
         }
     }
     // the multiply's pruning rules need the largest row norm and the longest row: reduce them here, where the rows are made
