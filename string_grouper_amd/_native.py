@@ -199,16 +199,40 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _dev_ptr(ints) -> Optional[int]:
+    return ints.ptr if isinstance(ints, DeviceInts) else ints
+
+
+_n_live = 0
+
+
+def live_handles() -> int:
+    """How many handles (``_Handle`` subclasses, ``DeviceInts`` among them) have been made and not yet freed."""
+    return _n_live
+
+
 class _Handle:
+    """Owner of one object of the library: ``free`` gives it back once, however often it is called; so does collection."""
     _free = None
+    _live = False
 
     def __init__(self, ctx: "Context", handle):
+        global _n_live
         self.ctx = ctx
         self.h = handle
+        self._live = True
+        _n_live += 1
 
-    def free(self):
+    def _release(self):
         if self.h is not None and self._free is not None:
             getattr(lib(), self._free)(self.h)
+
+    def free(self):
+        global _n_live
+        if self._live:
+            self._live = False
+            _n_live -= 1
+            self._release()
             self.h = None
 
     def __del__(self):
@@ -216,6 +240,35 @@ class _Handle:
             self.free()
         except Exception:
             pass
+
+
+class Scope:
+    """The Python side's ``Scratch`` (csrc/sg_internal.h): a ``with`` block that owns the handles made inside it -- anything
+    with ``free()`` -- and frees them when the block ends, by ``return``, by exception or by running out, last adopted first.
+    ``own(h)`` adopts (``None`` and a handle it already owns: nothing to do) and returns ``h``; ``keep(h)`` takes it out again
+    -- it is the caller's or the state's now -- and ``release(h)`` frees it early."""
+
+    def __init__(self):
+        self._held = []
+
+    def __enter__(self) -> "Scope":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        while self._held:
+            self._held.pop().free()
+
+    def own(self, h):
+        if h is not None and not any(x is h for x in self._held):
+            self._held.append(h)
+        return h
+
+    def keep(self, h):
+        self._held = [x for x in self._held if x is not h]
+        return h
+
+    def release(self, h) -> None:
+        self.keep(h).free()
 
 
 class Strings(_Handle):
@@ -357,7 +410,7 @@ class MatchList(_Handle):
         return row_ptr, cols[:m.value], vals[:m.value]
 
 
-class DeviceInts:
+class DeviceInts(_Handle):
     """A list of int32 numbers kept in device memory (sg_device_upload), with its host copy: ascending and distinct, unless
     ``any_order`` (the rows of ``csr_take_rows``, which the device checks against its matrix)."""
 
@@ -372,24 +425,29 @@ class DeviceInts:
         elif host.size and (host[0] < 0 or host[-1] > np.iinfo(np.int32).max or np.any(host[1:] <= host[:-1])):
             raise ValueError("bad argument: the list must be ascending, distinct and hold row numbers (0 .. 2^31 - 1)")
         self.host = host.astype(np.int32)
-        self.ctx = ctx
         out = C.c_void_p()
         check(lib().sg_device_upload(ctx.h, _ptr(self.host), int(self.host.nbytes), C.byref(out)))
-        self.ptr = out.value
+        super().__init__(ctx, out.value)
+        self.n = len(self.host)
+
+    @classmethod
+    def adopt(cls, ctx: "Context", d_ptr: Optional[int], n: int) -> "DeviceInts":
+        """Owner of a list the library made (``topn_forget``'s short rows): ``n`` numbers at ``d_ptr``, no host copy."""
+        self = cls.__new__(cls)
+        _Handle.__init__(self, ctx, d_ptr)
+        self.host, self.n = None, int(n)
+        return self
+
+    @property
+    def ptr(self) -> Optional[int]:
+        return self.h
 
     def __len__(self) -> int:
-        return len(self.host)
+        return self.n
 
-    def free(self) -> None:
-        if self.ptr and self.ctx.h is not None:
-            lib().sg_device_free(self.ctx.h, C.c_void_p(self.ptr))
-        self.ptr = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self):
+        if self.h and self.ctx.h is not None:
+            lib().sg_device_free(self.ctx.h, C.c_void_p(self.h))
 
 
 class Context:
@@ -752,23 +810,26 @@ class Context:
         return TopN(self, out)
 
     def topn_forget(self, res: TopN, dead: "DeviceInts", top_n: int):
-        """(``res`` without the rows and the columns of ``dead``, renumbered; device pointer of the surviving rows that were
-        full and are not any more -- ascending int32, ``device_free`` it --, how many) (include/sg_hip.h: sg_topn_forget)."""
+        """(``res`` without the rows and the columns of ``dead``, renumbered; the surviving rows that were full and are not any
+        more -- ascending, a ``DeviceInts`` without a host copy, the caller's to free) (include/sg_hip.h: sg_topn_forget)."""
         out, rows, n = C.c_void_p(), C.c_void_p(), C.c_int64()
         check(lib().sg_topn_forget(self.h, res.h, C.c_void_p(dead.ptr), len(dead), int(top_n), C.byref(out), C.byref(rows),
                                    C.byref(n)))
-        return TopN(self, out), rows.value or 0, n.value
+        return TopN(self, out), DeviceInts.adopt(self, rows.value, n.value)
 
-    def topn_put_rows(self, res: TopN, d_rows: int, n_rows: int, src: TopN) -> None:
-        """In place: row ``d_rows[k]`` (device int32, distinct) of ``res`` becomes row k of ``src`` (include/sg_hip.h:
-        sg_topn_put_rows)."""
+    def topn_put_rows(self, res: TopN, d_rows, n_rows: int, src: TopN) -> None:
+        """In place: row ``d_rows[k]`` (a ``DeviceInts`` or a device pointer: int32, distinct) of ``res`` becomes row k of
+        ``src`` (include/sg_hip.h: sg_topn_put_rows)."""
+        d_rows = _dev_ptr(d_rows)
         check(lib().sg_topn_put_rows(self.h, res.h, C.c_void_p(d_rows) if d_rows else None, int(n_rows), src.h))
 
-    def download_ints(self, d_ptr: int, n: int) -> np.ndarray:
-        """``n`` int32 numbers of device memory (a list the library made, e.g. ``topn_forget``'s) on the host."""
-        out = np.empty(max(int(n), 1), np.int32)
+    def download_ints(self, d_ints, n: Optional[int] = None) -> np.ndarray:
+        """The int32 numbers of a list in device memory on the host: a ``DeviceInts`` (e.g. ``topn_forget``'s), or a device
+        pointer and how many."""
+        n = len(d_ints) if n is None else int(n)
+        out = np.empty(max(n, 1), np.int32)
         if n:
-            check(lib().sg_device_download(self.h, C.c_void_p(d_ptr), int(n) * 4, _ptr(out)))
+            check(lib().sg_device_download(self.h, C.c_void_p(_dev_ptr(d_ints)), n * 4, _ptr(out)))
         return out[:n]
 
     def topn_zip(self, parts, col_offsets, top_n: int) -> TopN:

@@ -89,6 +89,12 @@ class StringColumn:
         self.n = len(offsets) - 1
         self.dev = None            # device handle (N.Strings), set by the vectoriser
 
+    def free(self) -> None:
+        """The device copy goes (if there is one); the host arrays stay."""
+        if self.dev is not None:
+            self.dev.free()
+            self.dev = None
+
 
 # ------------------------------------------------------------------------------------------------ Arrow buffers
 def to_arrow_buffers(strings):

@@ -71,6 +71,8 @@ class HipTfidfVectorizer:
         self._ctx = ctx
         self._vocab: Optional[N.Vocab] = None
         self._fit_sets: List[StringColumn] = []
+        self._fit_originals: List[StringColumn] = []
+        self._dev_of: Dict[int, StringColumn] = {}
         self._keys = None
         self._df = None
         self._idf = None
@@ -153,6 +155,19 @@ class HipTfidfVectorizer:
         self._fit_originals = list(sets)
         self._dev_of = {id(s): d for s, d in zip(sets, dev_sets)}
 
+    def handles(self) -> list:
+        """What the fit holds on the device: the vocabulary and the string columns that were uploaded for it."""
+        hs = [self._vocab] + [col.dev for col in self._fit_sets + self._fit_originals]
+        return [h for k, h in enumerate(hs) if h is not None and not any(h is x for x in hs[:k])]
+
+    def free(self) -> None:
+        """Release ``handles()``; the vectoriser is of no use afterwards."""
+        for h in self.handles():
+            h.free()
+        for col in self._fit_sets + self._fit_originals:
+            col.dev = None
+        self._fit_sets, self._fit_originals, self._dev_of = [], [], {}
+
     # the idf of a term is a function of its document count and the number of documents only: for fits of up to this many
     # documents the function is tabulated once per (documents, dtype) -- with numpy, so that log() stays sklearn's --, kept
     # on the device, and a fit() weights its terms there: no download of the counts, no upload of the weights, no
@@ -221,7 +236,7 @@ class HipTfidfVectorizer:
     def transform_prepared(self, s: StringColumn) -> N.Csr:
         if self._vocab is None:
             raise RuntimeError("vectoriser is not fitted")
-        dev = getattr(self, "_dev_of", {}).get(id(s))
+        dev = self._dev_of.get(id(s))
         if dev is None:
             if self._alphabet is not None:
                 dev = self._upload_symbols(self._as_symbols(s), self._alphabet)
