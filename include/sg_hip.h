@@ -60,9 +60,9 @@ const char *sg_last_error(void);
 /* Bumped whenever a signature or a struct of this header changes (round 4: 2 -- row_step arguments of round 3, sg_stats
  * grew; round 5: 3 -- sg_stats.prune_scored; 4 -- sg_topn_transpose_select; 5 -- sg_csr_concat; 6 -- sg_csr_select_rows,
  * sg_topn_drop_columns, sg_device_upload; 7 -- sg_topn_concat_rows, sg_topn_forget, sg_topn_put_rows, sg_csr_take_rows,
- * sg_device_download; 8 -- sg_csr_row_norms, sg_csr_vectoriser_words, sg_csr_column_counts, sg_vec_reweigh); a
- * binding compares it with the value it was written for right after loading the library. */
-#define SG_ABI_VERSION 8
+ * sg_device_download; 8 -- sg_csr_row_norms, sg_csr_vectoriser_words, sg_csr_column_counts, sg_vec_reweigh; 9 --
+ * sg_csr_pairs_dot); a binding compares it with the value it was written for right after loading the library. */
+#define SG_ABI_VERSION 9
 int sg_abi_version(void);
 int sg_device_count(int *count);
 /* hip_stream: a hipStream_t to launch on (e.g. torch.cuda.current_stream().cuda_stream), or NULL
@@ -235,6 +235,28 @@ int sg_csr_free(sg_csr *m);
  * added in the order scipy + numpy use (ascending column; first + pairwise sum of the rest), so the result
  * is bit-identical.  out_host: n_rows values of the matrices' type.  Rows must be sorted by column. */
 int sg_csr_rowwise_dot(sg_ctx *ctx, const sg_csr *A, const sg_csr *B, void *out_host);
+
+/* The similarity of NAMED row pairs: out_host[p] = (A . B^T)[d_left[p], d_right[p]], the element of sp_matmul_topn's product
+ * (string_grouper.py:725-743) for that pair -- and the pair form of compute_pairwise_similarities (string_grouper.py:55), which
+ * has to be handed the two rows of every pair as strings and vectorises them again.  A is n_a x V, B is n_b x V, of the same
+ * value type; they may be the same handle.  d_left, d_right: DEVICE arrays (sg_device_upload) of n_pairs row numbers, d_left[p]
+ * in [0, n_a), d_right[p] in [0, n_b); any order, a pair or a row may be named any number of times.  out_host: n_pairs values
+ * of the matrices' type, in the order of the pairs.
+ * The value is defined to the bit, and it is the MULTIPLY's, not sg_csr_rowwise_dot's: acc = +0.0, and for every column k that
+ * both rows hold, in ascending k, acc = rn(acc + rn(A[i, k] * B[j, k])) -- every product and every sum rounded to the value
+ * type on its own, zero products added like the others (a lone product of -0.0 gives +0.0).  No common column, or a row
+ * without entries: +0.0.  Every pair (i, j, score) that sg_spgemm_topn reports for the same matrices is reproduced bit for
+ * bit.  Values of any sign, NaN and inf flow through: this call has no gate.
+ * Refusals leave out_host untouched:
+ *   SG_ERR_BADARG   the matrices differ in their columns or in value type (seen on the host); an index outside its matrix, or
+ *                   a row NAMED BY A PAIR whose columns are not strictly ascending (seen on the device: one status word, a
+ *                   bit a cause, which comes back with the results -- the message names the causes).  A matrix made by
+ *                   sg_vec_transform, or one the multiply's gate has found cosine-like, is known to be sorted and is not
+ *                   checked again.
+ *   SG_ERR_OVERFLOW more than 2^36 pairs in one call.
+ * n_pairs == 0: SG_OK, nothing is read or written.  One launch, one read-back (the call's only synchronisation). */
+int sg_csr_pairs_dot(sg_ctx *ctx, const sg_csr *A, const sg_csr *B, const int32_t *d_left, const int32_t *d_right,
+                     int64_t n_pairs, void *out_host);
 
 /* ------------------------------------------------------------------ seam b2: sparse top-n multiply */
 /* Inverted index of B (n_right x V): for every term k the (row j, value) pairs, grouped by column

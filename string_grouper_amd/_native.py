@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SG_HIP_LIB") or os.path.join(_HERE, "libsg_hip.so")
 
 SG_OK, SG_ERR_BADARG, SG_ERR_OOM, SG_ERR_OVERFLOW, SG_ERR_HIP, SG_ERR_NODEVICE, SG_ERR_UNSUPPORTED = range(7)
 SG_F32, SG_F64 = 0, 1
-ABI_VERSION = 8          # include/sg_hip.h: SG_ABI_VERSION
+ABI_VERSION = 9          # include/sg_hip.h: SG_ABI_VERSION
 SG_K_TOKENIZE, SG_K_WEIGHT, SG_K_POSTINGS, SG_K_SPGEMM, SG_K_ZIP, SG_K_VOCAB, SG_K_SPGEMM_KERNEL, SG_K_COUNT = range(8)
 KERNEL_NAMES = ("tokenize", "weight", "postings", "spgemm_topn", "zip", "vocab", "spgemm_kernel")
 
@@ -116,6 +116,7 @@ ABI = {
     "sg_topn_put_rows": (C.c_int, [_P, _P, _P, C.c_int64, _P]),
     "sg_csr_take_rows": (C.c_int, [_P, _P, _P, C.c_int64, _PP]),
     "sg_csr_rowwise_dot": (C.c_int, [_P, _P, _P, _P]),
+    "sg_csr_pairs_dot": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P]),
     "sg_csr_row_norms": (C.c_int, [_P, _PP]),
     "sg_csr_vectoriser_words": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int32)]),
     "sg_csr_column_counts": (C.c_int, [_P, _P, _P]),
@@ -706,6 +707,25 @@ class Context:
         out = np.zeros(max(r, 1), code_np_dtype(d))
         check(lib().sg_csr_rowwise_dot(self.h, A.h, B.h, _ptr(out)))
         return out[:r]
+
+    def pairs_dot(self, A: Csr, B: Csr, left, right, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """(A . B^T)[left[p], right[p]] for every p, in the multiply's arithmetic -- ascending column, every product and
+        every sum rounded on its own, from +0.0 (include/sg_hip.h: sg_csr_pairs_dot).  ``left`` / ``right``: equally long
+        lists of row numbers of A / of B; a number outside its matrix, or an unsorted row that a pair names: ValueError.
+        ``out``: an array of the matrices' dtype with room for the pairs, to be filled instead of a new one (a refused call
+        leaves it as it was)."""
+        n = len(left)
+        if len(right) != n:
+            raise ValueError(f"bad argument: left has {n} entries, right has {len(right)}")
+        dtype = code_np_dtype(A.dims()[3])
+        if out is None:
+            out = np.zeros(n, dtype)
+        elif out.dtype != dtype or out.ndim != 1 or len(out) < n or not out.flags.c_contiguous:
+            raise ValueError(f"bad argument: out must be a contiguous {np.dtype(dtype).name} array of at least {n} entries")
+        with Scope() as s:
+            d_left, d_right = s.own(self.upload_ints(left)), s.own(self.upload_ints(right))
+            check(lib().sg_csr_pairs_dot(self.h, A.h, B.h, C.c_void_p(d_left.ptr), C.c_void_p(d_right.ptr), n, _ptr(out)))
+        return out[:n]
 
     def selfjoin_range(self, A: Csr, Bt: Postings, top_n: int, threshold: float, row_lo: int, row_hi: int, row_step: int = 1):
         """The rows [row_lo, row_hi) -- with ``row_step`` s > 1: row_hi - 1, row_hi - 1 - s, ... >= row_lo -- of the

@@ -31,6 +31,7 @@ import numpy as np
 import pandas as pd
 
 from . import engine as _engine_mod
+from .pairs import checked_pairs
 from .string_grouper import StringGrouper, StringGrouperConfig
 
 # options that define the vectoriser: a call may not change them (the corpus was fitted with them)
@@ -384,7 +385,8 @@ class Corpus:
         that still lie in the segments, until the next compaction); for a kept self-join (``keep_self_join``)
         ``self_join_full`` (whole multiplies made for it), ``self_join_served`` (calls answered from it),
         ``self_join_append_updates`` / ``self_join_remove_updates`` (changes it followed without a whole multiply) and
-        ``self_join_rows_refilled`` (rows a remove had to multiply again); ``idf_refits`` (calls of ``refit_idf``)."""
+        ``self_join_rows_refilled`` (rows a remove had to multiply again); ``idf_refits`` (calls of ``refit_idf``);
+        ``pair_calls`` / ``pairs_scored`` (calls of ``pair_similarities`` that reached the device, and their pairs)."""
         return dict(self._live().stats)
 
     def _rows_of(self, series, made):
@@ -438,3 +440,42 @@ class Corpus:
     def compute_pairwise_similarities(self, string_series_1: pd.Series, string_series_2: pd.Series, **kwargs) -> pd.Series:
         """Row-wise similarity of two equally long series."""
         return self._run(string_series_1, string_series_2, None, None, kwargs, lambda g: g.dot())
+
+    # ------------------------------------------------------------------ named pairs
+    def pair_similarities(self, left, right, duplicates: Optional[pd.Series] = None) -> np.ndarray:
+        """How similar are these particular records?  ``left[p]`` and ``right[p]`` are POSITIONS in the CURRENT
+        ``corpus.master`` (a sequence or array of ints; negative ones count from the end); the answer is a numpy array of
+        the corpus's dtype, one similarity a pair, in the order given.  With ``duplicates`` the right-hand positions count
+        through that Series, which is transformed once as a batch (``duplicates is corpus.master``: the resident rows).
+
+        The promise: for every pair (i, j) that ``match_strings`` reports for the same rows, the same bits -- a pair's score
+        is the element of the multiply's product, in its arithmetic (string_grouper_amd/pairs.py) -- but for the diagonal of a
+        self-join, which the frames set to 1.  ``compute_pairwise_similarities`` on the two gathered Series sums in numpy's
+        order and may differ in the last bit; it also reads and vectorises every string again, which this call does not:
+        the rows are on the device, two index lists go up and the scores come back (``stats['tokenisations']`` does not
+        move; ``stats['pair_calls']`` / ``['pairs_scored']`` count).  Appended rows waiting in the second segment and removed
+        rows still pending are served where they lie: no compaction (``stats['compactions']`` does not move).
+
+        Bools or non-integers: TypeError; lists of different lengths: ValueError; a position outside [-n, n): IndexError,
+        found before anything is uploaded; no pairs: an empty array and no device call."""
+        state = self._live()
+        self._same_engine()
+        if not hasattr(self._engine, "corpus_pairs"):
+            raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} scores no pairs")
+        if duplicates is not None and not StringGrouper._is_series_of_strings(duplicates):
+            raise TypeError('Input does not consist of pandas.Series containing only Strings')
+        n = len(self._master) + sum(len(s) for s, _ in self._pending)
+        resident = duplicates is None or (not self._pending and duplicates is self._master)
+        left, right = checked_pairs(left, right, n, n if resident else len(duplicates))
+        if len(left) == 0:
+            return np.zeros(0, self._config.tfidf_matrix_dtype)
+        if resident:
+            return self._engine.corpus_pairs(state, left, right, None)
+        made = []
+        try:
+            return self._engine.corpus_pairs(state, left, right, self._rows_of(duplicates, made))
+        finally:
+            for m in made:
+                csr = getattr(m, "csr", None)
+                if csr is not None:
+                    csr.free()

@@ -71,7 +71,8 @@ class CorpusState:
                       "reverse": 0, "reverse_fallbacks": 0, "appends": 0, "rows_appended": 0, "compactions": 0,
                       "segments": 1, "base_index_builds": 0, "removals": 0, "rows_removed": 0, "dead_rows": 0,
                       "self_join_full": 0, "self_join_served": 0, "self_join_append_updates": 0,
-                      "self_join_remove_updates": 0, "self_join_rows_refilled": 0, "idf_refits": 0}
+                      "self_join_remove_updates": 0, "self_join_rows_refilled": 0, "idf_refits": 0, "pair_calls": 0,
+                      "pairs_scored": 0}
         if base is not None:
             self.set_segments(CorpusSegment(base), None)
 
@@ -488,6 +489,23 @@ class CorpusEngine:
                 physical, pairs = pairs, s.own(self._drop_dead(state, pairs, pairs.dims()[1]))
                 s.release(physical)
             return self.ctx.topn_transpose_select(pairs, n_corpus, top_n)
+
+    # ------------------------------------------------------------------ named pairs
+    def corpus_pairs(self, state: CorpusState, left, right, other: Optional[DeviceMatrix] = None) -> np.ndarray:
+        """The similarity of the corpus rows ``left[p]`` and ``right[p]`` (LIVE numbering), or with ``other`` of the corpus
+        row ``left[p]`` and row ``right[p]`` of ``other``: the element the multiply reports for the pair, bit for bit
+        (sg_csr_pairs_dot).  The rows are read where they lie: live numbers become physical ones (``physical_rows``) and the
+        matrix is ``state.physical()`` -- the base segment, or with appended rows waiting the cached concatenation, dead rows
+        and all -- so a pair call never compacts.  No handle is made here but the state's own cached concatenation; the two
+        index lists live and die inside ``Context.pairs_dot``."""
+        left = state.physical_rows(np.asarray(left, dtype=np.int64))
+        right = np.asarray(right, dtype=np.int64)
+        if other is None:
+            right = state.physical_rows(right)
+        rows = state.physical()
+        state.stats["pair_calls"] += 1
+        state.stats["pairs_scored"] += len(left)
+        return self.ctx.pairs_dot(rows, rows if other is None else other.csr, left, right)
 
     # ------------------------------------------------------------------ a self-join that is kept (DESIGN.md section 9)
     def corpus_keep_self_join(self, state: CorpusState, top_n: int, threshold: float) -> None:

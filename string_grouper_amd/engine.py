@@ -116,6 +116,11 @@ class HipEngine(CorpusEngine):
         """Row-wise similarity of master and duplicates (string_grouper.py:433-440) on the device (K9)."""
         return self.ctx.rowwise_dot(A.csr, B.csr)
 
+    def pairs_dot(self, A: DeviceMatrix, B: DeviceMatrix, left, right) -> np.ndarray:
+        """(A . B^T)[left[p], right[p]] for every p: the element the top-n multiply reports for that pair, bit for bit
+        (include/sg_hip.h: sg_csr_pairs_dot).  ``left`` / ``right``: row numbers of A / of B, equally many."""
+        return self.ctx.pairs_dot(A.csr, B.csr, left, right)
+
     # ------------------------------------------------------------------ fused tail of fit() (K6)
     def match_list(self, A: DeviceMatrix, B: DeviceMatrix, top_n: int, threshold: float, self_join_fix: bool,
                    keep_on_device: bool = False):
@@ -287,6 +292,12 @@ class DistributedHipEngine(HipEngine):
         local = self.ctx.rowwise_dot(A.csr, B.csr)
         parts = D.all_gather_ragged(torch.from_numpy(np.ascontiguousarray(local)).to(A._ops.device), self.group)
         return torch.cat(parts).cpu().numpy()
+
+    def pairs_dot(self, A, B, left, right) -> np.ndarray:
+        raise NotImplementedError("pair similarities are single-GPU: a pair's two rows may live on different ranks")
+
+    def corpus_pairs(self, state, left, right, other=None) -> np.ndarray:
+        raise NotImplementedError("pair similarities are single-GPU: a pair's two rows may live on different ranks")
 
     def topn_multiply_blocked(self, A, B, n_blocks, top_n, threshold):
         if isinstance(A, ShardedMatrix):          # explicit n_blocks only cut the work differently: same result
