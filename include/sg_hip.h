@@ -61,8 +61,9 @@ const char *sg_last_error(void);
  * grew; round 5: 3 -- sg_stats.prune_scored; 4 -- sg_topn_transpose_select; 5 -- sg_csr_concat; 6 -- sg_csr_select_rows,
  * sg_topn_drop_columns, sg_device_upload; 7 -- sg_topn_concat_rows, sg_topn_forget, sg_topn_put_rows, sg_csr_take_rows,
  * sg_device_download; 8 -- sg_csr_row_norms, sg_csr_vectoriser_words, sg_csr_column_counts, sg_vec_reweigh; 9 --
- * sg_csr_pairs_dot); a binding compares it with the value it was written for right after loading the library. */
-#define SG_ABI_VERSION 9
+ * sg_csr_pairs_dot; 10 -- sg_topn_rescore, sg_rescore_field); a binding compares it with the value it was written for right
+ * after loading the library. */
+#define SG_ABI_VERSION 10
 int sg_abi_version(void);
 int sg_device_count(int *count);
 /* hip_stream: a hipStream_t to launch on (e.g. torch.cuda.current_stream().cuda_stream), or NULL
@@ -469,6 +470,46 @@ int sg_topn_forget(sg_ctx *ctx, const sg_topn *r, const int32_t *d_dead_sorted, 
  * passed over, nothing is read back).  src has r's n_cols and dtype and a stride not above r's, otherwise SG_ERR_BADARG.
  * No synchronisation. */
 int sg_topn_put_rows(sg_ctx *ctx, sg_topn *r, const int32_t *d_rows, int64_t n_rows, const sg_topn *src);
+
+/* ------------------------------------------------------------------ record matching: a result rescored on further fields */
+/* A record has several fields (name, address, city ...), each with its own matrices.  sg_topn_rescore takes the candidates one
+ * field's multiply found -- cand: R rows, N columns, stride S, counts -- scores every one of them on F further fields, weighs
+ * the scores into one, and filters, orders and cuts every row anew.  Candidates never leave the device.  (The reference has no
+ * analogue: it matches one column of strings, string_grouper.py:55-153; its users combine fields in pandas.)
+ *
+ * A field f = 1 .. F is two matrices A_f (the left records' rows) and B_f (the right records'; the same handle for a
+ * self-join), a weight, and per side an optional list of dead PHYSICAL rows (DEVICE memory, ascending and distinct -- the
+ * caller's responsibility): a resident corpus keeps removed rows in place, and result rows and columns count the live ones.
+ * For row i of cand and entry e < counts[i], with j = cols[i, e] and s_0 = vals[i, e]:
+ *   live -> physical   a = i + #{q : dead_a_f[q] - q <= i}, b likewise from j and dead_b_f (numpy: searchsorted(dead -
+ *                      arange(len(dead)), live, side="right")); no list: a = i, b = j.
+ *   field score        s_f = (A_f . B_f^T)[a, b] exactly as sg_csr_pairs_dot states it: ascending column, every product and
+ *                      every sum rounded on its own, from +0.0.
+ *   combined score     c = +0.0, then for f = 0 .. F in this order c = rn(c + rn(W_f * s_f)), W_f = (T)w_f with T the value
+ *                      type and w_0 the weight of the score cand carries: no fused multiply-add, no wider accumulator --
+ *                      numpy's acc = acc + W[f] * s[f] on arrays of type T.
+ *   filter             kept when c > (T)threshold, the multiply's rule: a NaN never passes, an inf passes and sorts first.
+ *   output row         row i of *out holds the kept entries by c descending (by VALUE: zeros of either sign are equal), then
+ *                      j ascending, and the first min(top_n, S) of them stay; the bits written are c's own.
+ * *out has R rows, N columns and the stride min(top_n, S); cand is only read.  The result feeds sg_matchlist_build like a
+ * multiply's.
+ * Refusals (SG_ERR_BADARG; nothing is returned, and the next call works):
+ *   seen on the host     n_fields outside 1 .. 7; top_n < 1; S > 2048; a weight that is not finite (in T); a field whose
+ *                        matrices differ from cand in value type, or from each other in columns; rows(A_f) - n_dead_a != R or
+ *                        rows(B_f) - n_dead_b != N;
+ *   seen on the device   a candidate column outside [0, N) -- nothing is read for it --, or a row of a field matrix that a
+ *                        candidate reads whose columns are not strictly ascending, for matrices not known to be sorted (as
+ *                        sg_csr_pairs_dot): one status word, a bit a cause, the call's only read-back. */
+typedef struct {
+    const sg_csr *A, *B;
+    double weight;
+    const int32_t *d_dead_a; /* NULL: none */
+    int32_t n_dead_a;
+    const int32_t *d_dead_b;
+    int32_t n_dead_b;
+} sg_rescore_field;
+int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
+                    double threshold, int32_t top_n, sg_topn **out);
 
 /* ------------------------------------------------------------------ measurement */
 enum { SG_K_TOKENIZE = 0, SG_K_WEIGHT = 1, SG_K_POSTINGS = 2, SG_K_SPGEMM = 3 /* the multiply's whole launch group */,

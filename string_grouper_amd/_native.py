@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SG_HIP_LIB") or os.path.join(_HERE, "libsg_hip.so")
 
 SG_OK, SG_ERR_BADARG, SG_ERR_OOM, SG_ERR_OVERFLOW, SG_ERR_HIP, SG_ERR_NODEVICE, SG_ERR_UNSUPPORTED = range(7)
 SG_F32, SG_F64 = 0, 1
-ABI_VERSION = 9          # include/sg_hip.h: SG_ABI_VERSION
+ABI_VERSION = 10         # include/sg_hip.h: SG_ABI_VERSION
 SG_K_TOKENIZE, SG_K_WEIGHT, SG_K_POSTINGS, SG_K_SPGEMM, SG_K_ZIP, SG_K_VOCAB, SG_K_SPGEMM_KERNEL, SG_K_COUNT = range(8)
 KERNEL_NAMES = ("tokenize", "weight", "postings", "spgemm_topn", "zip", "vocab", "spgemm_kernel")
 
@@ -26,6 +26,12 @@ KERNEL_NAMES = ("tokenize", "weight", "postings", "spgemm_topn", "zip", "vocab",
 class SgVecParams(C.Structure):
     _fields_ = [("ngram_size", C.c_int32), ("ascii_lower", C.c_int32), ("dtype", C.c_int32),
                 ("reserved", C.c_int32), ("delete_table", C.c_uint8 * 128)]
+
+
+class SgRescoreField(C.Structure):
+    """include/sg_hip.h: sg_rescore_field"""
+    _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("weight", C.c_double), ("d_dead_a", C.c_void_p),
+                ("n_dead_a", C.c_int32), ("d_dead_b", C.c_void_p), ("n_dead_b", C.c_int32)]
 
 
 class SgStats(C.Structure):
@@ -117,6 +123,7 @@ ABI = {
     "sg_csr_take_rows": (C.c_int, [_P, _P, _P, C.c_int64, _PP]),
     "sg_csr_rowwise_dot": (C.c_int, [_P, _P, _P, _P]),
     "sg_csr_pairs_dot": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P]),
+    "sg_topn_rescore": (C.c_int, [_P, _P, C.c_double, C.POINTER(SgRescoreField), C.c_int32, C.c_double, C.c_int32, _PP]),
     "sg_csr_row_norms": (C.c_int, [_P, _PP]),
     "sg_csr_vectoriser_words": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int32)]),
     "sg_csr_column_counts": (C.c_int, [_P, _P, _P]),
@@ -842,6 +849,25 @@ class Context:
         ``src`` (include/sg_hip.h: sg_topn_put_rows)."""
         d_rows = _dev_ptr(d_rows)
         check(lib().sg_topn_put_rows(self.h, res.h, C.c_void_p(d_rows) if d_rows else None, int(n_rows), src.h))
+
+    def topn_rescore(self, cand: TopN, w0: float, fields, threshold: float, top_n: int) -> TopN:
+        """The candidates of ``cand`` scored on further fields, weighed, filtered, re-ordered and cut, on the device
+        (include/sg_hip.h: sg_topn_rescore).  ``fields``: 1 to 7 of ``(A: Csr, B: Csr, weight, dead_a: DeviceInts | None,
+        dead_b: DeviceInts | None)`` -- the left and right records' rows of the field (the same handle for a self-join), and
+        per side the dead physical rows of a corpus that has removed rows pending.  c = w0 * s_0 + sum of weight_f * s_f, every
+        product and every sum rounded on its own, in this order; kept when c > threshold; by c descending, then column; at
+        most ``top_n`` a row.  ``cand`` is only read.  A refusal of the device (a column outside the result, an unsorted row
+        that a candidate reads): ValueError."""
+        fields = list(fields)
+        arr = (SgRescoreField * max(len(fields), 1))()
+        for k, (A, B, weight, dead_a, dead_b) in enumerate(fields):
+            a, b = (getattr(m.h, "value", m.h) for m in (A, B))          # (a handle is a c_void_p or its integer)
+            arr[k] = SgRescoreField(a, b, float(weight), None if dead_a is None else dead_a.ptr,
+                                    0 if dead_a is None else len(dead_a), None if dead_b is None else dead_b.ptr,
+                                    0 if dead_b is None else len(dead_b))
+        out = C.c_void_p()
+        check(lib().sg_topn_rescore(self.h, cand.h, float(w0), arr, len(fields), float(threshold), int(top_n), C.byref(out)))
+        return TopN(self, out)
 
     def download_ints(self, d_ints, n: Optional[int] = None) -> np.ndarray:
         """The int32 numbers of a list in device memory on the host: a ``DeviceInts`` (e.g. ``topn_forget``'s), or a device

@@ -25,6 +25,7 @@ two matrices.  The methods have the signatures of the module-level functions (st
 """
 from __future__ import annotations
 
+import inspect
 from typing import Optional
 
 import numpy as np
@@ -143,8 +144,41 @@ class _CorpusGrouper(StringGrouper):
         self._made = []
 
 
+class _RecordGrouper(_CorpusGrouper):
+    """_CorpusGrouper whose match list is the engine's over RECORDS: the corpus finds the candidates, further corpora score them
+    on their fields, and the weighed sum is what the list holds (CorpusEngine.corpus_records_topn).  Everything behind the
+    list -- the frames, the groups -- is StringGrouper's own."""
+
+    def __init__(self, corpus: "Corpus", others, weights, cand, dup_fields, master, duplicates=None, master_id=None,
+                 duplicates_id=None, **kwargs):
+        self._others, self._weights, self._cand, self._dup_fields = others, weights, cand, dup_fields
+        super().__init__(corpus, master, duplicates, master_id, duplicates_id, **kwargs)
+
+    def _can_fuse_on_device(self) -> bool:
+        return True                           # (explicit n_blocks were refused by the caller; there is no host route)
+
+    def _engine_match_list(self, eng, master_matrix, duplicate_matrix, fix: bool):
+        fields = None
+        if self._dup_fields is not None:                             # one transform a field (duplicates[0] may be corpus.master)
+            fields = [o._rows_of(series, self._made) for o, series in zip(self._others, self._dup_fields)]
+        cand_top_n, cand_threshold = self._cand
+        top_n = cand_top_n if self._max_n_matches is None else min(int(self._max_n_matches), cand_top_n)
+        keep = 'keep_on_device' in inspect.signature(eng.corpus_records_topn).parameters   # engine doubles may lack it
+        try:
+            return eng.corpus_records_topn(self._corpus._live(), [o._live() for o in self._others], duplicate_matrix, fields,
+                                           self._weights, cand_top_n, cand_threshold, top_n, self._config.min_similarity, fix,
+                                           **({'keep_on_device': True} if keep else {}))
+        except OverflowError as e:
+            # fit() answers an OverflowError with the block-wise multiply of ONE field: that is no record match.  There is no
+            # block-wise route for records, so the call is refused instead
+            raise ValueError(f"records x candidates exceed what one result on the device can index ({e}): lower "
+                             f"candidates['max_n_matches'] (now {cand_top_n}) or match the records in batches of duplicates") from e
+
+
 class Corpus:
     """A master list fitted once and kept on the device; see the module docstring."""
+    MAX_RECORD_FIELDS = 7                     # further fields of a record call (include/sg_hip.h: sg_topn_rescore)
+    MAX_RECORD_CANDIDATES = 2048              # candidates a record: the stride sg_topn_rescore takes
 
     def __init__(self, master: pd.Series, master_id: Optional[pd.Series] = None, **kwargs):
         StringGrouper(master, master_id=master_id, **kwargs)        # the reference's validation of data and options
@@ -386,7 +420,9 @@ class Corpus:
         ``self_join_full`` (whole multiplies made for it), ``self_join_served`` (calls answered from it),
         ``self_join_append_updates`` / ``self_join_remove_updates`` (changes it followed without a whole multiply) and
         ``self_join_rows_refilled`` (rows a remove had to multiply again); ``idf_refits`` (calls of ``refit_idf``);
-        ``pair_calls`` / ``pairs_scored`` (calls of ``pair_similarities`` that reached the device, and their pairs)."""
+        ``pair_calls`` / ``pairs_scored`` (calls of ``pair_similarities`` that reached the device, and their pairs);
+        ``record_calls`` (calls of ``match_records`` / ``group_similar_records`` this corpus took part in, as the one that
+        finds the candidates or as a further field)."""
         return dict(self._live().stats)
 
     def _rows_of(self, series, made):
@@ -479,3 +515,123 @@ class Corpus:
                 csr = getattr(m, "csr", None)
                 if csr is not None:
                     csr.free()
+
+    # ------------------------------------------------------------------ records of several fields
+    def _record_call(self, others, duplicates, duplicates_id, weights, candidates, kwargs, finish):
+        """The checks of ``match_records`` / ``group_similar_records``, then the call."""
+        state = self._live()
+        self._same_engine()
+        if not hasattr(self._engine, "corpus_records_topn"):
+            raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} matches no records")
+        if isinstance(others, Corpus) or not isinstance(others, (list, tuple)) or not all(isinstance(o, Corpus) for o in others):
+            raise TypeError("others must be a list of Corpus objects, one for every further field")
+        others = list(others)
+        if not 1 <= len(others) <= self.MAX_RECORD_FIELDS:
+            raise ValueError(f"{len(others)} further fields: between 1 and {self.MAX_RECORD_FIELDS} are expected")
+        n = len(self._master) + sum(len(s) for s, _ in self._pending)
+        for o in others:
+            o._live()
+            o._same_engine()
+            if o._engine is not self._engine:
+                raise RuntimeError("the corpora were built on different engines")
+            if np.dtype(o._config.tfidf_matrix_dtype) != np.dtype(self._config.tfidf_matrix_dtype):
+                raise ValueError(f"tfidf_matrix_dtype={o._config.tfidf_matrix_dtype!r} of a further corpus differs from the "
+                                 f"corpus's tfidf_matrix_dtype={self._config.tfidf_matrix_dtype!r}")
+            m = len(o._master) + sum(len(s) for s, _ in o._pending)
+            if m != n:
+                raise ValueError(f"the corpora differ in length ({m} and {n} rows): row p of every corpus must be record p")
+        if kwargs.get("n_blocks") is not None:
+            raise NotImplementedError("record matching takes no explicit n_blocks: the candidates stay on one device")
+        options = self._options(kwargs)
+        for o in others:
+            o._options({k: v for k, v in kwargs.items() if k in VECTORISER_OPTIONS})
+        # weights: one a field, this corpus's first; used as given
+        if weights is None:
+            weights = [1.0 / (len(others) + 1)] * (len(others) + 1)
+        else:
+            try:
+                weights = [float(w) for w in weights]
+            except (TypeError, ValueError):
+                raise TypeError("weights must be numbers, one for every field (this corpus's first)")
+            if len(weights) != len(others) + 1:
+                raise ValueError(f"{len(weights)} weights for {len(others) + 1} fields: one a field is expected, this corpus's first")
+            if not all(np.isfinite(w) and w > 0 for w in weights):
+                raise ValueError("weights must be finite and greater than 0")
+        # duplicates: one Series a field, equally long
+        dup_fields = None
+        if duplicates is not None:
+            if isinstance(duplicates, pd.Series) or not isinstance(duplicates, (list, tuple)):
+                raise TypeError("duplicates must be a list of pandas.Series, one for every field (this corpus's first)")
+            if len(duplicates) != len(others) + 1:
+                raise ValueError(f"{len(duplicates)} duplicates Series for {len(others) + 1} fields: one a field is expected")
+            for d in duplicates:
+                if not StringGrouper._is_series_of_strings(d):
+                    raise TypeError('Duplicates input does not consist of pandas.Series containing only Strings')
+            if len({len(d) for d in duplicates}) != 1:
+                raise ValueError("the duplicates Series differ in length: row p of every Series must be record p")
+            dup_fields = list(duplicates[1:])
+        elif duplicates_id is not None:
+            raise ValueError("duplicates_id without duplicates")
+        # candidates: the two options of the primary multiply
+        candidates = {} if candidates is None else candidates
+        if not isinstance(candidates, dict) or set(candidates) - {"min_similarity", "max_n_matches"}:
+            raise TypeError("candidates takes min_similarity and max_n_matches only, as a dict")
+        cand_threshold = float(candidates.get("min_similarity", self._config.min_similarity))
+        cand_top_n = candidates.get("max_n_matches", self._config.max_n_matches)
+        n_right = n if duplicates is None else len(duplicates[0])
+        if cand_top_n is None:
+            cand_top_n = n_right
+        if isinstance(cand_top_n, (bool, np.bool_)) or not isinstance(cand_top_n, (int, np.integer)) or cand_top_n < 1:
+            if n_right > 0:
+                raise ValueError(f"candidates: max_n_matches={cand_top_n!r}: a whole number of at least 1 is expected")
+            cand_top_n = 1
+        if cand_top_n > self.MAX_RECORD_CANDIDATES:
+            raise ValueError(f"candidates: max_n_matches={cand_top_n} exceeds the {self.MAX_RECORD_CANDIDATES} candidates a record "
+                             f"that can be rescored: set candidates=dict(max_n_matches=...) to at most that")
+        g = _RecordGrouper(self, others, weights, (int(cand_top_n), cand_threshold), dup_fields, self.master,
+                           None if duplicates is None else duplicates[0], self.master_id, duplicates_id, **options)
+        for o in others:
+            o._join_pending()
+        try:
+            return finish(g)
+        finally:
+            g._release()
+
+    def match_records(self, others, duplicates=None, duplicates_id: Optional[pd.Series] = None, weights=None, candidates=None,
+                      **kwargs) -> pd.DataFrame:
+        """Match RECORDS of several fields.  This corpus holds one field of every record (say the names), ``others`` -- a list
+        of 1 to 7 ``Corpus`` objects -- the further fields (addresses, cities ...): row p of every corpus is record p, which is
+        the caller's duty (append to and remove from all of them together; different lengths: ValueError).  The call is
+        ``match_strings`` with another similarity:
+
+        1. this corpus finds the candidates: its multiply at ``candidates=dict(min_similarity=..., max_n_matches=...)`` (the
+           corpus's own options by default; at most 2 048 a record), served as ``match_strings`` is -- the resident index,
+           the forward and the reverse path, a kept self-join;
+        2. every candidate pair is scored on every further field, on the device, with the very bits
+           ``other.pair_similarities(left_positions, right_positions)`` returns for it;
+        3. ``similarity = weights[0] * s_0 + weights[1] * s_1 + ...`` in this order, in the corpus's dtype, every product and
+           every sum rounded on its own.  ``weights``: one a field, this corpus's first, finite and > 0, equal shares
+           ``1 / (fields)`` by default.  They are used as given: make them sum to 1 and ``min_similarity`` keeps its scale;
+        4. pairs with ``similarity > min_similarity`` stay, a record's pairs are ordered by similarity descending, then
+           position, and the first ``max_n_matches`` stay (``None``: all candidates).
+
+        Candidates never leave the device; only the surviving pairs are downloaded.  ``duplicates``: None -- the records
+        against themselves -- or a list of one Series a field (this corpus's first), equally long, each transformed once
+        with its corpus's vocabulary; ``duplicates_id`` as in ``match_strings``.  Every other option of ``match_strings``
+        (``ignore_index``, ``force_symmetries`` ...) means what it means there, applied to the combined similarity -- so in a
+        self-join a record always matches itself with 1, and with ``force_symmetries`` the list is symmetric.  Vectoriser
+        options that differ from a corpus's: ValueError; explicit ``n_blocks``: NotImplementedError; records x candidates
+        beyond what one result on the device can index (2 * 10^9 cells): ValueError -- there is no block-wise route for
+        records, and the one-field match ``match_strings`` falls back to is never returned in its place.  ``duplicates``
+        whose first Series is ``corpus.master`` are still duplicates: the further Series given are the ones scored.
+
+        The frame is ``match_strings(corpus.master, duplicates[0], corpus.master_id, duplicates_id)``'s, with the combined
+        similarity; there are no per-field columns (``pair_similarities`` of each corpus gives them for the pairs of the
+        frame).  No further corpus is compacted or indexed by the call (``stats['record_calls']`` counts it on every corpus
+        that took part)."""
+        return self._record_call(others, duplicates, duplicates_id, weights, candidates, kwargs, lambda g: g.fit().get_matches())
+
+    def group_similar_records(self, others, weights=None, candidates=None, **kwargs):
+        """For every record the representative of its group of similar records: ``group_similar_strings(corpus.master,
+        corpus.master_id)`` over the match list of ``match_records(others, weights=..., candidates=...)``."""
+        return self._record_call(others, None, None, weights, candidates, kwargs, lambda g: g.fit().get_groups())

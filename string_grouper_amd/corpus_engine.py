@@ -1,6 +1,7 @@
 """The engine's side of a resident corpus (string_grouper_amd/corpus.py): what the corpus keeps on the
 device (``CorpusState``), its rows as the front end sees them (``CorpusMatrix``), and ``CorpusEngine`` -- fit, transform,
-append, remove, compact, refit, the multiplies against the corpus's own indexes and the self-join that is kept.
+append, remove, compact, refit, the multiplies against the corpus's own indexes, named pairs, records of several fields and
+the self-join that is kept.
 
 One rule for device handles: whoever makes one puts it into a scope (``N.Scope``) or into the state, and no function frees
 an argument it was handed -- but the ones whose name says so (``free``, ``drop_whole``, ``drop_kept``, ``corpus_free``)."""
@@ -72,7 +73,7 @@ class CorpusState:
                       "segments": 1, "base_index_builds": 0, "removals": 0, "rows_removed": 0, "dead_rows": 0,
                       "self_join_full": 0, "self_join_served": 0, "self_join_append_updates": 0,
                       "self_join_remove_updates": 0, "self_join_rows_refilled": 0, "idf_refits": 0, "pair_calls": 0,
-                      "pairs_scored": 0}
+                      "pairs_scored": 0, "record_calls": 0}
         if base is not None:
             self.set_segments(CorpusSegment(base), None)
 
@@ -192,8 +193,9 @@ class CorpusMatrix(DeviceMatrix):
 
 class CorpusEngine:
     """The resident-corpus half of ``HipEngine`` (string_grouper_amd/engine.py), which inherits it.  Of the engine it needs
-    ``self.ctx`` (the library context), ``self.timings`` (the dict bench.py reads) and ``self._topn_device`` (the generic
-    top-n multiply, for new rows against the corpus when no index of the corpus serves) -- nothing else."""
+    ``self.ctx`` (the library context), ``self.timings`` (the dict bench.py reads), ``self._topn_device`` (the generic
+    top-n multiply, for new rows against the corpus when no index of the corpus serves) and ``self._match_list_from_topn`` (the
+    fused tail K6, for the list of a record call) -- nothing else."""
     # reverse path of a resident corpus (DESIGN.md section 9): the pair slots (new rows x per-row cap) it may hold; a call
     # whose complete pair list would need more takes the forward path
     CORPUS_PAIR_BUDGET = 1 << 27
@@ -506,6 +508,50 @@ class CorpusEngine:
         state.stats["pair_calls"] += 1
         state.stats["pairs_scored"] += len(left)
         return self.ctx.pairs_dot(rows, rows if other is None else other.csr, left, right)
+
+    # ------------------------------------------------------------------ records of several fields
+    MAX_RECORD_FIELDS = 7                     # sg_topn_rescore: further fields a call
+
+    def corpus_records_topn(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
+                            B_fields: Optional[List[DeviceMatrix]], weights, cand_top_n: int, cand_threshold: float,
+                            top_n: int, threshold: float, self_join_fix: bool, keep_on_device: bool = False):
+        """The match list of RECORDS: the corpus ``state`` finds the candidates, the corpora ``others`` -- row p of every
+        corpus is record p -- score them on their fields, and the weighed sum is filtered, ordered and cut on the device
+        (sg_topn_rescore) before the list is built (K6).  Returns what ``match_list`` returns.
+
+        ``B``: the right-hand rows of the primary field -- ``state.matrix`` itself for a self-join, else the transformed
+        duplicates -- and ``B_fields`` the further fields' (None for a self-join).  The primary multiply is ``_topn_device``'s
+        at (``cand_top_n``, ``cand_threshold``): the resident index, the forward and the reverse path and a kept self-join serve
+        as they do for ``match_strings``.  A further field is read where it lies: ``physical()`` with the dead list, live
+        numbers turned into physical ones by the kernel -- a record call compacts no secondary corpus and builds no index
+        of one.  Every handle made here lives in a scope: the candidates in one that ends with the rescoring, the rescored result
+        in the method's (``_match_list_from_topn`` frees it early, as it frees a multiply's)."""
+        t = time.perf_counter()
+        A = state.matrix
+        self_join = B_fields is None          # (duplicates whose first Series is corpus.master have B is A and fields of their own)
+        if len(others) != len(weights) - 1 or not 1 <= len(others) <= self.MAX_RECORD_FIELDS:
+            raise ValueError(f"between 1 and {self.MAX_RECORD_FIELDS} further fields, and one weight a field, are expected")
+        if self_join and B is not A:
+            raise ValueError("duplicates of the first field without duplicates of the further fields")
+        for k, o in enumerate(others):
+            if o.matrix.shape[0] != A.shape[0]:
+                raise ValueError(f"the corpora differ in length ({o.matrix.shape[0]} and {A.shape[0]} rows): row p of every "
+                                 f"corpus must be record p")
+            if not self_join and B_fields[k].shape[0] != B.shape[0]:
+                raise ValueError(f"the duplicates differ in length ({B_fields[k].shape[0]} and {B.shape[0]} rows)")
+        with N.Scope() as s:
+            with N.Scope() as before:         # the candidates go as soon as they are rescored
+                cand = before.own(self._topn_device(A, B, cand_top_n, cand_threshold))
+                fields = []
+                for k, o in enumerate(others):
+                    rows = o.physical()       # (the state's own cached concatenation when rows wait in a delta)
+                    right = rows if self_join else B_fields[k].csr
+                    fields.append((rows, right, weights[k + 1], o.dead_dev, o.dead_dev if self_join else None))
+                res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n))
+            for st in [state] + list(others):
+                st.stats["record_calls"] += 1
+            # (_match_list_from_topn frees the result once the list is built; if it raises before that, the scope does)
+            return self._match_list_from_topn(res, A.dtype, B.shape[0], self_join_fix, keep_on_device, t)
 
     # ------------------------------------------------------------------ a self-join that is kept (DESIGN.md section 9)
     def corpus_keep_self_join(self, state: CorpusState, top_n: int, threshold: float) -> None:

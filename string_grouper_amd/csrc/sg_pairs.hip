@@ -13,9 +13,8 @@
 // the smaller one is retired and the next one loaded -- a merge by chunks -- and when a chunk of A is retired its products
 // are added lane by lane, lowest first, into an accumulator that every lane of the group holds: the order of the adds is
 // the column order whatever the chunking.
-#include "sg_k4_device.h"
+#include "sg_pairs_device.h"   // the merge itself (pair_rows_dot), shared with sg_rescore.hip
 
-#define SG_PAIR_LANES 8
 #define SG_PAIR_BLOCK 256   // 32 pairs a block
 
 // status word of a call, one bit a cause
@@ -23,24 +22,6 @@
 #define SG_PAIR_BAD_RIGHT 2u      // an entry of `right` outside [0, rows of B)
 #define SG_PAIR_UNSORTED_A 4u     // a row of A that some pair reads is not in strictly ascending column order
 #define SG_PAIR_UNSORTED_B 8u
-
-// entries [lo, hi) of a row, the group's lanes striding over them: does a column fail to exceed the one before it?
-__device__ __forceinline__ bool row_not_ascending(const int32_t *__restrict__ idx, int64_t lo, int64_t hi, int l) {
-    bool bad = false;
-    for (int64_t q = lo + 1 + l; q < hi; q += SG_PAIR_LANES) bad |= idx[q] <= idx[q - 1];
-    return bad;
-}
-
-// the products of a retired chunk of A, lane 0's first: `hits` (group-uniform) has bit s set when lane s holds one
-template <typename T>
-__device__ __forceinline__ T add_in_lane_order(T acc, T prod, uint32_t hits) {
-#pragma unroll
-    for (int s = 0; s < SG_PAIR_LANES; ++s) {
-        const T ps = __shfl(prod, s, SG_PAIR_LANES);
-        if ((hits >> s) & 1u) acc = add_rn<T>(acc, ps);
-    }
-    return acc;
-}
 
 template <typename T>
 __global__ void __launch_bounds__(SG_PAIR_BLOCK) pairs_dot_kernel(
@@ -62,48 +43,9 @@ __global__ void __launch_bounds__(SG_PAIR_BLOCK) pairs_dot_kernel(
     if (check_a && row_not_ascending(a_indices, a0, a1, l)) atomicOr(status, SG_PAIR_UNSORTED_A);
     if (check_b && row_not_ascending(b_indices, b0, b1, l)) atomicOr(status, SG_PAIR_UNSORTED_B);
 
-    // a lane without an entry holds a column no entry has (-2 in A's chunk, -1 in B's: they never meet either)
-    int64_t pa = a0, pb = b0;
-    int ka = pa + l < a1 ? a_indices[pa + l] : -2, kb = pb + l < b1 ? b_indices[pb + l] : -1;
-    T va = pa + l < a1 ? a_data[pa + l] : (T)0, vb = pb + l < b1 ? b_data[pb + l] : (T)0;
-    T acc = (T)0, prod = (T)0;
-    bool hit = false;
-    while (pa < a1 && pb < b1) {
-        int src = -1;
-#pragma unroll
-        for (int s = 0; s < G; ++s)
-            if (__shfl(kb, s, G) == ka) src = s;
-        const T vb_hit = __shfl(vb, src & (G - 1), G);
-        if (src >= 0) {   // (at most once for an entry of A: B's columns are distinct)
-            prod = mul_rn<T>(va, vb_hit);
-            hit = true;
-        }
-        const int64_t in_a = a1 - pa, in_b = b1 - pb;
-        const int last_a = __shfl(ka, (int)(in_a < G ? in_a : G) - 1, G), last_b = __shfl(kb, (int)(in_b < G ? in_b : G) - 1, G);
-        if (last_a <= last_b) {   // nothing further in B meets this chunk of A
-            const uint32_t hits = (uint32_t)(__ballot(hit) >> group_shift) & ((1u << G) - 1u);
-            if (hits) acc = add_in_lane_order<T>(acc, prod, hits);
-            hit = false;
-            pa += G;
-            ka = pa + l < a1 ? a_indices[pa + l] : -2;
-            va = pa + l < a1 ? a_data[pa + l] : (T)0;
-        }
-        if (last_b <= last_a) {
-            pb += G;
-            kb = pb + l < b1 ? b_indices[pb + l] : -1;
-            vb = pb + l < b1 ? b_data[pb + l] : (T)0;
-        }
-    }
-    if (pa < a1) {   // B ran out first: the products the current chunk of A has met so far
-        const uint32_t hits = (uint32_t)(__ballot(hit) >> group_shift) & ((1u << G) - 1u);
-        if (hits) acc = add_in_lane_order<T>(acc, prod, hits);
-    }
+    const T acc = pair_rows_dot<T>(a_indices, a_data, a0, a1, b_indices, b_data, b0, b1, l, group_shift);
     if (l == 0) out[p] = acc;
 }
-
-// Column order is what the merge rests on.  A matrix the vectoriser made has it by construction, one the cosine gate has
-// passed (sg_csr_props) has been measured; any other is checked by the kernel, row by row, for the rows the pairs name.
-static bool known_ascending(const sg_csr *m) { return m->props_state == 1 || (m->props_state == 0 && m->from_vectoriser); }
 
 extern "C" int sg_csr_pairs_dot(sg_ctx *ctx, const sg_csr *A, const sg_csr *B, const int32_t *d_left, const int32_t *d_right,
                                 int64_t n_pairs, void *out_host) {

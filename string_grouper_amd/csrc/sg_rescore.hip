@@ -1,0 +1,292 @@
+// Rescoring a top-n result on further fields (include/sg_hip.h: sg_topn_rescore; DESIGN.md section 4, "Record rescoring").
+// Every candidate (i, j, s_0) of a fixed-stride result is scored on F further pairs of CSR matrices, the scores are weighed into
+//     c = +0.0;  c = rn(c + rn(W_0 * s_0));  for f = 1 .. F:  c = rn(c + rn(W_f * s_f))
+// and every row is filtered (c > threshold), ordered (c descending by value, then column ascending) and cut.  Candidates never
+// leave the device: what the named-pairs route moves through the host per field -- two position lists up, the scores down --
+// is read here where the multiply left it.
+//
+// Two launches.  rescore_score_kernel: SG_PAIR_LANES lanes a row (of at most SG_RESCORE_CHUNK of its entries; a longer row is
+// dealt to several groups), field by field: the row of A_f is found once, then the group walks the row's candidates with the
+// merge of sg_pairs_device.h -- pairs_dot_kernel's, so s_f is sg_csr_pairs_dot's value to the bit -- and lane 0 keeps c in a
+// scratch array of the candidates' shape.  rescore_select_*_kernel: a rank by counting -- an entry's place is the number of
+// kept entries of its row that go before it -- which needs no sort network and no exchange between lanes: eight lanes a row
+// reading the row's few scores from cache for a row of at most 64 candidates (rows of name lists hold about four), a block
+// with the row in LDS for the rows above that (up to 2 048 entries), which the first kernel lists on the device.
+#include "sg_pairs_device.h"
+
+#define SG_RESCORE_BLOCK 256
+#define SG_RESCORE_CHUNK 64        // entries of a row one group scores
+#define SG_RESCORE_MAX_FIELDS 7
+#define SG_RESCORE_MAX_STRIDE 2048
+#define SG_RESCORE_SHORT 64        // rows of up to this many candidates: eight lanes select them; above: a block
+
+// status word of a call: bit 0 a candidate column outside [0, N); bit 1 + 2 f / 2 + 2 f a row of A_f / B_f that a candidate
+// reads and that is not in strictly ascending column order
+#define SG_RESCORE_BAD_COLUMN 1u
+
+template <typename T>
+struct RescoreField {
+    const int64_t *a_indptr;
+    const int32_t *a_indices;
+    const T *a_data;
+    const int64_t *b_indptr;
+    const int32_t *b_indices;
+    const T *b_data;
+    const int32_t *dead_a, *dead_b;   // dead PHYSICAL rows, ascending and distinct (null: none)
+    int32_t n_dead_a, n_dead_b;
+    int32_t check_a, check_b;         // != 0: the matrix is not known to be sorted, look at the rows that are read
+    T w;
+};
+template <typename T>
+struct RescoreFields {
+    RescoreField<T> f[SG_RESCORE_MAX_FIELDS];
+};
+
+// live row -> physical row: live + #{q : dead[q] - q <= live} (CorpusState.physical_rows: searchsorted(dead - arange, live,
+// side="right")).  dead[q] - q never falls as q grows, so the count is found by bisection.  The result is at most
+// live + n_dead: inside the matrix whenever its rows are the live rows + n_dead, whatever the list holds.
+__device__ __forceinline__ int64_t physical_row(int64_t live, const int32_t *__restrict__ dead, int32_t n_dead) {
+    int32_t lo = 0, hi = n_dead;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if ((int64_t)dead[mid] - mid <= live) lo = mid + 1;
+        else hi = mid;
+    }
+    return live + lo;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(SG_RESCORE_BLOCK) rescore_score_kernel(
+    const int32_t *__restrict__ cols, const T *__restrict__ vals, const int32_t *__restrict__ counts, int64_t n_rows,
+    int64_t n_cols, int32_t stride, int32_t chunks, T w0, RescoreFields<T> fields, int32_t n_fields, uint32_t *status,
+    T *__restrict__ comb) {
+    constexpr int G = SG_PAIR_LANES;
+    const int l = threadIdx.x & (G - 1);
+    const int group_shift = threadIdx.x & (SG_WAVE - 1) & ~(G - 1);   // the group's first lane in its wave
+    const int64_t g = ((int64_t)blockIdx.x * SG_RESCORE_BLOCK + threadIdx.x) / G;
+    const int64_t row = g / chunks;
+    if (row >= n_rows) return;   // (everything below is uniform over the group: its lanes leave, loop and shuffle together)
+    int32_t cnt = counts[row];
+    cnt = cnt < 0 ? 0 : (cnt > stride ? stride : cnt);
+    const int32_t e0 = (int32_t)(g - row * chunks) * SG_RESCORE_CHUNK;
+    const int32_t e1 = cnt < e0 + SG_RESCORE_CHUNK ? cnt : e0 + SG_RESCORE_CHUNK;
+    if (e0 >= e1) return;
+    const int64_t base = row * (int64_t)stride;
+    for (int f = 0; f < n_fields; ++f) {
+        const RescoreField<T> &F = fields.f[f];
+        const int64_t a = physical_row(row, F.dead_a, F.n_dead_a);
+        const int64_t a0 = F.a_indptr[a], a1 = F.a_indptr[a + 1];
+        if (F.check_a && row_not_ascending(F.a_indices, a0, a1, l)) atomicOr(status, 2u << (2 * f));
+        for (int32_t e = e0; e < e1; ++e) {
+            const int64_t j = cols[base + e];
+            if (j < 0 || j >= n_cols) {   // nothing of a field is read for it; the call is refused
+                if (l == 0 && f == 0) {
+                    atomicOr(status, SG_RESCORE_BAD_COLUMN);
+                    comb[base + e] = (T)NAN;
+                }
+                continue;
+            }
+            const int64_t b = physical_row(j, F.dead_b, F.n_dead_b);
+            const int64_t b0 = F.b_indptr[b], b1 = F.b_indptr[b + 1];
+            if (F.check_b && row_not_ascending(F.b_indices, b0, b1, l)) atomicOr(status, 4u << (2 * f));
+            const T s = pair_rows_dot<T>(F.a_indices, F.a_data, a0, a1, F.b_indices, F.b_data, b0, b1, l, group_shift);
+            if (l == 0) {   // (lane 0 alone reads and writes the candidate's c: its own stores, in program order)
+                const T c = f == 0 ? add_rn<T>((T)0, mul_rn<T>(w0, vals[base + e])) : comb[base + e];
+                comb[base + e] = add_rn<T>(c, mul_rn<T>(F.w, s));
+            }
+        }
+    }
+}
+
+// An entry that fails the filter takes part in nothing: as a NaN it neither goes before another entry nor equals one.
+template <typename T>
+__device__ __forceinline__ T kept_or_nan(T c, T threshold) {
+    return c > threshold ? c : (T)NAN;
+}
+// does the kept entry (cq, jq) at place q go before the kept entry (c, j) at place e?  By value (zeros of either sign are
+// equal), then by column, then -- for a caller-made result that names a column twice -- by place, so that ranks are distinct.
+template <typename T>
+__device__ __forceinline__ bool goes_before(T cq, int32_t jq, int32_t q, T c, int32_t j, int32_t e) {
+    return cq > c || (cq == c && (jq < j || (jq == j && q < e)));
+}
+
+template <typename T>
+__global__ void __launch_bounds__(SG_RESCORE_BLOCK) rescore_select_short_kernel(
+    const int32_t *__restrict__ cols, const T *__restrict__ comb, const int32_t *__restrict__ counts, int64_t n_rows,
+    int32_t stride, T threshold, int32_t stride_out, int32_t *__restrict__ out_cols, T *__restrict__ out_vals,
+    int32_t *__restrict__ out_counts, int32_t *__restrict__ long_rows, uint32_t *n_long) {
+    constexpr int G = SG_PAIR_LANES;
+    const int l = threadIdx.x & (G - 1);
+    const int64_t row = ((int64_t)blockIdx.x * SG_RESCORE_BLOCK + threadIdx.x) / G;
+    if (row >= n_rows) return;
+    int32_t cnt = counts[row];
+    cnt = cnt < 0 ? 0 : (cnt > stride ? stride : cnt);
+    if (cnt > SG_RESCORE_SHORT) {   // (only with a stride above SG_RESCORE_SHORT: the list is there) a block's row
+        if (l == 0) long_rows[atomicAdd(n_long, 1u)] = (int32_t)row;
+        return;
+    }
+    const int32_t *rc = cols + row * (int64_t)stride;
+    const T *rs = comb + row * (int64_t)stride;
+    const int64_t out = row * (int64_t)stride_out;
+    for (int32_t e = l; e < cnt; e += G) {
+        const T c = kept_or_nan<T>(rs[e], threshold);
+        if (!(c == c)) continue;
+        const int32_t j = rc[e];
+        int32_t rank = 0;
+        for (int32_t q = 0; q < cnt; ++q) rank += goes_before<T>(kept_or_nan<T>(rs[q], threshold), rc[q], q, c, j, e) ? 1 : 0;
+        if (rank < stride_out) {
+            out_cols[out + rank] = j;
+            out_vals[out + rank] = c;
+        }
+    }
+    if (l == 0) {
+        int32_t kept = 0;
+        for (int32_t q = 0; q < cnt; ++q) kept += rs[q] > threshold ? 1 : 0;
+        out_counts[row] = kept < stride_out ? kept : stride_out;
+    }
+}
+
+// The rows the short kernel listed (more than SG_RESCORE_SHORT candidates), a block a row at a time: the grid is fixed, a block
+// takes the list's entries blockIdx.x, blockIdx.x + gridDim.x, ...  The order of the list is the order the groups arrived in;
+// every row is written by its own block alone, so it shows nowhere.
+template <typename T>
+__global__ void __launch_bounds__(SG_RESCORE_BLOCK) rescore_select_block_kernel(
+    const int32_t *__restrict__ cols, const T *__restrict__ comb, const int32_t *__restrict__ counts, int32_t stride,
+    T threshold, int32_t stride_out, int32_t *__restrict__ out_cols, T *__restrict__ out_vals,
+    int32_t *__restrict__ out_counts, const int32_t *__restrict__ long_rows, const uint32_t *__restrict__ n_long) {
+    __shared__ T s_c[SG_RESCORE_MAX_STRIDE];
+    __shared__ int32_t s_j[SG_RESCORE_MAX_STRIDE];
+    __shared__ int32_t s_kept;
+    const uint32_t n = *n_long;
+    for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) {
+        const int64_t row = long_rows[k];
+        int32_t cnt = counts[row];
+        cnt = cnt < 0 ? 0 : (cnt > stride ? stride : cnt);   // (stride <= SG_RESCORE_MAX_STRIDE: checked by the driver)
+        const int64_t base = row * (int64_t)stride, out = row * (int64_t)stride_out;
+        if (threadIdx.x == 0) s_kept = 0;
+        __syncthreads();
+        int32_t mine = 0;
+        for (int32_t e = threadIdx.x; e < cnt; e += SG_RESCORE_BLOCK) {
+            const T c = kept_or_nan<T>(comb[base + e], threshold);
+            s_c[e] = c;
+            s_j[e] = cols[base + e];
+            mine += c == c ? 1 : 0;
+        }
+        if (mine) atomicAdd(&s_kept, mine);
+        __syncthreads();
+        for (int32_t e = threadIdx.x; e < cnt; e += SG_RESCORE_BLOCK) {
+            const T c = s_c[e];
+            if (!(c == c)) continue;
+            const int32_t j = s_j[e];
+            int32_t rank = 0;
+            for (int32_t q = 0; q < cnt; ++q) rank += goes_before<T>(s_c[q], s_j[q], q, c, j, e) ? 1 : 0;
+            if (rank < stride_out) {
+                out_cols[out + rank] = j;
+                out_vals[out + rank] = c;
+            }
+        }
+        if (threadIdx.x == 0) out_counts[row] = s_kept < stride_out ? s_kept : stride_out;
+        __syncthreads();   // the next row reuses the block's LDS
+    }
+}
+
+template <typename T>
+static int rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
+                   double threshold, sg_topn *r, uint32_t *d_status, void *d_comb, int32_t *d_long_rows) {
+    RescoreFields<T> dev;
+    memset(&dev, 0, sizeof(dev));
+    for (int f = 0; f < n_fields; ++f) {
+        const sg_rescore_field &h = fields[f];
+        RescoreField<T> &d = dev.f[f];
+        d.a_indptr = h.A->d_indptr, d.a_indices = h.A->d_indices, d.a_data = (const T *)h.A->d_data;
+        d.b_indptr = h.B->d_indptr, d.b_indices = h.B->d_indices, d.b_data = (const T *)h.B->d_data;
+        d.dead_a = h.d_dead_a, d.dead_b = h.d_dead_b, d.n_dead_a = h.n_dead_a, d.n_dead_b = h.n_dead_b;
+        d.check_a = known_ascending(h.A) ? 0 : 1, d.check_b = known_ascending(h.B) ? 0 : 1;
+        d.w = (T)h.weight;
+    }
+    constexpr int per_block = SG_RESCORE_BLOCK / SG_PAIR_LANES;
+    const int32_t chunks = (cand->stride + SG_RESCORE_CHUNK - 1) / SG_RESCORE_CHUNK;
+    const int64_t score_blocks = (cand->n_rows * chunks + per_block - 1) / per_block;
+    hipLaunchKernelGGL(rescore_score_kernel<T>, dim3((unsigned)score_blocks), dim3(SG_RESCORE_BLOCK), 0, ctx->stream,
+                       cand->d_cols, (const T *)cand->d_vals, cand->d_counts, cand->n_rows, cand->n_cols, cand->stride, chunks,
+                       (T)w0, dev, n_fields, d_status, (T *)d_comb);
+    SG_HIP_TRY(hipGetLastError());
+    // the select kernel is chosen ROW BY ROW: eight lanes for a row of up to SG_RESCORE_SHORT candidates, whatever the stride;
+    // the rows above it are listed on the device (no read-back) and taken by a fixed grid of blocks
+    const int64_t blocks = (cand->n_rows + per_block - 1) / per_block;
+    hipLaunchKernelGGL(rescore_select_short_kernel<T>, dim3((unsigned)blocks), dim3(SG_RESCORE_BLOCK), 0, ctx->stream,
+                       cand->d_cols, (const T *)d_comb, cand->d_counts, cand->n_rows, cand->stride, (T)threshold, r->stride,
+                       r->d_cols, (T *)r->d_vals, r->d_counts, d_long_rows, d_status + 1);
+    if (cand->stride > SG_RESCORE_SHORT) {
+        SG_HIP_TRY(hipGetLastError());
+        const int64_t grid = std::min<int64_t>(cand->n_rows, (int64_t)ctx->num_cu * 8);
+        hipLaunchKernelGGL(rescore_select_block_kernel<T>, dim3((unsigned)grid), dim3(SG_RESCORE_BLOCK), 0, ctx->stream,
+                           cand->d_cols, (const T *)d_comb, cand->d_counts, cand->stride, (T)threshold, r->stride, r->d_cols,
+                           (T *)r->d_vals, r->d_counts, d_long_rows, d_status + 1);
+    }
+    SG_HIP_TRY(hipGetLastError());
+    return SG_OK;
+}
+
+static bool weight_ok(double w, int32_t dtype) { return std::isfinite(w) && (dtype == SG_F64 || std::isfinite((float)w)); }
+
+extern "C" int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
+                               double threshold, int32_t top_n, sg_topn **out) {
+    SG_REQUIRE(ctx && cand && out, "null argument");
+    SG_REQUIRE(n_fields >= 1 && n_fields <= SG_RESCORE_MAX_FIELDS, "between 1 and 7 further fields are expected");
+    SG_REQUIRE(fields != nullptr, "null argument");
+    SG_REQUIRE(top_n >= 1, "top_n must be at least 1");
+    SG_REQUIRE(cand->stride >= 1 && cand->stride <= SG_RESCORE_MAX_STRIDE, "the candidates' stride exceeds 2048: ask the multiply for fewer a row");
+    SG_REQUIRE(weight_ok(w0, cand->dtype), "a weight is not finite");
+    for (int f = 0; f < n_fields; ++f) {
+        const sg_rescore_field &h = fields[f];
+        SG_REQUIRE(h.A && h.B, "a field's matrix is null");
+        SG_REQUIRE(weight_ok(h.weight, cand->dtype), "a weight is not finite");
+        SG_REQUIRE(h.A->dtype == cand->dtype && h.B->dtype == cand->dtype, "a field's matrices differ from the candidates in value type");
+        SG_REQUIRE(h.A->n_cols == h.B->n_cols, "a field's matrices differ in shape (their columns)");
+        SG_REQUIRE(h.n_dead_a >= 0 && h.n_dead_b >= 0 && (h.n_dead_a == 0 || h.d_dead_a) && (h.n_dead_b == 0 || h.d_dead_b),
+                   "a list of dead rows is null or has a negative length");
+        SG_REQUIRE(h.A->n_rows - h.n_dead_a == cand->n_rows, "a field's left matrix has not the candidates' rows (dead rows apart)");
+        SG_REQUIRE(h.B->n_rows - h.n_dead_b == cand->n_cols, "a field's right matrix has not the candidates' columns as rows (dead rows apart)");
+    }
+    constexpr int per_block = SG_RESCORE_BLOCK / SG_PAIR_LANES;
+    const int64_t chunks = (cand->stride + SG_RESCORE_CHUNK - 1) / SG_RESCORE_CHUNK;
+    if ((cand->n_rows * chunks + per_block - 1) / per_block > INT32_MAX || cand->n_rows > INT32_MAX) {
+        sg_set_error("%lld rows of candidates exceed one launch: rescore them in pieces", (long long)cand->n_rows);
+        return SG_ERR_OVERFLOW;
+    }
+    for (int f = 0; f < n_fields; ++f) {
+        if (fields[f].A->rows_of) SG_TRY(sg_csr_ensure_rows(ctx, fields[f].A));
+        if (fields[f].B->rows_of && fields[f].B != fields[f].A) SG_TRY(sg_csr_ensure_rows(ctx, fields[f].B));
+    }
+    TopnPtr r;
+    SG_TRY(topn_alloc(ctx, cand->n_rows, cand->n_cols, std::min<int32_t>(top_n, cand->stride), cand->dtype, &r));
+    if (cand->n_rows == 0) {
+        *out = r.release();
+        return SG_OK;
+    }
+    const size_t s = cand->dtype == SG_F64 ? 8 : 4, head = 16;   // the status word and the long rows' counter, then c of every candidate
+    Scratch tmp(ctx);
+    char *d_buf = nullptr;
+    SG_TRY(tmp.alloc(head + (size_t)cand->n_rows * (size_t)cand->stride * s, &d_buf));
+    int32_t *d_long_rows = nullptr;   // the rows of more than SG_RESCORE_SHORT candidates (word 1 of the head counts them)
+    if (cand->stride > SG_RESCORE_SHORT) SG_TRY(tmp.alloc((size_t)cand->n_rows, &d_long_rows));
+    SG_HIP_TRY(hipMemsetAsync(d_buf, 0, head, ctx->stream));
+    SG_TRY(by_dtype(cand->dtype, [&](auto t) {
+        return rescore<decltype(t)>(ctx, cand, w0, fields, n_fields, threshold, r.get(), (uint32_t *)d_buf, d_buf + head, d_long_rows);
+    }));
+    uint32_t status = 0;
+    SG_TRY(sg_fetch(ctx, &status, d_buf, 4));   // the one read-back
+    if (status) {
+        std::string what;
+        if (status & SG_RESCORE_BAD_COLUMN) what += "a candidate's column lies outside the result's columns; ";
+        for (int f = 0; f < n_fields; ++f) {
+            if (status & (2u << (2 * f))) what += "a row of field " + std::to_string(f + 1) + "'s left matrix that a candidate reads is not sorted by column (strictly ascending); ";
+            if (status & (4u << (2 * f))) what += "a row of field " + std::to_string(f + 1) + "'s right matrix that a candidate reads is not sorted by column (strictly ascending); ";
+        }
+        sg_set_error("bad argument: %s", what.c_str());
+        return SG_ERR_BADARG;
+    }
+    *out = r.release();
+    return SG_OK;
+}

@@ -361,10 +361,8 @@ class StringGrouper(object):
             # symmetrise, compaction (K3 + K4 + K6); only (master_side, dupe_side, similarity) comes back
             eng = _engine_mod.get_engine()
             fix = bool(self._config.force_symmetries and self._duplicates is None)
-            keep = 'keep_on_device' in inspect.signature(eng.match_list).parameters   # engine doubles may lack it
             try:
-                out = eng.match_list(master_matrix, duplicate_matrix, self._max_n_matches, self._config.min_similarity,
-                                     fix, **({'keep_on_device': True} if keep else {}))
+                out = self._engine_match_list(eng, master_matrix, duplicate_matrix, fix)
             except OverflowError:
                 # the one exception the reference's fit() handles (string_grouper.py:397-413): fall back to the
                 # block-wise multiply with the reference's own guess of the split
@@ -408,6 +406,13 @@ class StringGrouper(object):
         self._matches_list = self._get_matches_list(matches)
         self.is_build = True
         return self
+
+    def _engine_match_list(self, eng, master_matrix, duplicate_matrix, fix: bool):
+        """The engine call behind the fused tail: (master_side, dupe_side, similarity, true_max_n_matches[, the list on the
+        device]).  A subclass whose list comes from another pipeline of the engine overrides it (corpus.py: records)."""
+        keep = 'keep_on_device' in inspect.signature(eng.match_list).parameters   # engine doubles may lack it
+        return eng.match_list(master_matrix, duplicate_matrix, self._max_n_matches, self._config.min_similarity,
+                              fix, **({'keep_on_device': True} if keep else {}))
 
     def _can_fuse_on_device(self) -> bool:
         """The fused device tail is used unless a caller replaced one of the hooks the reference exposes
