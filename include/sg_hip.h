@@ -61,9 +61,9 @@ const char *sg_last_error(void);
  * grew; round 5: 3 -- sg_stats.prune_scored; 4 -- sg_topn_transpose_select; 5 -- sg_csr_concat; 6 -- sg_csr_select_rows,
  * sg_topn_drop_columns, sg_device_upload; 7 -- sg_topn_concat_rows, sg_topn_forget, sg_topn_put_rows, sg_csr_take_rows,
  * sg_device_download; 8 -- sg_csr_row_norms, sg_csr_vectoriser_words, sg_csr_column_counts, sg_vec_reweigh; 9 --
- * sg_csr_pairs_dot; 10 -- sg_topn_rescore, sg_rescore_field); a binding compares it with the value it was written for right
- * after loading the library. */
-#define SG_ABI_VERSION 10
+ * sg_csr_pairs_dot; 10 -- sg_topn_rescore, sg_rescore_field; 11 -- sg_topn_union); a binding compares it with the value it was
+ * written for right after loading the library. */
+#define SG_ABI_VERSION 11
 int sg_abi_version(void);
 int sg_device_count(int *count);
 /* hip_stream: a hipStream_t to launch on (e.g. torch.cuda.current_stream().cuda_stream), or NULL
@@ -473,7 +473,8 @@ int sg_topn_put_rows(sg_ctx *ctx, sg_topn *r, const int32_t *d_rows, int64_t n_r
 
 /* ------------------------------------------------------------------ record matching: a result rescored on further fields */
 /* A record has several fields (name, address, city ...), each with its own matrices.  sg_topn_rescore takes the candidates one
- * field's multiply found -- cand: R rows, N columns, stride S, counts -- scores every one of them on F further fields, weighs
+ * field's multiply found (or several fields' multiplies, united by sg_topn_union below) -- cand: R rows, N columns, stride S,
+ * counts -- scores every one of them on F further fields, weighs
  * the scores into one, and filters, orders and cuts every row anew.  Candidates never leave the device.  (The reference has no
  * analogue: it matches one column of strings, string_grouper.py:55-153; its users combine fields in pandas.)
  *
@@ -510,6 +511,33 @@ typedef struct {
 } sg_rescore_field;
 int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
                     double threshold, int32_t top_n, sg_topn **out);
+/* sg_topn_union: the candidates of SEVERAL fields' multiplies as one candidate result.  Two records that agree on address and
+ * city but whose names fall below the candidate threshold are never compared when the names alone find the candidates; record
+ * linkage takes the candidates from the union of several fields' matches instead.  (The reference has no analogue: it matches
+ * one column of strings, string_grouper.py:55-153; its users unite per-field frames in pandas.)
+ *
+ * parts[0 .. P), P in 2 .. 8: fixed-stride results over the same records -- R rows, N columns, one value type; the strides S_p
+ * may differ.  Of row i of part p the first clamp(counts_p[i], 0, S_p) entries count, as in sg_topn_rescore.  parts[0] is the
+ * PRIMARY field's result and its values are that field's scores; of the other parts only the columns are read.  `primary`: the
+ * primary field's A, B and dead-row lists with the meaning they have in sg_topn_rescore (its weight is ignored).
+ *   row i of *out   the distinct columns that row i of any part names, in ascending column order; counts[i] is their number
+ *                   (a column that one part names twice -- only a caller-made part can -- counts once).
+ *   value of j      part 0's row i holds j: the bits of that entry, as they are (NaN, inf, the sign of a zero; named twice:
+ *                   the entry at the lowest place).  Otherwise (A . B^T)[a, b] exactly as sg_csr_pairs_dot / sg_topn_rescore
+ *                   state it -- a, b from the live numbers i, j through the dead lists, ascending column, every product and
+ *                   every sum rounded on its own, from +0.0: what the primary multiply would have written for the pair.
+ * *out has R rows, N columns, the parts' value type and the stride max(1, largest counts[i]), which comes back together with
+ * the status word in the call's single read-back.  The parts are only read.  The result feeds sg_topn_rescore like a
+ * multiply's (its rows are in column order, not score order: sg_topn_rescore orders anew).
+ * Refusals (SG_ERR_BADARG; nothing is returned, and the next call works):
+ *   seen on the host     n_parts outside 2 .. 8; parts that differ in rows, columns or value type; the sum of the S_p above
+ *                        2048; a primary whose matrices differ from the parts in value type, or from each other in columns;
+ *                        rows(A) - n_dead_a != R or rows(B) - n_dead_b != N;
+ *   seen on the device   a counted column outside [0, N) -- nothing is read for it --, or a row of A or B that a filled
+ *                        candidate reads whose columns are not strictly ascending, for a matrix not known to be sorted: one
+ *                        status word, a bit a cause.
+ * R x stride beyond the 32-bit result index: SG_ERR_OVERFLOW. */
+int sg_topn_union(sg_ctx *ctx, const sg_topn *const *parts, int32_t n_parts, const sg_rescore_field *primary, sg_topn **out);
 
 /* ------------------------------------------------------------------ measurement */
 enum { SG_K_TOKENIZE = 0, SG_K_WEIGHT = 1, SG_K_POSTINGS = 2, SG_K_SPGEMM = 3 /* the multiply's whole launch group */,

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SG_HIP_LIB") or os.path.join(_HERE, "libsg_hip.so")
 
 SG_OK, SG_ERR_BADARG, SG_ERR_OOM, SG_ERR_OVERFLOW, SG_ERR_HIP, SG_ERR_NODEVICE, SG_ERR_UNSUPPORTED = range(7)
 SG_F32, SG_F64 = 0, 1
-ABI_VERSION = 10         # include/sg_hip.h: SG_ABI_VERSION
+ABI_VERSION = 11       # include/sg_hip.h: SG_ABI_VERSION
 SG_K_TOKENIZE, SG_K_WEIGHT, SG_K_POSTINGS, SG_K_SPGEMM, SG_K_ZIP, SG_K_VOCAB, SG_K_SPGEMM_KERNEL, SG_K_COUNT = range(8)
 KERNEL_NAMES = ("tokenize", "weight", "postings", "spgemm_topn", "zip", "vocab", "spgemm_kernel")
 
@@ -124,6 +124,7 @@ ABI = {
     "sg_csr_rowwise_dot": (C.c_int, [_P, _P, _P, _P]),
     "sg_csr_pairs_dot": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P]),
     "sg_topn_rescore": (C.c_int, [_P, _P, C.c_double, C.POINTER(SgRescoreField), C.c_int32, C.c_double, C.c_int32, _PP]),
+    "sg_topn_union": (C.c_int, [_P, C.POINTER(_P), C.c_int32, C.POINTER(SgRescoreField), _PP]),
     "sg_csr_row_norms": (C.c_int, [_P, _PP]),
     "sg_csr_vectoriser_words": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int32)]),
     "sg_csr_column_counts": (C.c_int, [_P, _P, _P]),
@@ -867,6 +868,24 @@ class Context:
                                     0 if dead_b is None else len(dead_b))
         out = C.c_void_p()
         check(lib().sg_topn_rescore(self.h, cand.h, float(w0), arr, len(fields), float(threshold), int(top_n), C.byref(out)))
+        return TopN(self, out)
+
+    def topn_union(self, parts, primary) -> TopN:
+        """The candidates of several fields' multiplies over the same records as ONE candidate result (include/sg_hip.h:
+        sg_topn_union).  ``parts``: 2 to 8 ``TopN`` of the same rows, columns and dtype, the primary field's first;
+        ``primary``: ``(A: Csr, B: Csr, dead_a: DeviceInts | None, dead_b: DeviceInts | None)`` of the primary field, as a
+        field of ``topn_rescore``.  A row of the result holds the distinct columns its parts name, ascending; a column of
+        ``parts[0]`` keeps its bits, any other gets the primary field's score of the pair, bit for bit the multiply's.  The
+        stride is the longest row (at least 1).  The parts are only read.  A refusal of the device (a column outside the
+        result, an unsorted row that a filled candidate reads): ValueError."""
+        parts = list(parts)
+        arr = (C.c_void_p * max(len(parts), 1))(*[getattr(p.h, "value", p.h) for p in parts])
+        A, B, dead_a, dead_b = primary
+        a, b = (getattr(m.h, "value", m.h) for m in (A, B))
+        field = SgRescoreField(a, b, 1.0, None if dead_a is None else dead_a.ptr, 0 if dead_a is None else len(dead_a),
+                               None if dead_b is None else dead_b.ptr, 0 if dead_b is None else len(dead_b))
+        out = C.c_void_p()
+        check(lib().sg_topn_union(self.h, arr, len(parts), C.byref(field), C.byref(out)))
         return TopN(self, out)
 
     def download_ints(self, d_ints, n: Optional[int] = None) -> np.ndarray:

@@ -150,8 +150,11 @@ class _RecordGrouper(_CorpusGrouper):
     list -- the frames, the groups -- is StringGrouper's own."""
 
     def __init__(self, corpus: "Corpus", others, weights, cand, dup_fields, master, duplicates=None, master_id=None,
-                 duplicates_id=None, **kwargs):
+                 duplicates_id=None, candidate_fields=(0,), **kwargs):
+        """``cand``: (max_n_matches, min_similarity) of the candidates -- with ``candidate_fields`` other than ``(0,)`` a list
+        of them, one a candidate field (CorpusEngine.corpus_records_union_topn)."""
         self._others, self._weights, self._cand, self._dup_fields = others, weights, cand, dup_fields
+        self._candidate_fields = tuple(candidate_fields)
         super().__init__(corpus, master, duplicates, master_id, duplicates_id, **kwargs)
 
     def _can_fuse_on_device(self) -> bool:
@@ -161,6 +164,8 @@ class _RecordGrouper(_CorpusGrouper):
         fields = None
         if self._dup_fields is not None:                             # one transform a field (duplicates[0] may be corpus.master)
             fields = [o._rows_of(series, self._made) for o, series in zip(self._others, self._dup_fields)]
+        if self._candidate_fields != (0,):
+            return self._union_match_list(eng, duplicate_matrix, fields, fix)
         cand_top_n, cand_threshold = self._cand
         top_n = cand_top_n if self._max_n_matches is None else min(int(self._max_n_matches), cand_top_n)
         keep = 'keep_on_device' in inspect.signature(eng.corpus_records_topn).parameters   # engine doubles may lack it
@@ -173,6 +178,19 @@ class _RecordGrouper(_CorpusGrouper):
             # block-wise route for records, so the call is refused instead
             raise ValueError(f"records x candidates exceed what one result on the device can index ({e}): lower "
                              f"candidates['max_n_matches'] (now {cand_top_n}) or match the records in batches of duplicates") from e
+
+    def _union_match_list(self, eng, duplicate_matrix, fields, fix: bool):
+        """Candidates from several fields: every candidate field's multiply, united and rescored on the device."""
+        all_candidates = sum(k for k, _ in self._cand)
+        top_n = all_candidates if self._max_n_matches is None else min(int(self._max_n_matches), all_candidates)
+        try:
+            return eng.corpus_records_union_topn(self._corpus._live(), [o._live() for o in self._others], duplicate_matrix, fields,
+                                                 self._weights, self._candidate_fields, self._cand, top_n,
+                                                 self._config.min_similarity, fix, keep_on_device=True)
+        except OverflowError as e:            # (as for one candidate field: there is no block-wise route for records)
+            raise ValueError(f"records x candidates exceed what one result on the device can index ({e}): lower "
+                             f"candidates['max_n_matches'] (now {[k for k, _ in self._cand]} on the fields "
+                             f"{list(self._candidate_fields)}) or match the records in batches of duplicates") from e
 
 
 class Corpus:
@@ -422,7 +440,8 @@ class Corpus:
         ``self_join_rows_refilled`` (rows a remove had to multiply again); ``idf_refits`` (calls of ``refit_idf``);
         ``pair_calls`` / ``pairs_scored`` (calls of ``pair_similarities`` that reached the device, and their pairs);
         ``record_calls`` (calls of ``match_records`` / ``group_similar_records`` this corpus took part in, as the one that
-        finds the candidates or as a further field)."""
+        finds the candidates or as a further field) and ``record_union_calls`` (those of them with several
+        ``candidate_fields``, counted on the corpora that found candidates)."""
         return dict(self._live().stats)
 
     def _rows_of(self, series, made):
@@ -517,7 +536,7 @@ class Corpus:
                     csr.free()
 
     # ------------------------------------------------------------------ records of several fields
-    def _record_call(self, others, duplicates, duplicates_id, weights, candidates, kwargs, finish):
+    def _record_call(self, others, duplicates, duplicates_id, weights, candidates, kwargs, finish, candidate_fields=(0,)):
         """The checks of ``match_records`` / ``group_similar_records``, then the call."""
         state = self._live()
         self._same_engine()
@@ -572,24 +591,55 @@ class Corpus:
             dup_fields = list(duplicates[1:])
         elif duplicates_id is not None:
             raise ValueError("duplicates_id without duplicates")
-        # candidates: the two options of the primary multiply
+        # candidate_fields: the fields whose multiplies find the candidates (0: this corpus, k: others[k - 1])
+        if isinstance(candidate_fields, (str, bytes)) or not hasattr(candidate_fields, "__iter__"):
+            raise TypeError("candidate_fields must be a sequence of field positions (0: this corpus, k: others[k - 1])")
+        candidate_fields = tuple(candidate_fields)
+        if not all(isinstance(f, (int, np.integer)) and not isinstance(f, (bool, np.bool_)) for f in candidate_fields):
+            raise TypeError("candidate_fields must be a sequence of field positions (0: this corpus, k: others[k - 1])")
+        candidate_fields = tuple(int(f) for f in candidate_fields)
+        if not all(0 <= f <= len(others) for f in candidate_fields):
+            raise ValueError(f"candidate_fields={candidate_fields}: positions between 0 and {len(others)} are expected for "
+                             f"{len(others) + 1} fields")
+        if 0 not in candidate_fields or any(a >= b for a, b in zip(candidate_fields, candidate_fields[1:])):
+            raise ValueError(f"candidate_fields={candidate_fields}: distinct positions in ascending order, 0 (this corpus) among "
+                             f"them, are expected")
+        if candidate_fields != (0,) and not hasattr(self._engine, "corpus_records_union_topn"):
+            raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} unites no "
+                                      f"candidates of several fields")
+        # candidates: the two options of a candidate field's multiply -- one dict for every candidate field, or one a field
         candidates = {} if candidates is None else candidates
-        if not isinstance(candidates, dict) or set(candidates) - {"min_similarity", "max_n_matches"}:
-            raise TypeError("candidates takes min_similarity and max_n_matches only, as a dict")
-        cand_threshold = float(candidates.get("min_similarity", self._config.min_similarity))
-        cand_top_n = candidates.get("max_n_matches", self._config.max_n_matches)
+        if isinstance(candidates, list) and all(isinstance(c, dict) for c in candidates):
+            if len(candidates) != len(candidate_fields):
+                raise ValueError(f"{len(candidates)} candidates dicts for {len(candidate_fields)} candidate fields: one a "
+                                 f"candidate field (or one for all) is expected")
+        else:
+            candidates = [candidates] * len(candidate_fields)
         n_right = n if duplicates is None else len(duplicates[0])
-        if cand_top_n is None:
-            cand_top_n = n_right
-        if isinstance(cand_top_n, (bool, np.bool_)) or not isinstance(cand_top_n, (int, np.integer)) or cand_top_n < 1:
-            if n_right > 0:
-                raise ValueError(f"candidates: max_n_matches={cand_top_n!r}: a whole number of at least 1 is expected")
-            cand_top_n = 1
-        if cand_top_n > self.MAX_RECORD_CANDIDATES:
-            raise ValueError(f"candidates: max_n_matches={cand_top_n} exceeds the {self.MAX_RECORD_CANDIDATES} candidates a record "
-                             f"that can be rescored: set candidates=dict(max_n_matches=...) to at most that")
-        g = _RecordGrouper(self, others, weights, (int(cand_top_n), cand_threshold), dup_fields, self.master,
-                           None if duplicates is None else duplicates[0], self.master_id, duplicates_id, **options)
+        cand = []
+        for f, options_f in zip(candidate_fields, candidates):
+            if not isinstance(options_f, dict) or set(options_f) - {"min_similarity", "max_n_matches"}:
+                raise TypeError("candidates takes min_similarity and max_n_matches only, as a dict")
+            config = (self if f == 0 else others[f - 1])._config     # a field's own corpus fills what the dict leaves out
+            cand_threshold = float(options_f.get("min_similarity", config.min_similarity))
+            cand_top_n = options_f.get("max_n_matches", config.max_n_matches)
+            if cand_top_n is None:
+                cand_top_n = n_right
+            if isinstance(cand_top_n, (bool, np.bool_)) or not isinstance(cand_top_n, (int, np.integer)) or cand_top_n < 1:
+                if n_right > 0:
+                    raise ValueError(f"candidates: max_n_matches={cand_top_n!r}: a whole number of at least 1 is expected")
+                cand_top_n = 1
+            if cand_top_n > self.MAX_RECORD_CANDIDATES:
+                raise ValueError(f"candidates: max_n_matches={cand_top_n} exceeds the {self.MAX_RECORD_CANDIDATES} candidates a record "
+                                 f"that can be rescored: set candidates=dict(max_n_matches=...) to at most that")
+            cand.append((int(cand_top_n), cand_threshold))
+        if sum(k for k, _ in cand) > self.MAX_RECORD_CANDIDATES:
+            raise ValueError(f"candidates: the max_n_matches of the candidate fields {list(candidate_fields)} "
+                             f"({' + '.join(str(k) for k, _ in cand)}) exceed together the {self.MAX_RECORD_CANDIDATES} candidates a "
+                             f"record that can be united and rescored")
+        g = _RecordGrouper(self, others, weights, cand[0] if candidate_fields == (0,) else cand, dup_fields, self.master,
+                           None if duplicates is None else duplicates[0], self.master_id, duplicates_id,
+                           candidate_fields=candidate_fields, **options)
         for o in others:
             o._join_pending()
         try:
@@ -598,7 +648,7 @@ class Corpus:
             g._release()
 
     def match_records(self, others, duplicates=None, duplicates_id: Optional[pd.Series] = None, weights=None, candidates=None,
-                      **kwargs) -> pd.DataFrame:
+                      candidate_fields=(0,), **kwargs) -> pd.DataFrame:
         """Match RECORDS of several fields.  This corpus holds one field of every record (say the names), ``others`` -- a list
         of 1 to 7 ``Corpus`` objects -- the further fields (addresses, cities ...): row p of every corpus is record p, which is
         the caller's duty (append to and remove from all of them together; different lengths: ValueError).  The call is
@@ -628,10 +678,23 @@ class Corpus:
         The frame is ``match_strings(corpus.master, duplicates[0], corpus.master_id, duplicates_id)``'s, with the combined
         similarity; there are no per-field columns (``pair_similarities`` of each corpus gives them for the pairs of the
         frame).  No further corpus is compacted or indexed by the call (``stats['record_calls']`` counts it on every corpus
-        that took part)."""
-        return self._record_call(others, duplicates, duplicates_id, weights, candidates, kwargs, lambda g: g.fit().get_matches())
+        that took part).
 
-    def group_similar_records(self, others, weights=None, candidates=None, **kwargs):
+        ``candidate_fields``: the fields that find the candidates, as ascending distinct positions -- 0 is this corpus, k is
+        ``others[k - 1]``, and 0 is always among them; ``(0,)`` by default, which is the call described above.  With several,
+        the candidates of a record are the UNION, over the candidate fields, of what that field's ``match_strings`` reports at
+        its candidate options -- two records that share address and city are compared although their names share nothing.
+        ``candidates`` is then one dict for every candidate field (a field's own corpus options fill what it leaves out) or a
+        list of dicts, one a candidate field; their ``max_n_matches`` may be at most 2 048 TOGETHER (ValueError), and
+        ``max_n_matches=None`` of the call keeps all of them.  Every candidate gets the same combined similarity of step 3,
+        with ``s_f`` the bits ``corpus_f.pair_similarities`` returns, whichever field found it: the union and the missing
+        scores are made on the device (``stats['record_union_calls']`` counts the call on the candidate fields' corpora).  A
+        further corpus named as a candidate field is treated as this corpus is -- it builds its index and a self-join
+        compacts it; the others are still only read."""
+        return self._record_call(others, duplicates, duplicates_id, weights, candidates, kwargs, lambda g: g.fit().get_matches(),
+                                 candidate_fields)
+
+    def group_similar_records(self, others, weights=None, candidates=None, candidate_fields=(0,), **kwargs):
         """For every record the representative of its group of similar records: ``group_similar_strings(corpus.master,
-        corpus.master_id)`` over the match list of ``match_records(others, weights=..., candidates=...)``."""
-        return self._record_call(others, None, None, weights, candidates, kwargs, lambda g: g.fit().get_groups())
+        corpus.master_id)`` over the match list of ``match_records(others, weights=..., candidates=..., candidate_fields=...)``."""
+        return self._record_call(others, None, None, weights, candidates, kwargs, lambda g: g.fit().get_groups(), candidate_fields)

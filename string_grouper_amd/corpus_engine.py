@@ -73,7 +73,7 @@ class CorpusState:
                       "segments": 1, "base_index_builds": 0, "removals": 0, "rows_removed": 0, "dead_rows": 0,
                       "self_join_full": 0, "self_join_served": 0, "self_join_append_updates": 0,
                       "self_join_remove_updates": 0, "self_join_rows_refilled": 0, "idf_refits": 0, "pair_calls": 0,
-                      "pairs_scored": 0, "record_calls": 0}
+                      "pairs_scored": 0, "record_calls": 0, "record_union_calls": 0}
         if base is not None:
             self.set_segments(CorpusSegment(base), None)
 
@@ -552,6 +552,67 @@ class CorpusEngine:
                 st.stats["record_calls"] += 1
             # (_match_list_from_topn frees the result once the list is built; if it raises before that, the scope does)
             return self._match_list_from_topn(res, A.dtype, B.shape[0], self_join_fix, keep_on_device, t)
+
+    MAX_UNION_CANDIDATES = 2048               # sg_topn_union: the candidate fields' strides together
+
+    def corpus_records_union_topn(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
+                                  B_fields: Optional[List[DeviceMatrix]], weights, candidate_fields, cands, top_n: int,
+                                  threshold: float, self_join_fix: bool, keep_on_device: bool = False):
+        """``corpus_records_topn`` with candidates from SEVERAL fields: ``candidate_fields`` -- ascending positions, 0 the corpus
+        ``state``, k ``others[k - 1]``, 0 always among them -- each find candidates with a multiply of their own at
+        ``cands[.] = (cand_top_n, cand_threshold)``, the results are united on the device (sg_topn_union: a record's distinct
+        candidates, with the primary field's score for the ones the primary multiply did not find) and the union is rescored,
+        filtered, ordered and cut exactly as one field's candidates are.  Returns what ``match_list`` returns.
+
+        Every candidate multiply is ``_topn_device``'s on that field's own matrices: its resident index, the forward and the
+        reverse path and a kept self-join serve as they do for ``match_strings`` -- so a corpus named as a candidate field is
+        treated as the primary is (it builds its index; a self-join compacts it).  A corpus that is NOT a candidate field is
+        read where it lies, as in ``corpus_records_topn``: never compacted, never indexed.  The rows and the dead lists the
+        union and the rescoring read are taken AFTER the multiplies, which may have compacted a candidate corpus; results number
+        the live rows, which no compaction changes."""
+        t = time.perf_counter()
+        self_join = B_fields is None
+        states = [state] + list(others)
+        candidate_fields = [int(f) for f in candidate_fields]
+        if len(others) != len(weights) - 1 or not 1 <= len(others) <= self.MAX_RECORD_FIELDS:
+            raise ValueError(f"between 1 and {self.MAX_RECORD_FIELDS} further fields, and one weight a field, are expected")
+        if (len(candidate_fields) < 2 or candidate_fields[0] != 0 or candidate_fields[-1] > len(others)
+                or any(a >= b for a, b in zip(candidate_fields, candidate_fields[1:])) or len(cands) != len(candidate_fields)):
+            raise ValueError("candidate_fields: at least two distinct ascending field positions, 0 among them, and one pair of "
+                             "candidate options a field, are expected")
+        if self_join and B is not state.matrix:
+            raise ValueError("duplicates of the first field without duplicates of the further fields")
+        for k, o in enumerate(others):
+            if o.matrix.shape[0] != state.matrix.shape[0]:
+                raise ValueError(f"the corpora differ in length ({o.matrix.shape[0]} and {state.matrix.shape[0]} rows): row p of "
+                                 f"every corpus must be record p")
+            if not self_join and B_fields[k].shape[0] != B.shape[0]:
+                raise ValueError(f"the duplicates differ in length ({B_fields[k].shape[0]} and {B.shape[0]} rows)")
+        n_right = B.shape[0]
+        if sum(max(min(int(k), n_right), 1) for k, _ in cands) > self.MAX_UNION_CANDIDATES:
+            raise ValueError(f"the candidate fields' max_n_matches exceed {self.MAX_UNION_CANDIDATES} together")
+        with N.Scope() as s:
+            with N.Scope() as before:         # the candidates go as soon as they are rescored
+                with N.Scope() as per_field:  # ... and every field's own as soon as they are united
+                    parts = []
+                    for f, (cand_top_n, cand_threshold) in zip(candidate_fields, cands):
+                        A_f = states[f].matrix
+                        B_f = A_f if self_join else (B if f == 0 else B_fields[f - 1])
+                        parts.append(per_field.own(self._topn_device(A_f, B_f, cand_top_n, cand_threshold)))
+                    right = state.physical() if self_join else B.csr
+                    cand = before.own(self.ctx.topn_union(parts, (state.physical(), right, state.dead_dev,
+                                                                  state.dead_dev if self_join else None)))
+                fields = []
+                for k, o in enumerate(others):
+                    right = None if self_join else B_fields[k].csr
+                    rows = o.physical()       # (the state's own cached concatenation when rows wait in a delta)
+                    fields.append((rows, rows if self_join else right, weights[k + 1], o.dead_dev, o.dead_dev if self_join else None))
+                res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n))
+            for st in states:
+                st.stats["record_calls"] += 1
+            for f in candidate_fields:
+                states[f].stats["record_union_calls"] += 1
+            return self._match_list_from_topn(res, state.matrix.dtype, n_right, self_join_fix, keep_on_device, t)
 
     # ------------------------------------------------------------------ a self-join that is kept (DESIGN.md section 9)
     def corpus_keep_self_join(self, state: CorpusState, top_n: int, threshold: float) -> None:

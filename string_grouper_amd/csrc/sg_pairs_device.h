@@ -77,7 +77,21 @@ __device__ __forceinline__ T pair_rows_dot(const int32_t *__restrict__ a_indices
     return acc;
 }
 
-// Column order is what the merge rests on.  A matrix the vectoriser made has it by construction, one the cosine gate has
+// live row -> physical row: live + #{q : dead[q] - q <= live} (CorpusState.physical_rows: searchsorted(dead - arange, live,
+// side="right")).  dead[q] - q never falls as q grows, so the count is found by bisection.  The result is at most
+// live + n_dead: inside the matrix whenever its rows are the live rows + n_dead, whatever the list holds.  (sg_rescore.hip and
+// sg_union.hip: a resident corpus keeps removed rows in place, results number the live ones.)
+__device__ __forceinline__ int64_t physical_row(int64_t live, const int32_t *__restrict__ dead, int32_t n_dead) {
+    int32_t lo = 0, hi = n_dead;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if ((int64_t)dead[mid] - mid <= live) lo = mid + 1;
+        else hi = mid;
+    }
+    return live + lo;
+}
+
+// Column order is what the merge rests on. A matrix the vectoriser made has it by construction, one the cosine gate has
 // passed (sg_csr_props) has been measured; any other is checked by the kernel, row by row, for the rows the pairs name.
 static inline bool known_ascending(const sg_csr *m) { return m->props_state == 1 || (m->props_state == 0 && m->from_vectoriser); }
 

@@ -42,19 +42,6 @@ struct RescoreFields {
     RescoreField<T> f[SG_RESCORE_MAX_FIELDS];
 };
 
-// live row -> physical row: live + #{q : dead[q] - q <= live} (CorpusState.physical_rows: searchsorted(dead - arange, live,
-// side="right")).  dead[q] - q never falls as q grows, so the count is found by bisection.  The result is at most
-// live + n_dead: inside the matrix whenever its rows are the live rows + n_dead, whatever the list holds.
-__device__ __forceinline__ int64_t physical_row(int64_t live, const int32_t *__restrict__ dead, int32_t n_dead) {
-    int32_t lo = 0, hi = n_dead;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if ((int64_t)dead[mid] - mid <= live) lo = mid + 1;
-        else hi = mid;
-    }
-    return live + lo;
-}
-
 template <typename T>
 __global__ void __launch_bounds__(SG_RESCORE_BLOCK) rescore_score_kernel(
     const int32_t *__restrict__ cols, const T *__restrict__ vals, const int32_t *__restrict__ counts, int64_t n_rows,

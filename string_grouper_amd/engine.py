@@ -302,6 +302,9 @@ class DistributedHipEngine(HipEngine):
     def corpus_records_topn(self, *args, **kwargs):
         raise NotImplementedError("record matching is single-GPU: a candidate's rows may live on different ranks")
 
+    def corpus_records_union_topn(self, *args, **kwargs):
+        raise NotImplementedError("record matching is single-GPU: a candidate's rows may live on different ranks")
+
     def topn_multiply_blocked(self, A, B, n_blocks, top_n, threshold):
         if isinstance(A, ShardedMatrix):          # explicit n_blocks only cut the work differently: same result
             return self.topn_multiply(A, B, top_n, threshold).astype(np.float64)

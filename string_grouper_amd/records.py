@@ -13,8 +13,9 @@ from .corpus import Corpus
 
 
 def match_records(fields, duplicates=None, master_id: Optional[pd.Series] = None, duplicates_id: Optional[pd.Series] = None,
-                  weights=None, candidates=None, **kwargs) -> pd.DataFrame:
-    """``fields``: a list of 2 to 8 equally long Series, one a field of the records; the first finds the candidates.
+                  weights=None, candidates=None, candidate_fields=(0,), **kwargs) -> pd.DataFrame:
+    """``fields``: a list of 2 to 8 equally long Series, one a field of the records; the first finds the candidates --
+    with ``candidate_fields`` (positions in ``fields``, 0 among them) the union of several fields' matches does.
     ``duplicates``: None or as many Series.  Everything else as in ``Corpus.match_records``; vectoriser options in
     ``kwargs`` (``ngram_size``, ``tfidf_matrix_dtype`` ...) apply to every field."""
     if isinstance(fields, pd.Series) or not isinstance(fields, (list, tuple)) or len(fields) < 2:
@@ -26,7 +27,7 @@ def match_records(fields, duplicates=None, master_id: Optional[pd.Series] = None
         for k, series in enumerate(fields):
             corpora.append(Corpus(series, master_id=master_id if k == 0 else None, **kwargs))
         return corpora[0].match_records(corpora[1:], duplicates=duplicates, duplicates_id=duplicates_id, weights=weights,
-                                        candidates=candidates, **kwargs)
+                                        candidates=candidates, candidate_fields=candidate_fields, **kwargs)
     finally:
         for c in corpora:
             c.close()
