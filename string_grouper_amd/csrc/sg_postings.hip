@@ -182,18 +182,25 @@ __global__ void __launch_bounds__(256) postings_fill(const int64_t *__restrict__
 // row pointers, entries, LDS, store -- so that the build ran at the latency of its loads, not at any bandwidth
 // (profiles/r04_s1_kernel_stats_baseline.csv: 0.31 ms for 100 MB).
 #define SG_POST_ROWS 4    // rows per sixteen lanes and trip
+// Where part `part` of a tile's `split` parts begins, in rows from the tile's start: part * tile_cols / split, rounded down to a
+// multiple of 64 rows (part == split: the tile's end).  `split` is any integer, not only a power of two -- so that the
+// workgroups of a launch can be made to fill the chip (plan_build, choose_split); count, fill and tables agree on the
+// boundaries through this one function and through the workgroup's number w = tile * split + part.
+__host__ __device__ __forceinline__ int64_t part_begin(int32_t part, int32_t split, int32_t tile_log2) {
+    return part >= split ? (int64_t)1 << tile_log2 : ((((int64_t)part << tile_log2) / split) & ~(int64_t)63);
+}
 __global__ void __launch_bounds__(1024) postings_count_lds(const int64_t *__restrict__ indptr,
                                                            const int32_t *__restrict__ indices, int64_t n_rows,
                                                            int32_t tile_log2, int32_t n_terms, int32_t split,
-                                                           uint32_t *__restrict__ cnt /* [wgs][n_terms] */) {
+                                                           uint32_t *__restrict__ cnt /* [wgs][n_terms] */,
+                                                           uint32_t *__restrict__ cnt16 /* [wgs][(n_terms + 1) / 2], or null */) {
     extern __shared__ uint32_t hist[];
     const int64_t t = blockIdx.x / split;
     const int32_t part = blockIdx.x % split;
     for (int k = threadIdx.x; k < n_terms; k += blockDim.x) hist[k] = 0;
     __syncthreads();
-    const int64_t part_rows = ((int64_t)1 << tile_log2) / split;
-    const int64_t j0 = (t << tile_log2) + part * part_rows;
-    int64_t j1 = j0 + part_rows;
+    const int64_t j0 = (t << tile_log2) + part_begin(part, split, tile_log2);
+    int64_t j1 = (t << tile_log2) + part_begin(part + 1, split, tile_log2);
     if (j1 > n_rows) j1 = n_rows;
     const int sub = threadIdx.x & 15;
     const int64_t groups = blockDim.x >> 4;
@@ -205,18 +212,35 @@ __global__ void __launch_bounds__(1024) postings_count_lds(const int64_t *__rest
             lo[r] = valid ? indptr[jb + r] : 0;
             hi[r] = valid ? indptr[jb + r + 1] : 0;
         }
-        int32_t k0[SG_POST_ROWS];
+        // a row's first 32 entries, two a lane, in flight together (a name has 19 on average: most rows have a 17th, and one
+        // row after the other waiting for its own was a chain of four round trips a trip)
+        int32_t k0[SG_POST_ROWS], k1[SG_POST_ROWS];
 #pragma unroll
-        for (int r = 0; r < SG_POST_ROWS; ++r) k0[r] = lo[r] + sub < hi[r] ? indices[lo[r] + sub] : -1;
+        for (int r = 0; r < SG_POST_ROWS; ++r) {
+            k0[r] = lo[r] + sub < hi[r] ? indices[lo[r] + sub] : -1;
+            k1[r] = lo[r] + sub + 16 < hi[r] ? indices[lo[r] + sub + 16] : -1;
+        }
 #pragma unroll
         for (int r = 0; r < SG_POST_ROWS; ++r) {
             if (k0[r] >= 0) atomicAdd(&hist[k0[r]], 1u);
-            for (int64_t p = lo[r] + sub + 16; p < hi[r]; p += 16) atomicAdd(&hist[indices[p]], 1u);   // rows beyond 16 entries
+            if (k1[r] >= 0) atomicAdd(&hist[k1[r]], 1u);
+            for (int64_t p = lo[r] + sub + 32; p < hi[r]; p += 16) atomicAdd(&hist[indices[p]], 1u);   // rows beyond 32 entries
         }
     }
     __syncthreads();
     uint32_t *mine = cnt + (int64_t)blockIdx.x * n_terms;
     for (int k = threadIdx.x; k < n_terms; k += blockDim.x) mine[k] = hist[k];
+    // The part's own counts once more, 16 bits a term and packed as the staged fill keeps them in LDS: the column scan turns
+    // `cnt` into running sums, and the fill would otherwise count the part's rows a second time.  (A count beyond 16 bits
+    // is cut: such a part holds more entries than the fill stages, and it does not read these.)
+    if (cnt16) {
+        const int w16 = (n_terms + 1) >> 1;
+        uint32_t *mine16 = cnt16 + (int64_t)blockIdx.x * w16;
+        for (int w = threadIdx.x; w < w16; w += blockDim.x) {
+            const uint32_t a = hist[2 * w], b = 2 * w + 1 < n_terms ? hist[2 * w + 1] : 0u;
+            mine16[w] = (a < 0xffffu ? a : 0xffffu) | ((b < 0xffffu ? b : 0xffffu) << 16);
+        }
+    }
 }
 
 // Per term: counts of the workgroups -> entries of the term in EARLIER workgroups (in place), the term's total, and
@@ -333,9 +357,8 @@ __global__ void __launch_bounds__(1024) postings_fill_lds(const int64_t *__restr
         for (int k = threadIdx.x; k < n_terms; k += blockDim.x)
             if (is_frequent[k]) atomicOr(&freq_bits[k >> 5], 1u << (k & 31));
     __syncthreads();
-    const int64_t part_rows = ((int64_t)1 << tile_log2) / split;
-    const int64_t j0 = (t << tile_log2) + part * part_rows;
-    int64_t j1 = j0 + part_rows;
+    const int64_t j0 = (t << tile_log2) + part_begin(part, split, tile_log2);
+    int64_t j1 = (t << tile_log2) + part_begin(part + 1, split, tile_log2);
     if (j1 > n_rows) j1 = n_rows;
     const int lane = threadIdx.x & 63, sub = lane & 15;
     (void)lane;
@@ -409,60 +432,104 @@ __global__ void __launch_bounds__(1024) postings_fill_lds(const int64_t *__restr
     }
 }
 
-// ---- Round 6: the filter postings STAGED in LDS and written cell by cell.
+// ---- The filter postings STAGED in LDS and written cell by cell.
 // postings_fill_lds stores every posting where its cursor says: 4 bytes to a line of its own -- the term-major order the
-// multiply streams puts the postings of one row 18 300 lists apart --, and those stores were half the kernel (0.12 of 0.27 ms
-// at 663 k, probe builds of round 4; 1.9 ms at 5 M).  But the entries of a (term, part) CELL are neighbours in the index, and
-// most entries live in cells of many (frequent terms: a part of 1024 rows holds 4.3 entries per non-empty cell, 56 % of the
-// entries in cells of eight or more).  So a workgroup works its part off in CHUNKS of rows whose postings fit the LDS beside
-// the counters: (1) the chunk's entries are counted per term in packed 16-bit counters (and the rows' frequent-part norms
-// computed); (2) a prefix sum turns the counts into the cells' places inside the chunk; (3) every posting is made and put
-// at its place in LDS; (4) waves copy the staged run out, 64 consecutive staged postings a trip: lanes in the same cell write
-// neighbouring words, a trip touches ~15 lines instead of 64.  Where a cell starts in the index is the workgroup's row of
-// `cnt` (entries in earlier workgroups) + the term's start, advanced by the chunk's count -- the row is this workgroup's
-// alone, and the tables the multiply reads are written from `cnt` BEFORE this kernel runs.  A chunk that does not fit the
-// stage (rows far longer than the build's mean) is written posting by posting through the same cursors.
+// multiply streams puts the postings of one row 18 300 lists apart --, and those stores were half the kernel.  But the
+// entries of a (term, part) CELL are neighbours in the index, and most entries live in cells of many (frequent terms: a part
+// of 1024 rows holds 4.3 entries per non-empty cell, 56 % of the entries in cells of eight or more).  So a workgroup works its
+// part off in CHUNKS of rows whose postings fit the LDS beside packed 16-bit counters:
+//   (1) the chunk's entries per term.  A part that IS one chunk -- what plan_build aims for -- loads them: the count pass
+//       counted exactly these rows and left the counts packed (cnt16), so the rows are read ONCE here.  A part of several
+//       chunks (long strings, a forced split) counts every chunk itself, as it must: the count pass knows the part only.
+//   (2) a prefix sum turns the counts into the cells' places inside the chunk;
+//   (3) every posting is made and put at its place in LDS, its term beside it (16 bits: the vocabulary fits the LDS path);
+//       the row's frequent-part norm is summed by the row's sixteen lanes in the same trip, before they emit;
+//   (4) waves copy the staged run out, 64 consecutive staged postings a trip: lanes in the same cell write neighbouring
+//       words, a trip touches ~15 lines instead of 64.  A lane knows its posting's term, so nothing is searched and no empty
+//       cell is visited: the first lane of every run of one term in the trip (a "head") fetches where the cell starts in
+//       the index -- the term's start + the workgroup's row of `cnt` (entries in earlier workgroups; the tables the multiply
+//       reads are written from `cnt` BEFORE this kernel runs) -- and hands it to the run's other lanes by a shuffle.
+// A part of one chunk never writes its row of `cnt`.  A part of several advances a cell's start by the chunk's count once a
+// cell, by the lane that holds the cell's first staged posting, behind a barrier after the copy (a cell that straddles two
+// trips is read by two heads) -- plain loads and stores of the one workgroup that owns the row.  A chunk that does not fit
+// the stage (rows far longer than the build's mean) is written posting by posting through the same cursors.
 // Filter postings only: the exact kernel's postings, when they are wanted at all, keep postings_fill_lds.
 __device__ __forceinline__ uint32_t lds_get16(const uint32_t *w, uint32_t k) { return (w[k >> 1] >> ((k & 1u) << 4)) & 0xffffu; }
+// words of LDS for a chunk's row pointers (relative to the chunk's first entry; one more than rows)
+__host__ __device__ __forceinline__ uint32_t staged_rowp_words(int32_t chunk_rows) { return ((uint32_t)chunk_rows + 4u) & ~3u; }
 template <typename T>
 __global__ void __launch_bounds__(1024) postings_fill_staged(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                                              const T *__restrict__ data, int64_t n_rows, int32_t tile_log2,
                                                              int32_t n_terms, int32_t split, int32_t chunk_rows, uint32_t stage_cap,
-                                                             uint32_t *cnt /* [wgs][n_terms] */, const uint32_t *__restrict__ term_start,
+                                                             uint32_t stage_alloc /* postings the stage has room for (>= stage_cap) */,
+                                                             uint32_t *cnt /* [wgs][n_terms] */,
+                                                             const uint32_t *__restrict__ cnt16 /* [wgs][(n_terms + 1) / 2] */,
+                                                             const uint32_t *__restrict__ term_start,
                                                              const uint8_t *__restrict__ is_frequent, uint32_t *__restrict__ out_filt,
                                                              float inv_norm_up, int32_t fold_log2) {
     extern __shared__ uint32_t lds[];
     const uint32_t w16 = ((uint32_t)n_terms + 1u) >> 1;            // words of packed 16-bit counters
     uint32_t *lcnt = lds;
     uint32_t *freq_bits = lcnt + ((w16 + 3u) & ~3u);
-    float *fqrow = reinterpret_cast<float *>(freq_bits + (((uint32_t)n_terms + 31u) >> 5));
-    uint32_t *wave_tot = reinterpret_cast<uint32_t *>(fqrow + chunk_rows);
-    uint32_t *stage = wave_tot + 32;
+    uint32_t *wave_tot = freq_bits + (((uint32_t)n_terms + 31u) >> 5);
+    uint32_t *rowp = wave_tot + 32;
+    uint32_t *stage = rowp + staged_rowp_words(chunk_rows);
+    uint16_t *sterm = reinterpret_cast<uint16_t *>(stage + stage_alloc);
     const int64_t t = blockIdx.x / split;
     const int32_t part = blockIdx.x % split;
     uint32_t *mine = cnt + (int64_t)blockIdx.x * n_terms;
-    for (uint32_t k = threadIdx.x; k < (((uint32_t)n_terms + 31u) >> 5); k += blockDim.x) freq_bits[k] = 0;
-    __syncthreads();
-    for (int k = threadIdx.x; k < n_terms; k += blockDim.x)
-        if (is_frequent[k]) atomicOr(&freq_bits[k >> 5], 1u << (k & 31));
-    __syncthreads();
-    const int64_t part_rows = ((int64_t)1 << tile_log2) / split;
-    const int64_t j0 = (t << tile_log2) + part * part_rows;
-    int64_t j1 = j0 + part_rows;
+    const int64_t j0 = (t << tile_log2) + part_begin(part, split, tile_log2);
+    int64_t j1 = (t << tile_log2) + part_begin(part + 1, split, tile_log2);
     if (j1 > n_rows) j1 = n_rows;
+    if (j1 <= j0) return;                                          // (a part behind the last row)
     const int lane = threadIdx.x & 63, sub = lane & 15, wave = threadIdx.x >> 6;
     const int64_t groups = blockDim.x >> 4;
-    const uint32_t last_k = (uint32_t)n_terms - 1u;
     // A workgroup whose part holds a chunk that does not fit the stage writes ALL its chunks posting by posting: its cursors
-    // are then only ever touched by atomics, a staging workgroup's only by the plain loads and stores of the one thread that
-    // owns a term -- never both (atomics are served by the L2, plain loads may come from the L1: mixing them per workgroup
-    // needed loads and stores through the fabric, which doubled the kernel -- 0.53 instead of 0.26 ms at 663 k).
+    // are then only ever touched by atomics, a staging workgroup's only by plain loads and stores -- never both (atomics
+    // are served by the L2, plain loads may come from the L1: mixing them per workgroup needed loads and stores through the
+    // fabric, which doubled the kernel -- 0.53 instead of 0.26 ms at 663 k).
     bool any_big = false;
     for (int64_t c0 = j0; c0 < j1; c0 += chunk_rows) {
         const int64_t c1 = c0 + chunk_rows < j1 ? c0 + chunk_rows : j1;
         const int64_t e = indptr[c1] - indptr[c0];
         any_big = any_big || e > (int64_t)stage_cap || e > 65535;
     }
+    const bool one_chunk = j1 - j0 <= chunk_rows && !any_big;
+    // Everything a workgroup fetches before it can start is issued together -- one round trip to memory, not one a loop trip
+    // (a workgroup is alone on its CU, nothing hides a chain of dependent loads).
+    // * One bit per term from the column scan's byte flags: a thread makes a whole word, its eight loads in flight at once.
+    {
+        const uint32_t *flags4 = reinterpret_cast<const uint32_t *>(is_frequent);   // (allocated beyond a multiple of four bytes)
+        for (uint32_t w = threadIdx.x; w < (((uint32_t)n_terms + 31u) >> 5); w += blockDim.x) {
+            uint32_t f[8];
+#pragma unroll
+            for (uint32_t q = 0; q < 8; ++q) f[q] = (w * 8u + q) * 4u < (uint32_t)n_terms ? flags4[w * 8u + q] : 0u;
+            uint32_t bits = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < 32; ++i)
+                if (w * 32u + i < (uint32_t)n_terms && ((f[i >> 2] >> ((i & 3u) << 3)) & 0xffu)) bits |= 1u << i;
+            freq_bits[w] = bits;
+        }
+    }
+    // * A chunk's row pointers, relative to its first entry (a staged chunk holds fewer than 2^16), so that a trip over the
+    //   rows waits for its entries only.
+    auto load_row_pointers = [&](int64_t c0, int64_t c1) {
+        const int64_t base = indptr[c0];
+        for (int64_t i = threadIdx.x; i <= c1 - c0; i += blockDim.x) rowp[i] = (uint32_t)(indptr[c0 + i] - base);
+    };
+    if (one_chunk) {   // (1), loaded
+        const uint32_t *mine16 = cnt16 + (int64_t)blockIdx.x * w16;
+        for (uint32_t w0 = threadIdx.x; w0 < w16; w0 += blockDim.x * 8u) {
+            uint32_t v[8];
+#pragma unroll
+            for (uint32_t q = 0; q < 8; ++q) v[q] = w0 + q * blockDim.x < w16 ? mine16[w0 + q * blockDim.x] : 0u;
+#pragma unroll
+            for (uint32_t q = 0; q < 8; ++q)
+                if (w0 + q * blockDim.x < w16) lcnt[w0 + q * blockDim.x] = v[q];
+        }
+        load_row_pointers(j0, j1);
+    }
+    __syncthreads();
     for (int64_t c0 = j0; c0 < j1; c0 += chunk_rows) {
         const int64_t c1 = c0 + chunk_rows < j1 ? c0 + chunk_rows : j1;
         // every wave makes the same number of trips, so that the cross-lane sums below always run with all lanes
@@ -495,60 +562,48 @@ __global__ void __launch_bounds__(1024) postings_fill_staged(const int64_t *__re
                     }
                 }
             }
-            __syncthreads();
             continue;
         }
-        for (uint32_t w = threadIdx.x; w < w16; w += blockDim.x) lcnt[w] = 0;
-        __syncthreads();
-        // ---- (1) count per term; the rows' frequent-part norms
-        for (int64_t it = 0; it < trips; ++it) {
-            const int64_t jb = c0 + (it * groups + (threadIdx.x >> 4)) * SG_POST_ROWS;
-            int64_t lo[SG_POST_ROWS], hi[SG_POST_ROWS];
+        const int64_t chunk_base = indptr[c0];
+        if (!one_chunk) {
+            // ---- (1), counted: this chunk's entries per term
+            for (uint32_t w = threadIdx.x; w < w16; w += blockDim.x) lcnt[w] = 0;
+            load_row_pointers(c0, c1);
+            __syncthreads();
+            for (int64_t it = 0; it < trips; ++it) {
+                const int64_t jb = c0 + (it * groups + (threadIdx.x >> 4)) * SG_POST_ROWS;
+                int64_t lo[SG_POST_ROWS], hi[SG_POST_ROWS];
 #pragma unroll
-            for (int r = 0; r < SG_POST_ROWS; ++r) {
-                const bool valid = jb + r < c1;
-                lo[r] = valid ? indptr[jb + r] : 0;
-                hi[r] = valid ? indptr[jb + r + 1] : 0;
-            }
-            int32_t k0[SG_POST_ROWS];
-            T v0[SG_POST_ROWS];
-#pragma unroll
-            for (int r = 0; r < SG_POST_ROWS; ++r) {
-                const bool have = lo[r] + sub < hi[r];
-                k0[r] = have ? indices[lo[r] + sub] : -1;
-                v0[r] = have ? data[lo[r] + sub] : (T)0;
-            }
-#pragma unroll
-            for (int r = 0; r < SG_POST_ROWS; ++r) {
-                // norm of the row's frequent part relative to norm_up, rounded up (the order of the additions is free: the
-                // result is rounded up with a margin far above the rounding of a double sum)
-                double f2 = 0.0;
-                if (k0[r] >= 0) {
-                    atomicAdd(&lcnt[(uint32_t)k0[r] >> 1], 1u << (((uint32_t)k0[r] & 1u) << 4));
-                    if ((freq_bits[k0[r] >> 5] >> (k0[r] & 31)) & 1u) f2 = (double)v0[r] * (double)v0[r];
+                for (int r = 0; r < SG_POST_ROWS; ++r) {
+                    const bool valid = jb + r < c1;
+                    lo[r] = valid ? chunk_base + rowp[jb + r - c0] : 0;
+                    hi[r] = valid ? chunk_base + rowp[jb + r - c0 + 1] : 0;
                 }
-                for (int64_t p = lo[r] + sub + 16; p < hi[r]; p += 16) {
-                    const int32_t k = indices[p];
-                    atomicAdd(&lcnt[(uint32_t)k >> 1], 1u << (((uint32_t)k & 1u) << 4));
-                    if ((freq_bits[k >> 5] >> (k & 31)) & 1u) f2 += (double)data[p] * (double)data[p];
+                int32_t k0[SG_POST_ROWS], k1[SG_POST_ROWS];
+#pragma unroll
+                for (int r = 0; r < SG_POST_ROWS; ++r) {
+                    k0[r] = lo[r] + sub < hi[r] ? indices[lo[r] + sub] : -1;
+                    k1[r] = lo[r] + sub + 16 < hi[r] ? indices[lo[r] + sub + 16] : -1;
                 }
 #pragma unroll
-                for (int d = 8; d > 0; d >>= 1) {
-                    const uint64_t bits = (uint64_t)__double_as_longlong(f2);
-                    const uint32_t l = (uint32_t)__shfl_xor((int)(uint32_t)bits, d, 64), h = (uint32_t)__shfl_xor((int)(uint32_t)(bits >> 32), d, 64);
-                    f2 += __longlong_as_double((long long)(((uint64_t)h << 32) | l));
+                for (int r = 0; r < SG_POST_ROWS; ++r) {
+                    if (k0[r] >= 0) atomicAdd(&lcnt[(uint32_t)k0[r] >> 1], 1u << (((uint32_t)k0[r] & 1u) << 4));
+                    if (k1[r] >= 0) atomicAdd(&lcnt[(uint32_t)k1[r] >> 1], 1u << (((uint32_t)k1[r] & 1u) << 4));
+                    for (int64_t p = lo[r] + sub + 32; p < hi[r]; p += 16) {
+                        const uint32_t k = (uint32_t)indices[p];
+                        atomicAdd(&lcnt[k >> 1], 1u << ((k & 1u) << 4));
+                    }
                 }
-                if (sub == 0 && jb + r < c1) fqrow[jb + r - c0] = frequent_norm_ratio_of(f2, inv_norm_up);
             }
+            __syncthreads();
         }
-        __syncthreads();
         // ---- (2) counts -> where every term's cell starts inside the chunk (a thread takes a run of words)
+        uint32_t tot;
         {
             const uint32_t per = (w16 + blockDim.x - 1u) / blockDim.x;
-            const uint32_t wa = threadIdx.x * per, wb = wa + per < w16 ? wa + per : w16;
+            const uint32_t wa = threadIdx.x * per < w16 ? threadIdx.x * per : w16, wb = wa + per < w16 ? wa + per : w16;
             uint32_t sum = 0;
             for (uint32_t w = wa; w < wb; ++w) sum += (lcnt[w] & 0xffffu) + (lcnt[w] >> 16);
-            uint32_t tot;
             uint32_t run = block_exclusive_scan<uint32_t>(sum, wave_tot, &tot);
             for (uint32_t w = wa; w < wb; ++w) {
                 const uint32_t c = lcnt[w];
@@ -567,91 +622,101 @@ __global__ void __launch_bounds__(1024) postings_fill_staged(const int64_t *__re
 #pragma unroll
             for (int r = 0; r < SG_POST_ROWS; ++r) {
                 const bool valid = jb + r < c1;
-                lo[r] = valid ? indptr[jb + r] : 0;
-                hi[r] = valid ? indptr[jb + r + 1] : 0;
+                lo[r] = valid ? chunk_base + rowp[jb + r - c0] : 0;
+                hi[r] = valid ? chunk_base + rowp[jb + r - c0 + 1] : 0;
             }
-            int32_t k0[SG_POST_ROWS];
-            T v0[SG_POST_ROWS];
+            // the lane's first two entries of every row (a row's first 32): all loads before the first use
+            int32_t k0[SG_POST_ROWS], k1[SG_POST_ROWS];
+            T v0[SG_POST_ROWS], v1[SG_POST_ROWS];
 #pragma unroll
             for (int r = 0; r < SG_POST_ROWS; ++r) {
-                const bool have = lo[r] + sub < hi[r];
+                const bool have = lo[r] + sub < hi[r], more = lo[r] + sub + 16 < hi[r];
                 k0[r] = have ? indices[lo[r] + sub] : -1;
                 v0[r] = have ? data[lo[r] + sub] : (T)0;
+                k1[r] = more ? indices[lo[r] + sub + 16] : -1;
+                v1[r] = more ? data[lo[r] + sub + 16] : (T)0;
             }
 #pragma unroll
             for (int r = 0; r < SG_POST_ROWS; ++r) {
-                const float fq = jb + r < c1 ? fqrow[jb + r - c0] : 0.f;
+                // norm of the row's frequent part relative to norm_up, rounded up (the order of the additions is free: the
+                // result is rounded up with a margin far above the rounding of a double sum)
+                double f2 = 0.0;
+                if (k0[r] >= 0 && ((freq_bits[k0[r] >> 5] >> (k0[r] & 31)) & 1u)) f2 = (double)v0[r] * (double)v0[r];
+                if (k1[r] >= 0 && ((freq_bits[k1[r] >> 5] >> (k1[r] & 31)) & 1u)) f2 += (double)v1[r] * (double)v1[r];
+                for (int64_t p = lo[r] + sub + 32; p < hi[r]; p += 16) {
+                    const int32_t k = indices[p];
+                    if ((freq_bits[k >> 5] >> (k & 31)) & 1u) f2 += (double)data[p] * (double)data[p];
+                }
+#pragma unroll
+                for (int d = 8; d > 0; d >>= 1) {
+                    const uint64_t bits = (uint64_t)__double_as_longlong(f2);
+                    const uint32_t l = (uint32_t)__shfl_xor((int)(uint32_t)bits, d, 64), h = (uint32_t)__shfl_xor((int)(uint32_t)(bits >> 32), d, 64);
+                    f2 += __longlong_as_double((long long)(((uint64_t)h << 32) | l));
+                }
+                const float fq = frequent_norm_ratio_of(f2, inv_norm_up);
                 const uint32_t col = (uint32_t)(jb + r - (t << tile_log2));
                 if (k0[r] >= 0) {
                     const uint32_t sh = ((uint32_t)k0[r] & 1u) << 4;
                     const uint32_t pos = (atomicAdd(&lcnt[(uint32_t)k0[r] >> 1], 1u << sh) >> sh) & 0xffffu;
                     stage[pos] = filter_posting(col, (float)v0[r], fq, tile_log2, inv_norm_up, (uint32_t)t, fold_log2);
+                    sterm[pos] = (uint16_t)k0[r];
                 }
-                for (int64_t p = lo[r] + sub + 16; p < hi[r]; p += 16) {
+                if (k1[r] >= 0) {
+                    const uint32_t sh = ((uint32_t)k1[r] & 1u) << 4;
+                    const uint32_t pos = (atomicAdd(&lcnt[(uint32_t)k1[r] >> 1], 1u << sh) >> sh) & 0xffffu;
+                    stage[pos] = filter_posting(col, (float)v1[r], fq, tile_log2, inv_norm_up, (uint32_t)t, fold_log2);
+                    sterm[pos] = (uint16_t)k1[r];
+                }
+                for (int64_t p = lo[r] + sub + 32; p < hi[r]; p += 16) {
                     const uint32_t k = (uint32_t)indices[p];
                     const uint32_t sh = (k & 1u) << 4;
                     const uint32_t pos = (atomicAdd(&lcnt[k >> 1], 1u << sh) >> sh) & 0xffffu;
                     stage[pos] = filter_posting(col, (float)data[p], fq, tile_log2, inv_norm_up, (uint32_t)t, fold_log2);
+                    sterm[pos] = (uint16_t)k;
                 }
             }
         }
         __syncthreads();
-        // ---- (4) out: a wave takes 64 terms at a time, whose cells are one run of the stage.  Where the cells start in the
-        // index (the workgroup's cursors: a round trip to the L2) is fetched for EIGHT such groups before the first is copied:
-        // one group after the other, the kernel waited for that load eighteen times a chunk (0.26 of its 0.27 ms at 663 k).
+        // ---- (4) out: a wave takes 64 consecutive staged postings a trip, EIGHT trips with their loads (the heads' cell
+        // starts: a round trip to the L2) issued before the first is copied
         {
             constexpr int FB = 8;
-            const uint32_t n_tg = ((uint32_t)n_terms + 63u) >> 6, waves = (uint32_t)(blockDim.x >> 6);
-            for (uint32_t tg0 = (uint32_t)wave; tg0 < n_tg; tg0 += waves * FB) {
-                uint32_t end_k[FB], start_k[FB], before[FB], G[FB];
-                bool mine_has[FB];
+            const uint32_t stride = (uint32_t)blockDim.x;           // postings all waves take in one trip
+            for (uint32_t e0 = (uint32_t)wave * 64u; e0 < tot; e0 += stride * FB) {
+                uint32_t delta[FB];
+                bool head[FB];
 #pragma unroll
                 for (int b = 0; b < FB; ++b) {
-                    const uint32_t tg = tg0 + (uint32_t)b * waves;
-                    const uint32_t k = tg * 64u + (uint32_t)lane;
-                    const bool live = tg < n_tg;
-                    const uint32_t kc = k < last_k ? k : last_k;                   // (lanes past the last term: empty cells at the end)
-                    end_k[b] = live ? lds_get16(lcnt, kc) : 0u;
-                    start_k[b] = (!live || k == 0u) ? 0u : lds_get16(lcnt, (k - 1u) < last_k ? k - 1u : last_k);
-                    mine_has[b] = live && k <= last_k && end_k[b] > start_k[b];
-                }
-#pragma unroll
-                for (int b = 0; b < FB; ++b) {
-                    const uint32_t k = (tg0 + (uint32_t)b * waves) * 64u + (uint32_t)lane;
-                    before[b] = mine_has[b] ? mine[k] : 0u;
-                    G[b] = mine_has[b] ? term_start[k] : 0u;
-                }
-#pragma unroll
-                for (int b = 0; b < FB; ++b) {
-                    const uint32_t tg = tg0 + (uint32_t)b * waves;
-                    if (tg >= n_tg) break;
-                    const uint32_t k = tg * 64u + (uint32_t)lane;
-                    G[b] += before[b];
-                    const uint32_t S = (uint32_t)__builtin_amdgcn_readlane((int)start_k[b], 0);
-                    const uint32_t Eg = (uint32_t)__builtin_amdgcn_readlane((int)end_k[b], 63);
-                    for (uint32_t e0 = S; e0 < Eg; e0 += 64u) {
-                        const uint32_t e = e0 + (uint32_t)lane;
-                        // the cell of staged posting e: the first of the 64 terms whose end lies behind e
-                        uint32_t lo = 0u, hi = 63u;
-#pragma unroll
-                        for (int step = 0; step < 6; ++step) {
-                            const uint32_t mid = (lo + hi) >> 1;
-                            const uint32_t km = tg * 64u + mid;
-                            const bool right = lds_get16(lcnt, km < last_k ? km : last_k) > e;
-                            hi = right ? mid : hi;
-                            lo = right ? lo : mid + 1u;
-                        }
-                        const uint32_t tsel = lo < 63u ? lo : 63u;
-                        const uint32_t kt = tg * 64u + tsel;
-                        const uint32_t start_t = kt == 0u ? 0u : lds_get16(lcnt, (kt - 1u) < last_k ? kt - 1u : last_k);
-                        const uint32_t G_t = (uint32_t)__shfl((int)G[b], (int)tsel, 64);
-                        if (e < Eg) out_filt[G_t + (e - start_t)] = stage[e];
+                    const uint32_t e = e0 + (uint32_t)b * stride + (uint32_t)lane;
+                    const uint32_t k = e < tot ? (uint32_t)sterm[e] : 0xffffffffu;
+                    const uint32_t before = (uint32_t)__shfl_up((int)k, 1, 64);
+                    head[b] = e < tot && (lane == 0 || k != before);
+                    delta[b] = 0u;
+                    if (head[b]) {   // index position of staged posting e' of this cell = delta + e'
+                        const uint32_t start = k == 0u ? 0u : lds_get16(lcnt, k - 1u);
+                        delta[b] = term_start[k] + mine[k] - start;
                     }
-                    if (mine_has[b]) mine[k] = before[b] + (end_k[b] - start_k[b]);
+                }
+#pragma unroll
+                for (int b = 0; b < FB; ++b) {
+                    const uint32_t e = e0 + (uint32_t)b * stride + (uint32_t)lane;
+                    const uint64_t heads = __ballot(head[b]) & (~0ull >> (63 - lane));      // heads at or below this lane
+                    const int src = heads ? 63 - __builtin_clzll(heads) : 0;
+                    const uint32_t d = (uint32_t)__shfl((int)delta[b], src, 64);
+                    if (e < tot) out_filt[d + e] = stage[e];
                 }
             }
         }
         __syncthreads();
+        if (!one_chunk) {
+            // the next chunk's cells start behind this one's: once a cell, by the lane that holds its first staged posting
+            for (uint32_t e = threadIdx.x; e < tot; e += blockDim.x) {
+                const uint32_t k = (uint32_t)sterm[e];
+                const uint32_t start = k == 0u ? 0u : lds_get16(lcnt, k - 1u);
+                if (e == start) mine[k] += lds_get16(lcnt, k) - start;
+            }
+            __syncthreads();
+        }
     }
 }
 
@@ -1007,10 +1072,68 @@ struct BuildPlan {   // everything the build decides before it allocates (plan_b
     // the staged fill's geometry (LDS path)
     bool staged = false;
     int32_t chunk_rows = 0;
-    uint32_t stage_cap = 0;
+    uint32_t stage_cap = 0;        // entries a chunk may hold to be staged (SG_FILL_STAGE_CAP lowers it)
+    uint32_t stage_alloc = 0;      // entries the stage has room for
     size_t staged_lds = 0;
     int32_t split = 1;
 };
+
+// ---- How many parts a tile is counted and filled in (staged fill).  Count and fill run one workgroup per part, and the fill's
+// LDS lets ONE workgroup live on a CU.  Equal workgroups run in rounds of as many as are resident, and a round costs the same
+// whether it is full or not: 544 parts on 256 CUs were three rounds for 2.1 rounds of work, the last on an eighth of the
+// chip.  The model below prices every split and takes the cheapest:
+//   a round of the fill   = per term and chunk (counters loaded or cleared, prefix sum, flags) + per posting of the part; a part
+//                           of several chunks counts its rows itself: more per posting;
+//   the table             = per cell of the [workgroup][term] table: the count pass writes it (and its packed copy), the
+//                           column scan reads and writes it.  (The tables kernel reads one row a tile whatever the split,
+//                           and the count pass's row work does not depend on the split: neither is priced.)
+// The constants are microseconds on MI355X, fitted to the kernels' times under forced splits 3 .. 7 at 663 k names (136 tiles,
+// 15 014 terms, 18.9 entries a row; profiles/postings_units_ab.log, where the fit is written out): fill 230 / 270 / 173 / 198 /
+// 188 us measured, 229 / 270 / 172 / 201 / 187 by the model.  (Taken before the fill staged its row pointers and loaded 32
+// entries of a row at once, which made it a tenth faster at split 5: the figures are high by about that much.)  They only
+// have to rank the splits: a wrong choice costs time, never a result.
+struct SplitCost {
+    int32_t split = 1;
+    int64_t parts = 0, part_rows = 0, chunks = 0, fill_rounds = 0;
+    double fill_us = 0, table_us = 0, total_us = 0;
+};
+static constexpr double SG_SPLIT_US_PER_TERM_AND_CHUNK = 0.78e-3, SG_SPLIT_US_PER_POSTING = 2.9e-3, SG_SPLIT_US_PER_POSTING_RECOUNT = 0.53e-3,
+                        SG_SPLIT_US_PER_CELL = 3.7e-6;
+static constexpr int32_t SG_SPLIT_MAX = 16, SG_SPLIT_MIN_PART_ROWS = 512;
+static SplitCost split_cost(int32_t split, int32_t tile_log2, int64_t n_tiles, int64_t n_terms, double mean_nnz, int32_t chunk_rows,
+                            int32_t num_cu) {
+    SplitCost c;
+    c.split = split;
+    c.parts = n_tiles * split;
+    for (int32_t part = 0; part < split; ++part) {
+        const int64_t rows = part_begin(part + 1, split, tile_log2) - part_begin(part, split, tile_log2);
+        if (rows > c.part_rows) c.part_rows = rows;
+    }
+    const int64_t cus = num_cu > 0 ? num_cu : 1;
+    c.fill_rounds = (c.parts + cus - 1) / cus;
+    c.chunks = (c.part_rows + chunk_rows - 1) / chunk_rows;
+    const double postings = (double)c.part_rows * mean_nnz;
+    c.fill_us = (double)c.fill_rounds * ((double)c.chunks * SG_SPLIT_US_PER_TERM_AND_CHUNK * (double)n_terms +
+                                         (SG_SPLIT_US_PER_POSTING + (c.chunks > 1 ? SG_SPLIT_US_PER_POSTING_RECOUNT : 0.0)) * postings);
+    c.table_us = SG_SPLIT_US_PER_CELL * (double)c.parts * (double)n_terms;
+    c.total_us = c.fill_us + c.table_us;
+    return c;
+}
+static int32_t choose_split(sg_ctx *ctx, const BuildPlan &pl, int64_t n_terms, double mean_nnz) {
+    SplitCost best;
+    const bool say = ctx->opt_is("SG_POSTINGS_PLAN", '1');   // (the model's figures on stderr, for the logs under profiles/)
+    for (int32_t s = 1; s <= SG_SPLIT_MAX; ++s) {
+        if (s > 1 && (pl.tile_cols / s < SG_SPLIT_MIN_PART_ROWS || pl.n_bins * s + 1 >= ((int64_t)1 << 31))) break;
+        const SplitCost c = split_cost(s, pl.tile_log2, pl.n_tiles, n_terms, mean_nnz, pl.chunk_rows, ctx->num_cu);
+        if (say)
+            fprintf(stderr, "sg postings plan: split %d: %lld parts of <= %lld rows (%lld chunks), %lld rounds of the fill, us fill %.1f table %.1f = %.1f\n",
+                    s, (long long)c.parts, (long long)c.part_rows, (long long)c.chunks, (long long)c.fill_rounds, c.fill_us, c.table_us, c.total_us);
+        if (s == 1 || c.total_us < best.total_us) best = c;
+    }
+    if (say) fprintf(stderr, "sg postings plan: chosen split %d (%lld tiles, %lld terms, chunks of %d rows)\n", best.split, (long long)pl.n_tiles,
+                     (long long)n_terms, pl.chunk_rows);
+    return best.split;
+}
 
 static int plan_build(sg_ctx *ctx, const sg_csr *B, int32_t tile_cols, int32_t flags, bool cosine_like, float max_norm2,
                       BuildPlan *out) {
@@ -1093,40 +1216,41 @@ static int plan_build(sg_ctx *ctx, const sg_csr *B, int32_t tile_cols, int32_t f
         pl.freq_min = fm < 1.0 ? 1u : (uint32_t)fm;
     }
     if (pl.lds_path) {
-        // Round 6: filter postings staged in LDS and written cell by cell (postings_fill_staged) -- when only the filter
-        // postings are written (the exact kernel's are lazy) and a chunk of at least 64 rows fits the stage.  The stage
-        // takes what the packed counters leave of 158 KiB: one workgroup per CU, so tiles are split until there are two
-        // workgroups per CU (parts of >= 512 rows) and a launch does not end with a few CUs working alone.
-        pl.staged = pl.lazy_full && !ctx->opt_is("SG_FILL_STAGED", '0');
+        // Filter postings staged in LDS and written cell by cell (postings_fill_staged) -- when only the filter postings are
+        // written (the exact kernel's are lazy) and a chunk of at least 64 rows fits the stage.  The stage -- six bytes a
+        // posting: the posting and its term -- takes what the packed counters leave of 158 KiB: one workgroup per CU.  A
+        // chunk is as many rows (a multiple of 64, 2048 at most) as fit it at 1.2 x the mean row, and choose_split then
+        // looks for parts that are ONE chunk and whose rounds fill the chip.
+        pl.staged = pl.lazy_full && !ctx->opt_is("SG_FILL_STAGED", '0') && B->n_cols <= 65535;
         const double mean_nnz = B->n_rows > 0 ? (double)B->nnz / (double)B->n_rows : 1.0;
         if (pl.staged) {
             const size_t fixed0 = ((((size_t)B->n_cols + 1) / 2 + 3) & ~(size_t)3) * 4 + (((size_t)B->n_cols + 31) / 32) * 4 + 32 * 4;
-            pl.chunk_rows = 2048;
-            for (;;) {
-                const size_t fixed = fixed0 + (size_t)pl.chunk_rows * 4;
-                const size_t room = fixed + 16384 < 158 * 1024 ? 158 * 1024 - fixed : 0;
-                pl.stage_cap = (uint32_t)(room / 4);
-                if (pl.stage_cap > 65535u) pl.stage_cap = 65535u;
-                if ((double)pl.chunk_rows * mean_nnz * 1.2 + 64.0 <= (double)pl.stage_cap || pl.chunk_rows <= 64) break;
-                pl.chunk_rows >>= 1;
-            }
-            pl.staged = (double)pl.chunk_rows * mean_nnz * 1.2 + 64.0 <= (double)pl.stage_cap;
-            pl.staged_lds = fixed0 + (size_t)pl.chunk_rows * 4 + (size_t)pl.stage_cap * 4;
+            const size_t room = fixed0 + 16384 < 158 * 1024 ? 158 * 1024 - fixed0 : 0;
+            // rows r of a chunk: 6 bytes a posting for r x 1.2 x the mean row + 64 postings, 4 bytes a row pointer
+            const double per_row = (mean_nnz * 1.2 > 1.0 ? mean_nnz * 1.2 : 1.0) * 6.0 + 4.0;
+            const double fit = ((double)room - 64.0 * 6.0 - 32.0) / per_row;
+            pl.chunk_rows = fit >= 2048.0 ? 2048 : (fit > 0.0 ? (int32_t)fit & ~63 : 0);
+            pl.staged = pl.chunk_rows >= 64;
+            const size_t rowp_bytes = (size_t)staged_rowp_words(pl.chunk_rows) * 4;
+            pl.stage_alloc = pl.staged ? (uint32_t)((room - rowp_bytes) / 6) & ~1u : 0u;
+            if (pl.stage_alloc > 65534u) pl.stage_alloc = 65534u;
+            pl.stage_cap = pl.stage_alloc;
+            pl.staged_lds = fixed0 + rowp_bytes + (size_t)pl.stage_alloc * 6;
             if (const char *v = ctx->opt("SG_FILL_STAGE_CAP"))    // test hook: chunks that do not fit go posting by posting
                 if (atoi(v) > 0 && (uint32_t)atoi(v) < pl.stage_cap) pl.stage_cap = (uint32_t)atoi(v);
         }
-        // fewer tiles than CUs: split every tile between 2 or 4 workgroups (parts of >= 1024 rows)
         int32_t split = 1;
-        while (split < 4 && pl.n_tiles * split < ctx->num_cu && (tile_cols / (split * 2)) >= 1024 &&
-               (pl.n_bins * split * 2 + 1) < ((int64_t)1 << 31))
-            split *= 2;
-        if (pl.staged)
-            while (split < 8 && pl.n_tiles * split < 2 * (int64_t)ctx->num_cu && (tile_cols / (split * 2)) >= 512 &&
+        if (pl.staged) {
+            split = choose_split(ctx, pl, B->n_cols, mean_nnz);
+        } else {
+            // fewer tiles than CUs: split every tile between 2 or 4 workgroups (parts of >= 1024 rows)
+            while (split < 4 && pl.n_tiles * split < ctx->num_cu && (tile_cols / (split * 2)) >= 1024 &&
                    (pl.n_bins * split * 2 + 1) < ((int64_t)1 << 31))
                 split *= 2;
-        if (const char *e = ctx->opt("SG_POSTINGS_SPLIT")) {
+        }
+        if (const char *e = ctx->opt("SG_POSTINGS_SPLIT")) {   // test and A/B hook: any number of parts up to SG_SPLIT_MAX
             const int o = atoi(e);
-            if ((o == 1 || o == 2 || o == 4) && tile_cols / o >= 64 && pl.n_bins * o + 1 < ((int64_t)1 << 31)) split = o;
+            if (o >= 1 && o <= SG_SPLIT_MAX && tile_cols / o >= 64 && pl.n_bins * o + 1 < ((int64_t)1 << 31)) split = o;
         }
         pl.split = split;
     }
@@ -1313,6 +1437,7 @@ static int alloc_index(sg_ctx *ctx, sg_postings *p, const sg_csr *B_in, const sg
 // list lengths, their frequent flags and the lists' starts on the way and writes the filter postings too; `values_only`
 // (sg_postings_ensure_full) re-reads the starts and writes the postings proper alone.
 static int lds_count_scan_fill(sg_ctx *ctx, sg_postings *p, uint32_t *cnt /* [workgroup][term] (see postings_count_lds) */,
+                               uint32_t *cnt16 /* the parts' own counts, packed, for the staged fill; or null */,
                                uint32_t *term_len, uint8_t *is_frequent, bool values_only, bool fill) {
     const sg_csr *B = &p->src;
     const int32_t split = p->split > 0 ? p->split : 1;
@@ -1324,7 +1449,7 @@ static int lds_count_scan_fill(sg_ctx *ctx, sg_postings *p, uint32_t *cnt /* [wo
     const int32_t fold_log2 = values_only ? 0 : p->fold_log2;
     SG_TRY(allow_dynamic_lds<postings_count_lds>(124 * 1024));
     hipLaunchKernelGGL(postings_count_lds, dim3(wgs), dim3(1024), (size_t)B->n_cols * 4, ctx->stream, B->d_indptr, B->d_indices,
-                       B->n_rows, p->tile_log2, (int32_t)B->n_cols, split, cnt);
+                       B->n_rows, p->tile_log2, (int32_t)B->n_cols, split, cnt, cnt16);
     hipLaunchKernelGGL(postings_colscan_kernel, dim3((unsigned)((B->n_cols + 63) / 64)), dim3(1024), 0, ctx->stream, cnt,
                        (int32_t)wgs64, (int32_t)B->n_cols, values_only ? 0u : p->freq_min, term_len, is_frequent);
     // the terms' lists back to back: starts of the lists, the last entry receives the total (= nnz)
@@ -1347,13 +1472,14 @@ static int fill_lds_path(sg_ctx *ctx, sg_postings *p, const BuildPlan &plan) {
     const sg_csr *B = &p->src;
     const unsigned wgs = (unsigned)((int64_t)p->n_tiles * plan.split);
     Scratch scratch(ctx);
-    uint32_t *cnt = nullptr;
+    uint32_t *cnt = nullptr, *cnt16 = nullptr;
     uint8_t *is_frequent = nullptr;
     SG_TRY(scratch.alloc((size_t)((int64_t)p->n_tiles * plan.split * B->n_cols) + 1, &cnt));
+    if (plan.staged) SG_TRY(scratch.alloc((size_t)((int64_t)p->n_tiles * plan.split * ((B->n_cols + 1) / 2)) + 1, &cnt16));
     SG_TRY(scratch.alloc((size_t)B->n_cols + 4, &is_frequent));
     SG_TRY(sg_alloc(ctx, (size_t)B->n_cols + 2, &p->d_term_start));
-    // (the staged fill comes after the tables: it advances the workgroups' rows of `cnt`)
-    SG_TRY(lds_count_scan_fill(ctx, p, cnt, p->d_term_len, is_frequent, /*values_only=*/false, /*fill=*/!plan.staged));
+    // (the staged fill comes after the tables: a part of several chunks advances its workgroup's row of `cnt`)
+    SG_TRY(lds_count_scan_fill(ctx, p, cnt, cnt16, p->d_term_len, is_frequent, /*values_only=*/false, /*fill=*/!plan.staged));
     // the tables kernel writes the null postings and the scoring context as well (write_aux has them on the other path)
     if (p->d_fwd_ptr) SG_TRY(ctx->alloc(256, (void **)&p->d_score_ctx));
     hipLaunchKernelGGL(postings_tables_kernel, dim3((unsigned)((B->n_cols + 64) / 64)), dim3(1024), 0, ctx->stream, (const uint32_t *)cnt,
@@ -1367,7 +1493,8 @@ static int fill_lds_path(sg_ctx *ctx, sg_postings *p, const BuildPlan &plan) {
             SG_TRY(allow_dynamic_lds<kern>(160 * 1024));
             hipLaunchKernelGGL(kern, dim3(wgs), dim3(1024), plan.staged_lds, ctx->stream, B->d_indptr,
                                B->d_indices, (const T *)B->d_data, B->n_rows, p->tile_log2, (int32_t)B->n_cols, plan.split,
-                               plan.chunk_rows, plan.stage_cap, cnt, (const uint32_t *)p->d_term_start, (const uint8_t *)is_frequent,
+                               plan.chunk_rows, plan.stage_cap, plan.stage_alloc, cnt, (const uint32_t *)cnt16,
+                               (const uint32_t *)p->d_term_start, (const uint8_t *)is_frequent,
                                p->d_filt, 1.0f / p->norm_up, p->fold_log2);
             return SG_OK;
         }));
@@ -1572,7 +1699,7 @@ int sg_postings_ensure_full(sg_ctx *ctx, const sg_postings *cp) {
     const int32_t split = p->split > 0 ? p->split : 1;
     if (st == SG_OK) st = scratch.alloc((size_t)((int64_t)p->n_tiles * split * B->n_cols) + 1, &cnt);
     if (st == SG_OK) st = scratch.alloc((size_t)B->n_cols + 2, &len_scratch);
-    if (st == SG_OK) st = lds_count_scan_fill(ctx, p, cnt, len_scratch, nullptr, /*values_only=*/true, /*fill=*/true);
+    if (st == SG_OK) st = lds_count_scan_fill(ctx, p, cnt, nullptr, len_scratch, nullptr, /*values_only=*/true, /*fill=*/true);
     if (st != SG_OK) {     // (the scratch takes the two arrays back)
         p->d_vals = nullptr;
         p->d_rows = nullptr;
