@@ -250,7 +250,10 @@ struct SgScoreCtx {
     //   word 0  first entry of the row among the packed rows (`fwd`)        } what the exact scoring needs of the row: a
     //   word 1  the row's own index (position -> row)                       } candidate that passes costs no pointer fetch
     //   word 2  the row's entries (bits [0, 31)); bit 31: no 8-bit copy (more than SG_Q8_MAX_ENTRIES entries: always passes)
-    //   word 3  0
+    //   word 3  four REST NORMS, a byte each (byte f: boundary SG_Q8_REST_UNIT(f)): the least integer r with
+    //           r >= sqrt(sum of bq_e^2 over the entries e >= 4 u), what the record still holds behind its unit u -- or 255:
+    //           nothing known (the root is 255 or more, or the index was built with SG_Q8_EARLY=0).  The second filter stops
+    //           reading a record whose rest cannot lift the bound over the bar (q8_passes).  Unused by rows without a copy.
     //   words 4 .. 63  entries in ascending term order, (term << 8) | bq, bq = ceil(value / norm_up * 255) -- rounded UP, so
     //           sum_k a_k * bq_k * norm_up / 255 is an upper bound of the pair's score; zero behind the row's last entry
     //           (only the 16-byte units a row uses are written, and read: 28 entries fit the first 128-byte line)
@@ -263,6 +266,9 @@ struct SgScoreCtx {
 };
 #define SG_Q8_STRIDE 256u
 #define SG_Q8_MAX_ENTRIES 60u   // 16 units of 16 bytes: the header, then four entries a unit
+// the four units behind which a record's rest norm is stored (ascending; scripts/k4p_q8_early_exit_model.py chose them)
+#define SG_Q8_REST_UNIT(f) ((f) == 0 ? 2u : (f) == 1 ? 3u : (f) == 2 ? 4u : 6u)
+#define SG_Q8_REST_UNKNOWN 255u
 
 // Groups of identical right-hand rows (sg_collapse.hip): the index is built over one representative per group.
 struct SgCollapse {
@@ -311,6 +317,7 @@ struct sg_postings {
     void *d_blk = nullptr;               // row blocks at a fixed stride (SgScoreCtx::blk)
     uint32_t blk_bytes = 0;
     void *d_q8 = nullptr;                // 8-bit copies of the rows at a fixed stride (SgScoreCtx::q8), (n_right + 1) records
+    mutable bool q8_early = true;        // the records hold their rest norms (false: all "unknown", SG_Q8_EARLY=0); sg_postings_sync_q8_early
     // 4-byte "filter postings", same order as the postings proper (only for cosine-like B): the column inside its tile
     // (or super-tile), the value and the norm of the row's frequent part (terms of list length >= freq_min), both
     // quantised UPWARDS relative to norm_up.  The fields differ between the tile-by-tile form (fold_log2 == 0) and the
@@ -422,6 +429,9 @@ int sg_csr_props(sg_ctx *ctx, const sg_csr *m, bool *cosine_like, float *max_nor
 bool sg_pruned_supports_tile(int32_t tile_log2);
 int sg_postings_ensure_full(sg_ctx *ctx, const sg_postings *p);   // sg_postings.hip: the exact kernel's postings, on demand
 bool sg_q8_applies(const sg_ctx *ctx, const sg_postings *Bt, double threshold);   // sg_spgemm_pruned.hip: second filter in this call?
+// sg_postings.hip: the records' rest norms as the context's SG_Q8_EARLY asks NOW (re-written in place where the index was
+// built under the other setting); called by the multiply before a launch that reads the records
+int sg_postings_sync_q8_early(sg_ctx *ctx, const sg_postings *Bt);
 int sg_spgemm_pruned_launch(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t keep, sg_topn *r,
                             double threshold, double delta, uint32_t *row_counter,
                             uint32_t *flagged_count, uint32_t *flagged_rows, unsigned long long *stats);

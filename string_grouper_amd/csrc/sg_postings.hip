@@ -846,10 +846,25 @@ struct PermutedLenLoad {
 __device__ __forceinline__ uint32_t sg_q8_units(int64_t nnz) {
     return nnz > (int64_t)SG_Q8_MAX_ENTRIES ? 1u : (uint32_t)((nnz + 7) >> 2);   // (the header + four entries a unit)
 }
+// The header's fourth word: four REST NORMS of the record (SgScoreCtx, sg_internal.h), a byte each -- the root of the sum of
+// bq^2 over the entries behind unit SG_Q8_REST_UNIT(f), rounded UP, so that the second filter may bound what it has not
+// read (Cauchy-Schwarz, q8_passes).  The sum is an integer (at most 60 * 255^2 < 2^22: exact in 32 bits, and exact as a
+// float, whose root is then off by one at most); the root is settled in integers: the least r with r * r >= s.  A root of
+// 255 or more is stored as SG_Q8_REST_UNKNOWN, which the reader takes for "no bound" -- as it takes every field of an
+// index built with SG_Q8_EARLY=0 (`unknown` = all ones), the switch: no check can fire then.
+__device__ __forceinline__ uint32_t q8_root_up(uint32_t s) {
+    uint32_t r = (uint32_t)sqrtf((float)s);
+    while (r * r < s) ++r;
+    while (r > 0u && (r - 1u) * (r - 1u) >= s) --r;
+    return r < SG_Q8_REST_UNKNOWN ? r : SG_Q8_REST_UNKNOWN;
+}
+__device__ __forceinline__ uint32_t q8_rest_word(const uint32_t (&sums)[4], uint32_t unknown) {
+    return unknown | q8_root_up(sums[0]) | (q8_root_up(sums[1]) << 8) | (q8_root_up(sums[2]) << 16) | (q8_root_up(sums[3]) << 24);
+}
 template <typename T>
 __device__ __forceinline__ void q8_write_unit(uint4 *__restrict__ rec, uint32_t u, const int32_t *__restrict__ indices,
                                               const T *__restrict__ data, int64_t src, int64_t nnz, uint32_t first_packed,
-                                              uint32_t name, float inv_norm) {
+                                              uint32_t name, float inv_norm, uint32_t rest_unknown) {
     auto entry = [&](int64_t e) -> uint32_t {
         if (e >= nnz) return 0u;
         const float q = ceilf((float)data[src + e] * inv_norm * 255.0f * 1.000002f);
@@ -858,7 +873,15 @@ __device__ __forceinline__ void q8_write_unit(uint4 *__restrict__ rec, uint32_t 
     };
     uint4 w;
     if (u == 0) {
-        w = make_uint4(first_packed, name, (uint32_t)nnz | (nnz <= (int64_t)SG_Q8_MAX_ENTRIES ? 0u : 0x80000000u), 0u);
+        const bool whole = nnz <= (int64_t)SG_Q8_MAX_ENTRIES;
+        uint32_t sums[4] = {0u, 0u, 0u, 0u};
+        for (int64_t e = 4 * (int64_t)SG_Q8_REST_UNIT(0); whole && e < nnz; ++e) {   // (from the first boundary on)
+            const uint32_t bq = entry(e) & 255u;
+#pragma unroll
+            for (int f = 0; f < 4; ++f)
+                if (e >= 4 * (int64_t)SG_Q8_REST_UNIT(f)) sums[f] += bq * bq;
+        }
+        w = make_uint4(first_packed, name, (uint32_t)nnz | (whole ? 0u : 0x80000000u), q8_rest_word(sums, whole ? rest_unknown : ~0u));
     } else {
         const int64_t e0 = 4 * (int64_t)u - 4;
         w = make_uint4(entry(e0), entry(e0 + 1), entry(e0 + 2), entry(e0 + 3));
@@ -871,14 +894,14 @@ template <typename T>
 __global__ void __launch_bounds__(256) q8_pack_kernel(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                                       const T *__restrict__ data, int64_t n_rows,
                                                       const uint32_t *__restrict__ orig_of /* position -> row; null: identity */,
-                                                      uint4 *__restrict__ q8, float inv_norm) {
+                                                      uint4 *__restrict__ q8, float inv_norm, uint32_t rest_unknown) {
     const int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const uint32_t sub = threadIdx.x & 15;
     if (p >= n_rows) return;
     const int64_t base = indptr[0], src = indptr[p], n = indptr[p + 1] - src;
     if (sub < sg_q8_units(n))
         q8_write_unit<T>(q8 + p * (SG_Q8_STRIDE / 16), sub, indices, data, src, n, (uint32_t)(src - base),
-                         orig_of ? orig_of[p] : (uint32_t)p, inv_norm);
+                         orig_of ? orig_of[p] : (uint32_t)p, inv_norm, rest_unknown);
 }
 
 // ONE read of the source rows for every copy of them the index keeps (round 4).  Position p of the index holds row
@@ -894,6 +917,9 @@ __global__ void __launch_bounds__(256) q8_pack_kernel(const int64_t *__restrict_
 // loads of a stage issued before the first is used, and a row's first 32 entries in flight together: the kernel ran at the
 // latency of its chain (0.21 ms for 0.4 GB); (d) the 8-bit records are put together from the registers that hold the
 // entries (four shuffles a round), not by reading the row a second time.
+// The record's rest norms (q8_rest_word) are summed the same way: every lane adds the squares of its own entries behind each
+// of the four boundaries, round by round, the sixteen lanes' sums are added once the whole row has been seen, and the header
+// -- which therefore is the LAST unit written -- takes the word.
 #ifndef SG_GATHER_ROWS     // (A/B knob of the build: scripts/build_variant.sh)
 #define SG_GATHER_ROWS 2
 #endif
@@ -932,7 +958,8 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const int64_t *__restr
                                                           const int64_t *__restrict__ perm_ptr, int32_t *__restrict__ perm_indices,
                                                           T *__restrict__ perm_data,
                                                           uint32_t *__restrict__ fwd_ptr /* null: no packed rows */, void *__restrict__ fwd,
-                                                          uint4 *__restrict__ q8 /* null: no 8-bit copies */, float inv_norm) {
+                                                          uint4 *__restrict__ q8 /* null: no 8-bit copies */, float inv_norm,
+                                                          uint32_t rest_unknown /* all ones: SG_Q8_EARLY=0 */) {
     const int64_t grp = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const int sub = threadIdx.x & 15;
     const int64_t p0 = grp * SG_GATHER_ROWS;
@@ -986,10 +1013,14 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const int64_t *__restr
         if (!valid[i]) continue;
         const uint32_t units = q8 ? sg_q8_units(n[i]) : 0u;
         uint4 *rec = q8 ? q8 + p * (SG_Q8_STRIDE / 16) : nullptr;
-        if (sub == 0) {
-            if (fwd_ptr) reinterpret_cast<uint2 *>(fwd_ptr)[p] = make_uint2((uint32_t)dst[i], g[i]);
-            if (q8) rec[0] = make_uint4((uint32_t)dst[i], g[i], (uint32_t)n[i] | (n[i] <= (int32_t)SG_Q8_MAX_ENTRIES ? 0u : 0x80000000u), 0u);
-        }
+        if (sub == 0 && fwd_ptr) reinterpret_cast<uint2 *>(fwd_ptr)[p] = make_uint2((uint32_t)dst[i], g[i]);
+        uint32_t rest[4] = {0u, 0u, 0u, 0u};   // this lane's share of the sums of bq^2 behind the four boundaries
+        auto add_rest = [&](uint32_t wq, int32_t e) {
+            const uint32_t bq = wq & 255u;
+#pragma unroll
+            for (int f = 0; f < 4; ++f)
+                if (e >= 4 * (int32_t)SG_Q8_REST_UNIT(f)) rest[f] += bq * bq;
+        };
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const int32_t e = sub + 16 * r;
@@ -999,7 +1030,11 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const int64_t *__restr
                 perm_data[dst[i] + e] = v[i][r];
                 if (fwd) store_packed<T>(fwd, dst[i] + e, k[i][r], v[i][r]);
             }
-            if (units > 1u && 16 * r < n[i]) q8_write_round(rec, r, q8_entry_of<T>(k[i][r], v[i][r], have, inv_norm), sub, units);
+            if (units > 1u && 16 * r < n[i]) {
+                const uint32_t wq = q8_entry_of<T>(k[i][r], v[i][r], have, inv_norm);
+                add_rest(wq, e);
+                q8_write_round(rec, r, wq, sub, units);
+            }
         }
         for (int r = 2; 16 * r < n[i]; ++r) {     // rows beyond 32 entries
             const int32_t e = sub + 16 * r;
@@ -1011,9 +1046,44 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const int64_t *__restr
                 perm_data[dst[i] + e] = vv;
                 if (fwd) store_packed<T>(fwd, dst[i] + e, kk, vv);
             }
-            if (units > 1u && r < 4) q8_write_round(rec, r, q8_entry_of<T>(kk, vv, have, inv_norm), sub, units);
+            if (units > 1u && r < 4) {
+                const uint32_t wq = q8_entry_of<T>(kk, vv, have, inv_norm);
+                add_rest(wq, e);
+                q8_write_round(rec, r, wq, sub, units);
+            }
+        }
+        if (q8) {
+            const bool whole = n[i] <= (int32_t)SG_Q8_MAX_ENTRIES;
+            if (units > 1u) {   // (the same for the sixteen lanes of a row)
+#pragma unroll
+                for (int f = 0; f < 4; ++f)
+#pragma unroll
+                    for (int d = 1; d < 16; d <<= 1) rest[f] += (uint32_t)__shfl_xor((int)rest[f], d, 64);
+            }
+            if (sub == 0)
+                rec[0] = make_uint4((uint32_t)dst[i], g[i], (uint32_t)n[i] | (whole ? 0u : 0x80000000u),
+                                    q8_rest_word(rest, whole ? rest_unknown : ~0u));
         }
     }
+}
+
+// The rest norms of records that are already written, from the records themselves: the switch SG_Q8_EARLY holds for the
+// multiplies that follow it, also over an index built before it was set (sg_postings_sync_q8_early) -- the two settings can
+// then be compared on ONE index, posting for posting the same.  A thread a record; only the header's fourth word is written.
+__global__ void __launch_bounds__(256) q8_rest_kernel(uint4 *__restrict__ q8, int64_t n_rows, uint32_t rest_unknown) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_rows) return;
+    uint32_t *rec = reinterpret_cast<uint32_t *>(q8 + p * (SG_Q8_STRIDE / 16));
+    const uint32_t word2 = rec[2], n = word2 & 0x7fffffffu;
+    const bool whole = (word2 >> 31) == 0u && n <= SG_Q8_MAX_ENTRIES;
+    uint32_t sums[4] = {0u, 0u, 0u, 0u};
+    for (uint32_t e = 4u * SG_Q8_REST_UNIT(0); whole && rest_unknown == 0u && e < n; ++e) {
+        const uint32_t bq = rec[4u + e] & 255u;
+#pragma unroll
+        for (int f = 0; f < 4; ++f)
+            if (e >= 4u * SG_Q8_REST_UNIT(f)) sums[f] += bq * bq;
+    }
+    rec[3] = q8_rest_word(sums, whole ? rest_unknown : ~0u);
 }
 
 __global__ void score_ctx_kernel(SgScoreCtx v, SgScoreCtx *out) {
@@ -1052,6 +1122,19 @@ static SgScoreCtx score_ctx_of(const sg_postings *p) {
     sc.q8 = (const uint4 *)p->d_q8;
     sc.q8_scale = p->d_q8 ? __builtin_nextafterf((float)(255.0 / (double)p->norm_up * (1.0 - 1e-6)), 0.f) : 0.f;
     return sc;
+}
+
+// SG_Q8_EARLY=0: the records' rest norms are all written as "unknown", so that the second filter reads every record to its
+// end as it did before it had them (A/B and test hook; the multiply itself has one code path)
+static uint32_t q8_rest_unknown(const sg_ctx *ctx) { return ctx->opt_is("SG_Q8_EARLY", '0') ? ~0u : 0u; }
+int sg_postings_sync_q8_early(sg_ctx *ctx, const sg_postings *Bt) {
+    const bool want = q8_rest_unknown(ctx) == 0u;
+    if (!Bt->d_q8 || Bt->q8_early == want || Bt->n_right <= 0) return SG_OK;
+    hipLaunchKernelGGL(q8_rest_kernel, dim3((unsigned)((Bt->n_right + 255) / 256)), dim3(256), 0, ctx->stream, (uint4 *)Bt->d_q8,
+                       Bt->n_right, want ? 0u : ~0u);
+    if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
+    Bt->q8_early = want;
+    return SG_OK;
 }
 
 // a tile's counters ([term], a workgroup's own) + one bit per term (frequent or not) in LDS
@@ -1288,6 +1371,7 @@ static uint64_t gcd_u64(uint64_t a, uint64_t b) {
 static int build_permuted(sg_ctx *ctx, const sg_csr *B, int64_t tile_cols, sg_postings *p,
                           SgCollapse *pending /* B = pending->unique, its rows not written yet; or null */,
                           EarlyRows *rows /* packed rows and 8-bit copies to write along (null members: none) */, float inv_norm) {
+    const uint32_t rest_unknown = q8_rest_unknown(ctx);
     if (ctx->opt_is("SG_PERMUTE", '0') || B->n_rows <= 2 * tile_cols || B->n_rows >= ((int64_t)1 << 31) || B->nnz <= 0) return SG_OK;
     const uint64_t n = (uint64_t)B->n_rows;
     uint64_t mult = (uint64_t)(0.6180339887498949 * (double)n) | 1ull;
@@ -1331,7 +1415,8 @@ static int build_permuted(sg_ctx *ctx, const sg_csr *B, int64_t tile_cols, sg_po
         using T = decltype(tag);
         hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(grid), dim3(256), 0, ctx->stream, src->d_indptr, src->d_indices,
                            (const T *)src->d_data, B->n_rows, (const uint32_t *)orig_of, rep_rows, rep_start, rep_len,
-                           (const int64_t *)ptr, idx, (T *)val, rows->fwd_ptr, rows->fwd, (uint4 *)(rows->fwd_ptr ? rows->q8 : nullptr), inv_norm);
+                           (const int64_t *)ptr, idx, (T *)val, rows->fwd_ptr, rows->fwd, (uint4 *)(rows->fwd_ptr ? rows->q8 : nullptr), inv_norm,
+                           rest_unknown);
         return SG_OK;
     });
     if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
@@ -1409,6 +1494,7 @@ static int alloc_index(sg_ctx *ctx, sg_postings *p, const sg_csr *B_in, const sg
         SG_TRY(row_block_bytes(ctx, B, &p->blk_bytes));
         if (p->blk_bytes) SG_TRY(ctx->alloc((size_t)p->blk_bytes * ((size_t)B->n_rows + 1), &p->d_blk));
     }
+    p->q8_early = q8_rest_unknown(ctx) == 0u;   // (what either record writer of this build stores)
     if (rows->written) {          // written along with the rows' copy in position order (build_permuted)
         p->d_fwd = early.keep(rows->fwd);
         p->d_fwd_ptr = early.keep(rows->fwd_ptr);
@@ -1579,7 +1665,8 @@ static int pack_rows(sg_ctx *ctx, sg_postings *p, bool rows_written) {
                                (const T *)B->d_data, B->n_rows, B->nnz, (const uint32_t *)p->d_orig_of, p->d_fwd_ptr, p->d_fwd);
             if (p->d_q8 && B->n_rows > 0)
                 hipLaunchKernelGGL(q8_pack_kernel<T>, dim3(g4), dim3(256), 0, ctx->stream, B->d_indptr, B->d_indices,
-                                   (const T *)B->d_data, B->n_rows, (const uint32_t *)p->d_orig_of, (uint4 *)p->d_q8, 1.0f / p->norm_up);
+                                   (const T *)B->d_data, B->n_rows, (const uint32_t *)p->d_orig_of, (uint4 *)p->d_q8, 1.0f / p->norm_up,
+                                   q8_rest_unknown(ctx));
             return SG_OK;
         });
         if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;

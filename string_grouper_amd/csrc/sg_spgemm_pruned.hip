@@ -360,13 +360,17 @@ __device__ __forceinline__ void row_values(const int *hk, const T *ha, const int
     for (int q = 0; q < N; ++q) out[q] = found[q] ? v[q] : (T)0;
 }
 
+// (`matched`: the sum of a_k^2 over the terms looked up so far -- what of row i the record has met, for the early exit below)
 template <typename T, bool WIDE>
-__device__ __forceinline__ float q8_unit(uint4 w, const int *hk, const T *ha, int nnz, float ub) {
+__device__ __forceinline__ float q8_unit(uint4 w, const int *hk, const T *ha, int nnz, float ub, float &matched) {
     const uint32_t e[4] = {w.x, w.y, w.z, w.w};   // (an entry behind the row's last is 0: term 0 times bq = 0)
     if (WIDE) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            ub = __builtin_fmaf((float)row_value<T, true>(hk, ha, (int)(e[q] >> 8), nnz), (float)(e[q] & 255u), ub);
+        for (int q = 0; q < 4; ++q) {
+            const float a = (float)row_value<T, true>(hk, ha, (int)(e[q] >> 8), nnz);
+            ub = __builtin_fmaf(a, (float)(e[q] & 255u), ub);
+            matched = __builtin_fmaf(a, a, matched);
+        }
         return ub;
     }
     const int t[4] = {(int)(e[0] >> 8), (int)(e[1] >> 8), (int)(e[2] >> 8), (int)(e[3] >> 8)};
@@ -374,9 +378,57 @@ __device__ __forceinline__ float q8_unit(uint4 w, const int *hk, const T *ha, in
     row_values<T, 4>(hk, ha, t, a);
 #pragma unroll
     for (int q = 0; q < 4; ++q) ub = __builtin_fmaf((float)a[q], (float)(e[q] & 255u), ub);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) matched = __builtin_fmaf((float)a[q], (float)a[q], matched);
     return ub;
 }
 
+// sum over the wave's lanes, the same in every lane's view (a scalar): four DPP steps inside a row of sixteen, the four rows by name
+__device__ __forceinline__ float wave_sum(float v) {
+#define SG_DPP_F32(x, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), ctrl, 0xf, 0xf, true))
+    v += SG_DPP_F32(v, 0xB1);    // quad_perm [1, 0, 3, 2]
+    v += SG_DPP_F32(v, 0x4E);    // quad_perm [2, 3, 0, 1]
+    v += SG_DPP_F32(v, 0x141);   // row_half_mirror
+    v += SG_DPP_F32(v, 0x140);   // row_mirror
+#undef SG_DPP_F32
+    return (wave_read<float>(v, 0) + wave_read<float>(v, 16)) + (wave_read<float>(v, 32) + wave_read<float>(v, 48));
+}
+
+// ||a||^2 of the row staged in LDS -- of the FLOAT values the bound multiplies, every term of the row -- times 1 + 2e-5: see
+// q8_passes.  Once per call of the survivor routine (a call per 64 candidates), from the row's stage: the round loop's kernel
+// carries nothing for it.
+template <typename T, bool WIDE>
+__device__ __forceinline__ float staged_row_norm2_up(const int *hk, const T *ha, int nnz) {
+    const int lane = threadIdx.x;
+    float s = 0.f;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int at = lane + 64 * h;
+        const bool holds = WIDE ? at < nnz : hk[at] != -1;   // (wide: the sorted row itself; else the hash, -1 = free slot)
+        const float a = holds ? (float)ha[at] : 0.f;
+        s = __builtin_fmaf(a, a, s);
+    }
+    return wave_sum(s) * 1.00002f;
+}
+
+// EARLY EXIT.  A lane stops reading its record behind unit u -- one of the four boundaries the header has a rest norm R_u
+// for (SgScoreCtx, sg_internal.h; written by K3) -- when
+//        fl(ub + A_rest * R_u) < bar * (1 - 2e-5),
+// A_rest = sqrt(na2_up - matched).  Such a lane would have failed `ub >= bar` at the end, so the set that passes, the
+// statistics and every result bit are what they were; a lane that is never stopped computes the same ub, bit for bit.  Proof:
+//   * the terms of a row are distinct, so the entries not yet read meet only terms of row i that no entry read so far has
+//     met: by Cauchy-Schwarz they add at most  sqrt(sum of those a_k^2) * sqrt(sum of the unread bq_e^2)  to the exact U,
+//     over the float values a_k the bound multiplies;
+//   * R_u >= the second root: K3 rounds it up in integers (and 255 = "unknown" never rejects);
+//   * A_rest >= the first: na2_up = fl(sum of ALL a_k^2) * 1.00002 exceeds the exact sum by 1.9e-5 of it (the float sum of
+//     128 terms loses less than 1e-6), `matched` exceeds the exact matched sum by at most 60 * 2^-24 = 3.6e-6 of the whole,
+//     the subtraction loses 2^-24, the hardware root (v_sqrt_f32, one ulp) 2^-23 -- and the floor of 1e-30 under the root
+//     keeps its argument a normal number;
+//   * the final ub is the float fma chain continued from this ub over at most 60 entries: at most (1 + 2^-24)^60 times the
+//     exact  ub + rest;  with the rounding of the test's own fma and of the bar's product, all of it is below 5e-6, and the
+//     bar is lowered by 2e-5.  (bar <= 0: the left side is never negative, nothing is rejected.)
+// The existing 3e-5 allowance is not drawn on.  The unit behind u was requested before the test (it is the same line, or the
+// record's second): a stopped lane has read one unit more than it needed, and none after that.
 template <typename T, bool WIDE>
 __device__ __forceinline__ bool q8_passes(int j, const int *hk, const T *ha, int nnz, const uint4 *__restrict__ q8, float bar,
                                           uint32_t &pb, uint32_t &pe, int &row_of_j) {
@@ -387,20 +439,30 @@ __device__ __forceinline__ bool q8_passes(int j, const int *hk, const T *ha, int
         cur = load_global_u4(q8, rec);
         nxt = load_global_u4(q8, rec + 1);
     }
+    const float na2_up = staged_row_norm2_up<T, WIDE>(hk, ha, nnz);
+    const float bar_lo = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(bar * 0.99998f)));
     const uint32_t n_j = cur.z & 0x7fffffffu;
     const bool whole = (cur.z >> 31) == 0u;
+    const uint32_t rest = cur.w;
     pb = cur.x;
     pe = cur.x + n_j;
     row_of_j = have ? (int)cur.y : j;
-    const uint32_t units = whole ? (n_j + 7u) >> 2 : 1u;   // 16-byte units of the record in use (unit 0: the header)
-    float ub = 0.f;
+    uint32_t units = whole ? (n_j + 7u) >> 2 : 1u;   // 16-byte units of the record in use (unit 0: the header)
+    float ub = 0.f, matched = 0.f;
     SG_WD_DECL(wd_q);
     for (uint32_t u = 1u;; ++u) {   // the unit behind the one being worked off is on its way (same line: from the cache)
         SG_WD(wd_q, 20, 25)
         if (__ballot(u < units) == 0) break;
         cur = nxt;
         if (u + 1u < units) nxt = load_global_u4(q8, rec + u + 1u);
-        if (u < units) ub = q8_unit<T, WIDE>(cur, hk, ha, nnz, ub);
+        if (u < units) ub = q8_unit<T, WIDE>(cur, hk, ha, nnz, ub, matched);
+        // (u is the wave's: which field, if any, is a scalar matter)
+        const int f = u == SG_Q8_REST_UNIT(0) ? 0 : u == SG_Q8_REST_UNIT(1) ? 8 : u == SG_Q8_REST_UNIT(2) ? 16 : u == SG_Q8_REST_UNIT(3) ? 24 : -1;
+        if (f >= 0) {
+            const uint32_t r8 = (rest >> f) & 255u;
+            const float a_rest = __builtin_amdgcn_sqrtf(fmaxf(na2_up - matched, 1e-30f));
+            if (u + 1u < units && r8 != SG_Q8_REST_UNKNOWN && __builtin_fmaf(a_rest, (float)r8, ub) < bar_lo) units = u + 1u;
+        }
     }
     return have && (!whole || ub >= bar);
 }
@@ -2096,6 +2158,7 @@ static int launch_pruned(const PrunedJob &job, const PrunedLaunch &l) {
     // (SHARE: see the kernel; only the forms that can run in parts have the second instantiation)
     constexpr bool SPLITS = SYM && !WIDE && FOLD_LOG2 > 0;
     const bool share = SPLITS && (l.heavy_count != nullptr || l.part_cfg != 0u);
+    if (sg_q8_applies(ctx, Bt, (double)thr)) SG_TRY(sg_postings_sync_q8_early(ctx, Bt));
     auto kernel = share ? spgemm_topn_pruned_kernel<T, TILE_LOG2, SYM, WIDE, FOLD_LOG2, SPLITS>
                         : spgemm_topn_pruned_kernel<T, TILE_LOG2, SYM, WIDE, FOLD_LOG2, false>;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, ctx->stream, A->d_indptr,
