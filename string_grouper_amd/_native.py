@@ -34,6 +34,13 @@ class SgRescoreField(C.Structure):
                 ("n_dead_a", C.c_int32), ("d_dead_b", C.c_void_p), ("n_dead_b", C.c_int32)]
 
 
+def _rescore_field(A, B, weight, dead_a, dead_b) -> SgRescoreField:
+    """A field of ``Context.topn_rescore`` / the primary of ``Context.topn_union`` as the library reads it."""
+    a, b = (getattr(m.h, "value", m.h) for m in (A, B))                  # (a handle is a c_void_p or its integer)
+    dead = [(None, 0) if d is None else (d.ptr, len(d)) for d in (dead_a, dead_b)]
+    return SgRescoreField(a, b, float(weight), *dead[0], *dead[1])
+
+
 class SgStats(C.Structure):
     _fields_ = [("ms", C.c_float * SG_K_COUNT), ("macs", C.c_int64), ("spgemm_bytes", C.c_int64),
                 ("out_nnz", C.c_int64), ("prune_rows", C.c_int64), ("prune_postings", C.c_int64),
@@ -861,11 +868,8 @@ class Context:
         that a candidate reads): ValueError."""
         fields = list(fields)
         arr = (SgRescoreField * max(len(fields), 1))()
-        for k, (A, B, weight, dead_a, dead_b) in enumerate(fields):
-            a, b = (getattr(m.h, "value", m.h) for m in (A, B))          # (a handle is a c_void_p or its integer)
-            arr[k] = SgRescoreField(a, b, float(weight), None if dead_a is None else dead_a.ptr,
-                                    0 if dead_a is None else len(dead_a), None if dead_b is None else dead_b.ptr,
-                                    0 if dead_b is None else len(dead_b))
+        for k, field in enumerate(fields):
+            arr[k] = _rescore_field(*field)
         out = C.c_void_p()
         check(lib().sg_topn_rescore(self.h, cand.h, float(w0), arr, len(fields), float(threshold), int(top_n), C.byref(out)))
         return TopN(self, out)
@@ -881,9 +885,7 @@ class Context:
         parts = list(parts)
         arr = (C.c_void_p * max(len(parts), 1))(*[getattr(p.h, "value", p.h) for p in parts])
         A, B, dead_a, dead_b = primary
-        a, b = (getattr(m.h, "value", m.h) for m in (A, B))
-        field = SgRescoreField(a, b, 1.0, None if dead_a is None else dead_a.ptr, 0 if dead_a is None else len(dead_a),
-                               None if dead_b is None else dead_b.ptr, 0 if dead_b is None else len(dead_b))
+        field = _rescore_field(A, B, 1.0, dead_a, dead_b)
         out = C.c_void_p()
         check(lib().sg_topn_union(self.h, arr, len(parts), C.byref(field), C.byref(out)))
         return TopN(self, out)

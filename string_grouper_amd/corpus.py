@@ -164,33 +164,30 @@ class _RecordGrouper(_CorpusGrouper):
         fields = None
         if self._dup_fields is not None:                             # one transform a field (duplicates[0] may be corpus.master)
             fields = [o._rows_of(series, self._made) for o, series in zip(self._others, self._dup_fields)]
-        if self._candidate_fields != (0,):
-            return self._union_match_list(eng, duplicate_matrix, fields, fix)
-        cand_top_n, cand_threshold = self._cand
-        top_n = cand_top_n if self._max_n_matches is None else min(int(self._max_n_matches), cand_top_n)
-        keep = 'keep_on_device' in inspect.signature(eng.corpus_records_topn).parameters   # engine doubles may lack it
         try:
+            if self._candidate_fields != (0,):
+                return self._union_match_list(eng, duplicate_matrix, fields, fix)
+            cand_top_n, cand_threshold = self._cand
+            top_n = cand_top_n if self._max_n_matches is None else min(int(self._max_n_matches), cand_top_n)
+            keep = 'keep_on_device' in inspect.signature(eng.corpus_records_topn).parameters   # engine doubles may lack it
             return eng.corpus_records_topn(self._corpus._live(), [o._live() for o in self._others], duplicate_matrix, fields,
                                            self._weights, cand_top_n, cand_threshold, top_n, self._config.min_similarity, fix,
                                            **({'keep_on_device': True} if keep else {}))
         except OverflowError as e:
             # fit() answers an OverflowError with the block-wise multiply of ONE field: that is no record match.  There is no
             # block-wise route for records, so the call is refused instead
+            now = (f"{self._cand[0]}" if self._candidate_fields == (0,) else
+                   f"{[k for k, _ in self._cand]} on the fields {list(self._candidate_fields)}")
             raise ValueError(f"records x candidates exceed what one result on the device can index ({e}): lower "
-                             f"candidates['max_n_matches'] (now {cand_top_n}) or match the records in batches of duplicates") from e
+                             f"candidates['max_n_matches'] (now {now}) or match the records in batches of duplicates") from e
 
     def _union_match_list(self, eng, duplicate_matrix, fields, fix: bool):
         """Candidates from several fields: every candidate field's multiply, united and rescored on the device."""
         all_candidates = sum(k for k, _ in self._cand)
         top_n = all_candidates if self._max_n_matches is None else min(int(self._max_n_matches), all_candidates)
-        try:
-            return eng.corpus_records_union_topn(self._corpus._live(), [o._live() for o in self._others], duplicate_matrix, fields,
-                                                 self._weights, self._candidate_fields, self._cand, top_n,
-                                                 self._config.min_similarity, fix, keep_on_device=True)
-        except OverflowError as e:            # (as for one candidate field: there is no block-wise route for records)
-            raise ValueError(f"records x candidates exceed what one result on the device can index ({e}): lower "
-                             f"candidates['max_n_matches'] (now {[k for k, _ in self._cand]} on the fields "
-                             f"{list(self._candidate_fields)}) or match the records in batches of duplicates") from e
+        return eng.corpus_records_union_topn(self._corpus._live(), [o._live() for o in self._others], duplicate_matrix, fields,
+                                             self._weights, self._candidate_fields, self._cand, top_n,
+                                             self._config.min_similarity, fix, keep_on_device=True)
 
 
 class Corpus:

@@ -526,32 +526,8 @@ class CorpusEngine:
         numbers turned into physical ones by the kernel -- a record call compacts no secondary corpus and builds no index
         of one.  Every handle made here lives in a scope: the candidates in one that ends with the rescoring, the rescored result
         in the method's (``_match_list_from_topn`` frees it early, as it frees a multiply's)."""
-        t = time.perf_counter()
-        A = state.matrix
-        self_join = B_fields is None          # (duplicates whose first Series is corpus.master have B is A and fields of their own)
-        if len(others) != len(weights) - 1 or not 1 <= len(others) <= self.MAX_RECORD_FIELDS:
-            raise ValueError(f"between 1 and {self.MAX_RECORD_FIELDS} further fields, and one weight a field, are expected")
-        if self_join and B is not A:
-            raise ValueError("duplicates of the first field without duplicates of the further fields")
-        for k, o in enumerate(others):
-            if o.matrix.shape[0] != A.shape[0]:
-                raise ValueError(f"the corpora differ in length ({o.matrix.shape[0]} and {A.shape[0]} rows): row p of every "
-                                 f"corpus must be record p")
-            if not self_join and B_fields[k].shape[0] != B.shape[0]:
-                raise ValueError(f"the duplicates differ in length ({B_fields[k].shape[0]} and {B.shape[0]} rows)")
-        with N.Scope() as s:
-            with N.Scope() as before:         # the candidates go as soon as they are rescored
-                cand = before.own(self._topn_device(A, B, cand_top_n, cand_threshold))
-                fields = []
-                for k, o in enumerate(others):
-                    rows = o.physical()       # (the state's own cached concatenation when rows wait in a delta)
-                    right = rows if self_join else B_fields[k].csr
-                    fields.append((rows, right, weights[k + 1], o.dead_dev, o.dead_dev if self_join else None))
-                res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n))
-            for st in [state] + list(others):
-                st.stats["record_calls"] += 1
-            # (_match_list_from_topn frees the result once the list is built; if it raises before that, the scope does)
-            return self._match_list_from_topn(res, A.dtype, B.shape[0], self_join_fix, keep_on_device, t)
+        return self._records_topn(state, others, B, B_fields, weights, None, [(cand_top_n, cand_threshold)], top_n, threshold,
+                                  self_join_fix, keep_on_device)
 
     MAX_UNION_CANDIDATES = 2048               # sg_topn_union: the candidate fields' strides together
 
@@ -570,49 +546,69 @@ class CorpusEngine:
         read where it lies, as in ``corpus_records_topn``: never compacted, never indexed.  The rows and the dead lists the
         union and the rescoring read are taken AFTER the multiplies, which may have compacted a candidate corpus; results number
         the live rows, which no compaction changes."""
+        return self._records_topn(state, others, B, B_fields, weights, candidate_fields, cands, top_n, threshold,
+                                  self_join_fix, keep_on_device)
+
+    def _records_topn(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
+                      B_fields: Optional[List[DeviceMatrix]], weights, candidate_fields, cands, top_n: int, threshold: float,
+                      self_join_fix: bool, keep_on_device: bool):
+        """The body of both record calls: validate, find the candidates -- ``candidate_fields`` None: the primary field's
+        multiply at ``cands[0]``; else one multiply a candidate field and their union --, take the fields' rows and dead
+        lists, rescore, count, build the list."""
         t = time.perf_counter()
-        self_join = B_fields is None
+        A = state.matrix
+        self_join = B_fields is None          # (duplicates whose first Series is corpus.master have B is A and fields of their own)
         states = [state] + list(others)
-        candidate_fields = [int(f) for f in candidate_fields]
+        union = candidate_fields is not None
+        if union:
+            candidate_fields = [int(f) for f in candidate_fields]
         if len(others) != len(weights) - 1 or not 1 <= len(others) <= self.MAX_RECORD_FIELDS:
             raise ValueError(f"between 1 and {self.MAX_RECORD_FIELDS} further fields, and one weight a field, are expected")
-        if (len(candidate_fields) < 2 or candidate_fields[0] != 0 or candidate_fields[-1] > len(others)
-                or any(a >= b for a, b in zip(candidate_fields, candidate_fields[1:])) or len(cands) != len(candidate_fields)):
+        if union and (len(candidate_fields) < 2 or candidate_fields[0] != 0 or candidate_fields[-1] > len(others)
+                      or any(a >= b for a, b in zip(candidate_fields, candidate_fields[1:]))
+                      or len(cands) != len(candidate_fields)):
             raise ValueError("candidate_fields: at least two distinct ascending field positions, 0 among them, and one pair of "
                              "candidate options a field, are expected")
-        if self_join and B is not state.matrix:
+        if self_join and B is not A:
             raise ValueError("duplicates of the first field without duplicates of the further fields")
         for k, o in enumerate(others):
-            if o.matrix.shape[0] != state.matrix.shape[0]:
-                raise ValueError(f"the corpora differ in length ({o.matrix.shape[0]} and {state.matrix.shape[0]} rows): row p of "
-                                 f"every corpus must be record p")
+            if o.matrix.shape[0] != A.shape[0]:
+                raise ValueError(f"the corpora differ in length ({o.matrix.shape[0]} and {A.shape[0]} rows): row p of every "
+                                 f"corpus must be record p")
             if not self_join and B_fields[k].shape[0] != B.shape[0]:
                 raise ValueError(f"the duplicates differ in length ({B_fields[k].shape[0]} and {B.shape[0]} rows)")
         n_right = B.shape[0]
-        if sum(max(min(int(k), n_right), 1) for k, _ in cands) > self.MAX_UNION_CANDIDATES:
+        if union and sum(max(min(int(k), n_right), 1) for k, _ in cands) > self.MAX_UNION_CANDIDATES:
             raise ValueError(f"the candidate fields' max_n_matches exceed {self.MAX_UNION_CANDIDATES} together")
+        rights = [B] + list(B_fields or [])   # (a self-join reads none of them)
+
+        def field(k: int):
+            """Field k as ``Context.topn_rescore`` takes it, read where it lies NOW: after the multiplies."""
+            rows = states[k].physical()       # (the state's own cached concatenation when rows wait in a delta)
+            dead = states[k].dead_dev
+            return rows, rows if self_join else rights[k].csr, weights[k], dead, dead if self_join else None
+
         with N.Scope() as s:
             with N.Scope() as before:         # the candidates go as soon as they are rescored
-                with N.Scope() as per_field:  # ... and every field's own as soon as they are united
-                    parts = []
-                    for f, (cand_top_n, cand_threshold) in zip(candidate_fields, cands):
-                        A_f = states[f].matrix
-                        B_f = A_f if self_join else (B if f == 0 else B_fields[f - 1])
-                        parts.append(per_field.own(self._topn_device(A_f, B_f, cand_top_n, cand_threshold)))
-                    right = state.physical() if self_join else B.csr
-                    cand = before.own(self.ctx.topn_union(parts, (state.physical(), right, state.dead_dev,
-                                                                  state.dead_dev if self_join else None)))
-                fields = []
-                for k, o in enumerate(others):
-                    right = None if self_join else B_fields[k].csr
-                    rows = o.physical()       # (the state's own cached concatenation when rows wait in a delta)
-                    fields.append((rows, rows if self_join else right, weights[k + 1], o.dead_dev, o.dead_dev if self_join else None))
+                if not union:
+                    cand = before.own(self._topn_device(A, B, *cands[0]))
+                else:
+                    with N.Scope() as per_field:  # ... and every field's own as soon as they are united
+                        parts = []
+                        for f, (cand_top_n, cand_threshold) in zip(candidate_fields, cands):
+                            A_f = states[f].matrix
+                            B_f = A_f if self_join else rights[f]
+                            parts.append(per_field.own(self._topn_device(A_f, B_f, cand_top_n, cand_threshold)))
+                        rows, right, _, dead_a, dead_b = field(0)
+                        cand = before.own(self.ctx.topn_union(parts, (rows, right, dead_a, dead_b)))
+                fields = [field(k) for k in range(1, len(states))]
                 res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n))
             for st in states:
                 st.stats["record_calls"] += 1
-            for f in candidate_fields:
+            for f in candidate_fields or ():
                 states[f].stats["record_union_calls"] += 1
-            return self._match_list_from_topn(res, state.matrix.dtype, n_right, self_join_fix, keep_on_device, t)
+            # (_match_list_from_topn frees the result once the list is built; if it raises before that, the scope does)
+            return self._match_list_from_topn(res, A.dtype, n_right, self_join_fix, keep_on_device, t)
 
     # ------------------------------------------------------------------ a self-join that is kept (DESIGN.md section 9)
     def corpus_keep_self_join(self, state: CorpusState, top_n: int, threshold: float) -> None:

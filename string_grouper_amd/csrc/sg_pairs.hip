@@ -6,16 +6,9 @@
 // sum), which is what compute_pairwise_similarities (string_grouper.py:55) gives for the same pair.  No gate: values of any
 // sign, NaN and inf flow through.
 //
-// Lanes ("Pair similarities"): SG_PAIR_LANES = 8 lanes a pair, eight pairs a wave.  The two rows are
-// walked in chunks of eight entries, one entry a lane (a chunk is one 32-byte piece of the column array and one of the
-// values: the lanes of a group read neighbours, not 64 lines of their own as a thread a pair would).  Every lane compares
-// its entry of A's chunk with the eight columns of B's chunk (shuffles inside the group), the chunk whose last column is
-// the smaller one is retired and the next one loaded -- a merge by chunks -- and when a chunk of A is retired its products
-// are added lane by lane, lowest first, into an accumulator that every lane of the group holds: the order of the adds is
-// the column order whatever the chunking.
-#include "sg_pairs_device.h"   // the merge itself (pair_rows_dot), shared with sg_rescore.hip
-
-#define SG_PAIR_BLOCK 256   // 32 pairs a block
+// Lanes ("Pair similarities"): SG_PAIR_LANES = 8 lanes a pair, eight pairs a wave, and the walk of
+// sg_pairs_device.h -- the left row, then the one column the pair names -- over a field without dead lists.
+#include "sg_pairs_device.h"
 
 // status word of a call, one bit a cause
 #define SG_PAIR_BAD_LEFT 1u       // an entry of `left` outside [0, rows of A)
@@ -24,11 +17,10 @@
 #define SG_PAIR_UNSORTED_B 8u
 
 template <typename T>
-__global__ void __launch_bounds__(SG_PAIR_BLOCK) pairs_dot_kernel(
-    const int64_t *__restrict__ a_indptr, const int32_t *__restrict__ a_indices, const T *__restrict__ a_data, int64_t n_a,
-    const int64_t *__restrict__ b_indptr, const int32_t *__restrict__ b_indices, const T *__restrict__ b_data, int64_t n_b,
-    const int32_t *__restrict__ left, const int32_t *__restrict__ right, int64_t n_pairs, int check_a, int check_b,
-    uint32_t *status, T *out) {
+__global__ void __launch_bounds__(SG_PAIR_BLOCK) pairs_dot_kernel(PairField<T> F, int64_t n_a, int64_t n_b,
+                                                                  const int32_t *__restrict__ left,
+                                                                  const int32_t *__restrict__ right, int64_t n_pairs,
+                                                                  uint32_t *status, T *out) {
     constexpr int G = SG_PAIR_LANES;
     const int l = threadIdx.x & (G - 1);
     const int group_shift = threadIdx.x & (SG_WAVE - 1) & ~(G - 1);   // the group's first lane in its wave
@@ -39,11 +31,9 @@ __global__ void __launch_bounds__(SG_PAIR_BLOCK) pairs_dot_kernel(
         if (l == 0) atomicOr(status, (i < 0 || i >= n_a ? SG_PAIR_BAD_LEFT : 0u) | (j < 0 || j >= n_b ? SG_PAIR_BAD_RIGHT : 0u));
         return;
     }
-    const int64_t a0 = a_indptr[i], a1 = a_indptr[i + 1], b0 = b_indptr[j], b1 = b_indptr[j + 1];
-    if (check_a && row_not_ascending(a_indices, a0, a1, l)) atomicOr(status, SG_PAIR_UNSORTED_A);
-    if (check_b && row_not_ascending(b_indices, b0, b1, l)) atomicOr(status, SG_PAIR_UNSORTED_B);
-
-    const T acc = pair_rows_dot<T>(a_indices, a_data, a0, a1, b_indices, b_data, b0, b1, l, group_shift);
+    int64_t a0, a1;
+    pair_left_row<T>(F, i, l, status, SG_PAIR_UNSORTED_A, a0, a1);
+    const T acc = pair_score<T>(F, a0, a1, j, l, group_shift, status, SG_PAIR_UNSORTED_B);
     if (l == 0) out[p] = acc;
 }
 
@@ -55,13 +45,8 @@ extern "C" int sg_csr_pairs_dot(sg_ctx *ctx, const sg_csr *A, const sg_csr *B, c
     SG_REQUIRE(n_pairs >= 0, "negative number of pairs");
     if (n_pairs == 0) return SG_OK;
     SG_REQUIRE(d_left && d_right && out_host, "null argument");
-    const int64_t blocks = (n_pairs + SG_PAIR_BLOCK / SG_PAIR_LANES - 1) / (SG_PAIR_BLOCK / SG_PAIR_LANES);
-    if (blocks > INT32_MAX) {
-        sg_set_error("%lld pairs exceed one launch: score them in pieces", (long long)n_pairs);
-        return SG_ERR_OVERFLOW;
-    }
-    if (A->rows_of) SG_TRY(sg_csr_ensure_rows(ctx, A));
-    if (B->rows_of && B != A) SG_TRY(sg_csr_ensure_rows(ctx, B));
+    if (pair_blocks(n_pairs) > INT32_MAX) return exceeds_one_launch(n_pairs, "pairs", "score");
+    SG_TRY(ensure_pair_rows(ctx, A, B));
     const size_t s = A->dtype == SG_F64 ? 8 : 4, head = 16;   // the status word, then the results (aligned for either type)
     const size_t bytes = head + (size_t)n_pairs * s;
     Scratch tmp(ctx);
@@ -73,12 +58,12 @@ extern "C" int sg_csr_pairs_dot(sg_ctx *ctx, const sg_csr *A, const sg_csr *B, c
         return SG_ERR_OOM;
     }
     SG_HIP_TRY(hipMemsetAsync(d_buf, 0, head, ctx->stream));
+    const sg_rescore_field field = {A, B, 1.0, nullptr, 0, nullptr, 0};   // (no dead lists: the pairs name physical rows)
     by_dtype(A->dtype, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL(pairs_dot_kernel<T>, dim3((unsigned)blocks), dim3(SG_PAIR_BLOCK), 0, ctx->stream, A->d_indptr,
-                           A->d_indices, (const T *)A->d_data, A->n_rows, B->d_indptr, B->d_indices, (const T *)B->d_data,
-                           B->n_rows, d_left, d_right, n_pairs, known_ascending(A) ? 0 : 1, known_ascending(B) ? 0 : 1,
-                           (uint32_t *)d_buf, (T *)(d_buf + head));
+        hipLaunchKernelGGL(pairs_dot_kernel<T>, dim3((unsigned)pair_blocks(n_pairs)), dim3(SG_PAIR_BLOCK), 0, ctx->stream,
+                           make_pair_field<T>(field), A->n_rows, B->n_rows, d_left, d_right, n_pairs, (uint32_t *)d_buf,
+                           (T *)(d_buf + head));
         return SG_OK;
     });
     SG_HIP_TRY(hipGetLastError());
@@ -86,10 +71,12 @@ extern "C" int sg_csr_pairs_dot(sg_ctx *ctx, const sg_csr *A, const sg_csr *B, c
     uint32_t status = 0;
     memcpy(&status, h_buf.get(), 4);
     if (status) {
-        sg_set_error("bad argument: %s%s%s%s", status & SG_PAIR_BAD_LEFT ? "a left index lies outside A's rows; " : "",
-                     status & SG_PAIR_BAD_RIGHT ? "a right index lies outside B's rows; " : "",
-                     status & SG_PAIR_UNSORTED_A ? "a row of A that a pair names is not sorted by column (strictly ascending); " : "",
-                     status & SG_PAIR_UNSORTED_B ? "a row of B that a pair names is not sorted by column (strictly ascending); " : "");
+        std::string what;
+        if (status & SG_PAIR_BAD_LEFT) what += "a left index lies outside A's rows; ";
+        if (status & SG_PAIR_BAD_RIGHT) what += "a right index lies outside B's rows; ";
+        if (status & SG_PAIR_UNSORTED_A) what += unsorted_row("A", "pair names");
+        if (status & SG_PAIR_UNSORTED_B) what += unsorted_row("B", "pair names");
+        sg_set_error("bad argument: %s", what.c_str());
         return SG_ERR_BADARG;
     }
     memcpy(out_host, h_buf.get() + head, (size_t)n_pairs * s);

@@ -5,17 +5,16 @@
 // leave the device: what the named-pairs route moves through the host per field -- two position lists up, the scores down --
 // is read here where the multiply left it.
 //
-// Two launches.  rescore_score_kernel: SG_PAIR_LANES lanes a row (of at most SG_RESCORE_CHUNK of its entries; a longer row is
-// dealt to several groups), field by field: the row of A_f is found once, then the group walks the row's candidates with the
-// merge of sg_pairs_device.h -- pairs_dot_kernel's, so s_f is sg_csr_pairs_dot's value to the bit -- and lane 0 keeps c in a
-// scratch array of the candidates' shape.  rescore_select_*_kernel: a rank by counting -- an entry's place is the number of
+// Two launches.  rescore_score_kernel: SG_PAIR_LANES lanes a row (of at most SG_PAIR_ROW_CHUNK of its entries; a longer row is
+// dealt to several groups), field by field, with the walk of sg_pairs_device.h -- pairs_dot_kernel's, so s_f is
+// sg_csr_pairs_dot's value to the bit: the row of A_f is found once, then the row's candidates are scored one by one -- and
+// lane 0 keeps c in a scratch array of the candidates' shape.  rescore_select_*_kernel: a rank by counting -- an entry's place is the number of
 // kept entries of its row that go before it -- which needs no sort network and no exchange between lanes: eight lanes a row
 // reading the row's few scores from cache for a row of at most 64 candidates (rows of name lists hold about four), a block
 // with the row in LDS for the rows above that (up to 2 048 entries), which the first kernel lists on the device.
 #include "sg_pairs_device.h"
 
 #define SG_RESCORE_BLOCK 256
-#define SG_RESCORE_CHUNK 64        // entries of a row one group scores
 #define SG_RESCORE_MAX_FIELDS 7
 #define SG_RESCORE_MAX_STRIDE 2048
 #define SG_RESCORE_SHORT 64        // rows of up to this many candidates: eight lanes select them; above: a block
@@ -25,45 +24,30 @@
 #define SG_RESCORE_BAD_COLUMN 1u
 
 template <typename T>
-struct RescoreField {
-    const int64_t *a_indptr;
-    const int32_t *a_indices;
-    const T *a_data;
-    const int64_t *b_indptr;
-    const int32_t *b_indices;
-    const T *b_data;
-    const int32_t *dead_a, *dead_b;   // dead PHYSICAL rows, ascending and distinct (null: none)
-    int32_t n_dead_a, n_dead_b;
-    int32_t check_a, check_b;         // != 0: the matrix is not known to be sorted, look at the rows that are read
-    T w;
-};
-template <typename T>
 struct RescoreFields {
-    RescoreField<T> f[SG_RESCORE_MAX_FIELDS];
+    PairField<T> f[SG_RESCORE_MAX_FIELDS];
 };
 
 template <typename T>
-__global__ void __launch_bounds__(SG_RESCORE_BLOCK) rescore_score_kernel(
+__global__ void __launch_bounds__(SG_PAIR_BLOCK) rescore_score_kernel(
     const int32_t *__restrict__ cols, const T *__restrict__ vals, const int32_t *__restrict__ counts, int64_t n_rows,
     int64_t n_cols, int32_t stride, int32_t chunks, T w0, RescoreFields<T> fields, int32_t n_fields, uint32_t *status,
     T *__restrict__ comb) {
     constexpr int G = SG_PAIR_LANES;
     const int l = threadIdx.x & (G - 1);
     const int group_shift = threadIdx.x & (SG_WAVE - 1) & ~(G - 1);   // the group's first lane in its wave
-    const int64_t g = ((int64_t)blockIdx.x * SG_RESCORE_BLOCK + threadIdx.x) / G;
+    const int64_t g = ((int64_t)blockIdx.x * SG_PAIR_BLOCK + threadIdx.x) / G;
     const int64_t row = g / chunks;
     if (row >= n_rows) return;   // (everything below is uniform over the group: its lanes leave, loop and shuffle together)
-    int32_t cnt = counts[row];
-    cnt = cnt < 0 ? 0 : (cnt > stride ? stride : cnt);
-    const int32_t e0 = (int32_t)(g - row * chunks) * SG_RESCORE_CHUNK;
-    const int32_t e1 = cnt < e0 + SG_RESCORE_CHUNK ? cnt : e0 + SG_RESCORE_CHUNK;
+    const int32_t cnt = counted(counts, row, stride);
+    const int32_t e0 = (int32_t)(g - row * chunks) * SG_PAIR_ROW_CHUNK;
+    const int32_t e1 = cnt < e0 + SG_PAIR_ROW_CHUNK ? cnt : e0 + SG_PAIR_ROW_CHUNK;
     if (e0 >= e1) return;
     const int64_t base = row * (int64_t)stride;
     for (int f = 0; f < n_fields; ++f) {
-        const RescoreField<T> &F = fields.f[f];
-        const int64_t a = physical_row(row, F.dead_a, F.n_dead_a);
-        const int64_t a0 = F.a_indptr[a], a1 = F.a_indptr[a + 1];
-        if (F.check_a && row_not_ascending(F.a_indices, a0, a1, l)) atomicOr(status, 2u << (2 * f));
+        const PairField<T> &F = fields.f[f];
+        int64_t a0, a1;
+        pair_left_row<T>(F, row, l, status, 2u << (2 * f), a0, a1);
         for (int32_t e = e0; e < e1; ++e) {
             const int64_t j = cols[base + e];
             if (j < 0 || j >= n_cols) {   // nothing of a field is read for it; the call is refused
@@ -73,10 +57,7 @@ __global__ void __launch_bounds__(SG_RESCORE_BLOCK) rescore_score_kernel(
                 }
                 continue;
             }
-            const int64_t b = physical_row(j, F.dead_b, F.n_dead_b);
-            const int64_t b0 = F.b_indptr[b], b1 = F.b_indptr[b + 1];
-            if (F.check_b && row_not_ascending(F.b_indices, b0, b1, l)) atomicOr(status, 4u << (2 * f));
-            const T s = pair_rows_dot<T>(F.a_indices, F.a_data, a0, a1, F.b_indices, F.b_data, b0, b1, l, group_shift);
+            const T s = pair_score<T>(F, a0, a1, j, l, group_shift, status, 4u << (2 * f));
             if (l == 0) {   // (lane 0 alone reads and writes the candidate's c: its own stores, in program order)
                 const T c = f == 0 ? add_rn<T>((T)0, mul_rn<T>(w0, vals[base + e])) : comb[base + e];
                 comb[base + e] = add_rn<T>(c, mul_rn<T>(F.w, s));
@@ -106,8 +87,7 @@ __global__ void __launch_bounds__(SG_RESCORE_BLOCK) rescore_select_short_kernel(
     const int l = threadIdx.x & (G - 1);
     const int64_t row = ((int64_t)blockIdx.x * SG_RESCORE_BLOCK + threadIdx.x) / G;
     if (row >= n_rows) return;
-    int32_t cnt = counts[row];
-    cnt = cnt < 0 ? 0 : (cnt > stride ? stride : cnt);
+    const int32_t cnt = counted(counts, row, stride);
     if (cnt > SG_RESCORE_SHORT) {   // (only with a stride above SG_RESCORE_SHORT: the list is there) a block's row
         if (l == 0) long_rows[atomicAdd(n_long, 1u)] = (int32_t)row;
         return;
@@ -147,8 +127,7 @@ __global__ void __launch_bounds__(SG_RESCORE_BLOCK) rescore_select_block_kernel(
     const uint32_t n = *n_long;
     for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) {
         const int64_t row = long_rows[k];
-        int32_t cnt = counts[row];
-        cnt = cnt < 0 ? 0 : (cnt > stride ? stride : cnt);   // (stride <= SG_RESCORE_MAX_STRIDE: checked by the driver)
+        const int32_t cnt = counted(counts, row, stride);   // (stride <= SG_RESCORE_MAX_STRIDE: checked by the driver)
         const int64_t base = row * (int64_t)stride, out = row * (int64_t)stride_out;
         if (threadIdx.x == 0) s_kept = 0;
         __syncthreads();
@@ -182,19 +161,10 @@ static int rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore
                    double threshold, sg_topn *r, uint32_t *d_status, void *d_comb, int32_t *d_long_rows) {
     RescoreFields<T> dev;
     memset(&dev, 0, sizeof(dev));
-    for (int f = 0; f < n_fields; ++f) {
-        const sg_rescore_field &h = fields[f];
-        RescoreField<T> &d = dev.f[f];
-        d.a_indptr = h.A->d_indptr, d.a_indices = h.A->d_indices, d.a_data = (const T *)h.A->d_data;
-        d.b_indptr = h.B->d_indptr, d.b_indices = h.B->d_indices, d.b_data = (const T *)h.B->d_data;
-        d.dead_a = h.d_dead_a, d.dead_b = h.d_dead_b, d.n_dead_a = h.n_dead_a, d.n_dead_b = h.n_dead_b;
-        d.check_a = known_ascending(h.A) ? 0 : 1, d.check_b = known_ascending(h.B) ? 0 : 1;
-        d.w = (T)h.weight;
-    }
+    for (int f = 0; f < n_fields; ++f) dev.f[f] = make_pair_field<T>(fields[f]);
     constexpr int per_block = SG_RESCORE_BLOCK / SG_PAIR_LANES;
-    const int32_t chunks = (cand->stride + SG_RESCORE_CHUNK - 1) / SG_RESCORE_CHUNK;
-    const int64_t score_blocks = (cand->n_rows * chunks + per_block - 1) / per_block;
-    hipLaunchKernelGGL(rescore_score_kernel<T>, dim3((unsigned)score_blocks), dim3(SG_RESCORE_BLOCK), 0, ctx->stream,
+    const int32_t chunks = (cand->stride + SG_PAIR_ROW_CHUNK - 1) / SG_PAIR_ROW_CHUNK;
+    hipLaunchKernelGGL(rescore_score_kernel<T>, dim3((unsigned)pair_blocks(cand->n_rows * chunks)), dim3(SG_PAIR_BLOCK), 0, ctx->stream,
                        cand->d_cols, (const T *)cand->d_vals, cand->d_counts, cand->n_rows, cand->n_cols, cand->stride, chunks,
                        (T)w0, dev, n_fields, d_status, (T *)d_comb);
     SG_HIP_TRY(hipGetLastError());
@@ -215,8 +185,6 @@ static int rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore
     return SG_OK;
 }
 
-static bool weight_ok(double w, int32_t dtype) { return std::isfinite(w) && (dtype == SG_F64 || std::isfinite((float)w)); }
-
 extern "C" int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
                                double threshold, int32_t top_n, sg_topn **out) {
     SG_REQUIRE(ctx && cand && out, "null argument");
@@ -225,27 +193,12 @@ extern "C" int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, cons
     SG_REQUIRE(top_n >= 1, "top_n must be at least 1");
     SG_REQUIRE(cand->stride >= 1 && cand->stride <= SG_RESCORE_MAX_STRIDE, "the candidates' stride exceeds 2048: ask the multiply for fewer a row");
     SG_REQUIRE(weight_ok(w0, cand->dtype), "a weight is not finite");
-    for (int f = 0; f < n_fields; ++f) {
-        const sg_rescore_field &h = fields[f];
-        SG_REQUIRE(h.A && h.B, "a field's matrix is null");
-        SG_REQUIRE(weight_ok(h.weight, cand->dtype), "a weight is not finite");
-        SG_REQUIRE(h.A->dtype == cand->dtype && h.B->dtype == cand->dtype, "a field's matrices differ from the candidates in value type");
-        SG_REQUIRE(h.A->n_cols == h.B->n_cols, "a field's matrices differ in shape (their columns)");
-        SG_REQUIRE(h.n_dead_a >= 0 && h.n_dead_b >= 0 && (h.n_dead_a == 0 || h.d_dead_a) && (h.n_dead_b == 0 || h.d_dead_b),
-                   "a list of dead rows is null or has a negative length");
-        SG_REQUIRE(h.A->n_rows - h.n_dead_a == cand->n_rows, "a field's left matrix has not the candidates' rows (dead rows apart)");
-        SG_REQUIRE(h.B->n_rows - h.n_dead_b == cand->n_cols, "a field's right matrix has not the candidates' columns as rows (dead rows apart)");
-    }
-    constexpr int per_block = SG_RESCORE_BLOCK / SG_PAIR_LANES;
-    const int64_t chunks = (cand->stride + SG_RESCORE_CHUNK - 1) / SG_RESCORE_CHUNK;
-    if ((cand->n_rows * chunks + per_block - 1) / per_block > INT32_MAX || cand->n_rows > INT32_MAX) {
-        sg_set_error("%lld rows of candidates exceed one launch: rescore them in pieces", (long long)cand->n_rows);
-        return SG_ERR_OVERFLOW;
-    }
-    for (int f = 0; f < n_fields; ++f) {
-        if (fields[f].A->rows_of) SG_TRY(sg_csr_ensure_rows(ctx, fields[f].A));
-        if (fields[f].B->rows_of && fields[f].B != fields[f].A) SG_TRY(sg_csr_ensure_rows(ctx, fields[f].B));
-    }
+    for (int f = 0; f < n_fields; ++f)
+        SG_TRY(check_pair_field(fields[f], cand->dtype, cand->n_rows, cand->n_cols, "a field's", "candidates", true));
+    const int64_t chunks = (cand->stride + SG_PAIR_ROW_CHUNK - 1) / SG_PAIR_ROW_CHUNK;
+    if (pair_blocks(cand->n_rows * chunks) > INT32_MAX || cand->n_rows > INT32_MAX)
+        return exceeds_one_launch(cand->n_rows, "rows of candidates", "rescore");
+    for (int f = 0; f < n_fields; ++f) SG_TRY(ensure_pair_rows(ctx, fields[f].A, fields[f].B));
     TopnPtr r;
     SG_TRY(topn_alloc(ctx, cand->n_rows, cand->n_cols, std::min<int32_t>(top_n, cand->stride), cand->dtype, &r));
     if (cand->n_rows == 0) {
@@ -268,8 +221,9 @@ extern "C" int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, cons
         std::string what;
         if (status & SG_RESCORE_BAD_COLUMN) what += "a candidate's column lies outside the result's columns; ";
         for (int f = 0; f < n_fields; ++f) {
-            if (status & (2u << (2 * f))) what += "a row of field " + std::to_string(f + 1) + "'s left matrix that a candidate reads is not sorted by column (strictly ascending); ";
-            if (status & (4u << (2 * f))) what += "a row of field " + std::to_string(f + 1) + "'s right matrix that a candidate reads is not sorted by column (strictly ascending); ";
+            const std::string field = "field " + std::to_string(f + 1);
+            if (status & (2u << (2 * f))) what += unsorted_row(field + "'s left matrix", "candidate reads");
+            if (status & (4u << (2 * f))) what += unsorted_row(field + "'s right matrix", "candidate reads");
         }
         sg_set_error("bad argument: %s", what.c_str());
         return SG_ERR_BADARG;

@@ -14,12 +14,11 @@
 // sort network, no exchange between lanes but the OR of their kept bits.  union_block_kernel: the rows above that (up to 2 048
 // entries), which the first kernel lists on the device, a block a row: the keys (column, entry number) sorted in LDS by a bitonic
 // network, equal neighbours dropped, the kept ones placed by a scan.  An entry of part 0 carries its value; any other is
-// written with its column complemented (~j < 0), which is what union_fill_kernel looks for: rescore_score_kernel's shape --
-// the row of A found once, then the row's marked entries walked with the merge.  union_copy_kernel: the rows at their stride.
+// written with its column complemented (~j < 0), which is what union_fill_kernel looks for: the walk of sg_pairs_device.h over
+// a row's marked entries, the row of A found when the first one shows.  union_copy_kernel: the rows at their stride.
 #include "sg_pairs_device.h"
 
 #define SG_UNION_BLOCK 256
-#define SG_UNION_CHUNK 64          // entries of a row one group fills
 #define SG_UNION_MAX_PARTS 8
 #define SG_UNION_MAX_ENTRIES 2048  // entries a row's parts hold together: the block kernel's LDS
 #define SG_UNION_SHORT 64          // rows of up to this many entries: eight lanes unite them; above: a block
@@ -36,24 +35,6 @@ struct UnionParts {
     int32_t stride[SG_UNION_MAX_PARTS];
     int32_t n;
 };
-
-template <typename T>
-struct UnionPrimary {
-    const int64_t *a_indptr;
-    const int32_t *a_indices;
-    const T *a_data;
-    const int64_t *b_indptr;
-    const int32_t *b_indices;
-    const T *b_data;
-    const int32_t *dead_a, *dead_b;   // dead PHYSICAL rows, ascending and distinct (null: none)
-    int32_t n_dead_a, n_dead_b;
-    int32_t check_a, check_b;         // != 0: the matrix is not known to be sorted, look at the rows that are read
-};
-
-__device__ __forceinline__ int32_t counted(const UnionParts &P, int p, int64_t row) {
-    const int32_t c = P.counts[p][row];
-    return c < 0 ? 0 : (c > P.stride[p] ? P.stride[p] : c);
-}
 
 template <typename T>
 __global__ void __launch_bounds__(SG_UNION_BLOCK) union_short_kernel(
@@ -73,8 +54,8 @@ __global__ void __launch_bounds__(SG_UNION_BLOCK) union_short_kernel(
     if (mine) {
 #pragma unroll
         for (int p = 0; p < SG_UNION_MAX_PARTS; ++p)
-            if (p < P.n) total += counted(P, p, row);
-        cnt0 = counted(P, 0, row);
+            if (p < P.n) total += counted(P.counts[p], row, P.stride[p]);
+        cnt0 = counted(P.counts[0], row, P.stride[0]);
         if (total > SG_UNION_SHORT) {   // a block's row
             if (l == 0) long_rows[atomicAdd(head + 1, 1u)] = (int32_t)row;
             mine = false;
@@ -85,7 +66,7 @@ __global__ void __launch_bounds__(SG_UNION_BLOCK) union_short_kernel(
 #pragma unroll
         for (int p = 0; p < SG_UNION_MAX_PARTS; ++p) {
             if (p < P.n) {
-                const int32_t c = counted(P, p, row);
+                const int32_t c = counted(P.counts[p], row, P.stride[p]);
                 const int32_t *src = P.cols[p] + row * (int64_t)P.stride[p];
                 for (int32_t e = l; e < c; e += G) row_j[off + e] = src[e];
                 off += c;
@@ -157,7 +138,7 @@ __global__ void __launch_bounds__(SG_UNION_BLOCK) union_block_kernel(
 #pragma unroll
         for (int p = 0; p < SG_UNION_MAX_PARTS; ++p) {
             if (p < P.n) {
-                const int32_t c = counted(P, p, row);
+                const int32_t c = counted(P.counts[p], row, P.stride[p]);
                 const int32_t *src = P.cols[p] + row * (int64_t)P.stride[p];
                 for (int32_t e = threadIdx.x; e < c; e += SG_UNION_BLOCK) {
                     const int32_t j = src[e];
@@ -169,7 +150,7 @@ __global__ void __launch_bounds__(SG_UNION_BLOCK) union_block_kernel(
             }
         }
         if (bad) atomicOr(head, SG_UNION_BAD_COLUMN);
-        const int32_t cnt0 = counted(P, 0, row);
+        const int32_t cnt0 = counted(P.counts[0], row, P.stride[0]);
         int32_t m = SG_UNION_SHORT * 2;   // the network's size: the power of two at or above total
         while (m < total) m <<= 1;
         for (int32_t e = total + threadIdx.x; e < m; e += SG_UNION_BLOCK) s_key[e] = NONE;
@@ -227,18 +208,18 @@ __global__ void __launch_bounds__(SG_UNION_BLOCK) union_block_kernel(
 }
 
 template <typename T>
-__global__ void __launch_bounds__(SG_UNION_BLOCK) union_fill_kernel(
+__global__ void __launch_bounds__(SG_PAIR_BLOCK) union_fill_kernel(
     int32_t *__restrict__ w_cols, T *__restrict__ w_vals, const int32_t *__restrict__ w_counts, int64_t n_rows, int64_t n_cols,
-    int32_t wide, int32_t chunks, UnionPrimary<T> F, uint32_t *head) {
+    int32_t wide, int32_t chunks, PairField<T> F, uint32_t *head) {
     constexpr int G = SG_PAIR_LANES;
     const int l = threadIdx.x & (G - 1);
     const int group_shift = threadIdx.x & (SG_WAVE - 1) & ~(G - 1);   // the group's first lane in its wave
-    const int64_t g = ((int64_t)blockIdx.x * SG_UNION_BLOCK + threadIdx.x) / G;
+    const int64_t g = ((int64_t)blockIdx.x * SG_PAIR_BLOCK + threadIdx.x) / G;
     const int64_t row = g / chunks;
     if (row >= n_rows) return;   // (everything below is uniform over the group: its lanes leave, loop and shuffle together)
     const int32_t cnt = w_counts[row];   // (at most `wide`: the union kernels counted it)
-    const int32_t e0 = (int32_t)(g - row * chunks) * SG_UNION_CHUNK;
-    const int32_t e1 = cnt < e0 + SG_UNION_CHUNK ? cnt : e0 + SG_UNION_CHUNK;
+    const int32_t e0 = (int32_t)(g - row * chunks) * SG_PAIR_ROW_CHUNK;
+    const int32_t e1 = cnt < e0 + SG_PAIR_ROW_CHUNK ? cnt : e0 + SG_PAIR_ROW_CHUNK;
     const int64_t base = row * (int64_t)wide;
     int64_t a0 = 0, a1 = -1;   // the row of A, found when the first marked entry shows
     for (int32_t e = e0; e < e1; ++e) {
@@ -246,15 +227,8 @@ __global__ void __launch_bounds__(SG_UNION_BLOCK) union_fill_kernel(
         if (mark >= 0) continue;
         const int64_t j = ~mark;   // in [0, n_cols): the union kernels keep no other column
         if (j >= n_cols) continue;
-        if (a1 < 0) {
-            const int64_t a = physical_row(row, F.dead_a, F.n_dead_a);
-            a0 = F.a_indptr[a], a1 = F.a_indptr[a + 1];
-            if (F.check_a && row_not_ascending(F.a_indices, a0, a1, l)) atomicOr(head, SG_UNION_BAD_A);
-        }
-        const int64_t b = physical_row(j, F.dead_b, F.n_dead_b);
-        const int64_t b0 = F.b_indptr[b], b1 = F.b_indptr[b + 1];
-        if (F.check_b && row_not_ascending(F.b_indices, b0, b1, l)) atomicOr(head, SG_UNION_BAD_B);
-        const T s = pair_rows_dot<T>(F.a_indices, F.a_data, a0, a1, F.b_indices, F.b_data, b0, b1, l, group_shift);
+        if (a1 < 0) pair_left_row<T>(F, row, l, head, SG_UNION_BAD_A, a0, a1);
+        const T s = pair_score<T>(F, a0, a1, j, l, group_shift, head, SG_UNION_BAD_B);
         if (l == 0) {   // (the group's other lanes have read this entry's mark above, and read no entry twice)
             w_vals[base + e] = s;
             w_cols[base + e] = (int32_t)j;
@@ -287,11 +261,6 @@ static int unite(sg_ctx *ctx, const sg_topn *const *parts, int32_t n_parts, cons
     memset(&P, 0, sizeof(P));
     P.n = n_parts;
     for (int p = 0; p < n_parts; ++p) P.cols[p] = parts[p]->d_cols, P.counts[p] = parts[p]->d_counts, P.stride[p] = parts[p]->stride;
-    UnionPrimary<T> F;
-    F.a_indptr = primary->A->d_indptr, F.a_indices = primary->A->d_indices, F.a_data = (const T *)primary->A->d_data;
-    F.b_indptr = primary->B->d_indptr, F.b_indices = primary->B->d_indices, F.b_data = (const T *)primary->B->d_data;
-    F.dead_a = primary->d_dead_a, F.dead_b = primary->d_dead_b, F.n_dead_a = primary->n_dead_a, F.n_dead_b = primary->n_dead_b;
-    F.check_a = known_ascending(primary->A) ? 0 : 1, F.check_b = known_ascending(primary->B) ? 0 : 1;
     constexpr int per_block = SG_UNION_BLOCK / SG_PAIR_LANES;
     // the kernel is chosen ROW BY ROW: eight lanes for a row of up to SG_UNION_SHORT entries, whatever the strides; the rows above
     // it are listed on the device (no read-back) and taken by a fixed grid of blocks
@@ -306,10 +275,10 @@ static int unite(sg_ctx *ctx, const sg_topn *const *parts, int32_t n_parts, cons
                            (const T *)first->d_vals, first->n_cols, wide, w_cols, (T *)w_vals, w_counts, d_long_rows, d_head);
         SG_HIP_TRY(hipGetLastError());
     }
-    const int32_t chunks = (wide + SG_UNION_CHUNK - 1) / SG_UNION_CHUNK;
-    const int64_t fill_blocks = (first->n_rows * chunks + per_block - 1) / per_block;
-    hipLaunchKernelGGL(union_fill_kernel<T>, dim3((unsigned)fill_blocks), dim3(SG_UNION_BLOCK), 0, ctx->stream, w_cols,
-                       (T *)w_vals, w_counts, first->n_rows, first->n_cols, wide, chunks, F, d_head);
+    const int32_t chunks = (wide + SG_PAIR_ROW_CHUNK - 1) / SG_PAIR_ROW_CHUNK;
+    hipLaunchKernelGGL(union_fill_kernel<T>, dim3((unsigned)pair_blocks(first->n_rows * chunks)), dim3(SG_PAIR_BLOCK), 0,
+                       ctx->stream, w_cols, (T *)w_vals, w_counts, first->n_rows, first->n_cols, wide, chunks,
+                       make_pair_field<T>(*primary), d_head);
     SG_HIP_TRY(hipGetLastError());
     return SG_OK;
 }
@@ -328,22 +297,11 @@ extern "C" int sg_topn_union(sg_ctx *ctx, const sg_topn *const *parts, int32_t n
     }
     SG_REQUIRE(wide <= SG_UNION_MAX_ENTRIES, "the parts' strides exceed 2048 together: ask the multiplies for fewer a row");
     const sg_topn *first = parts[0];
-    const sg_rescore_field &h = *primary;
-    SG_REQUIRE(h.A && h.B, "the primary field's matrix is null");
-    SG_REQUIRE(h.A->dtype == first->dtype && h.B->dtype == first->dtype, "the primary field's matrices differ from the parts in value type");
-    SG_REQUIRE(h.A->n_cols == h.B->n_cols, "the primary field's matrices differ in shape (their columns)");
-    SG_REQUIRE(h.n_dead_a >= 0 && h.n_dead_b >= 0 && (h.n_dead_a == 0 || h.d_dead_a) && (h.n_dead_b == 0 || h.d_dead_b),
-               "a list of dead rows is null or has a negative length");
-    SG_REQUIRE(h.A->n_rows - h.n_dead_a == first->n_rows, "the primary field's left matrix has not the parts' rows (dead rows apart)");
-    SG_REQUIRE(h.B->n_rows - h.n_dead_b == first->n_cols, "the primary field's right matrix has not the parts' columns as rows (dead rows apart)");
-    constexpr int per_block = SG_UNION_BLOCK / SG_PAIR_LANES;
-    const int64_t chunks = (wide + SG_UNION_CHUNK - 1) / SG_UNION_CHUNK;
-    if ((first->n_rows * chunks + per_block - 1) / per_block > INT32_MAX || first->n_rows > INT32_MAX) {
-        sg_set_error("%lld rows of candidates exceed one launch: unite them in pieces", (long long)first->n_rows);
-        return SG_ERR_OVERFLOW;
-    }
-    if (h.A->rows_of) SG_TRY(sg_csr_ensure_rows(ctx, h.A));
-    if (h.B->rows_of && h.B != h.A) SG_TRY(sg_csr_ensure_rows(ctx, h.B));
+    SG_TRY(check_pair_field(*primary, first->dtype, first->n_rows, first->n_cols, "the primary field's", "parts", false));
+    const int64_t chunks = (wide + SG_PAIR_ROW_CHUNK - 1) / SG_PAIR_ROW_CHUNK;
+    if (pair_blocks(first->n_rows * chunks) > INT32_MAX || first->n_rows > INT32_MAX)
+        return exceeds_one_launch(first->n_rows, "rows of candidates", "unite");
+    SG_TRY(ensure_pair_rows(ctx, primary->A, primary->B));
     TopnPtr r;
     if (first->n_rows == 0) {
         SG_TRY(topn_alloc(ctx, 0, first->n_cols, 1, first->dtype, &r));
@@ -369,8 +327,8 @@ extern "C" int sg_topn_union(sg_ctx *ctx, const sg_topn *const *parts, int32_t n
     if (head[0]) {
         std::string what;
         if (head[0] & SG_UNION_BAD_COLUMN) what += "a part's column lies outside the parts' columns; ";
-        if (head[0] & SG_UNION_BAD_A) what += "a row of the primary field's left matrix that a candidate reads is not sorted by column (strictly ascending); ";
-        if (head[0] & SG_UNION_BAD_B) what += "a row of the primary field's right matrix that a candidate reads is not sorted by column (strictly ascending); ";
+        if (head[0] & SG_UNION_BAD_A) what += unsorted_row("the primary field's left matrix", "candidate reads");
+        if (head[0] & SG_UNION_BAD_B) what += unsorted_row("the primary field's right matrix", "candidate reads");
         sg_set_error("bad argument: %s", what.c_str());
         return SG_ERR_BADARG;
     }
