@@ -61,9 +61,10 @@ const char *sg_last_error(void);
  * grew; round 5: 3 -- sg_stats.prune_scored; 4 -- sg_topn_transpose_select; 5 -- sg_csr_concat; 6 -- sg_csr_select_rows,
  * sg_topn_drop_columns, sg_device_upload; 7 -- sg_topn_concat_rows, sg_topn_forget, sg_topn_put_rows, sg_csr_take_rows,
  * sg_device_download; 8 -- sg_csr_row_norms, sg_csr_vectoriser_words, sg_csr_column_counts, sg_vec_reweigh; 9 --
- * sg_csr_pairs_dot; 10 -- sg_topn_rescore, sg_rescore_field; 11 -- sg_topn_union); a binding compares it with the value it was
- * written for right after loading the library. */
-#define SG_ABI_VERSION 11
+ * sg_csr_pairs_dot; 10 -- sg_topn_rescore, sg_rescore_field; 11 -- sg_topn_union; 12 -- sg_topn_rescore_floors,
+ * sg_matchlist_field_scores); a binding compares it
+ * with the value it was written for right after loading the library. */
+#define SG_ABI_VERSION 12
 int sg_abi_version(void);
 int sg_device_count(int *count);
 /* hip_stream: a hipStream_t to launch on (e.g. torch.cuda.current_stream().cuda_stream), or NULL
@@ -511,6 +512,26 @@ typedef struct {
 } sg_rescore_field;
 int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
                     double threshold, int32_t top_n, sg_topn **out);
+/* sg_topn_rescore_floors: sg_topn_rescore with a floor a FIELD.  "The city must agree" is a condition on one field, not on the
+ * weighed sum: a pair with name 1.0, address 1.0 and city 0.0 reaches 0.8 at weights 0.5 / 0.3 / 0.2.  (The reference has no
+ * analogue: it matches one column of strings, string_grouper.py:55-153; its users filter per-field frames in pandas.)
+ *
+ * floor0 is the floor m_0 of the score cand carries (s_0 = vals[i, e], as it is), floors[f - 1] the floor m_f of further field
+ * f = 1 .. n_fields; a NaN means the field has no floor.  Everything is sg_topn_rescore's -- s_f, c, the order, the cut -- but
+ * the filter:
+ *   filter             kept when c > (T)threshold AND s_f > (T)m_f for every field f with a floor.  Strict, as the threshold
+ *                      is; a NaN score never passes a floor.  Floors act BEFORE the cut: the first min(top_n, S) of the
+ *                      entries that passed stay.
+ * A candidate that a floor refuses on field f is scored on no field f' > f: no row of B_f' is read for it.  So the column order
+ * of a matrix not known to be sorted is looked at for the rows that are READ -- a row that only refused candidates name is not
+ * looked at, and a call sg_topn_rescore would refuse for that row is served.  A NaN that the data produces (no floor on that
+ * field) refuses nothing by itself: the candidate is scored on, its c is a NaN and the filter drops it, as in sg_topn_rescore.
+ * With every floor a NaN the result is sg_topn_rescore's to the bit.
+ * Refusals: those of sg_topn_rescore, and a floor that is infinite (SG_ERR_BADARG).  A candidate's column is range-checked
+ * before any floor is held against it: a column outside [0, N) refuses the call even where the primary's floor would have
+ * refused the candidate. */
+int sg_topn_rescore_floors(sg_ctx *ctx, const sg_topn *cand, double w0, double floor0, const sg_rescore_field *fields,
+                           const double *floors, int32_t n_fields, double threshold, int32_t top_n, sg_topn **out);
 /* sg_topn_union: the candidates of SEVERAL fields' multiplies as one candidate result.  Two records that agree on address and
  * city but whose names fall below the candidate threshold are never compared when the names alone find the candidates; record
  * linkage takes the candidates from the union of several fields' matches instead.  (The reference has no analogue: it matches
@@ -538,6 +559,26 @@ int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescor
  *                        status word, a bit a cause.
  * R x stride beyond the 32-bit result index: SG_ERR_OVERFLOW. */
 int sg_topn_union(sg_ctx *ctx, const sg_topn *const *parts, int32_t n_parts, const sg_rescore_field *primary, sg_topn **out);
+/* sg_matchlist_field_scores: which field carried a match.  A record call's list holds the weighed sum; this scores every entry
+ * of a device-resident list on 1 to 8 fields, so that the frame can show a column a field.  (The reference has no analogue:
+ * it matches one column of strings, string_grouper.py:55-153; its users join per-field frames in pandas.)
+ *
+ * ml: a list of R rows and N columns (sg_matchlist_build's; only read).  fields[0 .. n_fields): A_f, B_f and the dead-row
+ * lists with the meaning they have in sg_topn_rescore; the weight is ignored.  out_host: [n_fields][n_entries] values of the
+ * list's type, HOST memory.  Plane f holds, for every entry (i, j) of the list in list order, (A_f . B_f^T)[a, b] exactly as
+ * sg_csr_pairs_dot states it -- a, b from the live numbers i, j through the dead lists, ascending column, every product and
+ * every sum rounded on its own, from +0.0.  That holds for every entry, whatever the list's value there is: on the diagonal
+ * that sg_matchlist_build sets to 1 the plane holds the field's own product (0 for an empty row), and a mirrored entry is
+ * scored as the pair it names.  A list without entries is served: nothing is written.
+ * Refusals (SG_ERR_BADARG; out_host is left as it was, and the next call works):
+ *   seen on the host     n_fields outside 1 .. 8; a field whose matrices differ from the list in value type, or from each
+ *                        other in columns; rows(A_f) - n_dead_a != R or rows(B_f) - n_dead_b != N;
+ *   seen on the device   a column of the list outside [0, N) -- nothing is read for it --, or a row of a field matrix that an
+ *                        entry reads whose columns are not strictly ascending, for matrices not known to be sorted: one
+ *                        status word, a bit a cause, which comes back together with the planes in the call's only read-back.
+ * More entries than one launch takes: SG_ERR_OVERFLOW. */
+int sg_matchlist_field_scores(sg_ctx *ctx, const sg_matchlist *ml, const sg_rescore_field *fields, int32_t n_fields,
+                              void *out_host);
 
 /* ------------------------------------------------------------------ measurement */
 enum { SG_K_TOKENIZE = 0, SG_K_WEIGHT = 1, SG_K_POSTINGS = 2, SG_K_SPGEMM = 3 /* the multiply's whole launch group */,

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SG_HIP_LIB") or os.path.join(_HERE, "libsg_hip.so")
 
 SG_OK, SG_ERR_BADARG, SG_ERR_OOM, SG_ERR_OVERFLOW, SG_ERR_HIP, SG_ERR_NODEVICE, SG_ERR_UNSUPPORTED = range(7)
 SG_F32, SG_F64 = 0, 1
-ABI_VERSION = 11       # include/sg_hip.h: SG_ABI_VERSION
+ABI_VERSION = 12       # include/sg_hip.h: SG_ABI_VERSION
 SG_K_TOKENIZE, SG_K_WEIGHT, SG_K_POSTINGS, SG_K_SPGEMM, SG_K_ZIP, SG_K_VOCAB, SG_K_SPGEMM_KERNEL, SG_K_COUNT = range(8)
 KERNEL_NAMES = ("tokenize", "weight", "postings", "spgemm_topn", "zip", "vocab", "spgemm_kernel")
 
@@ -131,7 +131,10 @@ ABI = {
     "sg_csr_rowwise_dot": (C.c_int, [_P, _P, _P, _P]),
     "sg_csr_pairs_dot": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P]),
     "sg_topn_rescore": (C.c_int, [_P, _P, C.c_double, C.POINTER(SgRescoreField), C.c_int32, C.c_double, C.c_int32, _PP]),
+    "sg_topn_rescore_floors": (C.c_int, [_P, _P, C.c_double, C.c_double, C.POINTER(SgRescoreField), C.POINTER(C.c_double), C.c_int32,
+                                         C.c_double, C.c_int32, _PP]),
     "sg_topn_union": (C.c_int, [_P, C.POINTER(_P), C.c_int32, C.POINTER(SgRescoreField), _PP]),
+    "sg_matchlist_field_scores": (C.c_int, [_P, _P, C.POINTER(SgRescoreField), C.c_int32, _P]),
     "sg_csr_row_norms": (C.c_int, [_P, _PP]),
     "sg_csr_vectoriser_words": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int32)]),
     "sg_csr_column_counts": (C.c_int, [_P, _P, _P]),
@@ -424,6 +427,21 @@ class MatchList(_Handle):
         vals = np.empty(max(m.value, 1), code_np_dtype(d.value))
         check(lib().sg_matchlist_to_host(self.ctx.h, self.h, _ptr(row_ptr), _ptr(cols), _ptr(vals)))
         return row_ptr, cols[:m.value], vals[:m.value]
+
+    def field_scores(self, fields) -> np.ndarray:
+        """The list's entries scored on 1 to 8 fields: an array ``[len(fields), n_entries]`` of the list's dtype, plane f the
+        score of every entry's pair on field f, in list order, bit for bit ``Context.pairs_dot``'s (include/sg_hip.h:
+        sg_matchlist_field_scores).  ``fields``: ``(A: Csr, B: Csr, dead_a: DeviceInts | None, dead_b: DeviceInts | None)``
+        each, as the primary of ``Context.topn_union``.  The list is only read.  A refusal (a field that does not fit the
+        list, an unsorted row that an entry reads): ValueError."""
+        fields = list(fields)
+        _, m, d = self.dims()
+        arr = (SgRescoreField * max(len(fields), 1))()
+        for k, (A, B, dead_a, dead_b) in enumerate(fields):
+            arr[k] = _rescore_field(A, B, 1.0, dead_a, dead_b)
+        flat = np.zeros(max(len(fields) * m, 1), code_np_dtype(d))   # the planes one behind the other, n_entries apart
+        check(lib().sg_matchlist_field_scores(self.ctx.h, self.h, arr, len(fields), _ptr(flat)))
+        return flat[:len(fields) * m].reshape(len(fields), m)
 
 
 class DeviceInts(_Handle):
@@ -858,19 +876,31 @@ class Context:
         d_rows = _dev_ptr(d_rows)
         check(lib().sg_topn_put_rows(self.h, res.h, C.c_void_p(d_rows) if d_rows else None, int(n_rows), src.h))
 
-    def topn_rescore(self, cand: TopN, w0: float, fields, threshold: float, top_n: int) -> TopN:
+    def topn_rescore(self, cand: TopN, w0: float, fields, threshold: float, top_n: int, floors=None) -> TopN:
         """The candidates of ``cand`` scored on further fields, weighed, filtered, re-ordered and cut, on the device
         (include/sg_hip.h: sg_topn_rescore).  ``fields``: 1 to 7 of ``(A: Csr, B: Csr, weight, dead_a: DeviceInts | None,
         dead_b: DeviceInts | None)`` -- the left and right records' rows of the field (the same handle for a self-join), and
         per side the dead physical rows of a corpus that has removed rows pending.  c = w0 * s_0 + sum of weight_f * s_f, every
         product and every sum rounded on its own, in this order; kept when c > threshold; by c descending, then column; at
         most ``top_n`` a row.  ``cand`` is only read.  A refusal of the device (a column outside the result, an unsorted row
-        that a candidate reads): ValueError."""
+        that a candidate reads): ValueError.
+
+        ``floors``: None -- sg_topn_rescore -- or one entry a field, the candidates' own score first (``1 + len(fields)`` of
+        them), each None (no floor) or a number: a candidate is kept only when also ``s_f > floor_f`` on every field that has
+        one, before the cut (sg_topn_rescore_floors).  An infinite floor: ValueError."""
         fields = list(fields)
         arr = (SgRescoreField * max(len(fields), 1))()
         for k, field in enumerate(fields):
             arr[k] = _rescore_field(*field)
         out = C.c_void_p()
+        if floors is not None:
+            floors = [float("nan") if m is None else float(m) for m in floors]
+            if len(floors) != len(fields) + 1:
+                raise ValueError(f"{len(floors)} floors for {len(fields) + 1} fields: one a field is expected, the candidates' own first")
+            rest = (C.c_double * max(len(fields), 1))(*floors[1:])
+            check(lib().sg_topn_rescore_floors(self.h, cand.h, float(w0), floors[0], arr, rest, len(fields), float(threshold),
+                                               int(top_n), C.byref(out)))
+            return TopN(self, out)
         check(lib().sg_topn_rescore(self.h, cand.h, float(w0), arr, len(fields), float(threshold), int(top_n), C.byref(out)))
         return TopN(self, out)
 

@@ -150,17 +150,60 @@ class _RecordGrouper(_CorpusGrouper):
     list -- the frames, the groups -- is StringGrouper's own."""
 
     def __init__(self, corpus: "Corpus", others, weights, cand, dup_fields, master, duplicates=None, master_id=None,
-                 duplicates_id=None, candidate_fields=(0,), **kwargs):
+                 duplicates_id=None, candidate_fields=(0,), floors=None, field_scores=False, **kwargs):
         """``cand``: (max_n_matches, min_similarity) of the candidates -- with ``candidate_fields`` other than ``(0,)`` a list
-        of them, one a candidate field (CorpusEngine.corpus_records_union_topn)."""
+        of them, one a candidate field (CorpusEngine.corpus_records_union_topn).  ``floors``: None or one entry a field, each
+        None or a number; ``field_scores``: the list gets a column ``similarity_k`` a field.  The engine gets either keyword
+        only when it is set."""
         self._others, self._weights, self._cand, self._dup_fields = others, weights, cand, dup_fields
         self._candidate_fields = tuple(candidate_fields)
+        self._floors = floors
+        self._field_scores = bool(field_scores)
+        self._planes = None
         super().__init__(corpus, master, duplicates, master_id, duplicates_id, **kwargs)
 
     def _can_fuse_on_device(self) -> bool:
         return True                           # (explicit n_blocks were refused by the caller; there is no host route)
 
+    def _new_options(self) -> dict:
+        """The engine's keywords that are passed only when they are set, so that engine doubles without them keep working."""
+        return {**({} if self._floors is None else {'floors': self._floors}),
+                **({'field_scores': True} if self._field_scores else {})}
+
     def _engine_match_list(self, eng, master_matrix, duplicate_matrix, fix: bool):
+        out = self._engine_record_list(eng, master_matrix, duplicate_matrix, fix)
+        if self._field_scores:                # the engine's last element: the planes, one a field, in list order
+            self._planes, out = out[-1], out[:-1]
+        return out
+
+    def fit(self):
+        """StringGrouper's, and with ``field_scores`` the planes as further columns ``similarity_k`` of the match list
+        (float64, as ``similarity`` is).  They are added in place: the list on the device stays with the grouper."""
+        self._planes = None
+        super().fit()
+        if self._field_scores:
+            ml = self._matches_list
+            for k, plane in enumerate(self._planes):
+                ml[f'similarity_{k}'] = plane.astype(np.float64, copy=False)
+            self._planes = None
+        return self
+
+    def get_matches(self, ignore_index: Optional[bool] = None, include_zeroes: Optional[bool] = None) -> pd.DataFrame:
+        """StringGrouper's frame, and with ``field_scores`` the columns ``similarity_k`` right after ``similarity``.  The rows
+        ``include_zeroes`` adds come after the list's own, in the frame as in the list, and carry 0.0 in every field column
+        as they carry 0 in ``similarity``."""
+        frame = super().get_matches(ignore_index=ignore_index, include_zeroes=include_zeroes)
+        if not self._field_scores:
+            return frame
+        ml = self._matches_list
+        at = list(frame.columns).index('similarity') + 1
+        for k in range(len(self._others) + 1):
+            column = np.zeros(len(frame), np.float64)
+            column[:len(ml)] = ml[f'similarity_{k}'].to_numpy()
+            frame.insert(at + k, f'similarity_{k}', column)
+        return frame
+
+    def _engine_record_list(self, eng, master_matrix, duplicate_matrix, fix: bool):
         fields = None
         if self._dup_fields is not None:                             # one transform a field (duplicates[0] may be corpus.master)
             fields = [o._rows_of(series, self._made) for o, series in zip(self._others, self._dup_fields)]
@@ -172,7 +215,8 @@ class _RecordGrouper(_CorpusGrouper):
             keep = 'keep_on_device' in inspect.signature(eng.corpus_records_topn).parameters   # engine doubles may lack it
             return eng.corpus_records_topn(self._corpus._live(), [o._live() for o in self._others], duplicate_matrix, fields,
                                            self._weights, cand_top_n, cand_threshold, top_n, self._config.min_similarity, fix,
-                                           **({'keep_on_device': True} if keep else {}))
+                                           **({'keep_on_device': True} if keep else {}),
+                                           **self._new_options())
         except OverflowError as e:
             # fit() answers an OverflowError with the block-wise multiply of ONE field: that is no record match.  There is no
             # block-wise route for records, so the call is refused instead
@@ -187,7 +231,8 @@ class _RecordGrouper(_CorpusGrouper):
         top_n = all_candidates if self._max_n_matches is None else min(int(self._max_n_matches), all_candidates)
         return eng.corpus_records_union_topn(self._corpus._live(), [o._live() for o in self._others], duplicate_matrix, fields,
                                              self._weights, self._candidate_fields, self._cand, top_n,
-                                             self._config.min_similarity, fix, keep_on_device=True)
+                                             self._config.min_similarity, fix, keep_on_device=True,
+                                             **self._new_options())
 
 
 class Corpus:
@@ -437,8 +482,9 @@ class Corpus:
         ``self_join_rows_refilled`` (rows a remove had to multiply again); ``idf_refits`` (calls of ``refit_idf``);
         ``pair_calls`` / ``pairs_scored`` (calls of ``pair_similarities`` that reached the device, and their pairs);
         ``record_calls`` (calls of ``match_records`` / ``group_similar_records`` this corpus took part in, as the one that
-        finds the candidates or as a further field) and ``record_union_calls`` (those of them with several
-        ``candidate_fields``, counted on the corpora that found candidates)."""
+        finds the candidates or as a further field), ``record_union_calls`` (those of them with several
+        ``candidate_fields``, counted on the corpora that found candidates) and ``record_floor_calls`` (those of them with a
+        ``field_min_similarity``)."""
         return dict(self._live().stats)
 
     def _rows_of(self, series, made):
@@ -533,7 +579,8 @@ class Corpus:
                     csr.free()
 
     # ------------------------------------------------------------------ records of several fields
-    def _record_call(self, others, duplicates, duplicates_id, weights, candidates, kwargs, finish, candidate_fields=(0,)):
+    def _record_call(self, others, duplicates, duplicates_id, weights, candidates, kwargs, finish, candidate_fields=(0,),
+                     field_min_similarity=None, field_similarities=False):
         """The checks of ``match_records`` / ``group_similar_records``, then the call."""
         state = self._live()
         self._same_engine()
@@ -604,6 +651,40 @@ class Corpus:
         if candidate_fields != (0,) and not hasattr(self._engine, "corpus_records_union_topn"):
             raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} unites no "
                                       f"candidates of several fields")
+        # field_min_similarity: one floor a field, this corpus's first; None -- the whole or an entry -- is no floor
+        floors = None
+        if field_min_similarity is not None:
+            if isinstance(field_min_similarity, (str, bytes)) or not hasattr(field_min_similarity, "__len__"):
+                raise TypeError("field_min_similarity must be a sequence, one entry for every field (this corpus's first): a "
+                                "number or None")
+            floors = list(field_min_similarity)
+            if len(floors) != len(others) + 1:
+                raise ValueError(f"{len(floors)} entries of field_min_similarity for {len(others) + 1} fields: one a field is "
+                                 f"expected, this corpus's first")
+            for k, m in enumerate(floors):
+                if isinstance(m, (bool, np.bool_)):
+                    raise TypeError(f"field_min_similarity[{k}]={m!r}: a number or None is expected, not a bool")
+                if m is None:
+                    continue
+                if not isinstance(m, (int, float, np.integer, np.floating)) or not np.isfinite(m):
+                    raise ValueError(f"field_min_similarity[{k}]={m!r}: a finite real number or None is expected")
+                floors[k] = float(m)
+            if all(m is None for m in floors):               # no floor anywhere: the call it always was
+                floors = None
+        if floors is not None:
+            routes = ("corpus_records_topn",) if candidate_fields == (0,) else ("corpus_records_topn", "corpus_records_union_topn")
+            if not all("floors" in inspect.signature(getattr(self._engine, r)).parameters for r in routes):
+                raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} takes no "
+                                          f"field_min_similarity")
+        # field_similarities: a column a field in the frame
+        if not isinstance(field_similarities, (bool, np.bool_)):
+            raise TypeError(f"field_similarities={field_similarities!r}: True or False is expected")
+        field_similarities = bool(field_similarities)
+        if field_similarities:
+            routes = ("corpus_records_topn",) if candidate_fields == (0,) else ("corpus_records_topn", "corpus_records_union_topn")
+            if not all("field_scores" in inspect.signature(getattr(self._engine, r)).parameters for r in routes):
+                raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} gives no "
+                                          f"field_similarities")
         # candidates: the two options of a candidate field's multiply -- one dict for every candidate field, or one a field
         candidates = {} if candidates is None else candidates
         if isinstance(candidates, list) and all(isinstance(c, dict) for c in candidates):
@@ -636,7 +717,7 @@ class Corpus:
                              f"record that can be united and rescored")
         g = _RecordGrouper(self, others, weights, cand[0] if candidate_fields == (0,) else cand, dup_fields, self.master,
                            None if duplicates is None else duplicates[0], self.master_id, duplicates_id,
-                           candidate_fields=candidate_fields, **options)
+                           candidate_fields=candidate_fields, floors=floors, field_scores=field_similarities, **options)
         for o in others:
             o._join_pending()
         try:
@@ -645,7 +726,7 @@ class Corpus:
             g._release()
 
     def match_records(self, others, duplicates=None, duplicates_id: Optional[pd.Series] = None, weights=None, candidates=None,
-                      candidate_fields=(0,), **kwargs) -> pd.DataFrame:
+                      candidate_fields=(0,), field_min_similarity=None, field_similarities=False, **kwargs) -> pd.DataFrame:
         """Match RECORDS of several fields.  This corpus holds one field of every record (say the names), ``others`` -- a list
         of 1 to 7 ``Corpus`` objects -- the further fields (addresses, cities ...): row p of every corpus is record p, which is
         the caller's duty (append to and remove from all of them together; different lengths: ValueError).  The call is
@@ -673,9 +754,8 @@ class Corpus:
         whose first Series is ``corpus.master`` are still duplicates: the further Series given are the ones scored.
 
         The frame is ``match_strings(corpus.master, duplicates[0], corpus.master_id, duplicates_id)``'s, with the combined
-        similarity; there are no per-field columns (``pair_similarities`` of each corpus gives them for the pairs of the
-        frame).  No further corpus is compacted or indexed by the call (``stats['record_calls']`` counts it on every corpus
-        that took part).
+        similarity (``field_similarities=True`` adds a column a field, below).  No further corpus is compacted or indexed by
+        the call (``stats['record_calls']`` counts it on every corpus that took part).
 
         ``candidate_fields``: the fields that find the candidates, as ascending distinct positions -- 0 is this corpus, k is
         ``others[k - 1]``, and 0 is always among them; ``(0,)`` by default, which is the call described above.  With several,
@@ -687,11 +767,36 @@ class Corpus:
         with ``s_f`` the bits ``corpus_f.pair_similarities`` returns, whichever field found it: the union and the missing
         scores are made on the device (``stats['record_union_calls']`` counts the call on the candidate fields' corpora).  A
         further corpus named as a candidate field is treated as this corpus is -- it builds its index and a self-join
-        compacts it; the others are still only read."""
-        return self._record_call(others, duplicates, duplicates_id, weights, candidates, kwargs, lambda g: g.fit().get_matches(),
-                                 candidate_fields)
+        compacts it; the others are still only read.
 
-    def group_similar_records(self, others, weights=None, candidates=None, candidate_fields=(0,), **kwargs):
+        ``field_min_similarity``: a floor a FIELD -- one entry a field, this corpus's first, each ``None`` (no floor) or a
+        finite number (a wrong length, NaN, inf: ValueError; a bool: TypeError); ``None`` by default, which is the call
+        described above -- and so is a list whose entries are all ``None``.  "The city must agree" is a condition on one field, which no ``min_similarity`` of the weighed sum
+        can express.  With floors, step 4 keeps a pair when ``s_f > field_min_similarity[f]`` (in the corpus's dtype; strict,
+        as ``min_similarity`` is) for every field with a floor AND ``similarity > min_similarity``; the similarity, the order
+        and the cut are unchanged, and the floors act BEFORE the cut: the first ``max_n_matches`` of the pairs that passed
+        stay.  ``s_0`` is the score the candidate carries.  A floor may sit on any field, candidate field or not.  It is
+        decided on the device (``stats['record_floor_calls']`` counts the call), and a candidate a floor has refused is not
+        scored on the fields after it.  In a self-join a record still matches itself whatever the floors say, and with
+        ``force_symmetries`` the list is still symmetric: both are made after the floors, as they are made after
+        ``min_similarity``.
+
+        ``field_similarities=True``: which field carried a match.  The frame gets the columns ``similarity_0``,
+        ``similarity_1`` ... (float64, as ``similarity`` is) right after ``similarity``; k counts as in ``candidate_fields``.
+        For a row whose left and right records have the POSITIONS l and r, ``similarity_k`` is bit for bit
+        ``corpus_k.pair_similarities([l], [r], duplicates=...)[0]``, widened -- for every row of the frame: the diagonal a
+        self-join adds carries the field's own product there (not 1; 0 for an empty string), the mirrored rows of
+        ``force_symmetries`` the score of the pair they name.  The rows ``include_zeroes`` adds carry 0.0.  The list is scored
+        where it lies on the device, before it is freed or handed to the group kernels; the planes are a second read-back
+        after the list's own (``stats['record_field_score_calls']`` counts the call): no position list goes up, no label is
+        translated, whatever the index is.  Anything but a bool: TypeError."""
+        return self._record_call(others, duplicates, duplicates_id, weights, candidates, kwargs, lambda g: g.fit().get_matches(),
+                                 candidate_fields, field_min_similarity, field_similarities)
+
+    def group_similar_records(self, others, weights=None, candidates=None, candidate_fields=(0,), field_min_similarity=None,
+                              **kwargs):
         """For every record the representative of its group of similar records: ``group_similar_strings(corpus.master,
-        corpus.master_id)`` over the match list of ``match_records(others, weights=..., candidates=..., candidate_fields=...)``."""
-        return self._record_call(others, None, None, weights, candidates, kwargs, lambda g: g.fit().get_groups(), candidate_fields)
+        corpus.master_id)`` over the match list of ``match_records(others, weights=..., candidates=..., candidate_fields=...,
+        field_min_similarity=...)``."""
+        return self._record_call(others, None, None, weights, candidates, kwargs, lambda g: g.fit().get_groups(), candidate_fields,
+                                 field_min_similarity)

@@ -73,7 +73,8 @@ class CorpusState:
                       "segments": 1, "base_index_builds": 0, "removals": 0, "rows_removed": 0, "dead_rows": 0,
                       "self_join_full": 0, "self_join_served": 0, "self_join_append_updates": 0,
                       "self_join_remove_updates": 0, "self_join_rows_refilled": 0, "idf_refits": 0, "pair_calls": 0,
-                      "pairs_scored": 0, "record_calls": 0, "record_union_calls": 0}
+                      "pairs_scored": 0, "record_calls": 0, "record_union_calls": 0,
+                      "record_floor_calls": 0, "record_field_score_calls": 0}
         if base is not None:
             self.set_segments(CorpusSegment(base), None)
 
@@ -514,7 +515,8 @@ class CorpusEngine:
 
     def corpus_records_topn(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
                             B_fields: Optional[List[DeviceMatrix]], weights, cand_top_n: int, cand_threshold: float,
-                            top_n: int, threshold: float, self_join_fix: bool, keep_on_device: bool = False):
+                            top_n: int, threshold: float, self_join_fix: bool, keep_on_device: bool = False, floors=None,
+                            field_scores: bool = False):
         """The match list of RECORDS: the corpus ``state`` finds the candidates, the corpora ``others`` -- row p of every
         corpus is record p -- score them on their fields, and the weighed sum is filtered, ordered and cut on the device
         (sg_topn_rescore) before the list is built (K6).  Returns what ``match_list`` returns.
@@ -525,15 +527,26 @@ class CorpusEngine:
         as they do for ``match_strings``.  A further field is read where it lies: ``physical()`` with the dead list, live
         numbers turned into physical ones by the kernel -- a record call compacts no secondary corpus and builds no index
         of one.  Every handle made here lives in a scope: the candidates in one that ends with the rescoring, the rescored result
-        in the method's (``_match_list_from_topn`` frees it early, as it frees a multiply's)."""
+        in the method's (``_match_list_from_topn`` frees it early, as it frees a multiply's).
+
+        ``floors``: None, or one entry a field (``state``'s first), each None or a number: a candidate stays only when its
+        score on every field with a floor is above that floor, decided on the device before the cut
+        (sg_topn_rescore_floors).
+
+        ``field_scores``: the tuple returned gets one more element at its END, an array ``[fields, entries]`` of the corpus's
+        dtype: plane k holds, for every entry of the list in list order, the pair's score on field k (0: ``state``) with the
+        bits ``corpus_pairs`` of that field returns -- the diagonal and the mirrored entries of ``self_join_fix`` included,
+        which carry the field's own product.  The list is scored where it lies, after K6 and before it is freed or kept
+        (sg_matchlist_field_scores); the fields' rows and dead lists are the ones the rescoring read."""
         return self._records_topn(state, others, B, B_fields, weights, None, [(cand_top_n, cand_threshold)], top_n, threshold,
-                                  self_join_fix, keep_on_device)
+                                  self_join_fix, keep_on_device, floors, field_scores)
 
     MAX_UNION_CANDIDATES = 2048               # sg_topn_union: the candidate fields' strides together
 
     def corpus_records_union_topn(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
                                   B_fields: Optional[List[DeviceMatrix]], weights, candidate_fields, cands, top_n: int,
-                                  threshold: float, self_join_fix: bool, keep_on_device: bool = False):
+                                  threshold: float, self_join_fix: bool, keep_on_device: bool = False, floors=None,
+                                  field_scores: bool = False):
         """``corpus_records_topn`` with candidates from SEVERAL fields: ``candidate_fields`` -- ascending positions, 0 the corpus
         ``state``, k ``others[k - 1]``, 0 always among them -- each find candidates with a multiply of their own at
         ``cands[.] = (cand_top_n, cand_threshold)``, the results are united on the device (sg_topn_union: a record's distinct
@@ -545,16 +558,18 @@ class CorpusEngine:
         treated as the primary is (it builds its index; a self-join compacts it).  A corpus that is NOT a candidate field is
         read where it lies, as in ``corpus_records_topn``: never compacted, never indexed.  The rows and the dead lists the
         union and the rescoring read are taken AFTER the multiplies, which may have compacted a candidate corpus; results number
-        the live rows, which no compaction changes."""
+        the live rows, which no compaction changes.  ``floors`` as in ``corpus_records_topn``: the primary's floor is held
+        against the score the united candidate carries, the multiply's or the one the union filled in; ``field_scores`` as
+        there too."""
         return self._records_topn(state, others, B, B_fields, weights, candidate_fields, cands, top_n, threshold,
-                                  self_join_fix, keep_on_device)
+                                  self_join_fix, keep_on_device, floors, field_scores)
 
     def _records_topn(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
                       B_fields: Optional[List[DeviceMatrix]], weights, candidate_fields, cands, top_n: int, threshold: float,
-                      self_join_fix: bool, keep_on_device: bool):
+                      self_join_fix: bool, keep_on_device: bool, floors=None, field_scores: bool = False):
         """The body of both record calls: validate, find the candidates -- ``candidate_fields`` None: the primary field's
         multiply at ``cands[0]``; else one multiply a candidate field and their union --, take the fields' rows and dead
-        lists, rescore, count, build the list."""
+        lists, rescore, count, build the list and, with ``field_scores``, score it field by field."""
         t = time.perf_counter()
         A = state.matrix
         self_join = B_fields is None          # (duplicates whose first Series is corpus.master have B is A and fields of their own)
@@ -571,6 +586,8 @@ class CorpusEngine:
                              "candidate options a field, are expected")
         if self_join and B is not A:
             raise ValueError("duplicates of the first field without duplicates of the further fields")
+        if floors is not None and len(floors) != len(weights):
+            raise ValueError(f"{len(floors)} floors for {len(weights)} fields: one a field is expected")
         for k, o in enumerate(others):
             if o.matrix.shape[0] != A.shape[0]:
                 raise ValueError(f"the corpora differ in length ({o.matrix.shape[0]} and {A.shape[0]} rows): row p of every "
@@ -602,13 +619,35 @@ class CorpusEngine:
                         rows, right, _, dead_a, dead_b = field(0)
                         cand = before.own(self.ctx.topn_union(parts, (rows, right, dead_a, dead_b)))
                 fields = [field(k) for k in range(1, len(states))]
-                res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n))
+                if floors is None:
+                    res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n))
+                else:
+                    res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n, floors=list(floors)))
             for st in states:
                 st.stats["record_calls"] += 1
+                if floors is not None:
+                    st.stats["record_floor_calls"] += 1
+                if field_scores:
+                    st.stats["record_field_score_calls"] += 1
             for f in candidate_fields or ():
                 states[f].stats["record_union_calls"] += 1
             # (_match_list_from_topn frees the result once the list is built; if it raises before that, the scope does)
-            return self._match_list_from_topn(res, A.dtype, n_right, self_join_fix, keep_on_device, t)
+            if not field_scores:
+                return self._match_list_from_topn(res, A.dtype, n_right, self_join_fix, keep_on_device, t)
+            out = self._match_list_from_topn(res, A.dtype, n_right, self_join_fix, True, t)
+            kept = out[4]                     # the list on the device: scored before it is freed or handed on
+            t = time.perf_counter()
+            try:
+                planes = kept.ml.field_scores([(rows, right, dead_a, dead_b)
+                                               for rows, right, _, dead_a, dead_b in [field(0)] + fields])
+            except BaseException:
+                kept.free()
+                raise
+            self.timings["field_scores_s"] = time.perf_counter() - t
+            if keep_on_device:
+                return out + (planes,)
+            kept.free()
+            return out[:4] + (planes,)
 
     # ------------------------------------------------------------------ a self-join that is kept
     def corpus_keep_self_join(self, state: CorpusState, top_n: int, threshold: float) -> None:

@@ -12,6 +12,9 @@
 // kept entries of its row that go before it -- which needs no sort network and no exchange between lanes: eight lanes a row
 // reading the row's few scores from cache for a row of at most 64 candidates (rows of name lists hold about four), a block
 // with the row in LDS for the rows above that (up to 2 048 entries), which the first kernel lists on the device.
+//
+// sg_topn_rescore_floors: the same two launches with a floor a field in the filter (s_f > m_f, before the cut).  The scoring kernel
+// has a second instantiation for it (FLOORS, below); the select kernels are the same ones: a refused candidate's c is a NaN.
 #include "sg_pairs_device.h"
 
 #define SG_RESCORE_BLOCK 256
@@ -28,11 +31,26 @@ struct RescoreFields {
     PairField<T> f[SG_RESCORE_MAX_FIELDS];
 };
 
+// Floors (sg_topn_rescore_floors): a candidate must ALSO have s_f > m_f on every field f that has a floor, s_0 -- the score it
+// carries -- included.  `has`: bit 0 the primary's floor, bit f that of further field f; without a bit the value is not read.
 template <typename T>
+struct RescoreFloors {
+    T m[SG_RESCORE_MAX_FIELDS + 1];
+    uint32_t has;
+};
+struct NoFloors {};
+
+// FLOORS: the group follows the candidates a floor has refused in a mask of its own -- SG_PAIR_ROW_CHUNK = 64 entries at most,
+// a bit an entry, the same value in every lane because pair_score returns the score in every lane.  A refused candidate gets a
+// NaN as its c (the select kernels pass over a NaN) and is skipped on every later field: no row of B_f' is read for it, and
+// whether a merge runs never waits for a load of comb.  Only a floor sets a bit: a NaN that the data makes walks on, as without
+// floors.  So the column order of a matrix that is not known to be sorted is looked at for the rows that are READ: a row that
+// only refused candidates name is not.
+template <typename T, bool FLOORS>
 __global__ void __launch_bounds__(SG_PAIR_BLOCK) rescore_score_kernel(
     const int32_t *__restrict__ cols, const T *__restrict__ vals, const int32_t *__restrict__ counts, int64_t n_rows,
     int64_t n_cols, int32_t stride, int32_t chunks, T w0, RescoreFields<T> fields, int32_t n_fields, uint32_t *status,
-    T *__restrict__ comb) {
+    T *__restrict__ comb, std::conditional_t<FLOORS, RescoreFloors<T>, NoFloors> floors) {
     constexpr int G = SG_PAIR_LANES;
     const int l = threadIdx.x & (G - 1);
     const int group_shift = threadIdx.x & (SG_WAVE - 1) & ~(G - 1);   // the group's first lane in its wave
@@ -44,11 +62,14 @@ __global__ void __launch_bounds__(SG_PAIR_BLOCK) rescore_score_kernel(
     const int32_t e1 = cnt < e0 + SG_PAIR_ROW_CHUNK ? cnt : e0 + SG_PAIR_ROW_CHUNK;
     if (e0 >= e1) return;
     const int64_t base = row * (int64_t)stride;
+    uint64_t failed = 0;   // (FLOORS) bit e - e0: a floor has refused entry e
     for (int f = 0; f < n_fields; ++f) {
         const PairField<T> &F = fields.f[f];
         int64_t a0, a1;
         pair_left_row<T>(F, row, l, status, 2u << (2 * f), a0, a1);
         for (int32_t e = e0; e < e1; ++e) {
+            if constexpr (FLOORS)
+                if ((failed >> (e - e0)) & 1) continue;
             const int64_t j = cols[base + e];
             if (j < 0 || j >= n_cols) {   // nothing of a field is read for it; the call is refused
                 if (l == 0 && f == 0) {
@@ -57,7 +78,21 @@ __global__ void __launch_bounds__(SG_PAIR_BLOCK) rescore_score_kernel(
                 }
                 continue;
             }
+            if constexpr (FLOORS) {   // the primary's floor, before anything of a field is read (every lane reads the score)
+                if (f == 0 && (floors.has & 1u) && !(vals[base + e] > floors.m[0])) {
+                    failed |= (uint64_t)1 << (e - e0);
+                    if (l == 0) comb[base + e] = (T)NAN;
+                    continue;
+                }
+            }
             const T s = pair_score<T>(F, a0, a1, j, l, group_shift, status, 4u << (2 * f));
+            if constexpr (FLOORS) {
+                if (((floors.has >> (f + 1)) & 1u) && !(s > floors.m[f + 1])) {
+                    failed |= (uint64_t)1 << (e - e0);
+                    if (l == 0) comb[base + e] = (T)NAN;
+                    continue;
+                }
+            }
             if (l == 0) {   // (lane 0 alone reads and writes the candidate's c: its own stores, in program order)
                 const T c = f == 0 ? add_rn<T>((T)0, mul_rn<T>(w0, vals[base + e])) : comb[base + e];
                 comb[base + e] = add_rn<T>(c, mul_rn<T>(F.w, s));
@@ -158,15 +193,27 @@ __global__ void __launch_bounds__(SG_RESCORE_BLOCK) rescore_select_block_kernel(
 
 template <typename T>
 static int rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
-                   double threshold, sg_topn *r, uint32_t *d_status, void *d_comb, int32_t *d_long_rows) {
+                   double threshold, sg_topn *r, uint32_t *d_status, void *d_comb, int32_t *d_long_rows,
+                   const double *floors) {   // floors: null (sg_topn_rescore), or n_fields + 1 of them, the primary's first
     RescoreFields<T> dev;
     memset(&dev, 0, sizeof(dev));
     for (int f = 0; f < n_fields; ++f) dev.f[f] = make_pair_field<T>(fields[f]);
     constexpr int per_block = SG_RESCORE_BLOCK / SG_PAIR_LANES;
     const int32_t chunks = (cand->stride + SG_PAIR_ROW_CHUNK - 1) / SG_PAIR_ROW_CHUNK;
-    hipLaunchKernelGGL(rescore_score_kernel<T>, dim3((unsigned)pair_blocks(cand->n_rows * chunks)), dim3(SG_PAIR_BLOCK), 0, ctx->stream,
-                       cand->d_cols, (const T *)cand->d_vals, cand->d_counts, cand->n_rows, cand->n_cols, cand->stride, chunks,
-                       (T)w0, dev, n_fields, d_status, (T *)d_comb);
+    const dim3 grid_score((unsigned)pair_blocks(cand->n_rows * chunks));
+    if (!floors) {
+        hipLaunchKernelGGL((rescore_score_kernel<T, false>), grid_score, dim3(SG_PAIR_BLOCK), 0, ctx->stream, cand->d_cols,
+                           (const T *)cand->d_vals, cand->d_counts, cand->n_rows, cand->n_cols, cand->stride, chunks, (T)w0, dev,
+                           n_fields, d_status, (T *)d_comb, NoFloors{});
+    } else {
+        RescoreFloors<T> m;
+        memset(&m, 0, sizeof(m));
+        for (int f = 0; f <= n_fields; ++f)
+            if (!std::isnan(floors[f])) m.m[f] = (T)floors[f], m.has |= 1u << f;
+        hipLaunchKernelGGL((rescore_score_kernel<T, true>), grid_score, dim3(SG_PAIR_BLOCK), 0, ctx->stream, cand->d_cols,
+                           (const T *)cand->d_vals, cand->d_counts, cand->n_rows, cand->n_cols, cand->stride, chunks, (T)w0, dev,
+                           n_fields, d_status, (T *)d_comb, m);
+    }
     SG_HIP_TRY(hipGetLastError());
     // the select kernel is chosen ROW BY ROW: eight lanes for a row of up to SG_RESCORE_SHORT candidates, whatever the stride;
     // the rows above it are listed on the device (no read-back) and taken by a fixed grid of blocks
@@ -185,14 +232,21 @@ static int rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore
     return SG_OK;
 }
 
-extern "C" int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
-                               double threshold, int32_t top_n, sg_topn **out) {
-    SG_REQUIRE(ctx && cand && out, "null argument");
+static int rescore_count_ok(int32_t n_fields) {
     SG_REQUIRE(n_fields >= 1 && n_fields <= SG_RESCORE_MAX_FIELDS, "between 1 and 7 further fields are expected");
+    return SG_OK;
+}
+
+// both entries; floors: null, or n_fields + 1 doubles -- the primary's first -- a NaN for a field without one
+static int rescore_call(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
+                        double threshold, int32_t top_n, sg_topn **out, const double *floors) {
+    SG_REQUIRE(ctx && cand && out, "null argument");
+    SG_TRY(rescore_count_ok(n_fields));
     SG_REQUIRE(fields != nullptr, "null argument");
     SG_REQUIRE(top_n >= 1, "top_n must be at least 1");
     SG_REQUIRE(cand->stride >= 1 && cand->stride <= SG_RESCORE_MAX_STRIDE, "the candidates' stride exceeds 2048: ask the multiply for fewer a row");
     SG_REQUIRE(weight_ok(w0, cand->dtype), "a weight is not finite");
+    for (int f = 0; floors && f <= n_fields; ++f) SG_REQUIRE(!std::isinf(floors[f]), "a floor is infinite");
     for (int f = 0; f < n_fields; ++f)
         SG_TRY(check_pair_field(fields[f], cand->dtype, cand->n_rows, cand->n_cols, "a field's", "candidates", true));
     const int64_t chunks = (cand->stride + SG_PAIR_ROW_CHUNK - 1) / SG_PAIR_ROW_CHUNK;
@@ -213,7 +267,8 @@ extern "C" int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, cons
     if (cand->stride > SG_RESCORE_SHORT) SG_TRY(tmp.alloc((size_t)cand->n_rows, &d_long_rows));
     SG_HIP_TRY(hipMemsetAsync(d_buf, 0, head, ctx->stream));
     SG_TRY(by_dtype(cand->dtype, [&](auto t) {
-        return rescore<decltype(t)>(ctx, cand, w0, fields, n_fields, threshold, r.get(), (uint32_t *)d_buf, d_buf + head, d_long_rows);
+        return rescore<decltype(t)>(ctx, cand, w0, fields, n_fields, threshold, r.get(), (uint32_t *)d_buf, d_buf + head, d_long_rows,
+                                    floors);
     }));
     uint32_t status = 0;
     SG_TRY(sg_fetch(ctx, &status, d_buf, 4));   // the one read-back
@@ -230,4 +285,18 @@ extern "C" int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, cons
     }
     *out = r.release();
     return SG_OK;
+}
+
+extern "C" int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
+                               double threshold, int32_t top_n, sg_topn **out) {
+    return rescore_call(ctx, cand, w0, fields, n_fields, threshold, top_n, out, nullptr);
+}
+
+extern "C" int sg_topn_rescore_floors(sg_ctx *ctx, const sg_topn *cand, double w0, double floor0, const sg_rescore_field *fields,
+                                      const double *floors, int32_t n_fields, double threshold, int32_t top_n, sg_topn **out) {
+    SG_TRY(rescore_count_ok(n_fields));   // (before floors[] is copied: rescore_call holds the same check for both entries)
+    SG_REQUIRE(floors != nullptr, "null argument");
+    double all[SG_RESCORE_MAX_FIELDS + 1] = {floor0};
+    for (int f = 0; f < n_fields; ++f) all[f + 1] = floors[f];
+    return rescore_call(ctx, cand, w0, fields, n_fields, threshold, top_n, out, all);
 }

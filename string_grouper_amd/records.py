@@ -13,9 +13,12 @@ from .corpus import Corpus
 
 
 def match_records(fields, duplicates=None, master_id: Optional[pd.Series] = None, duplicates_id: Optional[pd.Series] = None,
-                  weights=None, candidates=None, candidate_fields=(0,), **kwargs) -> pd.DataFrame:
+                  weights=None, candidates=None, candidate_fields=(0,), field_min_similarity=None,
+                  field_similarities=False, **kwargs) -> pd.DataFrame:
     """``fields``: a list of 2 to 8 equally long Series, one a field of the records; the first finds the candidates --
     with ``candidate_fields`` (positions in ``fields``, 0 among them) the union of several fields' matches does.
+    ``field_min_similarity``: None or one floor a field (a number or None), in the order of ``fields``.
+    ``field_similarities=True``: a column ``similarity_k`` a field in the frame, k the position in ``fields``.
     ``duplicates``: None or as many Series.  Everything else as in ``Corpus.match_records``; vectoriser options in
     ``kwargs`` (``ngram_size``, ``tfidf_matrix_dtype`` ...) apply to every field."""
     if isinstance(fields, pd.Series) or not isinstance(fields, (list, tuple)) or len(fields) < 2:
@@ -27,7 +30,9 @@ def match_records(fields, duplicates=None, master_id: Optional[pd.Series] = None
         for k, series in enumerate(fields):
             corpora.append(Corpus(series, master_id=master_id if k == 0 else None, **kwargs))
         return corpora[0].match_records(corpora[1:], duplicates=duplicates, duplicates_id=duplicates_id, weights=weights,
-                                        candidates=candidates, candidate_fields=candidate_fields, **kwargs)
+                                        candidates=candidates, candidate_fields=candidate_fields,
+                                        field_min_similarity=field_min_similarity, field_similarities=field_similarities,
+                                        **kwargs)
     finally:
         for c in corpora:
             c.close()
