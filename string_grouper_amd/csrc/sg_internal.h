@@ -364,7 +364,7 @@ struct sg_postings {
     // thresholds below the pruned kernel's envelope: 14.6 -> 12.1 ms at 200 k names and 0.4 (scripts/exact_sym_probe.py).
     mutable sg_postings *exact_native = nullptr;
     // The pruned multiply's TILE-BY-TILE form of the same rows (2048-column tiles, an accumulator per column), built on demand
-    // for self-joins at thresholds below SG_ALT_FORM_BELOW (0.65): the stream form folds eight tiles onto one accumulator tile
+    // for products -- self-joins and one-sided ones -- at thresholds below SG_ALT_FORM_BELOW (0.65): the stream form folds eight tiles onto one accumulator tile
     // and its false alarms grow as the threshold falls -- 200 k names at 0.5: 9.6 ms against 5.6 (scripts/form_sweep.py).
     mutable sg_postings *alt_tile = nullptr;
     sg_csr built_from;                   // the matrix handed to the build (a copy of the struct, arrays borrowed: the caller keeps it alive -- include/sg_hip.h)

@@ -34,11 +34,13 @@
 #include <math.h>
 
 #include <memory>
-#include <optional>
 
 #include "sg_internal.h"
 
 #include "sg_k4_device.h"
+#include "sg_plan.h"
+
+static_assert(SG_PLAN_LANES == SG_TOPN_LANES, "sg_plan.h counts passes and register lists in the kernels' lanes");
 
 // "does any of the 16 bytes' worth of accumulators exceed thr": accumulators and thr are >= +0, so
 // IEEE order equals unsigned integer order and one v_max3_u32 + v_max_u32 + compare covers 4 floats
@@ -525,11 +527,7 @@ static int dispatch_spgemm(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, 
 unsigned sg_spgemm_exact_selfjoin_grid(const sg_ctx *ctx, const sg_postings *Bt) {
     if (!Bt) return (unsigned)ctx->num_cu * 2u;   // a handful of rows, if any
     // every row of the matrix: as many single-wave workgroups as the accumulator tiles leave room for, like the one-sided launch
-    const size_t lds = (size_t)(Bt->dtype == SG_F64 ? 8 : 4) << Bt->tile_log2;
-    int waves_per_cu = (int)(ctx->lds_per_cu / lds);
-    if (waves_per_cu > 32) waves_per_cu = 32;
-    if (waves_per_cu < 1) waves_per_cu = 1;
-    return (unsigned)ctx->num_cu * (unsigned)waves_per_cu;
+    return (unsigned)ctx->num_cu * (unsigned)sg_plan_waves_per_cu(ctx->lds_per_cu, Bt->dtype == SG_F64, Bt->tile_log2);
 }
 
 template <typename T, int TILE_LOG2>
@@ -584,10 +582,9 @@ static void record_bytes(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, do
 }
 
 // Three blocks of 512 left rows (start, middle, end) through the one-sided pruned kernel: what the filter passes per
-// row, extrapolated, priced against the exact kernel.  One host round trip.
-static int prune_pilot(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t stride, double threshold, double delta,
-                       bool symmetric, bool *keep_pruned) {
-    *keep_pruned = true;
+// row, extrapolated, priced against the exact kernel (sg_plan_pilot_prices).  One host round trip.
+static int prune_pilot(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, const SgPlanLeft &a, const SgPlanIndex &b,
+                       int32_t stride, double threshold, double delta, bool selfjoin, SgPilotPrices *prices) {
     const int64_t block = 512;
     TopnPtr scratch;
     SG_TRY(topn_alloc(ctx, block, Bt->n_right, stride, A->dtype, &scratch));
@@ -598,10 +595,10 @@ static int prune_pilot(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int3
     SG_TRY(tmp.alloc((size_t)8, &d_stats));
     SG_HIP_TRY(hipMemsetAsync(d_stats, 0, 8 * sizeof(unsigned long long), ctx->stream));
     const int64_t starts[3] = {0, (A->n_rows - block) / 2, A->n_rows - block};
-    for (int b = 0; b < 3; ++b) {
+    for (int k = 0; k < 3; ++k) {
         sg_csr view = *A;
         view.n_rows = block;
-        view.d_indptr = A->d_indptr + starts[b];
+        view.d_indptr = A->d_indptr + starts[k];
         view.owned = false;
         SG_HIP_TRY(hipMemsetAsync(words, 0, 8 * sizeof(uint32_t), ctx->stream));
         SG_HIP_TRY(hipMemsetAsync(scratch->d_counts, 0, sizeof(int32_t) * (size_t)block, ctx->stream));
@@ -613,20 +610,9 @@ static int prune_pilot(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int3
     SG_HIP_TRY(hipGetLastError());
     unsigned long long h[4] = {0, 0, 0, 0};
     SG_TRY(sg_fetch(ctx, h, d_stats, sizeof(h)));
-    const double s = A->dtype == SG_F64 ? 8.0 : 4.0;
-    const double rows = (double)A->n_rows, sampled = h[0] > 0 ? (double)h[0] : 1.0;
-    const double candidates = (double)h[2] * rows / sampled;
-    // fitted on scripts/family_sweep.py (profiles/r02_profile_k4p_v9b_sym.log): the pruned kernel pays per (row, tile)
-    // visit and per candidate it scores exactly (a candidate costs one walk over a right-hand row); the exact kernel
-    // pays its stream model (long lists stream at ~6 TB/s, the 3.7 TB/s of name data include its per-visit overhead)
-    // plus its own per-visit cost
-    const double row_len = Bt->n_right > 0 ? (double)Bt->nnz / (double)Bt->n_right : 0.0;
-    double ms_pruned = rows * (double)Bt->n_tiles * 2.0e-7 + candidates * 2.9e-9 * row_len;
-    if (symmetric) ms_pruned = 0.55 * ms_pruned + 0.3;   // profiles/r02_sessionM_sym_sweep.log
-    const double ms_exact = (double)h[3] * (4.0 + s) * 0.6 / 3.7e9 + rows * (double)Bt->n_tiles * 8.0e-7;
-    *keep_pruned = ms_pruned <= ms_exact;
-    ctx->pilot_ms_pruned = ms_pruned;
-    ctx->pilot_ms_exact = ms_exact;
+    *prices = sg_plan_pilot_prices(h, a, b, selfjoin);
+    ctx->pilot_ms_pruned = prices->ms_pruned;
+    ctx->pilot_ms_exact = prices->ms_exact;
     return SG_OK;
 }
 
@@ -679,143 +665,167 @@ static const sg_csr *companion_source(const sg_csr *A, const sg_postings *Bt) {
     return home->collapse ? home->collapse->unique : (Bt->built_from_valid ? &Bt->built_from : nullptr);
 }
 
-// ---- Which form runs: the exact kernel or the pruned one (sg_spgemm_pruned.hip), each one-sided or
-//      in the self-join form (A is the matrix the index was built from: every pair scored once, from the row with the larger
-//      index), and the index its launches run on
-struct SgPlan {
-    enum Form { EXACT, EXACT_SELFJOIN, PRUNED, PRUNED_SELFJOIN };
-    Form form = EXACT;
-    const sg_postings *index = nullptr;   // the caller's index, or one kept with it (sg_postings::alt_tile, exact_native)
-    int32_t stride = 0;                   // result columns per row
-    double threshold = 0.0;               // the caller's, clamped at 0
-    double delta = 0.0;                   // the pruned kernel's room below the threshold for its survivor bound
-};
+// ---- Which form runs.  The rule is sg_plan.h's; here are its inputs -- the switches, the two
+//      matrices as the numbers the rule reads -- and plan_multiply, which asks its questions in order and does the device
+//      work each answer calls for.
+static SgPlanSwitches multiply_switches(const sg_ctx *ctx) {   // unset or empty: the default
+    SgPlanSwitches sw;
+    const char *v = ctx->opt("SG_SYM");
+    sw.sym = v ? v[0] : 0;
+    sw.prune = !ctx->opt_is("SG_PRUNE", '0');
+    sw.alt_form = ctx->opt_int("SG_ALT_FORM", sw.alt_form);
+    sw.alt_form_below = ctx->opt_double("SG_ALT_FORM_BELOW", sw.alt_form_below);
+    sw.prune_max_mean_row = ctx->opt_double("SG_PRUNE_MAX_MEAN_ROW", sw.prune_max_mean_row);
+    sw.sym_min_rows = ctx->opt_int("SG_SYM_MIN_ROWS", sw.sym_min_rows);
+    sw.exact_sym_min_rows = ctx->opt_int("SG_EXACT_SYM_MIN_ROWS", sw.exact_sym_min_rows);
+    sw.exact_sym = ctx->opt_int("SG_EXACT_SYM", sw.exact_sym);
+    sw.prune_pilot = ctx->opt_int("SG_PRUNE_PILOT", sw.prune_pilot);
+    sw.exact_native = ctx->opt_int("SG_EXACT_NATIVE", sw.exact_native);
+    sw.tile_group = ctx->opt_int("SG_TILE_GROUP", sw.tile_group);
+    if ((v = ctx->opt("SG_PRUNE_MIN_THRESHOLD")) && *v) sw.prune_min_threshold = {true, atof(v)};
+    if ((v = ctx->opt("SG_PRUNE_DELTA")) && *v) sw.prune_delta = {true, atof(v)};
+    if ((v = ctx->opt("SG_WAVES_PER_CU")) && *v) sw.waves_per_cu = {true, atoi(v)};
+    return sw;
+}
 
-// row_range: the question of sg_selfjoin_range, a row range of a multi-GPU self-join -- can the pruned kernel's self-join
-// form take it on the index given, at any size and with one register list?  Anything else is not applicable there: no
-// index of the multiply's own, no exact kernel in the self-join form, no pilot.
+static void describe(const sg_csr *A, const sg_postings *Bt, SgPlanLeft *a, SgPlanIndex *b) {
+    a->n_rows = A->n_rows;
+    a->nnz = A->nnz;
+    a->f64 = A->dtype == SG_F64;
+    a->is_index_source = built_from(A, Bt);
+    b->cosine_like = Bt->cosine_like;
+    b->has_filter = Bt->d_filt != nullptr;
+    b->tile_form = Bt->tile_form;
+    b->pruned_tile = sg_pruned_supports_tile(Bt->tile_log2);
+    b->fold_log2 = Bt->fold_log2;
+    b->tile_log2 = Bt->tile_log2;
+    b->n_tiles = Bt->n_tiles;
+    b->n_right = Bt->n_right;
+    b->nnz = Bt->nnz;
+    b->n_terms = Bt->n_terms;
+    const sg_csr *from = companion_source(A, Bt);
+    b->source_rows = from ? from->n_rows : -1;
+}
+
 static int plan_multiply(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t top_n, double threshold, bool row_range,
                          SgPlan *plan) {
     *plan = SgPlan();
-    // only touched accumulators are candidates; with non-negative data (TF-IDF) touched == value > 0,
-    // so a negative threshold selects the same entries as 0
-    if (!(threshold > 0.0)) threshold = 0.0;
-    plan->threshold = threshold;
+    const SgPlanSwitches sw = multiply_switches(ctx);
+    SgPlanCall call;
+    call.threshold = plan->threshold = sg_plan_clamp_threshold(threshold);
+    call.row_range = row_range;
     plan->index = Bt;
     if (!result_stride(A->n_rows, top_n, Bt->n_right, &plan->stride))   // (row_range: not applicable, the caller's other path reports it)
         return row_range ? SG_OK : result_overflow(A->n_rows, plan->stride, "; split the left matrix");
-    const int32_t stride = plan->stride;
-    const bool prune_on = !ctx->opt_is("SG_PRUNE", '0');
-    // Threshold from which the pruned multiply takes a product: 0.45 in the stream form (below, its filter passes too much:
-    // profiles/r01_prune_tuning.log), 0.40 for a self-join that can run the tile-by-tile form on an index of its own (200 k names
-    // at 0.4: 9.9 ms against 12.1 for the exact kernel in the self-join form and 20.8 one-sided; at 0.35 the two are level:
-    // profiles/r06b_form_sweep.log).  SG_PRUNE_MIN_THRESHOLD overrides both.
-    auto prune_min_threshold = [ctx](bool tile_form) { return ctx->opt_double("SG_PRUNE_MIN_THRESHOLD", tile_form ? 0.40 : 0.45); };
+    call.stride = plan->stride;
+    SgPlanLeft a;
+    SgPlanIndex b;
+    describe(A, Bt, &a, &b);
 
-    // ---- which form of the pruned multiply?  The stream form (the index as built: 4096-column tiles folded eight to an
-    //      accumulator tile, second filter) is the fastest where most candidates are false alarms -- name-matching thresholds.
-    //      As the threshold falls, sums of eight unrelated columns cross the bar ever more often: from SG_ALT_FORM_BELOW (0.65)
-    //      down a self-join runs the tile-by-tile form on an index of its own, built once and kept with the index
-    //      (scripts/form_sweep.py, 200 k / 663 k names at 0.6: 5.4 / 31.4 ms stream, 3.4 / 24.1 ms tile by tile; at 0.8:
-    //      1.3 / 5.1 against 1.8 / 11.7).
-    //      One-sided products (master x duplicates) too: the index is then built from the matrix the caller's index was.
-    if (!row_range && Bt->cosine_like && Bt->d_filt && Bt->fold_log2 > 0 && stride <= 2 * SG_TOPN_LANES && A->n_rows > 0 &&
-        Bt->n_right > 0 && threshold < ctx->opt_double("SG_ALT_FORM_BELOW", 0.65) && threshold >= prune_min_threshold(true) &&
-        ctx->opt_int("SG_ALT_FORM", 1) != 0 && prune_on) {
-        const sg_csr *from = companion_source(A, Bt);
-        if (from && from->n_rows == Bt->n_right) SG_TRY(companion(ctx, owner(Bt), SgCompanion::alt_tile, from, &Bt));
+    // 1. the tile-by-tile form's index takes the caller's place BEFORE the envelope is judged: the threshold bar and the
+    //    delta are those of the index that will run
+    if (sg_plan_wants_tile_form(a, b, call, sw) && sg_plan_source_fits(b)) {
+        SG_TRY(companion(ctx, owner(Bt), SgCompanion::alt_tile, companion_source(A, Bt), &Bt));
+        describe(A, Bt, &a, &b);
     }
 
-    // ---- pruned multiply (sg_spgemm_pruned.hip) when both sides are cosine-like and one register list holds the row's
-    //      result, and there is room below the threshold for its survivor bound.  (top_n of 65 .. 128: the pruned kernel keeps
-    //      a row's best 64 in its register list; a row that fills the list may have more matches and is handed to the exact
-    //      kernel, which runs a pass per 64 entries -- rows_with_full_lists_kernel.)
-    bool prune = false, symmetric = false;
-    bool below = false;   // the threshold ALONE keeps the pruned kernel out: `symmetric` then says whether the EXACT kernel can
-                          // run the product in the self-join form (sg_spgemm_pruned_symmetric, exact_all)
-    if (prune_on && Bt->cosine_like && Bt->d_filt && stride <= 2 * SG_TOPN_LANES && A->n_rows > 0 && Bt->nnz > 0 &&
-        sg_pruned_supports_tile(Bt->tile_log2)) {
-        // ... and rows of more than 128 entries are beyond it altogether: where that is the AVERAGE row (strings of 130 characters
-        // and more) nearly every row would be passed on one by one -- 50 k strings of 155 entries: 68 ms that way, 37.5 the
-        // exact kernel alone (profiles/r06b_long_strings.log) -- the exact kernel takes the product as it does below the threshold
-        const bool thr_ok = threshold >= prune_min_threshold(Bt->tile_form) &&
-                            !((double)A->nnz > ctx->opt_double("SG_PRUNE_MAX_MEAN_ROW", 128.0) * (double)A->n_rows);   // below ~0.4 the filter passes too much (profiles/r01_prune_tuning.log)
-        if (thr_ok || !row_range) {
-            // tuned at 663 k: the tile-by-tile form 0.05 (profiles/r01_prune_tuning.log); the stream form, whose rounds are cheaper
-            // next to the exact scorings, 0.03 (profiles/r03_sessionG_H_delta.log: 9.76 / 9.95 / 10.10 ms at 0.03 / 0.04 / 0.05;
-            // with identical rows grouped the optimum is flat from 0.02 to 0.04: profiles/r03_sessionU_delta_freq_ab.log)
-            // (0.03 only where rows are sparse next to the vocabulary -- name data; on small vocabularies, the regime of the
-            //  pruned-or-exact pilot below, a tighter bound passes too many candidates: 0.05 as before)
-            const bool sparse_rows = A->n_rows > 0 && (double)A->nnz / (double)A->n_rows <= 0.004 * (double)Bt->n_terms;
-            double delta = ctx->opt_double("SG_PRUNE_DELTA", Bt->fold_log2 > 0 && sparse_rows ? 0.03 : 0.05);
-            if (delta > 0.5 * threshold) delta = 0.5 * threshold;
-            if (delta < 0.02) delta = 0.02;
-            plan->delta = delta;
-            bool a_ok = false;
-            float a_n2 = 0.f;
-            SG_TRY(sg_csr_props(ctx, A, &a_ok, &a_n2, nullptr));     // (the longest row is not asked for: it alone needs a look)
-            if (a_ok) {
-                // self-join: score every pair once, from the row with the larger index (sg_spgemm_pruned.hip, symmetric mode;
-                // rows the pruned kernel cannot take go through the exact kernel's self-join launch inside the same pass) --
-                // with a top_n of 65 .. 128 too, except on a row range (the pass sends a row's own matches through the pair
-                // list, whose second pass selects with two register lists) ...
-                // ... from the size at which halving the (row, tile) visits outweighs the second pass over the pair list
-                // and its host round trip: 0.58 vs 0.57 ms at 50 k rows, 0.95 vs 1.20 at 100 k, 14.0 vs 26.8 at 663 k
-                // (profiles/r02_sessionM_sym_sweep.log)
-                const int64_t sym_min_rows = ctx->opt_int("SG_SYM_MIN_ROWS", 65536);
-                symmetric = !ctx->opt_is("SG_SYM", '0') && stride <= (row_range ? 1 : 2) * SG_TOPN_LANES && built_from(A, Bt) &&
-                            (row_range || A->n_rows >= sym_min_rows || ctx->opt_is("SG_SYM", '1') ||
-                             // (the bar was set on names, 19 entries a row; longer rows cost more each and the form pays earlier --
-                             //  50 k rows of 96 entries: 10.1 ms one-sided, 6.95 in the self-join form -- and the exact kernel in
-                             //  the self-join form halves a product that is many times dearer at the same size)
-                             A->nnz >= (int64_t)19 * sym_min_rows ||
-                             (!thr_ok && A->n_rows >= (int64_t)ctx->opt_int("SG_EXACT_SYM_MIN_ROWS", 16384)));
-                prune = thr_ok;
-                below = !thr_ok;
-            }
-        }
+    // 2. inside the pruned kernel's envelope?  Then its delta, and what A is
+    bool a_cosine_like = false;
+    if (sg_plan_needs_props(a, b, call, sw)) {
+        plan->delta = sg_plan_delta(a, b, call, sw);
+        float a_n2 = 0.f;
+        SG_TRY(sg_csr_props(ctx, A, &a_cosine_like, &a_n2, nullptr));     // (the longest row is not asked for: it alone needs a look)
     }
-    const bool exact_sym_on = ctx->opt_int("SG_EXACT_SYM", 1) != 0;
-    bool exact_sym = !prune && below && symmetric && exact_sym_on;   // the EXACT kernel in the self-join form (every row through its self-join launch)
-    if (!prune) symmetric = false;
 
-    // ---- pruned or exact?  On a vocabulary that is small next to the rows (2-grams: a row holds 2 % of all terms) the
-    //      filter passes thousands of candidates per row and scoring them exactly costs more than the whole exact
-    //      multiply (119 vs 84 ms at 200 k 2-grams).  Nothing cheap predicts the candidates, so on such inputs three
-    //      blocks of 512 left rows are run through the pruned kernel first and the two costs are priced from what
-    //      they did (prune_pilot; constants fitted on the family sweep in profiles/r02_profile_k4p_v9b_sym.log).
-    if (!row_range && prune && A->n_rows >= 32768 && A->nnz > 0 && Bt->n_terms > 0 &&
-        (double)A->nnz / (double)A->n_rows > 0.004 * (double)Bt->n_terms && ctx->opt_int("SG_PRUNE_PILOT", 1) != 0) {
-        bool keep_pruned = true;
+    // 3. the form
+    plan->form = sg_plan_form(a, b, call, sw, a_cosine_like);
+
+    // 4. ... which a pilot may call off
+    if (sg_plan_pilot_due(a, b, call, sw, plan->form)) {
+        SgPilotPrices prices;
         SG_TRY(sg_csr_ensure_rows(ctx, A));     // (the pilot runs the one-sided kernel over blocks of A's rows)
-        SG_TRY(prune_pilot(ctx, A, Bt, stride, threshold, plan->delta, symmetric, &keep_pruned));
-        // (the exact kernel in the self-join form walks half the (row, tile) visits -- 200 k 2-grams: 63 ms one-sided; the
-        //  same factor the pilot grants the pruned kernel's self-join form)
-        if (symmetric && exact_sym_on && keep_pruned && ctx->pilot_ms_pruned > 0.55 * ctx->pilot_ms_exact + 0.3) keep_pruned = false;
-        if (!keep_pruned) {
-            exact_sym = symmetric && exact_sym_on;
-            prune = symmetric = false;
-        }
+        SG_TRY(prune_pilot(ctx, A, Bt, a, b, plan->stride, plan->threshold, plan->delta, plan->form == SgPlan::PRUNED_SELFJOIN, &prices));
+        plan->form = sg_plan_after_pilot(plan->form, prices, sw);
     }
 
-    const bool native_on = !row_range && ctx->opt_int("SG_EXACT_NATIVE", 1) != 0;
-    const int32_t native_tile_log2 = A->dtype == SG_F64 ? 10 : 11;
-    if (exact_sym && native_on && Bt->tile_log2 > native_tile_log2) {
-        // the exact kernel in the self-join form runs on ITS layout of the index (tile of 2048 / 1024 columns: twice the waves
-        // per CU), built once per index and kept with it -- also what the one-sided exact kernel runs on if the form is called
-        // off (pair list too small)
-        SG_TRY(companion(ctx, owner(Bt), SgCompanion::exact_native, A, &Bt));
-    } else if (!prune && !exact_sym && native_on && Bt->d_filt && Bt->nnz >= ((int64_t)1 << 20) && Bt->tile_log2 > native_tile_log2) {
-        // ... and the exact kernel ONE-SIDED (a master x duplicates product below the pruned multiply's thresholds, a self-join
-        // too small for the self-join form) on its own layout as well, where the product is worth a second index: the
-        // 4096-column tiles of the pruned multiply leave it half the waves per CU (200 k names at 0.4: 25.0 ms there, 20.8 on
-        // its own)
-        const sg_csr *from = companion_source(A, Bt);
-        if (from && from->n_rows == Bt->n_right) SG_TRY(companion(ctx, owner(Bt), SgCompanion::exact_native, from, &Bt));
+    // 5. the exact kernel's own layout of the index (as it stands after 1.)
+    const SgOwnIndex own = sg_plan_exact_own_index(a, b, call, sw, plan->form);
+    if (own != SgOwnIndex::none) {
+        SG_TRY(companion(ctx, owner(Bt), SgCompanion::exact_native, own == SgOwnIndex::from_left ? A : companion_source(A, Bt), &Bt));
+        describe(A, Bt, &a, &b);
     }
 
     plan->index = Bt;
-    plan->form = prune ? (symmetric ? SgPlan::PRUNED_SELFJOIN : SgPlan::PRUNED) : (exact_sym ? SgPlan::EXACT_SELFJOIN : SgPlan::EXACT);
+    plan->launch = sg_plan_launch_shape(a, b, plan->stride, ctx->num_cu, ctx->lds_per_cu, sw);
+    return SG_OK;
+}
+
+// What every product begins with: the driver's counters, the result's counts and the statistics words cleared by one
+// launch; then, for a plan in a self-join form, its pass (over the row range given).  *done: the pass took the product.
+static int zero_then_selfjoin_pass(sg_ctx *ctx, const sg_csr *A, const SgPlan &plan, sg_topn *r, uint32_t *counters, size_t n_counters,
+                                   size_t n_stat_words, bool *done, int64_t row_lo = 0, int64_t row_hi = -1,
+                                   int32_t **d_pairs = nullptr, int64_t *n_pairs = nullptr, int64_t row_step = 1) {
+    *done = false;
+    SG_TRY(SG_ZERO3(ctx, counters, sizeof(uint32_t) * n_counters, r->d_counts, sizeof(int32_t) * (size_t)A->n_rows,
+                    ctx->d_stat_words, n_stat_words * sizeof(int64_t)));
+    int st = SG_OK;
+    if (sg_plan_selfjoin(plan.form))
+        st = sg_spgemm_pruned_symmetric(ctx, A, plan.index, plan.stride, r, plan.threshold, plan.delta,
+                                        (unsigned long long *)(ctx->d_stat_words + 2), done, row_lo, row_hi, d_pairs, n_pairs, row_step,
+                                        plan.form == SgPlan::EXACT_SELFJOIN);
+    ctx->prune_symmetric = *done;
+    return st;
+}
+
+// The pruned kernel, one-sided, over every row; with a top_n of 65 .. 128 the rows whose list came out full join those it
+// handed over
+static int pruned_launches(sg_ctx *ctx, const sg_csr *A, const SgPlan &plan, sg_topn *r, uint32_t *row_counter, uint32_t *handed_count,
+                           uint32_t *handed_rows) {
+    SgTimer kt(ctx, SG_K_SPGEMM_KERNEL);
+    SG_TRY(sg_spgemm_pruned_launch(ctx, A, plan.index, plan.stride < SG_TOPN_LANES ? plan.stride : SG_TOPN_LANES, r, plan.threshold,
+                                   plan.delta, row_counter, handed_count, handed_rows, (unsigned long long *)(ctx->d_stat_words + 2)));
+    if (plan.stride > SG_TOPN_LANES && A->n_rows > 0) {
+        hipLaunchKernelGGL(rows_with_full_lists_kernel, dim3((unsigned)((A->n_rows + 255) / 256)), dim3(256), 0, ctx->stream,
+                           (const int32_t *)r->d_counts, A->n_rows, (int32_t)SG_TOPN_LANES, handed_count, handed_rows);
+        SG_HIP_TRY(hipGetLastError());
+    }
+    return SG_OK;
+}
+
+// Did the pruned kernel hand rows over?  Asked (four bytes read back) only where the answer saves work: the index build
+// leaves the exact kernel's postings out when the pruned multiply is expected to take everything
+// (sg_postings_ensure_full writes them on demand).  Where they exist the exact kernel's launch over the handed rows goes
+// out on the device-side count, as before the postings became lazy -- blocked and zipped multiplies enqueue without a
+// host round trip per part.
+static int rows_handed_over(sg_ctx *ctx, const sg_postings *Bt, const uint32_t *handed_count, bool *any) {
+    *any = true;
+    if (Bt->d_vals != nullptr || Bt->nnz <= 0) return SG_OK;
+    uint32_t *h_handed = (uint32_t *)(ctx->h_stat_words + 7);   // pinned
+    *h_handed = 0;
+    SG_TRY(sg_fetch(ctx, h_handed, handed_count, 4));
+    *any = *h_handed > 0;
+    return SG_OK;
+}
+
+// The exact kernel: a pass per register list of result columns, a launch per tile group; over every row, or over a
+// device-side list of rows
+static int exact_passes(sg_ctx *ctx, const sg_csr *A, const SgPlan &plan, sg_topn *r, uint32_t *counters, const uint32_t *row_list,
+                        const uint32_t *row_list_len) {
+    const sg_postings *Bt = plan.index;
+    const SgLaunchShape &sh = plan.launch;
+    if (A->n_rows <= 0) return SG_OK;
+    for (int pass = 0, li = 0; pass < sh.n_pass; ++pass) {
+        const int pass_off = pass * SG_TOPN_LANES;
+        const int keep = plan.stride - pass_off < SG_TOPN_LANES ? plan.stride - pass_off : SG_TOPN_LANES;
+        for (int g = 0; g < sh.n_groups; ++g, ++li) {
+            const int tb = g * sh.group;
+            const int te = tb + sh.group < Bt->n_tiles ? tb + sh.group : Bt->n_tiles;
+            SG_TRY(by_dtype(A->dtype, [&](auto tag) {
+                using T = decltype(tag);
+                return dispatch_spgemm<T>(ctx, A, Bt, tb, te, keep, pass_off, r, (T)plan.threshold, counters + li, sh.grid, row_list, row_list_len);
+            }));
+        }
+    }
     return SG_OK;
 }
 
@@ -823,109 +833,37 @@ static int plan_multiply(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, in
 // the pruned kernel handed over, or what a self-join pass that was called off left
 static int run_plan(sg_ctx *ctx, const sg_csr *A, const SgPlan &plan, sg_topn *r) {
     const sg_postings *Bt = plan.index;
-    const int32_t stride = plan.stride;
-    const double threshold = plan.threshold;
-    const bool prune = plan.form == SgPlan::PRUNED || plan.form == SgPlan::PRUNED_SELFJOIN;
-    const bool self_join = plan.form == SgPlan::PRUNED_SELFJOIN || plan.form == SgPlan::EXACT_SELFJOIN;
-    const size_t s = A->dtype == SG_F64 ? 8 : 4;
-
-    // tiles per launch: keep one launch's postings (~ nnz*(4+s)/n_tiles per tile) near 2 MiB so that
-    // they stay in every XCD's 4 MiB L2 while all rows stream over them
-    // Tile groups (separate launches over a few tiles each, running state kept in the output arrays)
-    // exist for right-hand sides whose postings exceed the 256 MiB Infinity Cache; below that one launch
-    // is faster (measured: 280 ms vs 415 ms at 663 k -- every launch has a tail and a state round trip).
-    int group = ctx->opt_int("SG_TILE_GROUP", 0);
-    if (group <= 0) {
-        const double bytes = (double)Bt->nnz * (double)(4 + s);
-        const double budget = 192.0 * 1024 * 1024;
-        group = bytes <= budget ? Bt->n_tiles : (int)((double)Bt->n_tiles * budget / bytes);
-        if (group < 1) group = 1;
-    }
-    if (group > Bt->n_tiles) group = Bt->n_tiles;
-    const int n_groups = (Bt->n_tiles + group - 1) / group;
-    const int n_pass = (stride + SG_TOPN_LANES - 1) / SG_TOPN_LANES;
-    const int n_launch = n_groups * n_pass;
-
-    const size_t lds = s << Bt->tile_log2;
-    int waves_per_cu = (int)(ctx->lds_per_cu / lds);
-    if (waves_per_cu > 32) waves_per_cu = 32;
-    if (waves_per_cu < 1) waves_per_cu = 1;
-    waves_per_cu = ctx->opt_int("SG_WAVES_PER_CU", waves_per_cu);
-    unsigned grid = (unsigned)ctx->num_cu * (unsigned)waves_per_cu;
-    if ((int64_t)grid > A->n_rows) grid = (unsigned)(A->n_rows > 0 ? A->n_rows : 1);
-
-    // counters: [0, n_launch] row counters of the exact launches; then the pruned kernel's row counter, the
+    const bool prune = sg_plan_pruned(plan.form);
+    // counters: [0, n_launch) row counters of the exact launches; then the pruned kernel's row counter, the
     // number of rows it handed over, and their list
-    const size_t n_words = (size_t)n_launch + 4;
+    const size_t n_launch = (size_t)plan.launch.n_launch(), n_words = n_launch + 4;
+    Scratch tmp(ctx);
     uint32_t *counters = nullptr;
-    SG_TRY(sg_alloc(ctx, n_words + (prune ? (size_t)A->n_rows : 0), &counters));
+    SG_TRY(tmp.alloc(n_words + (prune ? (size_t)A->n_rows : 0), &counters));
     uint32_t *handed_count = counters + n_launch + 2;
     uint32_t *handed_rows = counters + n_words;
-    int st = SG_OK;
-    {
-        SgTimer timer(ctx, SG_K_SPGEMM);
-        st = SG_ZERO3(ctx, counters, sizeof(uint32_t) * n_words, r->d_counts, sizeof(int32_t) * (size_t)A->n_rows,
-                      ctx->d_stat_words, 7 * sizeof(int64_t));   // ([0], [1]: written by the counting kernels at the end)
-        bool sym_done = false;
-        if (self_join && st == SG_OK)
-            st = sg_spgemm_pruned_symmetric(ctx, A, Bt, stride, r, threshold, plan.delta, (unsigned long long *)(ctx->d_stat_words + 2),
-                                            &sym_done, 0, -1, nullptr, nullptr, 1, plan.form == SgPlan::EXACT_SELFJOIN);
-        ctx->prune_symmetric = sym_done;
-        // everything below reads the rows of A itself (the self-join form read the index's copy in position order): the
-        // representatives' matrix of an index over groups is written now if it is still pending
-        if (!sym_done && st == SG_OK) st = sg_csr_ensure_rows(ctx, A);
-        if (prune && !sym_done && st == SG_OK) {
-            SgTimer kt(ctx, SG_K_SPGEMM_KERNEL);
-            st = sg_spgemm_pruned_launch(ctx, A, Bt, stride < SG_TOPN_LANES ? stride : SG_TOPN_LANES, r, threshold, plan.delta,
-                                         counters + n_launch + 1, handed_count, handed_rows,
-                                         (unsigned long long *)(ctx->d_stat_words + 2));
-            if (st == SG_OK && stride > SG_TOPN_LANES && A->n_rows > 0) {
-                hipLaunchKernelGGL(rows_with_full_lists_kernel, dim3((unsigned)((A->n_rows + 255) / 256)), dim3(256), 0, ctx->stream,
-                                   (const int32_t *)r->d_counts, A->n_rows, (int32_t)SG_TOPN_LANES, handed_count, handed_rows);
-                if (hipGetLastError() != hipSuccess) st = SG_ERR_HIP;
-            }
-        }
-        // The exact kernel: the whole product when the pruned multiply does not apply, or the rows it handed over -- whether
-        // there are any is read back (four bytes), because the index build leaves the exact kernel's postings out when
-        // the pruned multiply is expected to take everything (sg_postings_ensure_full writes them on demand).
-        bool need_exact = !prune && !sym_done;
-        if (prune && !sym_done && st == SG_OK && (Bt->d_vals != nullptr || Bt->nnz <= 0)) {
-            // the exact kernel's postings exist: its launch over the handed rows goes out on the device-side count, as
-            // before the postings became lazy -- blocked and zipped multiplies enqueue without a host round trip per part
-            need_exact = true;
-        } else if (prune && !sym_done && st == SG_OK) {
-            uint32_t *h_handed = (uint32_t *)(ctx->h_stat_words + 7);   // pinned
-            *h_handed = 0;
-            if (hipMemcpyAsync(h_handed, handed_count, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess)
-                st = SG_ERR_HIP;
-            need_exact = *h_handed > 0;
-        }
-        if (need_exact && st == SG_OK) st = sg_postings_ensure_full(ctx, Bt);
-        std::optional<SgTimer> exact_timer;   // the exact kernel's launches, when they are the whole product
-        if (!prune && !sym_done) exact_timer.emplace(ctx, SG_K_SPGEMM_KERNEL);
-        int li = 0;
-        for (int pass = 0; pass < n_pass && st == SG_OK && A->n_rows > 0 && need_exact; ++pass) {
-            const int pass_off = pass * SG_TOPN_LANES;
-            const int keep = stride - pass_off < SG_TOPN_LANES ? stride - pass_off : SG_TOPN_LANES;
-            for (int g = 0; g < n_groups && st == SG_OK; ++g, ++li) {
-                const int tb = g * group;
-                const int te = tb + group < Bt->n_tiles ? tb + group : Bt->n_tiles;
-                if (A->dtype == SG_F64)
-                    st = dispatch_spgemm<double>(ctx, A, Bt, tb, te, keep, pass_off, r, (double)threshold,
-                                                 counters + li, grid, prune ? handed_rows : nullptr, handed_count);
-                else
-                    st = dispatch_spgemm<float>(ctx, A, Bt, tb, te, keep, pass_off, r, (float)threshold,
-                                                counters + li, grid, prune ? handed_rows : nullptr, handed_count);
-            }
-        }
-        exact_timer.reset();   // stop event of the exact kernel's launches
-        if (prune && !sym_done && st == SG_OK &&   // (the self-join form has left its own count there)
-            hipMemcpyAsync(ctx->d_stat_words + 5, handed_count, 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-            st = SG_ERR_HIP;
+
+    SgTimer timer(ctx, SG_K_SPGEMM);
+    bool selfjoin_done = false;
+    SG_TRY(zero_then_selfjoin_pass(ctx, A, plan, r, counters, n_words, 7, &selfjoin_done));   // (stat words [0], [1]: written by the counting kernels at the end)
+    if (selfjoin_done) return SG_OK;
+    // everything below reads the rows of A itself (the self-join form read the index's copy in position order): the
+    // representatives' matrix of an index over groups is written now if it is still pending
+    SG_TRY(sg_csr_ensure_rows(ctx, A));
+    if (!prune) {   // the exact kernel's launches are the whole product
+        SG_TRY(sg_postings_ensure_full(ctx, Bt));
+        SgTimer kt(ctx, SG_K_SPGEMM_KERNEL);
+        return exact_passes(ctx, A, plan, r, counters, nullptr, handed_count);
     }
-    ctx->release(counters);
-    return st;
+    SG_TRY(pruned_launches(ctx, A, plan, r, counters + n_launch + 1, handed_count, handed_rows));
+    bool any_handed = false;
+    SG_TRY(rows_handed_over(ctx, Bt, handed_count, &any_handed));
+    if (any_handed) {
+        SG_TRY(sg_postings_ensure_full(ctx, Bt));
+        SG_TRY(exact_passes(ctx, A, plan, r, counters, handed_rows, handed_count));
+    }
+    SG_HIP_TRY(hipMemcpyAsync(ctx->d_stat_words + 5, handed_count, 4, hipMemcpyDeviceToDevice, ctx->stream));   // (the self-join form has left its own count there)
+    return SG_OK;
 }
 
 struct InnerMultiply {   // while it lives, sg_spgemm_topn runs for a wrapper that counts the kept entries itself
@@ -1047,26 +985,34 @@ static int spgemm_topn_left_groups(sg_ctx *ctx, const sg_csr *A, const sg_postin
     return SG_OK;
 }
 
+// Is this a product for the grouping of identical LEFT rows?  A one-sided one (A is not the matrix the index was built
+// from: a self-join groups its rows with the index), with the switches on, whose result the 32-bit result index holds
+static int left_groups_apply(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t top_n, bool *apply) {
+    *apply = false;
+    const bool off = ctx->opt_is("SG_COLLAPSE", '0') || ctx->opt_is("SG_COLLAPSE_LEFT", '0');   // (asked on every call: groups
+    if (off && A->left_groups) {   // ... and are given back when it is turned off                //  kept with A do not outlive the switch)
+        sg_collapse_free(A->left_groups);
+        A->left_groups = nullptr;
+        A->left_state = 0;
+    }
+    if (built_from(A, Bt) || off || A->left_state == 1 || A->n_cols != Bt->n_terms || A->dtype != Bt->dtype || top_n < 1) return SG_OK;
+    // (the result is one row per row of A whatever the number of groups: the 32-bit result index must hold it)
+    int32_t stride = 0;
+    if (!result_stride(A->n_rows, top_n, Bt->collapse ? Bt->collapse->n_orig : Bt->n_right, &stride))
+        return result_overflow(A->n_rows, stride, "; split the left matrix");
+    *apply = true;
+    return SG_OK;
+}
+
 extern "C" int sg_spgemm_topn(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int32_t top_n, double threshold,
                               int32_t sort, sg_topn **out) {
     SG_REQUIRE(ctx && A && Bt && out, "null argument");
-    {
-        // one-sided product (A is not the matrix the index was built from: a self-join groups its rows with the index)
-        const bool off = ctx->opt_is("SG_COLLAPSE", '0') || ctx->opt_is("SG_COLLAPSE_LEFT", '0');   // (asked on every call: groups
-        if (off && A->left_groups) {   // ... and are given back when it is turned off                //  kept with A do not outlive the switch)
-            sg_collapse_free(A->left_groups);
-            A->left_groups = nullptr;
-            A->left_state = 0;
-        }
-        if (!built_from(A, Bt) && !off && A->left_state != 1 && A->n_cols == Bt->n_terms && A->dtype == Bt->dtype && top_n >= 1) {
-            // (the result is one row per row of A whatever the number of groups: the 32-bit result index must hold it)
-            int32_t stride = 0;
-            if (!result_stride(A->n_rows, top_n, Bt->collapse ? Bt->collapse->n_orig : Bt->n_right, &stride))
-                return result_overflow(A->n_rows, stride, "; split the left matrix");
-            bool done = false;
-            SG_TRY(spgemm_topn_left_groups(ctx, A, Bt, top_n, threshold, sort, out, &done));
-            if (done) return SG_OK;
-        }
+    bool group_left = false;
+    SG_TRY(left_groups_apply(ctx, A, Bt, top_n, &group_left));
+    if (group_left) {
+        bool done = false;
+        SG_TRY(spgemm_topn_left_groups(ctx, A, Bt, top_n, threshold, sort, out, &done));
+        if (done) return SG_OK;
     }
     if (Bt->collapse) {
         SG_REQUIRE(A->n_cols == Bt->n_terms && A->dtype == Bt->dtype && top_n >= 1, "A and B differ in columns or value type, or top_n < 1");
@@ -1139,13 +1085,9 @@ extern "C" int sg_selfjoin_range(sg_ctx *ctx, const sg_csr *A, const sg_postings
     bool done = false;
     {
         SgTimer timer(ctx, SG_K_SPGEMM);
-        st = SG_ZERO2(ctx, r->d_counts, sizeof(int32_t) * (size_t)A->n_rows, ctx->d_stat_words, 8 * sizeof(int64_t));
-        if (st == SG_OK)
-            st = sg_spgemm_pruned_symmetric(ctx, A, Bt, plan.stride, r.get(), plan.threshold, plan.delta,
-                                            (unsigned long long *)(ctx->d_stat_words + 2), &done, row_lo, row_hi, d_pairs, n_pairs, row_step);
+        st = zero_then_selfjoin_pass(ctx, A, plan, r.get(), nullptr, 0, 8, &done, row_lo, row_hi, d_pairs, n_pairs, row_step);
     }
     record_bytes(ctx, A, Bt, plan.threshold);
-    ctx->prune_symmetric = done;
     if (st != SG_OK || !done) return st;   // a row for the exact kernel, or the pair list was full: the one-sided form is the caller's
     *out = r.release();
     *applicable = 1;

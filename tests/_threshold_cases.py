@@ -291,9 +291,10 @@ class Form(NamedTuple):
     max_name_thr: float = 2.0
 
 
-# The pruned kernels are reachable at every threshold used here with SG_PRUNE_MIN_THRESHOLD=0.25 (plan_multiply: the bar is a
-# tuning, 0.40 / 0.45 by default); the stream form below 0.65 needs SG_ALT_FORM=0, the tile-by-tile form from 0.65 up
-# SG_ALT_FORM_BELOW=2.  SG_PRUNE_PILOT=0: the pruned-or-exact pilot is a tuning of its own and would hand a dense case to the
+# The pruned kernels are reachable at every threshold used here with SG_PRUNE_MIN_THRESHOLD=0.25 (the rule is
+# string_grouper_amd/csrc/sg_plan.h, held at its bars by tests/test_multiply_plan_cpu.py: the bar is a tuning, 0.40 / 0.45 by
+# default -- sg_plan_min_threshold); the stream form below 0.65 needs SG_ALT_FORM=0, the tile-by-tile form from 0.65 up
+# SG_ALT_FORM_BELOW=2 (sg_plan_wants_tile_form).  SG_PRUNE_PILOT=0: the pruned-or-exact pilot is a tuning of its own and would hand a dense case to the
 # exact kernel.
 _PRUNED = {"SG_PRUNE_MIN_THRESHOLD": "0.25", "SG_PRUNE_PILOT": "0"}
 _STREAM = dict(_PRUNED, SG_ALT_FORM="0")
