@@ -62,9 +62,9 @@ const char *sg_last_error(void);
  * sg_topn_drop_columns, sg_device_upload; 7 -- sg_topn_concat_rows, sg_topn_forget, sg_topn_put_rows, sg_csr_take_rows,
  * sg_device_download; 8 -- sg_csr_row_norms, sg_csr_vectoriser_words, sg_csr_column_counts, sg_vec_reweigh; 9 --
  * sg_csr_pairs_dot; 10 -- sg_topn_rescore, sg_rescore_field; 11 -- sg_topn_union; 12 -- sg_topn_rescore_floors,
- * sg_matchlist_field_scores); a binding compares it
+ * sg_matchlist_field_scores; 13 -- sg_topn_rescore_skip_empty); a binding compares it
  * with the value it was written for right after loading the library. */
-#define SG_ABI_VERSION 12
+#define SG_ABI_VERSION 13
 int sg_abi_version(void);
 int sg_device_count(int *count);
 /* hip_stream: a hipStream_t to launch on (e.g. torch.cuda.current_stream().cuda_stream), or NULL
@@ -532,6 +532,40 @@ int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescor
  * refused the candidate. */
 int sg_topn_rescore_floors(sg_ctx *ctx, const sg_topn *cand, double w0, double floor0, const sg_rescore_field *fields,
                            const double *floors, int32_t n_fields, double threshold, int32_t top_n, sg_topn **out);
+/* sg_topn_rescore_skip_empty: sg_topn_rescore_floors with a record's EMPTY fields left out of the score.  A blank address is an
+ * empty row: its score is +0.0 and enters the weighed sum with its full weight, so two records with identical names and cities,
+ * one of them without an address, reach 0.7 at weights 0.5 / 0.3 / 0.2; record linkage expects that a field unknown for a pair
+ * takes no part in that pair and that its weight is shared among the fields that are known.  (The reference has no analogue: it
+ * matches one column of strings, string_grouper.py:55-153; its users fill blanks with "" and combine fields in pandas.)
+ *
+ * Field f = 0 .. n_fields is EMPTY FOR THE PAIR (i, j) when physical row a of A_f or physical row b of B_f has no entries:
+ * indptr[a + 1] == indptr[a], a and b from the live numbers i and j through the field's dead lists as in sg_topn_rescore.  A row
+ * that holds entries is not empty whatever its values are (stored zeros included), and even if the product is 0.  Field 0 is the
+ * field whose score cand carries: `primary` is its A, B and dead-row lists with the meaning they have in sg_topn_rescore (its
+ * weight is ignored; only the row bounds are read: nothing is merged, so no column order is looked at and no status bit is
+ * added).  primary NULL: field 0 is never empty.  floor0, floors: as in sg_topn_rescore_floors; floors NULL: no further field has
+ * a floor.  Everything is sg_topn_rescore_floors' -- s_f, W_f = (T)w_f, the order, the cut -- but:
+ *   combined score     c  = +0.0;  for f = 0 .. F, f not empty for the pair:  c  = rn(c  + rn(W_f * s_f))
+ *                      wp = +0.0;  for f = 0 .. F, f not empty for the pair:  wp = rn(wp + W_f)
+ *                      wt = +0.0;  for f = 0 .. F:                            wt = rn(wt + W_f)
+ *                      similarity = c                    when no field is empty for the pair: the bits of the call without
+ *                                                        the option
+ *                                 = rn(rn(c * wt) / wp)  when some are and wp > 0: ONE correctly rounded IEEE division in T, no
+ *                                                        reciprocal, no fused step; the product with wt keeps min_similarity's
+ *                                                        scale for weights that do not sum to 1
+ *                                 = NaN                  otherwise (every field is empty, or the weights of the others do not
+ *                                                        sum above 0): the pair is dropped
+ *   floors             a floor on a field that is empty for the pair is NOT held against it -- the primary's included when
+ *                      field 0 is empty; on the other fields floors act as before, ahead of the cut.
+ *   filter, order, cut on `similarity`: kept when similarity > (T)threshold (strict, a NaN never passes), by value descending,
+ *                      then column, the first min(top_n, S).
+ * Nothing of B_f is read for a pair whose left row is empty in field f: the whole row of candidates skips that field; a pair
+ * whose right row alone is empty is not merged either.  So, as with floors, column order is looked at for the rows that are READ.
+ * Refusals: those of sg_topn_rescore_floors, and a primary that check_pair_field refuses as an unweighed field (a null matrix,
+ * another value type, matrices that differ in columns, rows(A) - n_dead_a != R or rows(B) - n_dead_b != N; SG_ERR_BADARG). */
+int sg_topn_rescore_skip_empty(sg_ctx *ctx, const sg_topn *cand, double w0, double floor0, const sg_rescore_field *primary,
+                               const sg_rescore_field *fields, const double *floors, int32_t n_fields, double threshold,
+                               int32_t top_n, sg_topn **out);
 /* sg_topn_union: the candidates of SEVERAL fields' multiplies as one candidate result.  Two records that agree on address and
  * city but whose names fall below the candidate threshold are never compared when the names alone find the candidates; record
  * linkage takes the candidates from the union of several fields' matches instead.  (The reference has no analogue: it matches

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SG_HIP_LIB") or os.path.join(_HERE, "libsg_hip.so")
 
 SG_OK, SG_ERR_BADARG, SG_ERR_OOM, SG_ERR_OVERFLOW, SG_ERR_HIP, SG_ERR_NODEVICE, SG_ERR_UNSUPPORTED = range(7)
 SG_F32, SG_F64 = 0, 1
-ABI_VERSION = 12       # include/sg_hip.h: SG_ABI_VERSION
+ABI_VERSION = 13       # include/sg_hip.h: SG_ABI_VERSION
 SG_K_TOKENIZE, SG_K_WEIGHT, SG_K_POSTINGS, SG_K_SPGEMM, SG_K_ZIP, SG_K_VOCAB, SG_K_SPGEMM_KERNEL, SG_K_COUNT = range(8)
 KERNEL_NAMES = ("tokenize", "weight", "postings", "spgemm_topn", "zip", "vocab", "spgemm_kernel")
 
@@ -133,6 +133,8 @@ ABI = {
     "sg_topn_rescore": (C.c_int, [_P, _P, C.c_double, C.POINTER(SgRescoreField), C.c_int32, C.c_double, C.c_int32, _PP]),
     "sg_topn_rescore_floors": (C.c_int, [_P, _P, C.c_double, C.c_double, C.POINTER(SgRescoreField), C.POINTER(C.c_double), C.c_int32,
                                          C.c_double, C.c_int32, _PP]),
+    "sg_topn_rescore_skip_empty": (C.c_int, [_P, _P, C.c_double, C.c_double, C.POINTER(SgRescoreField), C.POINTER(SgRescoreField),
+                                             C.POINTER(C.c_double), C.c_int32, C.c_double, C.c_int32, _PP]),
     "sg_topn_union": (C.c_int, [_P, C.POINTER(_P), C.c_int32, C.POINTER(SgRescoreField), _PP]),
     "sg_matchlist_field_scores": (C.c_int, [_P, _P, C.POINTER(SgRescoreField), C.c_int32, _P]),
     "sg_csr_row_norms": (C.c_int, [_P, _PP]),
@@ -876,7 +878,8 @@ class Context:
         d_rows = _dev_ptr(d_rows)
         check(lib().sg_topn_put_rows(self.h, res.h, C.c_void_p(d_rows) if d_rows else None, int(n_rows), src.h))
 
-    def topn_rescore(self, cand: TopN, w0: float, fields, threshold: float, top_n: int, floors=None) -> TopN:
+    def topn_rescore(self, cand: TopN, w0: float, fields, threshold: float, top_n: int, floors=None, skip_empty: bool = False,
+                     primary=None) -> TopN:
         """The candidates of ``cand`` scored on further fields, weighed, filtered, re-ordered and cut, on the device
         (include/sg_hip.h: sg_topn_rescore).  ``fields``: 1 to 7 of ``(A: Csr, B: Csr, weight, dead_a: DeviceInts | None,
         dead_b: DeviceInts | None)`` -- the left and right records' rows of the field (the same handle for a self-join), and
@@ -887,17 +890,36 @@ class Context:
 
         ``floors``: None -- sg_topn_rescore -- or one entry a field, the candidates' own score first (``1 + len(fields)`` of
         them), each None (no floor) or a number: a candidate is kept only when also ``s_f > floor_f`` on every field that has
-        one, before the cut (sg_topn_rescore_floors).  An infinite floor: ValueError."""
+        one, before the cut (sg_topn_rescore_floors).  An infinite floor: ValueError.
+
+        ``skip_empty``: a field that is empty for a pair -- the physical row of either side has no entries -- is left out of
+        that pair's sum, its weight is shared among the others (``c * wt / wp``, every step rounded on its own, one division),
+        its floor is not held against the pair, and a pair all of whose fields are empty is dropped
+        (sg_topn_rescore_skip_empty).  ``primary``: ``(A, B, dead_a, dead_b)`` of the field whose score ``cand`` carries, as
+        ``topn_union`` takes it -- only its row bounds are read; None: that field is never empty.  Without ``skip_empty`` a
+        ``primary`` is a ValueError."""
+        if primary is not None and not skip_empty:
+            raise ValueError("a primary field is read with skip_empty alone")
         fields = list(fields)
         arr = (SgRescoreField * max(len(fields), 1))()
         for k, field in enumerate(fields):
             arr[k] = _rescore_field(*field)
         out = C.c_void_p()
+        if skip_empty:
+            floors = [None] * (len(fields) + 1) if floors is None else list(floors)
         if floors is not None:
             floors = [float("nan") if m is None else float(m) for m in floors]
             if len(floors) != len(fields) + 1:
                 raise ValueError(f"{len(floors)} floors for {len(fields) + 1} fields: one a field is expected, the candidates' own first")
             rest = (C.c_double * max(len(fields), 1))(*floors[1:])
+            if skip_empty:
+                first = None
+                if primary is not None:
+                    A, B, dead_a, dead_b = primary
+                    first = C.byref(_rescore_field(A, B, 1.0, dead_a, dead_b))
+                check(lib().sg_topn_rescore_skip_empty(self.h, cand.h, float(w0), floors[0], first, arr, rest, len(fields),
+                                                       float(threshold), int(top_n), C.byref(out)))
+                return TopN(self, out)
             check(lib().sg_topn_rescore_floors(self.h, cand.h, float(w0), floors[0], arr, rest, len(fields), float(threshold),
                                                int(top_n), C.byref(out)))
             return TopN(self, out)

@@ -150,15 +150,16 @@ class _RecordGrouper(_CorpusGrouper):
     list -- the frames, the groups -- is StringGrouper's own."""
 
     def __init__(self, corpus: "Corpus", others, weights, cand, dup_fields, master, duplicates=None, master_id=None,
-                 duplicates_id=None, candidate_fields=(0,), floors=None, field_scores=False, **kwargs):
+                 duplicates_id=None, candidate_fields=(0,), floors=None, field_scores=False, skip_empty=False, **kwargs):
         """``cand``: (max_n_matches, min_similarity) of the candidates -- with ``candidate_fields`` other than ``(0,)`` a list
         of them, one a candidate field (CorpusEngine.corpus_records_union_topn).  ``floors``: None or one entry a field, each
-        None or a number; ``field_scores``: the list gets a column ``similarity_k`` a field.  The engine gets either keyword
-        only when it is set."""
+        None or a number; ``field_scores``: the list gets a column ``similarity_k`` a field; ``skip_empty``: a field that is
+        empty for a pair takes no part in it.  The engine gets each keyword only when it is set."""
         self._others, self._weights, self._cand, self._dup_fields = others, weights, cand, dup_fields
         self._candidate_fields = tuple(candidate_fields)
         self._floors = floors
         self._field_scores = bool(field_scores)
+        self._skip_empty = bool(skip_empty)
         self._planes = None
         super().__init__(corpus, master, duplicates, master_id, duplicates_id, **kwargs)
 
@@ -168,7 +169,8 @@ class _RecordGrouper(_CorpusGrouper):
     def _new_options(self) -> dict:
         """The engine's keywords that are passed only when they are set, so that engine doubles without them keep working."""
         return {**({} if self._floors is None else {'floors': self._floors}),
-                **({'field_scores': True} if self._field_scores else {})}
+                **({'field_scores': True} if self._field_scores else {}),
+                **({'skip_empty': True} if self._skip_empty else {})}
 
     def _engine_match_list(self, eng, master_matrix, duplicate_matrix, fix: bool):
         out = self._engine_record_list(eng, master_matrix, duplicate_matrix, fix)
@@ -483,8 +485,8 @@ class Corpus:
         ``pair_calls`` / ``pairs_scored`` (calls of ``pair_similarities`` that reached the device, and their pairs);
         ``record_calls`` (calls of ``match_records`` / ``group_similar_records`` this corpus took part in, as the one that
         finds the candidates or as a further field), ``record_union_calls`` (those of them with several
-        ``candidate_fields``, counted on the corpora that found candidates) and ``record_floor_calls`` (those of them with a
-        ``field_min_similarity``)."""
+        ``candidate_fields``, counted on the corpora that found candidates), ``record_floor_calls`` (those of them with a
+        ``field_min_similarity``) and ``record_skip_empty_calls`` (those of them with ``empty_fields="skip"``)."""
         return dict(self._live().stats)
 
     def _rows_of(self, series, made):
@@ -580,7 +582,7 @@ class Corpus:
 
     # ------------------------------------------------------------------ records of several fields
     def _record_call(self, others, duplicates, duplicates_id, weights, candidates, kwargs, finish, candidate_fields=(0,),
-                     field_min_similarity=None, field_similarities=False):
+                     field_min_similarity=None, field_similarities=False, empty_fields="zero"):
         """The checks of ``match_records`` / ``group_similar_records``, then the call."""
         state = self._live()
         self._same_engine()
@@ -685,6 +687,16 @@ class Corpus:
             if not all("field_scores" in inspect.signature(getattr(self._engine, r)).parameters for r in routes):
                 raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} gives no "
                                           f"field_similarities")
+        # empty_fields: "zero" -- the call as it always was -- or "skip"
+        if not isinstance(empty_fields, str):
+            raise TypeError(f"empty_fields={empty_fields!r}: 'zero' or 'skip' is expected")
+        if empty_fields not in ("zero", "skip"):
+            raise ValueError(f"empty_fields={empty_fields!r}: 'zero' or 'skip' is expected")
+        if empty_fields == "skip":
+            routes = ("corpus_records_topn",) if candidate_fields == (0,) else ("corpus_records_topn", "corpus_records_union_topn")
+            if not all("skip_empty" in inspect.signature(getattr(self._engine, r)).parameters for r in routes):
+                raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} takes no "
+                                          f"empty_fields='skip'")
         # candidates: the two options of a candidate field's multiply -- one dict for every candidate field, or one a field
         candidates = {} if candidates is None else candidates
         if isinstance(candidates, list) and all(isinstance(c, dict) for c in candidates):
@@ -717,7 +729,8 @@ class Corpus:
                              f"record that can be united and rescored")
         g = _RecordGrouper(self, others, weights, cand[0] if candidate_fields == (0,) else cand, dup_fields, self.master,
                            None if duplicates is None else duplicates[0], self.master_id, duplicates_id,
-                           candidate_fields=candidate_fields, floors=floors, field_scores=field_similarities, **options)
+                           candidate_fields=candidate_fields, floors=floors, field_scores=field_similarities,
+                           skip_empty=empty_fields == "skip", **options)
         for o in others:
             o._join_pending()
         try:
@@ -726,7 +739,8 @@ class Corpus:
             g._release()
 
     def match_records(self, others, duplicates=None, duplicates_id: Optional[pd.Series] = None, weights=None, candidates=None,
-                      candidate_fields=(0,), field_min_similarity=None, field_similarities=False, **kwargs) -> pd.DataFrame:
+                      candidate_fields=(0,), field_min_similarity=None, field_similarities=False, empty_fields="zero",
+                      **kwargs) -> pd.DataFrame:
         """Match RECORDS of several fields.  This corpus holds one field of every record (say the names), ``others`` -- a list
         of 1 to 7 ``Corpus`` objects -- the further fields (addresses, cities ...): row p of every corpus is record p, which is
         the caller's duty (append to and remove from all of them together; different lengths: ValueError).  The call is
@@ -789,14 +803,40 @@ class Corpus:
         ``force_symmetries`` the score of the pair they name.  The rows ``include_zeroes`` adds carry 0.0.  The list is scored
         where it lies on the device, before it is freed or handed to the group kernels; the planes are a second read-back
         after the list's own (``stats['record_field_score_calls']`` counts the call): no position list goes up, no label is
-        translated, whatever the index is.  Anything but a bool: TypeError."""
+        translated, whatever the index is.  Anything but a bool: TypeError.
+
+        ``empty_fields``: ``"zero"`` (the default: the call described above, launch for launch) or ``"skip"`` (anything but a
+        str: TypeError; another string: ValueError).  Real records have blanks, and a blank field scores 0 and enters the sum
+        with its full weight: two records with identical names and cities, one of them without an address, reach 0.7 at
+        weights 0.5 / 0.3 / 0.2.  With ``"skip"`` a field that is EMPTY for a pair takes no part in that pair and its weight
+        is shared among the fields that are known.  A field is empty for a pair when the string of either record is empty
+        for that field's corpus: a string with no n-gram that the corpus knows -- ``""``, a string shorter than
+        ``ngram_size`` after the regex, and in ``duplicates`` a string made only of n-grams the corpus has never seen.  This
+        holds for this corpus's field as well.  Step 3 becomes, with ``W`` the weights in the corpus's dtype::
+
+            c  = sum of W[f] * s_f  over the fields that are not empty for the pair   (in field order, as in step 3)
+            wp = sum of W[f]        over the same fields
+            wt = sum of W[f]        over all fields
+            similarity = c               when no field is empty for the pair: bit for bit the similarity of "zero"
+                       = (c * wt) / wp   when some are: every step rounded on its own, one division
+                       dropped           when every field is empty
+
+        so on records without blanks the option changes no bit, and ``min_similarity`` keeps the scale it has for the
+        weights given.  A floor of ``field_min_similarity`` on a field that is empty for the pair is not held against it
+        (this corpus's floor included when its field is empty); on the other fields floors act as before.  The filter, the
+        order and the cut act on ``similarity`` as they always did.  The columns of ``field_similarities`` are unchanged: an
+        empty field shows its product, 0.0 -- so ``acc = acc + W[f] * similarity_f`` recombines to ``similarity`` only on rows
+        without an empty field.  In a self-join a record still matches itself with 1, also a record all of whose fields are
+        blank, and ``force_symmetries`` still gives a symmetric list.  All of it is decided on the device
+        (``stats['record_skip_empty_calls']`` counts the call on every corpus that took part); nothing of a field's right
+        rows is read for a record whose own field is blank."""
         return self._record_call(others, duplicates, duplicates_id, weights, candidates, kwargs, lambda g: g.fit().get_matches(),
-                                 candidate_fields, field_min_similarity, field_similarities)
+                                 candidate_fields, field_min_similarity, field_similarities, empty_fields)
 
     def group_similar_records(self, others, weights=None, candidates=None, candidate_fields=(0,), field_min_similarity=None,
-                              **kwargs):
+                              empty_fields="zero", **kwargs):
         """For every record the representative of its group of similar records: ``group_similar_strings(corpus.master,
         corpus.master_id)`` over the match list of ``match_records(others, weights=..., candidates=..., candidate_fields=...,
-        field_min_similarity=...)``."""
+        field_min_similarity=..., empty_fields=...)``."""
         return self._record_call(others, None, None, weights, candidates, kwargs, lambda g: g.fit().get_groups(), candidate_fields,
-                                 field_min_similarity)
+                                 field_min_similarity, False, empty_fields)

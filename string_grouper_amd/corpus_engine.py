@@ -74,7 +74,7 @@ class CorpusState:
                       "self_join_full": 0, "self_join_served": 0, "self_join_append_updates": 0,
                       "self_join_remove_updates": 0, "self_join_rows_refilled": 0, "idf_refits": 0, "pair_calls": 0,
                       "pairs_scored": 0, "record_calls": 0, "record_union_calls": 0,
-                      "record_floor_calls": 0, "record_field_score_calls": 0}
+                      "record_floor_calls": 0, "record_field_score_calls": 0, "record_skip_empty_calls": 0}
         if base is not None:
             self.set_segments(CorpusSegment(base), None)
 
@@ -516,7 +516,7 @@ class CorpusEngine:
     def corpus_records_topn(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
                             B_fields: Optional[List[DeviceMatrix]], weights, cand_top_n: int, cand_threshold: float,
                             top_n: int, threshold: float, self_join_fix: bool, keep_on_device: bool = False, floors=None,
-                            field_scores: bool = False):
+                            field_scores: bool = False, skip_empty: bool = False):
         """The match list of RECORDS: the corpus ``state`` finds the candidates, the corpora ``others`` -- row p of every
         corpus is record p -- score them on their fields, and the weighed sum is filtered, ordered and cut on the device
         (sg_topn_rescore) before the list is built (K6).  Returns what ``match_list`` returns.
@@ -537,16 +537,21 @@ class CorpusEngine:
         dtype: plane k holds, for every entry of the list in list order, the pair's score on field k (0: ``state``) with the
         bits ``corpus_pairs`` of that field returns -- the diagonal and the mirrored entries of ``self_join_fix`` included,
         which carry the field's own product.  The list is scored where it lies, after K6 and before it is freed or kept
-        (sg_matchlist_field_scores); the fields' rows and dead lists are the ones the rescoring read."""
+        (sg_matchlist_field_scores); the fields' rows and dead lists are the ones the rescoring read.
+
+        ``skip_empty``: a field that is empty for a pair -- the row of either record has no entries, ``state``'s field
+        included -- is left out of the pair's sum, its weight is shared among the others and its floor is not held; a pair
+        all of whose fields are empty is dropped (sg_topn_rescore_skip_empty, with ``state``'s rows as its primary).  The
+        planes of ``field_scores`` are unchanged by it."""
         return self._records_topn(state, others, B, B_fields, weights, None, [(cand_top_n, cand_threshold)], top_n, threshold,
-                                  self_join_fix, keep_on_device, floors, field_scores)
+                                  self_join_fix, keep_on_device, floors, field_scores, skip_empty)
 
     MAX_UNION_CANDIDATES = 2048               # sg_topn_union: the candidate fields' strides together
 
     def corpus_records_union_topn(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
                                   B_fields: Optional[List[DeviceMatrix]], weights, candidate_fields, cands, top_n: int,
                                   threshold: float, self_join_fix: bool, keep_on_device: bool = False, floors=None,
-                                  field_scores: bool = False):
+                                  field_scores: bool = False, skip_empty: bool = False):
         """``corpus_records_topn`` with candidates from SEVERAL fields: ``candidate_fields`` -- ascending positions, 0 the corpus
         ``state``, k ``others[k - 1]``, 0 always among them -- each find candidates with a multiply of their own at
         ``cands[.] = (cand_top_n, cand_threshold)``, the results are united on the device (sg_topn_union: a record's distinct
@@ -559,14 +564,15 @@ class CorpusEngine:
         read where it lies, as in ``corpus_records_topn``: never compacted, never indexed.  The rows and the dead lists the
         union and the rescoring read are taken AFTER the multiplies, which may have compacted a candidate corpus; results number
         the live rows, which no compaction changes.  ``floors`` as in ``corpus_records_topn``: the primary's floor is held
-        against the score the united candidate carries, the multiply's or the one the union filled in; ``field_scores`` as
-        there too."""
+        against the score the united candidate carries, the multiply's or the one the union filled in; ``field_scores`` and
+        ``skip_empty`` as there too (a candidate that a further field found may have an empty primary field)."""
         return self._records_topn(state, others, B, B_fields, weights, candidate_fields, cands, top_n, threshold,
-                                  self_join_fix, keep_on_device, floors, field_scores)
+                                  self_join_fix, keep_on_device, floors, field_scores, skip_empty)
 
     def _records_topn(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
                       B_fields: Optional[List[DeviceMatrix]], weights, candidate_fields, cands, top_n: int, threshold: float,
-                      self_join_fix: bool, keep_on_device: bool, floors=None, field_scores: bool = False):
+                      self_join_fix: bool, keep_on_device: bool, floors=None, field_scores: bool = False,
+                      skip_empty: bool = False):
         """The body of both record calls: validate, find the candidates -- ``candidate_fields`` None: the primary field's
         multiply at ``cands[0]``; else one multiply a candidate field and their union --, take the fields' rows and dead
         lists, rescore, count, build the list and, with ``field_scores``, score it field by field."""
@@ -619,7 +625,12 @@ class CorpusEngine:
                         rows, right, _, dead_a, dead_b = field(0)
                         cand = before.own(self.ctx.topn_union(parts, (rows, right, dead_a, dead_b)))
                 fields = [field(k) for k in range(1, len(states))]
-                if floors is None:
+                if skip_empty:
+                    rows, right, _, dead_a, dead_b = field(0)
+                    res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n,
+                                                      floors=None if floors is None else list(floors), skip_empty=True,
+                                                      primary=(rows, right, dead_a, dead_b)))
+                elif floors is None:
                     res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n))
                 else:
                     res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n, floors=list(floors)))
@@ -629,6 +640,8 @@ class CorpusEngine:
                     st.stats["record_floor_calls"] += 1
                 if field_scores:
                     st.stats["record_field_score_calls"] += 1
+                if skip_empty:
+                    st.stats["record_skip_empty_calls"] += 1
             for f in candidate_fields or ():
                 states[f].stats["record_union_calls"] += 1
             # (_match_list_from_topn frees the result once the list is built; if it raises before that, the scope does)

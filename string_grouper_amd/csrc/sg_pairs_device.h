@@ -129,6 +129,19 @@ __device__ __forceinline__ void pair_left_row(const PairField<T> &F, int64_t liv
     a0 = F.a_indptr[a], a1 = F.a_indptr[a + 1];
     if (F.check_a && row_not_ascending(F.a_indices, a0, a1, l)) atomicOr(status, bit);
 }
+// (pair_score's two halves on their own, for a caller that asks whether the row of B holds entries before it merges:
+// pair_right_row finds the entries [b0, b1) of the live row j, pair_score_rows looks at their order and merges)
+template <typename T>
+__device__ __forceinline__ void pair_right_row(const PairField<T> &F, int64_t j, int64_t &b0, int64_t &b1) {
+    const int64_t b = physical_row(j, F.dead_b, F.n_dead_b);
+    b0 = F.b_indptr[b], b1 = F.b_indptr[b + 1];
+}
+template <typename T>
+__device__ __forceinline__ T pair_score_rows(const PairField<T> &F, int64_t a0, int64_t a1, int64_t b0, int64_t b1, int l,
+                                             int group_shift, uint32_t *status, uint32_t bit) {
+    if (F.check_b && row_not_ascending(F.b_indices, b0, b1, l)) atomicOr(status, bit);
+    return pair_rows_dot<T>(F.a_indices, F.a_data, a0, a1, F.b_indices, F.b_data, b0, b1, l, group_shift);
+}
 template <typename T>
 __device__ __forceinline__ T pair_score(const PairField<T> &F, int64_t a0, int64_t a1, int64_t j, int l, int group_shift,
                                         uint32_t *status, uint32_t bit) {

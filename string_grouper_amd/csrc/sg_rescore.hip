@@ -15,6 +15,9 @@
 //
 // sg_topn_rescore_floors: the same two launches with a floor a field in the filter (s_f > m_f, before the cut).  The scoring kernel
 // has a second instantiation for it (FLOORS, below); the select kernels are the same ones: a refused candidate's c is a NaN.
+//
+// sg_topn_rescore_skip_empty: the same launches again, with a field that is EMPTY for a pair -- a row without entries on either
+// side -- left out of the pair's sum and its weight shared among the others (SKIP, below: a third instantiation).
 #include "sg_pairs_device.h"
 
 #define SG_RESCORE_BLOCK 256
@@ -40,17 +43,53 @@ struct RescoreFloors {
 };
 struct NoFloors {};
 
+// Empty fields (sg_topn_rescore_skip_empty): field f is empty for the pair (i, j) when the physical row of A_f or of B_f has no
+// entries.  `floors`: as above (has == 0: none).  The primary's row bounds and dead lists say whether field 0 -- the score the
+// candidate carries -- is empty (a_indptr null: never); nothing else of the primary is read.  `empty`: a byte a candidate, the
+// candidates' shape: bit 0 field 0, bit f + 1 further field f, set where the RIGHT row is the empty one (a left row that is
+// empty skips the field for the whole row of candidates: the group keeps those bits itself).
+template <typename T>
+struct RescoreSkip {
+    RescoreFloors<T> floors;
+    const int64_t *a_indptr, *b_indptr;
+    const int32_t *dead_a, *dead_b;
+    int32_t n_dead_a, n_dead_b;
+    uint8_t *empty;
+};
+template <typename T, bool FLOORS, bool SKIP>
+using RescoreExtra = std::conditional_t<SKIP, RescoreSkip<T>, std::conditional_t<FLOORS, RescoreFloors<T>, NoFloors>>;
+__device__ __forceinline__ const NoFloors &floors_of(const NoFloors &x) { return x; }
+template <typename T>
+__device__ __forceinline__ const RescoreFloors<T> &floors_of(const RescoreFloors<T> &x) { return x; }
+template <typename T>
+__device__ __forceinline__ const RescoreFloors<T> &floors_of(const RescoreSkip<T> &x) { return x.floors; }
+
+// one correctly rounded IEEE division in T: no reciprocal, no fused step (the project's flags compile `/` to the
+// v_div_scale / v_div_fmas / v_div_fixup sequence in both types)
+template <typename T>
+__device__ __forceinline__ T div_rn(T a, T b) { return a / b; }
+
 // FLOORS: the group follows the candidates a floor has refused in a mask of its own -- SG_PAIR_ROW_CHUNK = 64 entries at most,
 // a bit an entry, the same value in every lane because pair_score returns the score in every lane.  A refused candidate gets a
 // NaN as its c (the select kernels pass over a NaN) and is skipped on every later field: no row of B_f' is read for it, and
 // whether a merge runs never waits for a load of comb.  Only a floor sets a bit: a NaN that the data makes walks on, as without
 // floors.  So the column order of a matrix that is not known to be sorted is looked at for the rows that are READ: a row that
 // only refused candidates name is not.
-template <typename T, bool FLOORS>
+//
+// SKIP (with FLOORS): three steps.  Field 0 first, for every candidate of the group: is it empty for the pair (the primary's row
+// bounds), else the primary's floor, and c starts as +0.0 or rn(+0.0 + rn(W_0 * s_0)).  Then the fields as above, but a left row
+// without entries skips the field for the whole row of candidates -- nothing of B_f is read -- and a right row without entries
+// skips it for the candidate, before any floor of that field and without a merge; lane 0 notes it in the candidate's byte.  At
+// the end lane 0 rescales every candidate that has an empty field: wp from the weights of the fields that are NOT empty, in
+// ascending field order (the loops are unrolled: the byte selects, nothing in a register is indexed by it), then
+// rn(rn(c * wt) / wp), or a NaN when wp is not above 0 (every field empty).  A candidate without an empty field keeps c's bits.
+template <typename T, bool FLOORS, bool SKIP = false>
 __global__ void __launch_bounds__(SG_PAIR_BLOCK) rescore_score_kernel(
     const int32_t *__restrict__ cols, const T *__restrict__ vals, const int32_t *__restrict__ counts, int64_t n_rows,
     int64_t n_cols, int32_t stride, int32_t chunks, T w0, RescoreFields<T> fields, int32_t n_fields, uint32_t *status,
-    T *__restrict__ comb, std::conditional_t<FLOORS, RescoreFloors<T>, NoFloors> floors) {
+    T *__restrict__ comb, RescoreExtra<T, FLOORS, SKIP> extra) {
+    static_assert(FLOORS || !SKIP, "SKIP carries the floors' mask");
+    const auto &floors = floors_of(extra);
     constexpr int G = SG_PAIR_LANES;
     const int l = threadIdx.x & (G - 1);
     const int group_shift = threadIdx.x & (SG_WAVE - 1) & ~(G - 1);   // the group's first lane in its wave
@@ -63,10 +102,49 @@ __global__ void __launch_bounds__(SG_PAIR_BLOCK) rescore_score_kernel(
     if (e0 >= e1) return;
     const int64_t base = row * (int64_t)stride;
     uint64_t failed = 0;   // (FLOORS) bit e - e0: a floor has refused entry e
+    uint32_t left_empty = 0;   // (SKIP) bit 0: the primary's left row has no entries; bit f + 1: further field f's
+    if constexpr (SKIP) {
+        if (extra.a_indptr) {
+            const int64_t a = physical_row(row, extra.dead_a, extra.n_dead_a);
+            if (extra.a_indptr[a + 1] == extra.a_indptr[a]) left_empty = 1u;
+        }
+        for (int32_t e = e0; e < e1; ++e) {   // (every lane reads the same words: `failed` is the group's)
+            const int64_t j = cols[base + e];
+            if (j < 0 || j >= n_cols) {   // nothing of a field is read for it; the call is refused
+                failed |= (uint64_t)1 << (e - e0);
+                if (l == 0) {
+                    atomicOr(status, SG_RESCORE_BAD_COLUMN);
+                    comb[base + e] = (T)NAN;
+                }
+                continue;
+            }
+            bool right_empty = false;
+            if (!left_empty && extra.b_indptr) {
+                const int64_t b = physical_row(j, extra.dead_b, extra.n_dead_b);
+                right_empty = extra.b_indptr[b + 1] == extra.b_indptr[b];
+            }
+            const bool empty0 = left_empty || right_empty;
+            const T s0 = vals[base + e];
+            if (!empty0 && (floors.has & 1u) && !(s0 > floors.m[0])) {   // the primary's floor: not held where field 0 is empty
+                failed |= (uint64_t)1 << (e - e0);
+                if (l == 0) comb[base + e] = (T)NAN;
+                continue;
+            }
+            if (l == 0) {
+                comb[base + e] = empty0 ? (T)0 : add_rn<T>((T)0, mul_rn<T>(w0, s0));
+                extra.empty[base + e] = right_empty ? 1 : 0;
+            }
+        }
+    }
     for (int f = 0; f < n_fields; ++f) {
         const PairField<T> &F = fields.f[f];
         int64_t a0, a1;
         pair_left_row<T>(F, row, l, status, 2u << (2 * f), a0, a1);
+        if constexpr (SKIP)
+            if (a0 == a1) {   // empty on the left: the whole row of candidates skips the field
+                left_empty |= 2u << f;
+                continue;
+            }
         for (int32_t e = e0; e < e1; ++e) {
             if constexpr (FLOORS)
                 if ((failed >> (e - e0)) & 1) continue;
@@ -78,14 +156,25 @@ __global__ void __launch_bounds__(SG_PAIR_BLOCK) rescore_score_kernel(
                 }
                 continue;
             }
-            if constexpr (FLOORS) {   // the primary's floor, before anything of a field is read (every lane reads the score)
+            if constexpr (FLOORS && !SKIP) {   // the primary's floor, before anything of a field is read (every lane reads the score)
                 if (f == 0 && (floors.has & 1u) && !(vals[base + e] > floors.m[0])) {
                     failed |= (uint64_t)1 << (e - e0);
                     if (l == 0) comb[base + e] = (T)NAN;
                     continue;
                 }
             }
-            const T s = pair_score<T>(F, a0, a1, j, l, group_shift, status, 4u << (2 * f));
+            T s;
+            if constexpr (SKIP) {
+                int64_t b0, b1;
+                pair_right_row<T>(F, j, b0, b1);
+                if (b0 == b1) {   // empty on the right: no floor of the field is held, nothing is merged
+                    if (l == 0) extra.empty[base + e] |= (uint8_t)(2u << f);
+                    continue;
+                }
+                s = pair_score_rows<T>(F, a0, a1, b0, b1, l, group_shift, status, 4u << (2 * f));
+            } else {
+                s = pair_score<T>(F, a0, a1, j, l, group_shift, status, 4u << (2 * f));
+            }
             if constexpr (FLOORS) {
                 if (((floors.has >> (f + 1)) & 1u) && !(s > floors.m[f + 1])) {
                     failed |= (uint64_t)1 << (e - e0);
@@ -94,9 +183,27 @@ __global__ void __launch_bounds__(SG_PAIR_BLOCK) rescore_score_kernel(
                 }
             }
             if (l == 0) {   // (lane 0 alone reads and writes the candidate's c: its own stores, in program order)
-                const T c = f == 0 ? add_rn<T>((T)0, mul_rn<T>(w0, vals[base + e])) : comb[base + e];
+                const T c = !SKIP && f == 0 ? add_rn<T>((T)0, mul_rn<T>(w0, vals[base + e])) : comb[base + e];
                 comb[base + e] = add_rn<T>(c, mul_rn<T>(F.w, s));
             }
+        }
+    }
+    if constexpr (SKIP) {
+        if (l != 0) return;   // (no lane of the group shuffles from here on)
+        T wt = add_rn<T>((T)0, w0);
+#pragma unroll
+        for (int f = 0; f < SG_RESCORE_MAX_FIELDS; ++f)
+            if (f < n_fields) wt = add_rn<T>(wt, fields.f[f].w);
+        for (int32_t e = e0; e < e1; ++e) {
+            if ((failed >> (e - e0)) & 1) continue;
+            const uint32_t empty = left_empty | extra.empty[base + e];
+            if (!empty) continue;   // c as it is, to the bit
+            T wp = (T)0;
+            if (!(empty & 1u)) wp = add_rn<T>(wp, w0);
+#pragma unroll
+            for (int f = 0; f < SG_RESCORE_MAX_FIELDS; ++f)
+                if (f < n_fields && !((empty >> (f + 1)) & 1u)) wp = add_rn<T>(wp, fields.f[f].w);
+            comb[base + e] = wp > (T)0 ? div_rn<T>(mul_rn<T>(comb[base + e], wt), wp) : (T)NAN;
         }
     }
 }
@@ -194,22 +301,35 @@ __global__ void __launch_bounds__(SG_RESCORE_BLOCK) rescore_select_block_kernel(
 template <typename T>
 static int rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
                    double threshold, sg_topn *r, uint32_t *d_status, void *d_comb, int32_t *d_long_rows,
-                   const double *floors) {   // floors: null (sg_topn_rescore), or n_fields + 1 of them, the primary's first
+                   const double *floors,   // floors: null (sg_topn_rescore), or n_fields + 1 of them, the primary's first
+                   bool skip, const sg_rescore_field *primary, uint8_t *d_empty) {   // skip: sg_topn_rescore_skip_empty
     RescoreFields<T> dev;
     memset(&dev, 0, sizeof(dev));
     for (int f = 0; f < n_fields; ++f) dev.f[f] = make_pair_field<T>(fields[f]);
     constexpr int per_block = SG_RESCORE_BLOCK / SG_PAIR_LANES;
     const int32_t chunks = (cand->stride + SG_PAIR_ROW_CHUNK - 1) / SG_PAIR_ROW_CHUNK;
     const dim3 grid_score((unsigned)pair_blocks(cand->n_rows * chunks));
-    if (!floors) {
+    RescoreFloors<T> m;
+    memset(&m, 0, sizeof(m));
+    for (int f = 0; floors && f <= n_fields; ++f)
+        if (!std::isnan(floors[f])) m.m[f] = (T)floors[f], m.has |= 1u << f;
+    if (skip) {
+        RescoreSkip<T> x;
+        memset(&x, 0, sizeof(x));
+        x.floors = m, x.empty = d_empty;
+        if (primary) {
+            x.a_indptr = primary->A->d_indptr, x.b_indptr = primary->B->d_indptr;
+            x.dead_a = primary->d_dead_a, x.dead_b = primary->d_dead_b;
+            x.n_dead_a = primary->n_dead_a, x.n_dead_b = primary->n_dead_b;
+        }
+        hipLaunchKernelGGL((rescore_score_kernel<T, true, true>), grid_score, dim3(SG_PAIR_BLOCK), 0, ctx->stream, cand->d_cols,
+                           (const T *)cand->d_vals, cand->d_counts, cand->n_rows, cand->n_cols, cand->stride, chunks, (T)w0, dev,
+                           n_fields, d_status, (T *)d_comb, x);
+    } else if (!floors) {
         hipLaunchKernelGGL((rescore_score_kernel<T, false>), grid_score, dim3(SG_PAIR_BLOCK), 0, ctx->stream, cand->d_cols,
                            (const T *)cand->d_vals, cand->d_counts, cand->n_rows, cand->n_cols, cand->stride, chunks, (T)w0, dev,
                            n_fields, d_status, (T *)d_comb, NoFloors{});
     } else {
-        RescoreFloors<T> m;
-        memset(&m, 0, sizeof(m));
-        for (int f = 0; f <= n_fields; ++f)
-            if (!std::isnan(floors[f])) m.m[f] = (T)floors[f], m.has |= 1u << f;
         hipLaunchKernelGGL((rescore_score_kernel<T, true>), grid_score, dim3(SG_PAIR_BLOCK), 0, ctx->stream, cand->d_cols,
                            (const T *)cand->d_vals, cand->d_counts, cand->n_rows, cand->n_cols, cand->stride, chunks, (T)w0, dev,
                            n_fields, d_status, (T *)d_comb, m);
@@ -237,9 +357,11 @@ static int rescore_count_ok(int32_t n_fields) {
     return SG_OK;
 }
 
-// both entries; floors: null, or n_fields + 1 doubles -- the primary's first -- a NaN for a field without one
+// the three entries; floors: null, or n_fields + 1 doubles -- the primary's first -- a NaN for a field without one; skip:
+// sg_topn_rescore_skip_empty, with its primary (null: field 0 is never empty)
 static int rescore_call(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
-                        double threshold, int32_t top_n, sg_topn **out, const double *floors) {
+                        double threshold, int32_t top_n, sg_topn **out, const double *floors, bool skip = false,
+                        const sg_rescore_field *primary = nullptr) {
     SG_REQUIRE(ctx && cand && out, "null argument");
     SG_TRY(rescore_count_ok(n_fields));
     SG_REQUIRE(fields != nullptr, "null argument");
@@ -249,10 +371,12 @@ static int rescore_call(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_re
     for (int f = 0; floors && f <= n_fields; ++f) SG_REQUIRE(!std::isinf(floors[f]), "a floor is infinite");
     for (int f = 0; f < n_fields; ++f)
         SG_TRY(check_pair_field(fields[f], cand->dtype, cand->n_rows, cand->n_cols, "a field's", "candidates", true));
+    if (primary) SG_TRY(check_pair_field(*primary, cand->dtype, cand->n_rows, cand->n_cols, "the primary field's", "candidates", false));
     const int64_t chunks = (cand->stride + SG_PAIR_ROW_CHUNK - 1) / SG_PAIR_ROW_CHUNK;
     if (pair_blocks(cand->n_rows * chunks) > INT32_MAX || cand->n_rows > INT32_MAX)
         return exceeds_one_launch(cand->n_rows, "rows of candidates", "rescore");
     for (int f = 0; f < n_fields; ++f) SG_TRY(ensure_pair_rows(ctx, fields[f].A, fields[f].B));
+    if (primary) SG_TRY(ensure_pair_rows(ctx, primary->A, primary->B));
     TopnPtr r;
     SG_TRY(topn_alloc(ctx, cand->n_rows, cand->n_cols, std::min<int32_t>(top_n, cand->stride), cand->dtype, &r));
     if (cand->n_rows == 0) {
@@ -265,10 +389,12 @@ static int rescore_call(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_re
     SG_TRY(tmp.alloc(head + (size_t)cand->n_rows * (size_t)cand->stride * s, &d_buf));
     int32_t *d_long_rows = nullptr;   // the rows of more than SG_RESCORE_SHORT candidates (word 1 of the head counts them)
     if (cand->stride > SG_RESCORE_SHORT) SG_TRY(tmp.alloc((size_t)cand->n_rows, &d_long_rows));
+    uint8_t *d_empty = nullptr;       // (skip) a byte a candidate: the fields whose right row is empty
+    if (skip) SG_TRY(tmp.alloc((size_t)cand->n_rows * (size_t)cand->stride, &d_empty));
     SG_HIP_TRY(hipMemsetAsync(d_buf, 0, head, ctx->stream));
     SG_TRY(by_dtype(cand->dtype, [&](auto t) {
         return rescore<decltype(t)>(ctx, cand, w0, fields, n_fields, threshold, r.get(), (uint32_t *)d_buf, d_buf + head, d_long_rows,
-                                    floors);
+                                    floors, skip, primary, d_empty);
     }));
     uint32_t status = 0;
     SG_TRY(sg_fetch(ctx, &status, d_buf, 4));   // the one read-back
@@ -299,4 +425,13 @@ extern "C" int sg_topn_rescore_floors(sg_ctx *ctx, const sg_topn *cand, double w
     double all[SG_RESCORE_MAX_FIELDS + 1] = {floor0};
     for (int f = 0; f < n_fields; ++f) all[f + 1] = floors[f];
     return rescore_call(ctx, cand, w0, fields, n_fields, threshold, top_n, out, all);
+}
+
+extern "C" int sg_topn_rescore_skip_empty(sg_ctx *ctx, const sg_topn *cand, double w0, double floor0,
+                                          const sg_rescore_field *primary, const sg_rescore_field *fields, const double *floors,
+                                          int32_t n_fields, double threshold, int32_t top_n, sg_topn **out) {
+    SG_TRY(rescore_count_ok(n_fields));   // (before floors[] is copied)
+    double all[SG_RESCORE_MAX_FIELDS + 1];
+    for (int f = 0; f <= n_fields; ++f) all[f] = f == 0 ? floor0 : floors ? floors[f - 1] : NAN;
+    return rescore_call(ctx, cand, w0, fields, n_fields, threshold, top_n, out, all, true, primary);
 }

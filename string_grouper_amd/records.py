@@ -14,11 +14,13 @@ from .corpus import Corpus
 
 def match_records(fields, duplicates=None, master_id: Optional[pd.Series] = None, duplicates_id: Optional[pd.Series] = None,
                   weights=None, candidates=None, candidate_fields=(0,), field_min_similarity=None,
-                  field_similarities=False, **kwargs) -> pd.DataFrame:
+                  field_similarities=False, empty_fields="zero", **kwargs) -> pd.DataFrame:
     """``fields``: a list of 2 to 8 equally long Series, one a field of the records; the first finds the candidates --
     with ``candidate_fields`` (positions in ``fields``, 0 among them) the union of several fields' matches does.
     ``field_min_similarity``: None or one floor a field (a number or None), in the order of ``fields``.
     ``field_similarities=True``: a column ``similarity_k`` a field in the frame, k the position in ``fields``.
+    ``empty_fields``: ``"zero"`` (the default) or ``"skip"``: a field that is empty for a pair -- a string with no n-gram its
+    field knows, on either side -- takes no part in that pair and its weight is shared among the others.
     ``duplicates``: None or as many Series.  Everything else as in ``Corpus.match_records``; vectoriser options in
     ``kwargs`` (``ngram_size``, ``tfidf_matrix_dtype`` ...) apply to every field."""
     if isinstance(fields, pd.Series) or not isinstance(fields, (list, tuple)) or len(fields) < 2:
@@ -32,7 +34,8 @@ def match_records(fields, duplicates=None, master_id: Optional[pd.Series] = None
         return corpora[0].match_records(corpora[1:], duplicates=duplicates, duplicates_id=duplicates_id, weights=weights,
                                         candidates=candidates, candidate_fields=candidate_fields,
                                         field_min_similarity=field_min_similarity, field_similarities=field_similarities,
-                                        **kwargs)
+                                        **({} if isinstance(empty_fields, str) and empty_fields == "zero" else
+                                           {"empty_fields": empty_fields}), **kwargs)
     finally:
         for c in corpora:
             c.close()
