@@ -79,7 +79,7 @@ def composed(corpora, split):
 
 
 def new_split(eng, ctx, corpora):
-    """One new call taken apart, a wait after every step (the steps of CorpusEngine.corpus_records_union_topn)."""
+    """One new call taken apart, a wait after every step (the stages of CorpusEngine.corpus_records with candidate_fields)."""
     states = [c._live() for c in corpora]
     out = {}
 

@@ -25,7 +25,6 @@ two matrices.  The methods have the signatures of the module-level functions (st
 """
 from __future__ import annotations
 
-import inspect
 from typing import Optional
 
 import numpy as np
@@ -33,6 +32,7 @@ import pandas as pd
 
 from . import engine as _engine_mod
 from .pairs import checked_pairs
+from .record_call import MAX_RECORD_CANDIDATES, MAX_RECORD_FIELDS, RecordCall, checked_record_call
 from .string_grouper import StringGrouper, StringGrouperConfig
 
 # options that define the vectoriser: a call may not change them (the corpus was fitted with them)
@@ -146,44 +146,25 @@ class _CorpusGrouper(StringGrouper):
 
 class _RecordGrouper(_CorpusGrouper):
     """_CorpusGrouper whose match list is the engine's over RECORDS: the corpus finds the candidates, further corpora score them
-    on their fields, and the weighed sum is what the list holds (CorpusEngine.corpus_records_topn).  Everything behind the
-    list -- the frames, the groups -- is StringGrouper's own."""
+    on their fields, and the weighed sum is what the list holds (CorpusEngine.corpus_records).  Everything behind the list --
+    the frames, the groups -- is StringGrouper's own."""
 
-    def __init__(self, corpus: "Corpus", others, weights, cand, dup_fields, master, duplicates=None, master_id=None,
-                 duplicates_id=None, candidate_fields=(0,), floors=None, field_scores=False, skip_empty=False, **kwargs):
-        """``cand``: (max_n_matches, min_similarity) of the candidates -- with ``candidate_fields`` other than ``(0,)`` a list
-        of them, one a candidate field (CorpusEngine.corpus_records_union_topn).  ``floors``: None or one entry a field, each
-        None or a number; ``field_scores``: the list gets a column ``similarity_k`` a field; ``skip_empty``: a field that is
-        empty for a pair takes no part in it.  The engine gets each keyword only when it is set."""
-        self._others, self._weights, self._cand, self._dup_fields = others, weights, cand, dup_fields
-        self._candidate_fields = tuple(candidate_fields)
-        self._floors = floors
-        self._field_scores = bool(field_scores)
-        self._skip_empty = bool(skip_empty)
+    def __init__(self, corpus: "Corpus", others, call: RecordCall, dup_fields, master, duplicates=None, master_id=None,
+                 duplicates_id=None, **kwargs):
+        """``call``: the description of the call (string_grouper_amd/record_call.py), handed to the engine as it is."""
+        self._others, self._call, self._dup_fields = others, call, dup_fields
         self._planes = None
         super().__init__(corpus, master, duplicates, master_id, duplicates_id, **kwargs)
 
     def _can_fuse_on_device(self) -> bool:
         return True                           # (explicit n_blocks were refused by the caller; there is no host route)
 
-    def _new_options(self) -> dict:
-        """The engine's keywords that are passed only when they are set, so that engine doubles without them keep working."""
-        return {**({} if self._floors is None else {'floors': self._floors}),
-                **({'field_scores': True} if self._field_scores else {}),
-                **({'skip_empty': True} if self._skip_empty else {})}
-
-    def _engine_match_list(self, eng, master_matrix, duplicate_matrix, fix: bool):
-        out = self._engine_record_list(eng, master_matrix, duplicate_matrix, fix)
-        if self._field_scores:                # the engine's last element: the planes, one a field, in list order
-            self._planes, out = out[-1], out[:-1]
-        return out
-
     def fit(self):
         """StringGrouper's, and with ``field_scores`` the planes as further columns ``similarity_k`` of the match list
         (float64, as ``similarity`` is).  They are added in place: the list on the device stays with the grouper."""
         self._planes = None
         super().fit()
-        if self._field_scores:
+        if self._call.field_scores:
             ml = self._matches_list
             for k, plane in enumerate(self._planes):
                 ml[f'similarity_{k}'] = plane.astype(np.float64, copy=False)
@@ -195,7 +176,7 @@ class _RecordGrouper(_CorpusGrouper):
         ``include_zeroes`` adds come after the list's own, in the frame as in the list, and carry 0.0 in every field column
         as they carry 0 in ``similarity``."""
         frame = super().get_matches(ignore_index=ignore_index, include_zeroes=include_zeroes)
-        if not self._field_scores:
+        if not self._call.field_scores:
             return frame
         ml = self._matches_list
         at = list(frame.columns).index('similarity') + 1
@@ -205,42 +186,31 @@ class _RecordGrouper(_CorpusGrouper):
             frame.insert(at + k, f'similarity_{k}', column)
         return frame
 
-    def _engine_record_list(self, eng, master_matrix, duplicate_matrix, fix: bool):
+    def _engine_match_list(self, eng, master_matrix, duplicate_matrix, fix: bool):
+        """One engine call: the list as ``match_list`` gives it, kept on the device, and with ``field_scores`` the planes,
+        one a field, in list order (taken by ``fit``)."""
+        call = self._call
         fields = None
         if self._dup_fields is not None:                             # one transform a field (duplicates[0] may be corpus.master)
             fields = [o._rows_of(series, self._made) for o, series in zip(self._others, self._dup_fields)]
+        top_n = call.all_candidates if self._max_n_matches is None else min(int(self._max_n_matches), call.all_candidates)
         try:
-            if self._candidate_fields != (0,):
-                return self._union_match_list(eng, duplicate_matrix, fields, fix)
-            cand_top_n, cand_threshold = self._cand
-            top_n = cand_top_n if self._max_n_matches is None else min(int(self._max_n_matches), cand_top_n)
-            keep = 'keep_on_device' in inspect.signature(eng.corpus_records_topn).parameters   # engine doubles may lack it
-            return eng.corpus_records_topn(self._corpus._live(), [o._live() for o in self._others], duplicate_matrix, fields,
-                                           self._weights, cand_top_n, cand_threshold, top_n, self._config.min_similarity, fix,
-                                           **({'keep_on_device': True} if keep else {}),
-                                           **self._new_options())
+            out, self._planes = eng.corpus_records(self._corpus._live(), [o._live() for o in self._others], duplicate_matrix,
+                                                   fields, call, top_n, self._config.min_similarity, fix, keep_on_device=True)
+            return out
         except OverflowError as e:
             # fit() answers an OverflowError with the block-wise multiply of ONE field: that is no record match.  There is no
             # block-wise route for records, so the call is refused instead
-            now = (f"{self._cand[0]}" if self._candidate_fields == (0,) else
-                   f"{[k for k, _ in self._cand]} on the fields {list(self._candidate_fields)}")
+            now = (f"{[k for k, _ in call.candidates]} on the fields {list(call.candidate_fields)}" if call.union else
+                   f"{call.candidates[0][0]}")
             raise ValueError(f"records x candidates exceed what one result on the device can index ({e}): lower "
                              f"candidates['max_n_matches'] (now {now}) or match the records in batches of duplicates") from e
-
-    def _union_match_list(self, eng, duplicate_matrix, fields, fix: bool):
-        """Candidates from several fields: every candidate field's multiply, united and rescored on the device."""
-        all_candidates = sum(k for k, _ in self._cand)
-        top_n = all_candidates if self._max_n_matches is None else min(int(self._max_n_matches), all_candidates)
-        return eng.corpus_records_union_topn(self._corpus._live(), [o._live() for o in self._others], duplicate_matrix, fields,
-                                             self._weights, self._candidate_fields, self._cand, top_n,
-                                             self._config.min_similarity, fix, keep_on_device=True,
-                                             **self._new_options())
 
 
 class Corpus:
     """A master list fitted once and kept on the device; see the module docstring."""
-    MAX_RECORD_FIELDS = 7                     # further fields of a record call (include/sg_hip.h: sg_topn_rescore)
-    MAX_RECORD_CANDIDATES = 2048              # candidates a record: the stride sg_topn_rescore takes
+    MAX_RECORD_FIELDS = MAX_RECORD_FIELDS     # (string_grouper_amd/record_call.py)
+    MAX_RECORD_CANDIDATES = MAX_RECORD_CANDIDATES
 
     def __init__(self, master: pd.Series, master_id: Optional[pd.Series] = None, **kwargs):
         StringGrouper(master, master_id=master_id, **kwargs)        # the reference's validation of data and options
@@ -486,7 +456,8 @@ class Corpus:
         ``record_calls`` (calls of ``match_records`` / ``group_similar_records`` this corpus took part in, as the one that
         finds the candidates or as a further field), ``record_union_calls`` (those of them with several
         ``candidate_fields``, counted on the corpora that found candidates), ``record_floor_calls`` (those of them with a
-        ``field_min_similarity``) and ``record_skip_empty_calls`` (those of them with ``empty_fields="skip"``)."""
+        ``field_min_similarity``), ``record_field_score_calls`` (those of them with ``field_similarities=True``) and
+        ``record_skip_empty_calls`` (those of them with ``empty_fields="skip"``)."""
         return dict(self._live().stats)
 
     def _rows_of(self, series, made):
@@ -583,11 +554,13 @@ class Corpus:
     # ------------------------------------------------------------------ records of several fields
     def _record_call(self, others, duplicates, duplicates_id, weights, candidates, kwargs, finish, candidate_fields=(0,),
                      field_min_similarity=None, field_similarities=False, empty_fields="zero"):
-        """The checks of ``match_records`` / ``group_similar_records``, then the call."""
-        state = self._live()
+        """The checks of ``match_records`` / ``group_similar_records`` that need the corpora, the description of the call
+        (checked_record_call), what the engine can do of it, then the call."""
+        self._live()
         self._same_engine()
-        if not hasattr(self._engine, "corpus_records_topn"):
-            raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} matches no records")
+        name = getattr(self._engine, 'name', type(self._engine).__name__)
+        if not hasattr(self._engine, "corpus_records"):
+            raise NotImplementedError(f"the engine {name!r} matches no records")
         if isinstance(others, Corpus) or not isinstance(others, (list, tuple)) or not all(isinstance(o, Corpus) for o in others):
             raise TypeError("others must be a list of Corpus objects, one for every further field")
         others = list(others)
@@ -610,18 +583,6 @@ class Corpus:
         options = self._options(kwargs)
         for o in others:
             o._options({k: v for k, v in kwargs.items() if k in VECTORISER_OPTIONS})
-        # weights: one a field, this corpus's first; used as given
-        if weights is None:
-            weights = [1.0 / (len(others) + 1)] * (len(others) + 1)
-        else:
-            try:
-                weights = [float(w) for w in weights]
-            except (TypeError, ValueError):
-                raise TypeError("weights must be numbers, one for every field (this corpus's first)")
-            if len(weights) != len(others) + 1:
-                raise ValueError(f"{len(weights)} weights for {len(others) + 1} fields: one a field is expected, this corpus's first")
-            if not all(np.isfinite(w) and w > 0 for w in weights):
-                raise ValueError("weights must be finite and greater than 0")
         # duplicates: one Series a field, equally long
         dup_fields = None
         if duplicates is not None:
@@ -637,100 +598,16 @@ class Corpus:
             dup_fields = list(duplicates[1:])
         elif duplicates_id is not None:
             raise ValueError("duplicates_id without duplicates")
-        # candidate_fields: the fields whose multiplies find the candidates (0: this corpus, k: others[k - 1])
-        if isinstance(candidate_fields, (str, bytes)) or not hasattr(candidate_fields, "__iter__"):
-            raise TypeError("candidate_fields must be a sequence of field positions (0: this corpus, k: others[k - 1])")
-        candidate_fields = tuple(candidate_fields)
-        if not all(isinstance(f, (int, np.integer)) and not isinstance(f, (bool, np.bool_)) for f in candidate_fields):
-            raise TypeError("candidate_fields must be a sequence of field positions (0: this corpus, k: others[k - 1])")
-        candidate_fields = tuple(int(f) for f in candidate_fields)
-        if not all(0 <= f <= len(others) for f in candidate_fields):
-            raise ValueError(f"candidate_fields={candidate_fields}: positions between 0 and {len(others)} are expected for "
-                             f"{len(others) + 1} fields")
-        if 0 not in candidate_fields or any(a >= b for a, b in zip(candidate_fields, candidate_fields[1:])):
-            raise ValueError(f"candidate_fields={candidate_fields}: distinct positions in ascending order, 0 (this corpus) among "
-                             f"them, are expected")
-        if candidate_fields != (0,) and not hasattr(self._engine, "corpus_records_union_topn"):
-            raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} unites no "
-                                      f"candidates of several fields")
-        # field_min_similarity: one floor a field, this corpus's first; None -- the whole or an entry -- is no floor
-        floors = None
-        if field_min_similarity is not None:
-            if isinstance(field_min_similarity, (str, bytes)) or not hasattr(field_min_similarity, "__len__"):
-                raise TypeError("field_min_similarity must be a sequence, one entry for every field (this corpus's first): a "
-                                "number or None")
-            floors = list(field_min_similarity)
-            if len(floors) != len(others) + 1:
-                raise ValueError(f"{len(floors)} entries of field_min_similarity for {len(others) + 1} fields: one a field is "
-                                 f"expected, this corpus's first")
-            for k, m in enumerate(floors):
-                if isinstance(m, (bool, np.bool_)):
-                    raise TypeError(f"field_min_similarity[{k}]={m!r}: a number or None is expected, not a bool")
-                if m is None:
-                    continue
-                if not isinstance(m, (int, float, np.integer, np.floating)) or not np.isfinite(m):
-                    raise ValueError(f"field_min_similarity[{k}]={m!r}: a finite real number or None is expected")
-                floors[k] = float(m)
-            if all(m is None for m in floors):               # no floor anywhere: the call it always was
-                floors = None
-        if floors is not None:
-            routes = ("corpus_records_topn",) if candidate_fields == (0,) else ("corpus_records_topn", "corpus_records_union_topn")
-            if not all("floors" in inspect.signature(getattr(self._engine, r)).parameters for r in routes):
-                raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} takes no "
-                                          f"field_min_similarity")
-        # field_similarities: a column a field in the frame
-        if not isinstance(field_similarities, (bool, np.bool_)):
-            raise TypeError(f"field_similarities={field_similarities!r}: True or False is expected")
-        field_similarities = bool(field_similarities)
-        if field_similarities:
-            routes = ("corpus_records_topn",) if candidate_fields == (0,) else ("corpus_records_topn", "corpus_records_union_topn")
-            if not all("field_scores" in inspect.signature(getattr(self._engine, r)).parameters for r in routes):
-                raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} gives no "
-                                          f"field_similarities")
-        # empty_fields: "zero" -- the call as it always was -- or "skip"
-        if not isinstance(empty_fields, str):
-            raise TypeError(f"empty_fields={empty_fields!r}: 'zero' or 'skip' is expected")
-        if empty_fields not in ("zero", "skip"):
-            raise ValueError(f"empty_fields={empty_fields!r}: 'zero' or 'skip' is expected")
-        if empty_fields == "skip":
-            routes = ("corpus_records_topn",) if candidate_fields == (0,) else ("corpus_records_topn", "corpus_records_union_topn")
-            if not all("skip_empty" in inspect.signature(getattr(self._engine, r)).parameters for r in routes):
-                raise NotImplementedError(f"the engine {getattr(self._engine, 'name', type(self._engine).__name__)!r} takes no "
-                                          f"empty_fields='skip'")
-        # candidates: the two options of a candidate field's multiply -- one dict for every candidate field, or one a field
-        candidates = {} if candidates is None else candidates
-        if isinstance(candidates, list) and all(isinstance(c, dict) for c in candidates):
-            if len(candidates) != len(candidate_fields):
-                raise ValueError(f"{len(candidates)} candidates dicts for {len(candidate_fields)} candidate fields: one a "
-                                 f"candidate field (or one for all) is expected")
-        else:
-            candidates = [candidates] * len(candidate_fields)
         n_right = n if duplicates is None else len(duplicates[0])
-        cand = []
-        for f, options_f in zip(candidate_fields, candidates):
-            if not isinstance(options_f, dict) or set(options_f) - {"min_similarity", "max_n_matches"}:
-                raise TypeError("candidates takes min_similarity and max_n_matches only, as a dict")
-            config = (self if f == 0 else others[f - 1])._config     # a field's own corpus fills what the dict leaves out
-            cand_threshold = float(options_f.get("min_similarity", config.min_similarity))
-            cand_top_n = options_f.get("max_n_matches", config.max_n_matches)
-            if cand_top_n is None:
-                cand_top_n = n_right
-            if isinstance(cand_top_n, (bool, np.bool_)) or not isinstance(cand_top_n, (int, np.integer)) or cand_top_n < 1:
-                if n_right > 0:
-                    raise ValueError(f"candidates: max_n_matches={cand_top_n!r}: a whole number of at least 1 is expected")
-                cand_top_n = 1
-            if cand_top_n > self.MAX_RECORD_CANDIDATES:
-                raise ValueError(f"candidates: max_n_matches={cand_top_n} exceeds the {self.MAX_RECORD_CANDIDATES} candidates a record "
-                                 f"that can be rescored: set candidates=dict(max_n_matches=...) to at most that")
-            cand.append((int(cand_top_n), cand_threshold))
-        if sum(k for k, _ in cand) > self.MAX_RECORD_CANDIDATES:
-            raise ValueError(f"candidates: the max_n_matches of the candidate fields {list(candidate_fields)} "
-                             f"({' + '.join(str(k) for k, _ in cand)}) exceed together the {self.MAX_RECORD_CANDIDATES} candidates a "
-                             f"record that can be united and rescored")
-        g = _RecordGrouper(self, others, weights, cand[0] if candidate_fields == (0,) else cand, dup_fields, self.master,
-                           None if duplicates is None else duplicates[0], self.master_id, duplicates_id,
-                           candidate_fields=candidate_fields, floors=floors, field_scores=field_similarities,
-                           skip_empty=empty_fields == "skip", **options)
+        call = checked_record_call([c._config for c in [self] + others], n_right, weights, candidates, candidate_fields,
+                                   field_min_similarity, field_similarities, empty_fields)
+        missing = call.needs - getattr(self._engine, "RECORD_OPTIONS", frozenset())
+        for option, refusal in (("union", "unites no candidates of several fields"), ("floors", "takes no field_min_similarity"),
+                                ("field_scores", "gives no field_similarities"), ("skip_empty", "takes no empty_fields='skip'")):
+            if option in missing:
+                raise NotImplementedError(f"the engine {name!r} {refusal}")
+        g = _RecordGrouper(self, others, call, dup_fields, self.master, None if duplicates is None else duplicates[0],
+                           self.master_id, duplicates_id, **options)
         for o in others:
             o._join_pending()
         try:

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _native as N
 from .device_matrix import DeviceMatrix
+from .record_call import RecordCall
 from .strprep import StringColumn, _ascii_lower
 from .vectorizer import HipTfidfVectorizer
 
@@ -511,156 +512,114 @@ class CorpusEngine:
         return self.ctx.pairs_dot(rows, rows if other is None else other.csr, left, right)
 
     # ------------------------------------------------------------------ records of several fields
-    MAX_RECORD_FIELDS = 7                     # sg_topn_rescore: further fields a call
+    RECORD_OPTIONS = frozenset({"union", "floors", "field_scores", "skip_empty"})     # what RecordCall.needs may ask
 
-    def corpus_records_topn(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
-                            B_fields: Optional[List[DeviceMatrix]], weights, cand_top_n: int, cand_threshold: float,
-                            top_n: int, threshold: float, self_join_fix: bool, keep_on_device: bool = False, floors=None,
-                            field_scores: bool = False, skip_empty: bool = False):
-        """The match list of RECORDS: the corpus ``state`` finds the candidates, the corpora ``others`` -- row p of every
-        corpus is record p -- score them on their fields, and the weighed sum is filtered, ordered and cut on the device
-        (sg_topn_rescore) before the list is built (K6).  Returns what ``match_list`` returns.
+    def corpus_records(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
+                       B_fields: Optional[List[DeviceMatrix]], call: RecordCall, top_n: int, threshold: float,
+                       self_join_fix: bool, keep_on_device: bool = False):
+        """The match list of RECORDS as ``call`` describes it (string_grouper_amd/record_call.py): the candidate fields find
+        the candidates, every field -- ``state``'s first, row p of every corpus is record p -- scores them, and the weighed
+        sum is filtered, ordered and cut on the device (sg_topn_rescore; with ``call.floors`` a floor a field before the cut,
+        with ``call.skip_empty`` the fields empty for a pair left out) before the list is built (K6).  Returns ``(list,
+        planes)``: the list as ``match_list`` returns it for the same ``keep_on_device``; ``planes`` None, or with
+        ``call.field_scores`` an array ``[fields, entries]`` of the corpus's dtype, plane k every list entry's score on field k
+        with the bits ``corpus_pairs`` of that field returns, the diagonal and the mirrored entries of ``self_join_fix``
+        included (sg_matchlist_field_scores, on the list where it lies before it is freed or kept).
 
-        ``B``: the right-hand rows of the primary field -- ``state.matrix`` itself for a self-join, else the transformed
-        duplicates -- and ``B_fields`` the further fields' (None for a self-join).  The primary multiply is ``_topn_device``'s
-        at (``cand_top_n``, ``cand_threshold``): the resident index, the forward and the reverse path and a kept self-join serve
-        as they do for ``match_strings``.  A further field is read where it lies: ``physical()`` with the dead list, live
-        numbers turned into physical ones by the kernel -- a record call compacts no secondary corpus and builds no index
-        of one.  Every handle made here lives in a scope: the candidates in one that ends with the rescoring, the rescored result
-        in the method's (``_match_list_from_topn`` frees it early, as it frees a multiply's).
+        ``B``: the primary field's right-hand rows -- ``state.matrix`` itself for a self-join, else the transformed duplicates
+        -- and ``B_fields`` the further fields' (None for a self-join).  A candidate field's multiply is ``_topn_device``'s on
+        that field's own matrices: the resident index, the forward and the reverse path and a kept self-join serve as for
+        ``match_strings``, so a candidate field's corpus builds its index and a self-join compacts it.  Several candidate fields'
+        results are united on the device (sg_topn_union: the primary's score fills in what its multiply did not find).  A
+        corpus that is NOT a candidate field is read where it lies -- ``physical()`` with the dead list -- and is never
+        compacted, never indexed.  The rows and the dead lists the union, the rescoring and the planes read are taken AFTER
+        the multiplies, which may have compacted a candidate corpus; results number the live rows, which no compaction changes.
 
-        ``floors``: None, or one entry a field (``state``'s first), each None or a number: a candidate stays only when its
-        score on every field with a floor is above that floor, decided on the device before the cut
-        (sg_topn_rescore_floors).
-
-        ``field_scores``: the tuple returned gets one more element at its END, an array ``[fields, entries]`` of the corpus's
-        dtype: plane k holds, for every entry of the list in list order, the pair's score on field k (0: ``state``) with the
-        bits ``corpus_pairs`` of that field returns -- the diagonal and the mirrored entries of ``self_join_fix`` included,
-        which carry the field's own product.  The list is scored where it lies, after K6 and before it is freed or kept
-        (sg_matchlist_field_scores); the fields' rows and dead lists are the ones the rescoring read.
-
-        ``skip_empty``: a field that is empty for a pair -- the row of either record has no entries, ``state``'s field
-        included -- is left out of the pair's sum, its weight is shared among the others and its floor is not held; a pair
-        all of whose fields are empty is dropped (sg_topn_rescore_skip_empty, with ``state``'s rows as its primary).  The
-        planes of ``field_scores`` are unchanged by it."""
-        return self._records_topn(state, others, B, B_fields, weights, None, [(cand_top_n, cand_threshold)], top_n, threshold,
-                                  self_join_fix, keep_on_device, floors, field_scores, skip_empty)
-
-    MAX_UNION_CANDIDATES = 2048               # sg_topn_union: the candidate fields' strides together
-
-    def corpus_records_union_topn(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
-                                  B_fields: Optional[List[DeviceMatrix]], weights, candidate_fields, cands, top_n: int,
-                                  threshold: float, self_join_fix: bool, keep_on_device: bool = False, floors=None,
-                                  field_scores: bool = False, skip_empty: bool = False):
-        """``corpus_records_topn`` with candidates from SEVERAL fields: ``candidate_fields`` -- ascending positions, 0 the corpus
-        ``state``, k ``others[k - 1]``, 0 always among them -- each find candidates with a multiply of their own at
-        ``cands[.] = (cand_top_n, cand_threshold)``, the results are united on the device (sg_topn_union: a record's distinct
-        candidates, with the primary field's score for the ones the primary multiply did not find) and the union is rescored,
-        filtered, ordered and cut exactly as one field's candidates are.  Returns what ``match_list`` returns.
-
-        Every candidate multiply is ``_topn_device``'s on that field's own matrices: its resident index, the forward and the
-        reverse path and a kept self-join serve as they do for ``match_strings`` -- so a corpus named as a candidate field is
-        treated as the primary is (it builds its index; a self-join compacts it).  A corpus that is NOT a candidate field is
-        read where it lies, as in ``corpus_records_topn``: never compacted, never indexed.  The rows and the dead lists the
-        union and the rescoring read are taken AFTER the multiplies, which may have compacted a candidate corpus; results number
-        the live rows, which no compaction changes.  ``floors`` as in ``corpus_records_topn``: the primary's floor is held
-        against the score the united candidate carries, the multiply's or the one the union filled in; ``field_scores`` and
-        ``skip_empty`` as there too (a candidate that a further field found may have an empty primary field)."""
-        return self._records_topn(state, others, B, B_fields, weights, candidate_fields, cands, top_n, threshold,
-                                  self_join_fix, keep_on_device, floors, field_scores, skip_empty)
-
-    def _records_topn(self, state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
-                      B_fields: Optional[List[DeviceMatrix]], weights, candidate_fields, cands, top_n: int, threshold: float,
-                      self_join_fix: bool, keep_on_device: bool, floors=None, field_scores: bool = False,
-                      skip_empty: bool = False):
-        """The body of both record calls: validate, find the candidates -- ``candidate_fields`` None: the primary field's
-        multiply at ``cands[0]``; else one multiply a candidate field and their union --, take the fields' rows and dead
-        lists, rescore, count, build the list and, with ``field_scores``, score it field by field."""
+        Handles: the candidates live in a scope that ends with the rescoring, every candidate field's own in one that ends with
+        the union, the rescored result in the method's (``_match_list_from_topn`` frees it early, as it frees a multiply's)."""
         t = time.perf_counter()
-        A = state.matrix
+        states, rights = self._record_matrices(state, others, B, B_fields, call)
+        self_join = B_fields is None
+
+        def field(k: int):
+            """Field k as the union, the rescoring and the planes take it, read where it lies NOW: after the multiplies."""
+            rows = states[k].physical()       # (the state's own cached concatenation when rows wait in a delta)
+            dead = states[k].dead_dev
+            return (rows, rows, dead, dead) if self_join else (rows, rights[k].csr, dead, None)
+
+        with N.Scope() as s:
+            with N.Scope() as before:         # the candidates go as soon as they are rescored
+                cand = before.own(self._record_candidates(states, rights, call, self_join, field))
+                fields = [field(k) for k in range(1, call.n_fields)]
+                weighed = [(rows, right, w, dead_a, dead_b) for (rows, right, dead_a, dead_b), w in zip(fields, call.weights[1:])]
+                # one call: its options choose the library's entry (no floors and no skip: sg_topn_rescore, as always)
+                res = s.own(self.ctx.topn_rescore(cand, call.weights[0], weighed, threshold, top_n, floors=call.floors,
+                                                  skip_empty=call.skip_empty, primary=field(0) if call.skip_empty else None))
+            self._record_count(states, call)
+            # (_match_list_from_topn frees the result once the list is built; if it raises before that, the scope does)
+            out = self._match_list_from_topn(res, state.matrix.dtype, B.shape[0], self_join_fix,
+                                             keep_on_device or call.field_scores, t)
+        if not call.field_scores:
+            return out, None
+        return self._record_planes(out, [field(0)] + fields, keep_on_device)
+
+    @staticmethod
+    def _record_matrices(state: CorpusState, others: List[CorpusState], B: DeviceMatrix,
+                         B_fields: Optional[List[DeviceMatrix]], call: RecordCall):
+        """(every field's corpus, every field's right-hand rows), checked against each other and against ``call``."""
+        states, A = [state] + list(others), state.matrix
         self_join = B_fields is None          # (duplicates whose first Series is corpus.master have B is A and fields of their own)
-        states = [state] + list(others)
-        union = candidate_fields is not None
-        if union:
-            candidate_fields = [int(f) for f in candidate_fields]
-        if len(others) != len(weights) - 1 or not 1 <= len(others) <= self.MAX_RECORD_FIELDS:
-            raise ValueError(f"between 1 and {self.MAX_RECORD_FIELDS} further fields, and one weight a field, are expected")
-        if union and (len(candidate_fields) < 2 or candidate_fields[0] != 0 or candidate_fields[-1] > len(others)
-                      or any(a >= b for a, b in zip(candidate_fields, candidate_fields[1:]))
-                      or len(cands) != len(candidate_fields)):
-            raise ValueError("candidate_fields: at least two distinct ascending field positions, 0 among them, and one pair of "
-                             "candidate options a field, are expected")
+        if len(states) != call.n_fields:
+            raise ValueError(f"{len(states)} fields for a call of {call.n_fields}: one corpus a field is expected")
         if self_join and B is not A:
             raise ValueError("duplicates of the first field without duplicates of the further fields")
-        if floors is not None and len(floors) != len(weights):
-            raise ValueError(f"{len(floors)} floors for {len(weights)} fields: one a field is expected")
         for k, o in enumerate(others):
             if o.matrix.shape[0] != A.shape[0]:
                 raise ValueError(f"the corpora differ in length ({o.matrix.shape[0]} and {A.shape[0]} rows): row p of every "
                                  f"corpus must be record p")
             if not self_join and B_fields[k].shape[0] != B.shape[0]:
                 raise ValueError(f"the duplicates differ in length ({B_fields[k].shape[0]} and {B.shape[0]} rows)")
-        n_right = B.shape[0]
-        if union and sum(max(min(int(k), n_right), 1) for k, _ in cands) > self.MAX_UNION_CANDIDATES:
-            raise ValueError(f"the candidate fields' max_n_matches exceed {self.MAX_UNION_CANDIDATES} together")
-        rights = [B] + list(B_fields or [])   # (a self-join reads none of them)
+        return states, [B] + list(B_fields or [])   # (a self-join reads B alone, which is A)
 
-        def field(k: int):
-            """Field k as ``Context.topn_rescore`` takes it, read where it lies NOW: after the multiplies."""
-            rows = states[k].physical()       # (the state's own cached concatenation when rows wait in a delta)
-            dead = states[k].dead_dev
-            return rows, rows if self_join else rights[k].csr, weights[k], dead, dead if self_join else None
+    def _record_candidates(self, states: List[CorpusState], rights, call: RecordCall, self_join: bool, field) -> "N.TopN":
+        """The candidates: the primary field's multiply, or every candidate field's and their union -- the fields' own
+        results go as soon as they are united."""
+        if not call.union:
+            return self._topn_device(states[0].matrix, rights[0], *call.candidates[0])
+        with N.Scope() as per_field:
+            parts = []
+            for f, (cand_top_n, cand_threshold) in zip(call.candidate_fields, call.candidates):
+                A_f = states[f].matrix
+                parts.append(per_field.own(self._topn_device(A_f, A_f if self_join else rights[f], cand_top_n, cand_threshold)))
+            return self.ctx.topn_union(parts, field(0))
 
-        with N.Scope() as s:
-            with N.Scope() as before:         # the candidates go as soon as they are rescored
-                if not union:
-                    cand = before.own(self._topn_device(A, B, *cands[0]))
-                else:
-                    with N.Scope() as per_field:  # ... and every field's own as soon as they are united
-                        parts = []
-                        for f, (cand_top_n, cand_threshold) in zip(candidate_fields, cands):
-                            A_f = states[f].matrix
-                            B_f = A_f if self_join else rights[f]
-                            parts.append(per_field.own(self._topn_device(A_f, B_f, cand_top_n, cand_threshold)))
-                        rows, right, _, dead_a, dead_b = field(0)
-                        cand = before.own(self.ctx.topn_union(parts, (rows, right, dead_a, dead_b)))
-                fields = [field(k) for k in range(1, len(states))]
-                if skip_empty:
-                    rows, right, _, dead_a, dead_b = field(0)
-                    res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n,
-                                                      floors=None if floors is None else list(floors), skip_empty=True,
-                                                      primary=(rows, right, dead_a, dead_b)))
-                elif floors is None:
-                    res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n))
-                else:
-                    res = s.own(self.ctx.topn_rescore(cand, weights[0], fields, threshold, top_n, floors=list(floors)))
-            for st in states:
-                st.stats["record_calls"] += 1
-                if floors is not None:
-                    st.stats["record_floor_calls"] += 1
-                if field_scores:
-                    st.stats["record_field_score_calls"] += 1
-                if skip_empty:
-                    st.stats["record_skip_empty_calls"] += 1
-            for f in candidate_fields or ():
-                states[f].stats["record_union_calls"] += 1
-            # (_match_list_from_topn frees the result once the list is built; if it raises before that, the scope does)
-            if not field_scores:
-                return self._match_list_from_topn(res, A.dtype, n_right, self_join_fix, keep_on_device, t)
-            out = self._match_list_from_topn(res, A.dtype, n_right, self_join_fix, True, t)
-            kept = out[4]                     # the list on the device: scored before it is freed or handed on
-            t = time.perf_counter()
-            try:
-                planes = kept.ml.field_scores([(rows, right, dead_a, dead_b)
-                                               for rows, right, _, dead_a, dead_b in [field(0)] + fields])
-            except BaseException:
-                kept.free()
-                raise
-            self.timings["field_scores_s"] = time.perf_counter() - t
-            if keep_on_device:
-                return out + (planes,)
+    @staticmethod
+    def _record_count(states: List[CorpusState], call: RecordCall) -> None:
+        for st in states:
+            st.stats["record_calls"] += 1
+            if call.floors is not None:
+                st.stats["record_floor_calls"] += 1
+            if call.field_scores:
+                st.stats["record_field_score_calls"] += 1
+            if call.skip_empty:
+                st.stats["record_skip_empty_calls"] += 1
+        for f in call.candidate_fields if call.union else ():
+            states[f].stats["record_union_calls"] += 1
+
+    def _record_planes(self, out, fields, keep_on_device: bool):
+        """The list kept on the device (``out[4]``) scored field by field before it is freed or handed on."""
+        kept = out[4]
+        t = time.perf_counter()
+        try:
+            planes = kept.ml.field_scores(fields)
+        except BaseException:
             kept.free()
-            return out[:4] + (planes,)
+            raise
+        self.timings["field_scores_s"] = time.perf_counter() - t
+        if keep_on_device:
+            return out, planes
+        kept.free()
+        return out[:4], planes
 
     # ------------------------------------------------------------------ a self-join that is kept (DESIGN.md section 9)
     def corpus_keep_self_join(self, state: CorpusState, top_n: int, threshold: float) -> None:

@@ -299,10 +299,7 @@ class DistributedHipEngine(HipEngine):
     def corpus_pairs(self, state, left, right, other=None) -> np.ndarray:
         raise NotImplementedError("pair similarities are single-GPU: a pair's two rows may live on different ranks")
 
-    def corpus_records_topn(self, *args, **kwargs):
-        raise NotImplementedError("record matching is single-GPU: a candidate's rows may live on different ranks")
-
-    def corpus_records_union_topn(self, *args, **kwargs):
+    def corpus_records(self, *args, **kwargs):
         raise NotImplementedError("record matching is single-GPU: a candidate's rows may live on different ranks")
 
     def topn_multiply_blocked(self, A, B, n_blocks, top_n, threshold):

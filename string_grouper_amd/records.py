@@ -34,8 +34,7 @@ def match_records(fields, duplicates=None, master_id: Optional[pd.Series] = None
         return corpora[0].match_records(corpora[1:], duplicates=duplicates, duplicates_id=duplicates_id, weights=weights,
                                         candidates=candidates, candidate_fields=candidate_fields,
                                         field_min_similarity=field_min_similarity, field_similarities=field_similarities,
-                                        **({} if isinstance(empty_fields, str) and empty_fields == "zero" else
-                                           {"empty_fields": empty_fields}), **kwargs)
+                                        empty_fields=empty_fields, **kwargs)
     finally:
         for c in corpora:
             c.close()

@@ -1,55 +1,14 @@
-"""Record matching with empty fields left out, for the tests: the engine double of tests/_record_floor_oracle.py with the
-``skip_empty`` keyword (computed by ``ref_rescore_skip_empty`` of tests/_empty_field_cases.py), and the COMPOSED ROUTE that
-``match_records(empty_fields="skip")`` replaces -- ``match_strings`` at the candidate options (one a candidate field, united in
-pandas), ``pair_similarities`` a field, which strings are empty from the nnz of the rows ``corpus.vectorizer.transform`` gives,
-then the statement in numpy and pandas: the sums over the fields that are not empty, ``(c * wt) / wp``, the floors on the fields
-that are not empty, ``>``, the order and the cut.  For the CPU and the GPU tests alike.  TEST INFRASTRUCTURE ONLY."""
-from unittest import mock
-
+"""Record matching with empty fields left out, for the tests: the COMPOSED ROUTE that ``match_records(empty_fields="skip")``
+replaces -- ``match_strings`` at the candidate options (one a candidate field, united in pandas), ``pair_similarities`` a field,
+which strings are empty from the nnz of the rows ``corpus.vectorizer.transform`` gives, then the statement in numpy and pandas:
+the sums over the fields that are not empty, ``(c * wt) / wp``, the floors on the fields that are not empty, ``>``, the order
+and the cut.  For the CPU and the GPU tests alike.  TEST INFRASTRUCTURE ONLY."""
 import numpy as np
 import pandas as pd
 import scipy.sparse as sp
 
 from string_grouper_amd.string_grouper import StringGrouper
-from tests import _record_oracle as R
-from tests._empty_field_cases import ref_rescore_skip_empty
-from tests._record_floor_oracle import NOT_GIVEN, RecordFloorOracleEngine
-from tests._record_union_oracle import _grouper, _per_field, _sorted
-from tests._rescore_cases import Field
-
-
-class RecordEmptyOracleEngine(RecordFloorOracleEngine):
-    name = "oracle-corpus-records-empty"
-
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        self.skip_seen = []                   # of every record call: the keyword as it arrived, NOT_GIVEN when it did not
-
-    def corpus_fit(self, *args, **kwargs):
-        state = super().corpus_fit(*args, **kwargs)
-        state.stats.update(record_skip_empty_calls=0)
-        return state
-
-    def corpus_records_topn(self, state, others, B, B_fields, weights, cand_top_n, cand_threshold, top_n, threshold,
-                            self_join_fix, floors=NOT_GIVEN, field_scores=NOT_GIVEN, skip_empty=NOT_GIVEN):
-        self.skip_seen.append(skip_empty)
-        args = (state, others, B, B_fields, weights, cand_top_n, cand_threshold, top_n, threshold, self_join_fix)
-        if skip_empty is NOT_GIVEN or not skip_empty:
-            return super().corpus_records_topn(*args, floors=floors, field_scores=field_scores)
-        left = _sorted(state.matrix.m)
-        primary = Field(left, left if B_fields is None else _sorted(B.m), 1.0, None, None)
-        held = None if floors is NOT_GIVEN or floors is None else list(floors)
-        for st in [state] + list(others):
-            st.stats["record_skip_empty_calls"] += 1
-            if held is not None:
-                st.stats["record_floor_calls"] += 1
-        # the double's own body with the statement that leaves empty fields out in the place of ref_rescore (the floors go with
-        # it: the parent is called without them).  As in the parent, this rests on ``R.ref_rescore`` being called through its
-        # module; the CPU frame tests hold the frame to the composed route, which would show a patch that did not apply.
-        with mock.patch.object(R, "ref_rescore", lambda case: ref_rescore_skip_empty(case, primary, held)):
-            out = super().corpus_records_topn(*args, field_scores=field_scores)
-        self.floors_seen[-1] = floors         # (the parent noted NOT_GIVEN: what arrived HERE is what the tests ask for)
-        return out
+from tests._record_union_oracle import _grouper, _per_field
 
 
 # ------------------------------------------------------------------------------------------ the composed route

@@ -1,60 +1,11 @@
-"""Record matching with per-field floors for the tests: the engine double of tests/_record_oracle.py with the ``floors`` keyword
-(computed by ``ref_rescore_floors`` of tests/_floor_cases.py), and the COMPOSED ROUTE with floors -- ``combined_pairs``' steps
-with the floor mask between the sum and the filter -- that ``match_records(field_min_similarity=...)`` replaces, for the CPU and
-the GPU tests alike.  TEST INFRASTRUCTURE ONLY."""
-from unittest import mock
-
+"""Record matching with per-field floors for the tests: the COMPOSED ROUTE with floors -- ``combined_pairs``' steps of
+tests/_record_oracle.py with the floor mask between the sum and the filter -- that ``match_records(field_min_similarity=...)``
+replaces, for the CPU and the GPU tests alike.  TEST INFRASTRUCTURE ONLY."""
 import numpy as np
 import pandas as pd
 import scipy.sparse as sp
 
 from string_grouper_amd.string_grouper import StringGrouper
-from tests import _record_oracle as R
-from tests._floor_cases import ref_rescore_floors
-from tests._pair_cases import ref_pairs_dot
-
-NOT_GIVEN = object()
-
-
-class RecordFloorOracleEngine(R.RecordCorpusOracleEngine):
-    name = "oracle-corpus-records-floors"
-
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        self.floors_seen = []                 # of every record call: the keyword as it arrived, NOT_GIVEN when it did not
-        self.field_scores_seen = []           # likewise
-
-    def corpus_fit(self, *args, **kwargs):
-        state = super().corpus_fit(*args, **kwargs)
-        state.stats.update(record_floor_calls=0, record_field_score_calls=0)
-        return state
-
-    def corpus_records_topn(self, state, others, B, B_fields, weights, cand_top_n, cand_threshold, top_n, threshold,
-                            self_join_fix, floors=NOT_GIVEN, field_scores=NOT_GIVEN):
-        self.floors_seen.append(floors)
-        self.field_scores_seen.append(field_scores)
-        args = (state, others, B, B_fields, weights, cand_top_n, cand_threshold, top_n, threshold, self_join_fix)
-        if floors is NOT_GIVEN or floors is None:
-            out = super().corpus_records_topn(*args)
-        else:
-            for st in [state] + list(others):
-                st.stats["record_floor_calls"] += 1
-            # The double's own body with the statement that has floors in the place of ref_rescore.  This rests on the parent
-            # double calling ``R.ref_rescore(case)`` through its module: were the name ever bound locally there, the patch
-            # would silently apply no floor -- which the CPU frame tests would show, as they hold the frame to the composed
-            # route with floors (keep that comparison).
-            with mock.patch.object(R, "ref_rescore", lambda case: ref_rescore_floors(case, list(floors))):
-                out = super().corpus_records_topn(*args)
-        if field_scores is NOT_GIVEN or not field_scores:
-            return out
-        # the statement of the field columns: ref_pairs_dot of every entry of the list, a plane a field, the corpus's first
-        rows, cols = out[0], out[1]
-        lefts = [state.matrix] + [o.matrix for o in others]
-        rights = lefts if B_fields is None else [B] + list(B_fields)
-        for st in [state] + list(others):
-            st.stats["record_field_score_calls"] += 1
-        planes = np.stack([ref_pairs_dot(a.m, b.m, np.asarray(rows), np.asarray(cols)) for a, b in zip(lefts, rights)])
-        return tuple(out) + (planes,)
 
 
 def combined_pairs_floors(corpus, others, weights, candidates, min_similarity, max_n_matches, floors, duplicates=None,

@@ -1,34 +1,50 @@
 """Record matching for the tests: the corpus engine double that scores named pairs (tests/_pair_oracle.py) with the engine method
-of ``Corpus.match_records``, computed by ``ref_rescore`` (tests/_rescore_cases.py) on the double's scipy matrices, and the
-COMPOSED ROUTE -- ``match_strings`` at the candidate options, ``pair_similarities`` a further corpus, the numpy chain, ``>``, the
-order and the cut in pandas -- that ``match_records`` replaces, for the CPU and the GPU tests alike.  TEST INFRASTRUCTURE ONLY."""
+of ``Corpus.match_records`` -- ``corpus_records``, in a straight line from the statements of the device steps on the double's
+scipy matrices: ``topn_multiply`` a candidate field, ``ref_union`` (tests/_union_cases.py) of several, one of ``ref_rescore``,
+``ref_rescore_floors`` or ``ref_rescore_skip_empty`` (tests/_rescore_cases.py, _floor_cases.py, _empty_field_cases.py) and
+``ref_pairs_dot`` for the planes -- and the COMPOSED ROUTE -- ``match_strings`` at the candidate options, ``pair_similarities``
+a further corpus, the numpy chain, ``>``, the order and the cut in pandas -- that ``match_records`` replaces, for the CPU and the
+GPU tests alike.  TEST INFRASTRUCTURE ONLY."""
 import numpy as np
 import pandas as pd
 import scipy.sparse as sp
 
 from string_grouper_amd.string_grouper import StringGrouper
+from tests._empty_field_cases import ref_rescore_skip_empty
+from tests._floor_cases import ref_rescore_floors
+from tests._pair_cases import ref_pairs_dot
 from tests._pair_oracle import PairCorpusOracleEngine
 from tests._rescore_cases import Case, Field, ref_rescore
+from tests._union_cases import Part, UnionCase, ref_union
+
+ALL_OPTIONS = frozenset({"union", "floors", "field_scores", "skip_empty"})
 
 
-class RecordCorpusOracleEngine(PairCorpusOracleEngine):
+def _sorted(m):
+    m = sp.csr_matrix(m)
+    m.sort_indices()
+    return m
+
+
+class RecordOracleEngine(PairCorpusOracleEngine):
+    """``options``: the ``RECORD_OPTIONS`` of this double -- a double without one is an engine that cannot do it."""
     name = "oracle-corpus-records"
 
-    def __init__(self, *args, **kwargs):
+    def __init__(self, *args, options=ALL_OPTIONS, **kwargs):
         super().__init__(*args, **kwargs)
-        self.record_calls = []                # (candidate rows, further fields) of every call that reached the engine
+        self.RECORD_OPTIONS = frozenset(options)
+        self.calls_seen = []                  # the RecordCall of every call that reached the engine
+        self.record_calls = []                # (candidate rows, further fields) of every call with one candidate field
+        self.union_calls = []                 # (candidate fields, candidates before the union, after it) of every other call
 
     def corpus_fit(self, *args, **kwargs):
         state = super().corpus_fit(*args, **kwargs)
-        state.stats.update(record_calls=0)
+        state.stats.update(record_calls=0, record_union_calls=0, record_floor_calls=0, record_field_score_calls=0,
+                           record_skip_empty_calls=0)
         return state
 
-    def corpus_records_topn(self, state, others, B, B_fields, weights, cand_top_n, cand_threshold, top_n, threshold,
-                            self_join_fix):
-        A = state.matrix
-        self_join = B_fields is None
+    def _part(self, A, B, cand_top_n, cand_threshold, T):
         cand = sp.csr_matrix(self.topn_multiply(A, B, cand_top_n, cand_threshold))      # rows by score descending, then column
-        T = A.dtype.type
         R, N = cand.shape
         stride = max(min(int(cand_top_n), N), 1)
         counts = np.diff(cand.indptr).astype(np.int32)
@@ -36,29 +52,53 @@ class RecordCorpusOracleEngine(PairCorpusOracleEngine):
         for r in range(R):
             cols[r, :counts[r]] = cand.indices[cand.indptr[r]:cand.indptr[r + 1]]
             vals[r, :counts[r]] = cand.data[cand.indptr[r]:cand.indptr[r + 1]]
-        fields = []
-        for k, o in enumerate(others):
-            left = sp.csr_matrix(o.matrix.m)
-            left.sort_indices()
-            right = left if self_join else sp.csr_matrix(B_fields[k].m)
-            right.sort_indices()
-            fields.append(Field(left, right, weights[k + 1], None, None))
-        self.record_calls.append((R, len(fields)))
-        for st in [state] + list(others):
+        return Part(cols, vals, counts)
+
+    def corpus_records(self, state, others, B, B_fields, call, top_n, threshold, self_join_fix, keep_on_device=False):
+        self.calls_seen.append(call)
+        states = [state] + list(others)
+        lefts = [st.matrix for st in states]
+        rights = lefts if B_fields is None else [B] + list(B_fields)
+        T = state.matrix.dtype.type
+        R, N = state.matrix.shape[0], B.shape[0]
+        parts = [self._part(lefts[f], rights[f], k, m, T) for f, (k, m) in zip(call.candidate_fields, call.candidates)]
+        left_m = [_sorted(a.m) for a in lefts]
+        right_m = left_m if B_fields is None else [_sorted(b.m) for b in rights]     # (a self-join: one matrix a field)
+        fields = [Field(a, b, w, None, None) for a, b, w in zip(left_m, right_m, call.weights)]
+        if call.union:
+            cols, vals, counts = ref_union(UnionCase(parts, N, fields[0]))
+            self.union_calls.append((call.candidate_fields, int(sum(p.counts.sum() for p in parts)), int(counts.sum())))
+        else:
+            cols, vals, counts = parts[0]
+            self.record_calls.append((R, len(others)))
+        case = Case(cols, vals, counts, N, call.weights[0], fields[1:], threshold, top_n)
+        if call.skip_empty:
+            out_c, out_v, out_n = ref_rescore_skip_empty(case, fields[0], call.floors)
+        elif call.floors is not None:
+            out_c, out_v, out_n = ref_rescore_floors(case, list(call.floors))
+        else:
+            out_c, out_v, out_n = ref_rescore(case)
+        for st in states:
             st.stats["record_calls"] += 1
-        out_c, out_v, out_n = ref_rescore(Case(cols, vals, counts, N, weights[0], fields, threshold, top_n))
+            st.stats["record_floor_calls"] += call.floors is not None
+            st.stats["record_field_score_calls"] += call.field_scores
+            st.stats["record_skip_empty_calls"] += call.skip_empty
+        for f in call.candidate_fields if call.union else ():
+            states[f].stats["record_union_calls"] += 1
         true_max = int(out_n.max()) if R else 0
         mask = np.arange(out_c.shape[1])[None, :] < out_n[:, None]
         rows = np.repeat(np.arange(R, dtype=np.int64), out_n)
         cc, vv = out_c[mask].astype(np.int64), out_v[mask]
         if self_join_fix:                     # diagonal := 1, symmetrised, rows by column (StringGrouper's own two steps)
             m = StringGrouper._symmetrize_matrix(StringGrouper._fix_diagonal(sp.coo_matrix((vv, (rows, cc)), shape=(R, N))))
-            rows = np.repeat(np.arange(R, dtype=np.int64), np.diff(m.indptr))
-            return rows, m.indices.astype(np.int64), m.data.astype(T), true_max
-        if T == np.float32:                   # the reference's up-cast re-sorts a float32 result's rows by column
+            rows, cc, vv = np.repeat(np.arange(R, dtype=np.int64), np.diff(m.indptr)), m.indices.astype(np.int64), m.data.astype(T)
+        elif T == np.float32:                 # the reference's up-cast re-sorts a float32 result's rows by column
             order = np.lexsort((cc, rows))
             cc, vv = cc[order], vv[order]
-        return rows, cc, vv, true_max
+        planes = None
+        if call.field_scores:                 # ref_pairs_dot of every entry of the list, a plane a field, the corpus's first
+            planes = np.stack([ref_pairs_dot(a.m, b.m, rows, cc) for a, b in zip(lefts, rights)])
+        return (rows, cc, vv, true_max), planes
 
 
 # ------------------------------------------------------------------------------------------ the composed route

@@ -10,7 +10,7 @@ import string_grouper
 import string_grouper_amd as sga
 import string_grouper_amd.engine as E
 from tests._pair_oracle import PairCorpusOracleEngine
-from tests._record_oracle import RecordCorpusOracleEngine, composed_groups, composed_route
+from tests._record_oracle import RecordOracleEngine, composed_groups, composed_route
 from tests.test_corpus_cpu import CORPUS, NEW
 
 DTYPES = [np.float32, np.float64]
@@ -29,7 +29,7 @@ def _restore_engine():
 
 
 def _corpora(**kwargs):
-    eng = RecordCorpusOracleEngine(use_port=True)
+    eng = RecordOracleEngine(use_port=True)
     E.set_engine(eng)
     return sga.Corpus(CORPUS, **kwargs), sga.Corpus(ADDRESS, **kwargs), sga.Corpus(CITY, **kwargs), eng
 
@@ -79,7 +79,7 @@ def test_defaults_equal_shares_self_matches_and_symmetry(dtype):
 
 
 def test_the_module_level_function_builds_calls_and_closes():
-    eng = RecordCorpusOracleEngine(use_port=True)
+    eng = RecordOracleEngine(use_port=True)
     E.set_engine(eng)
     got = sga.match_records([CORPUS, ADDRESS, CITY], weights=W, candidates=CAND, min_similarity=0.3, max_n_matches=3,
                             force_symmetries=False)
@@ -193,7 +193,7 @@ def test_argument_checks():
 
 
 def test_all_candidates_of_a_list_longer_than_the_cap_are_refused():
-    E.set_engine(RecordCorpusOracleEngine(use_port=True))
+    E.set_engine(RecordOracleEngine(use_port=True))
     n = sga.Corpus.MAX_RECORD_CANDIDATES + 1
     long_a = pd.Series([f"a{i:04d}" for i in range(n)])
     long_b = pd.Series([f"b{i:04d}" for i in range(n)])
@@ -208,8 +208,8 @@ def test_all_candidates_of_a_list_longer_than_the_cap_are_refused():
     assert E.get_engine().record_calls == [] and a.stats["record_calls"] == 0
 
 
-class _OverflowingEngine(RecordCorpusOracleEngine):
-    def corpus_records_topn(self, *args, **kwargs):
+class _OverflowingEngine(RecordOracleEngine):
+    def corpus_records(self, *args, **kwargs):
         self.record_calls.append("overflow")
         raise OverflowError("rows x candidates exceed the result index")
 
@@ -249,7 +249,7 @@ def test_engines_that_match_no_records_and_engines_that_changed():
     names, addresses = sga.Corpus(CORPUS), sga.Corpus(ADDRESS)
     with pytest.raises(NotImplementedError, match="matches no records"):
         names.match_records([addresses])
-    E.set_engine(RecordCorpusOracleEngine(use_port=True))
+    E.set_engine(RecordOracleEngine(use_port=True))
     with pytest.raises(RuntimeError, match="engine has changed"):
         names.match_records([addresses])
     mine = sga.Corpus(CORPUS)
@@ -257,7 +257,7 @@ def test_engines_that_match_no_records_and_engines_that_changed():
         mine.match_records([addresses])
     from string_grouper_amd.engine import DistributedHipEngine
     with pytest.raises(NotImplementedError, match="single-GPU"):
-        DistributedHipEngine.corpus_records_topn(None)
+        DistributedHipEngine.corpus_records(None)
 
 
 def test_the_surface():

@@ -1,5 +1,5 @@
-"""CPU tests of ``empty_fields`` on the engine double of tests/_record_empty_oracle.py: the argument checks, the default route
-(``"zero"`` never reaches the engine), the frame with ``"skip"`` against the composed route -- with floors, with duplicates,
+"""CPU tests of ``empty_fields`` on the engine double of tests/_record_oracle.py: the argument checks, the default route
+(``"zero"`` asks the engine for no skip), the frame with ``"skip"`` against the composed route -- with floors, with duplicates,
 through the module-level function --, self matches, symmetry and groups, records without blanks, the counter, and the refusal
 of an engine without the capability.  No GPU."""
 import numpy as np
@@ -8,9 +8,8 @@ import pytest
 
 import string_grouper_amd as sga
 import string_grouper_amd.engine as E
-from tests._record_empty_oracle import RecordEmptyOracleEngine, composed_groups_skip, composed_route_skip, skip_pairs
-from tests._record_floor_oracle import NOT_GIVEN, RecordFloorOracleEngine
-from tests._record_oracle import composed_route
+from tests._record_empty_oracle import composed_groups_skip, composed_route_skip, skip_pairs
+from tests._record_oracle import ALL_OPTIONS, RecordOracleEngine, composed_route
 from tests.test_corpus_cpu import CORPUS, NEW
 from tests.test_match_records_cpu import ADDRESS, CAND, CITY, NEW_ADDRESS, NEW_CITY, W
 
@@ -38,8 +37,8 @@ def _restore_engine():
     E.set_engine(None)
 
 
-def _corpora(engine=RecordEmptyOracleEngine, address=ADDRESS_B, city=CITY_B, **kwargs):
-    eng = engine(use_port=True)
+def _corpora(options=ALL_OPTIONS, address=ADDRESS_B, city=CITY_B, **kwargs):
+    eng = RecordOracleEngine(use_port=True, options=options)
     E.set_engine(eng)
     return sga.Corpus(CORPUS, **kwargs), sga.Corpus(address, **kwargs), sga.Corpus(city, **kwargs), eng
 
@@ -57,7 +56,8 @@ def test_the_frame_with_skip_is_the_composed_route_s(dtype):
             want = composed_route_skip(names, others, W, CAND, thr, top_n, floors)
             pd.testing.assert_frame_equal(got, want)
             assert len(got)
-    assert eng.skip_seen == [True] * 9 and eng.floors_seen[0] is NOT_GIVEN and eng.floors_seen[-1] == [0.2, None, 0.5]
+    seen = eng.calls_seen
+    assert [c.skip_empty for c in seen] == [True] * 9 and seen[0].floors is None and seen[-1].floors == (0.2, None, 0.5)
     # the option decides: a pair with a blank address stays that the blank took under the threshold, and a floor on the
     # address is not held against it
     zero = names.match_records(others, weights=W, candidates=CAND, min_similarity=0.45, force_symmetries=False)
@@ -122,17 +122,17 @@ def test_zero_is_the_call_as_it_was_and_the_counter():
     names.match_records(others, weights=W, candidates=CAND, min_similarity=0.3, empty_fields="zero")
     names.group_similar_records(others, empty_fields="zero")
     sga.match_records([CORPUS, ADDRESS_B, CITY_B], empty_fields="zero")
-    assert eng.skip_seen == [NOT_GIVEN] * 4                                          # the keyword is not even passed
+    assert [c.skip_empty for c in eng.calls_seen] == [False] * 4                     # the descriptions do not ask to skip
     assert all(c.stats["record_skip_empty_calls"] == 0 and c.stats["record_calls"] == 3 for c in (names, addresses, cities))
     names.match_records(others, empty_fields="skip")
     names.group_similar_records(others, empty_fields="skip", field_min_similarity=[None, 0.5, None])
-    assert eng.skip_seen[4:] == [True, True]
+    assert [c.skip_empty for c in eng.calls_seen[4:]] == [True, True]
     assert all(c.stats["record_skip_empty_calls"] == 2 and c.stats["record_calls"] == 5 and c.stats["record_floor_calls"] == 1
                for c in (names, addresses, cities))
 
 
 def test_an_engine_double_without_the_keyword_still_serves_zero_and_refuses_skip():
-    names, addresses, cities, eng = _corpora(engine=RecordFloorOracleEngine)
+    names, addresses, cities, eng = _corpora(options=ALL_OPTIONS - {"skip_empty"})
     others = [addresses, cities]
     got = names.match_records(others, weights=W, candidates=CAND, min_similarity=0.3, force_symmetries=False, empty_fields="zero")
     pd.testing.assert_frame_equal(got, composed_route(names, others, W, CAND, 0.3, 20))
@@ -142,9 +142,7 @@ def test_an_engine_double_without_the_keyword_still_serves_zero_and_refuses_skip
             call(others, empty_fields="skip")
     assert eng.record_calls == calls                                                 # nothing reached the engine
     with pytest.raises(NotImplementedError, match="single-GPU"):
-        E.DistributedHipEngine.corpus_records_topn(None, skip_empty=True)
-    with pytest.raises(NotImplementedError, match="single-GPU"):
-        E.DistributedHipEngine.corpus_records_union_topn(None, skip_empty=True)
+        E.DistributedHipEngine.corpus_records(None)
 
 
 def test_argument_checks():
@@ -161,4 +159,4 @@ def test_argument_checks():
         sga.match_records([CORPUS, ADDRESS_B, CITY_B], empty_fields=None)
     with pytest.raises(ValueError, match="empty_fields"):
         sga.match_records([CORPUS, ADDRESS_B, CITY_B], empty_fields="none")
-    assert eng.skip_seen == []
+    assert eng.calls_seen == []

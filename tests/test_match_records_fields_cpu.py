@@ -1,5 +1,5 @@
-"""CPU tests of ``field_min_similarity`` and ``field_similarities`` on the engine double of tests/_record_floor_oracle.py:
-every argument check, the default route (the engine methods are called with the arguments they always got), the frame with
+"""CPU tests of ``field_min_similarity`` and ``field_similarities`` on the engine double of tests/_record_oracle.py:
+every argument check, the default route (the descriptions that reach the engine ask for no new option), the frame with
 floors against the composed route with floors, the groups, the field columns against ``pair_similarities`` on the double, the
 counters, and the refusal of an engine without the capability.  No GPU."""
 import numpy as np
@@ -8,9 +8,8 @@ import pytest
 
 import string_grouper_amd as sga
 import string_grouper_amd.engine as E
-from tests._record_floor_oracle import (NOT_GIVEN, RecordFloorOracleEngine, combined_pairs_floors, composed_groups_floors,
-                                        composed_route_floors)
-from tests._record_oracle import RecordCorpusOracleEngine, composed_route
+from tests._record_floor_oracle import combined_pairs_floors, composed_groups_floors, composed_route_floors
+from tests._record_oracle import ALL_OPTIONS, RecordOracleEngine, composed_route
 from tests.test_corpus_cpu import CORPUS, NEW
 from tests.test_match_records_cpu import ADDRESS, CAND, CITY, NEW_ADDRESS, NEW_CITY, W
 
@@ -23,8 +22,8 @@ def _restore_engine():
     E.set_engine(None)
 
 
-def _corpora(engine=RecordFloorOracleEngine, **kwargs):
-    eng = engine(use_port=True)
+def _corpora(options=ALL_OPTIONS, **kwargs):
+    eng = RecordOracleEngine(use_port=True, options=options)
     E.set_engine(eng)
     return sga.Corpus(CORPUS, **kwargs), sga.Corpus(ADDRESS, **kwargs), sga.Corpus(CITY, **kwargs), eng
 
@@ -51,7 +50,7 @@ def test_the_frame_with_floors_is_the_composed_route_s(dtype):
             pd.testing.assert_frame_equal(got, want)
         if any(x for x in floors):
             assert 0 < len(want) and len(composed_route_floors(names, others, W, CAND, 0.15, 20, floors)) < len(plain)
-    assert eng.floors_seen[-1] == [None, 0.0, None] and all(isinstance(x, float) for x in eng.floors_seen[0] if x is not None)
+    assert eng.calls_seen[-1].floors == (None, 0.0, None) and all(isinstance(x, float) for x in eng.calls_seen[0].floors if x is not None)
     # the floors act BEFORE the cut: a pair the floor lets through takes the place of one it refused
     moved = 0
     for top_n in (2, 3):                                                             # (the first place is the record itself)
@@ -97,17 +96,17 @@ def test_without_the_option_the_engine_is_called_as_before():
     names.match_records(others, weights=W, candidates=CAND, min_similarity=0.3)
     names.match_records(others, weights=W, candidates=CAND, min_similarity=0.3, field_min_similarity=None)
     names.group_similar_records(others)
-    assert eng.floors_seen == [NOT_GIVEN] * 3                                        # the keyword is not even passed
+    assert [c.floors for c in eng.calls_seen] == [None] * 3                          # the descriptions carry no floors
     assert all(c.stats["record_floor_calls"] == 0 and c.stats["record_calls"] == 3 for c in (names, addresses, cities))
     names.match_records(others, field_min_similarity=[None, 0.5, None])
     names.group_similar_records(others, field_min_similarity=(0.1, None, None))
-    assert eng.floors_seen[3:] == [[None, 0.5, None], [0.1, None, None]]
+    assert [c.floors for c in eng.calls_seen[3:]] == [(None, 0.5, None), (0.1, None, None)]
     assert all(c.stats["record_floor_calls"] == 2 and c.stats["record_calls"] == 5 for c in (names, addresses, cities))
     assert all(c.stats["pair_calls"] == 0 and c.stats["compactions"] == 0 for c in (names, addresses, cities))
 
 
 def test_an_engine_double_without_the_keyword_still_serves_the_old_call_and_refuses_the_new():
-    names, addresses, cities, eng = _corpora(engine=RecordCorpusOracleEngine)
+    names, addresses, cities, eng = _corpora(options=ALL_OPTIONS - {"floors"})
     others = [addresses, cities]
     got = names.match_records(others, weights=W, candidates=CAND, min_similarity=0.3, force_symmetries=False)
     pd.testing.assert_frame_equal(got, composed_route(names, others, W, CAND, 0.3, 20))
@@ -117,9 +116,7 @@ def test_an_engine_double_without_the_keyword_still_serves_the_old_call_and_refu
             call(others, field_min_similarity=[None, 0.5, None])
     assert eng.record_calls == calls                                                 # nothing reached the engine
     with pytest.raises(NotImplementedError, match="single-GPU"):
-        E.DistributedHipEngine.corpus_records_topn(None, floors=[None, 0.5])
-    with pytest.raises(NotImplementedError, match="single-GPU"):
-        E.DistributedHipEngine.corpus_records_union_topn(None, floors=[None, 0.5])
+        E.DistributedHipEngine.corpus_records(None)
 
 
 # ------------------------------------------------------------------------------------------ argument checks
@@ -139,11 +136,11 @@ def test_argument_checks():
         for bad in (0.5, "abc", 3):
             with pytest.raises(TypeError, match="sequence"):
                 call(others, field_min_similarity=bad)
-    assert eng.floors_seen == []
+    assert eng.calls_seen == []
     for good in ([0, None, 1], (np.float32(0.5), np.int64(0), -1.5), np.array([0.25, 0.5, 0.75]), [None, None, None]):
         names.match_records(others, field_min_similarity=good)
-    assert len(eng.floors_seen) == 4
-    assert eng.floors_seen[-1] is NOT_GIVEN and names.stats["record_floor_calls"] == 3   # nothing but None: the call it always was
+    assert len(eng.calls_seen) == 4
+    assert eng.calls_seen[-1].floors is None and names.stats["record_floor_calls"] == 3   # nothing but None: the call it always was
     with pytest.raises(ValueError, match="one a field"):
         sga.match_records([CORPUS, ADDRESS, CITY], field_min_similarity=[0.5])
     with pytest.raises(TypeError, match="bool"):
@@ -237,10 +234,10 @@ def test_without_field_similarities_the_engine_is_called_as_before_and_the_check
     names.match_records(others, weights=W, candidates=CAND, min_similarity=0.3)
     names.match_records(others, weights=W, candidates=CAND, min_similarity=0.3, field_similarities=False)
     names.group_similar_records(others)
-    assert eng.field_scores_seen == [NOT_GIVEN] * 3 == eng.floors_seen            # neither keyword is even passed
+    assert [(c.field_scores, c.floors) for c in eng.calls_seen] == [(False, None)] * 3    # neither option is asked for
     assert all(c.stats["record_field_score_calls"] == 0 for c in (names, addresses, cities))
     frame = names.match_records(others, field_similarities=True)
-    assert eng.field_scores_seen[3:] == [True] and eng.floors_seen[3:] == [NOT_GIVEN]
+    assert [(c.field_scores, c.floors) for c in eng.calls_seen[3:]] == [(True, None)]
     assert all(c.stats["record_field_score_calls"] == 1 and c.stats["pair_calls"] == 0 for c in (names, addresses, cities))
     assert {"similarity_0", "similarity_1", "similarity_2"} <= set(frame.columns)
     for bad in (1, 0, None, "yes", [True]):
@@ -248,11 +245,11 @@ def test_without_field_similarities_the_engine_is_called_as_before_and_the_check
             names.match_records(others, field_similarities=bad)
     with pytest.raises(TypeError):                                                   # there is no frame of pairs
         names.group_similar_records(others, field_similarities=True)
-    assert len(eng.field_scores_seen) == 4
+    assert len(eng.calls_seen) == 4
 
 
 def test_an_engine_double_without_field_scores_refuses_field_similarities():
-    names, addresses, cities, eng = _corpora(engine=RecordCorpusOracleEngine)
+    names, addresses, cities, eng = _corpora(options=ALL_OPTIONS - {"field_scores"})
     others = [addresses, cities]
     calls = list(eng.record_calls)
     with pytest.raises(NotImplementedError, match="field_similarities"):
@@ -260,6 +257,4 @@ def test_an_engine_double_without_field_scores_refuses_field_similarities():
     assert eng.record_calls == calls                                                 # nothing reached the engine
     names.match_records(others, field_similarities=False)
     with pytest.raises(NotImplementedError, match="single-GPU"):
-        E.DistributedHipEngine.corpus_records_topn(None, field_scores=True)
-    with pytest.raises(NotImplementedError, match="single-GPU"):
-        E.DistributedHipEngine.corpus_records_union_topn(None, field_scores=True)
+        E.DistributedHipEngine.corpus_records(None)

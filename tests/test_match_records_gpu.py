@@ -202,4 +202,4 @@ def N_live_handles():
 
 def test_the_multi_gpu_engine_refuses():
     with pytest.raises(NotImplementedError, match="single-GPU"):
-        E.DistributedHipEngine.corpus_records_topn(None)
+        E.DistributedHipEngine.corpus_records(None)

@@ -1,5 +1,5 @@
 """CPU tests of ``candidate_fields`` -- record matching with candidates from several fields -- on the engine double of
-tests/_record_union_oracle.py: every new argument check, the default's route, the frame against the composed union route
+tests/_record_oracle.py: every new argument check, the default's route, the frame against the composed union route
 (match_strings a candidate field, the union in pandas, pair_similarities on every field, the numpy chain), the counters, and the
 pair that only an address finds.  No GPU."""
 import numpy as np
@@ -8,8 +8,8 @@ import pytest
 
 import string_grouper_amd as sga
 import string_grouper_amd.engine as E
-from tests._record_oracle import RecordCorpusOracleEngine, composed_route
-from tests._record_union_oracle import RecordUnionOracleEngine, composed_union_groups, composed_union_route
+from tests._record_oracle import ALL_OPTIONS, RecordOracleEngine, composed_route
+from tests._record_union_oracle import composed_union_groups, composed_union_route
 from tests.test_corpus_cpu import CORPUS, NEW
 from tests.test_match_records_cpu import ADDRESS, CAND, CITY, NEW_ADDRESS, NEW_CITY, W
 
@@ -27,7 +27,7 @@ def _restore_engine():
 
 
 def _corpora(series=(CORPUS, ADDRESS, CITY), **kwargs):
-    eng = RecordUnionOracleEngine(use_port=True)
+    eng = RecordOracleEngine(use_port=True)
     E.set_engine(eng)
     return [sga.Corpus(s, **kwargs) for s in series] + [eng]
 
@@ -125,7 +125,7 @@ def test_the_default_takes_the_route_it_took_and_counts_as_it_did():
 
 
 def test_an_engine_without_the_union_refuses_it_and_serves_the_default():
-    E.set_engine(RecordCorpusOracleEngine(use_port=True))
+    E.set_engine(RecordOracleEngine(use_port=True, options=ALL_OPTIONS - {"union"}))
     names, addresses = sga.Corpus(CORPUS), sga.Corpus(ADDRESS)
     names.match_records([addresses], candidate_fields=(0,))
     with pytest.raises(NotImplementedError, match="unites no candidates"):
@@ -134,11 +134,11 @@ def test_an_engine_without_the_union_refuses_it_and_serves_the_default():
         names.group_similar_records([addresses], candidate_fields=(0, 1))
     from string_grouper_amd.engine import DistributedHipEngine
     with pytest.raises(NotImplementedError, match="single-GPU"):
-        DistributedHipEngine.corpus_records_union_topn(None)
+        DistributedHipEngine.corpus_records(None)
 
 
-class _OverflowingEngine(RecordUnionOracleEngine):
-    def corpus_records_union_topn(self, *args, **kwargs):
+class _OverflowingEngine(RecordOracleEngine):
+    def corpus_records(self, *args, **kwargs):
         self.union_calls.append("overflow")
         raise OverflowError("rows x candidates exceed the result index")
 
