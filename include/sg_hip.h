@@ -62,9 +62,9 @@ const char *sg_last_error(void);
  * sg_topn_drop_columns, sg_device_upload; 7 -- sg_topn_concat_rows, sg_topn_forget, sg_topn_put_rows, sg_csr_take_rows,
  * sg_device_download; 8 -- sg_csr_row_norms, sg_csr_vectoriser_words, sg_csr_column_counts, sg_vec_reweigh; 9 --
  * sg_csr_pairs_dot; 10 -- sg_topn_rescore, sg_rescore_field; 11 -- sg_topn_union; 12 -- sg_topn_rescore_floors,
- * sg_matchlist_field_scores; 13 -- sg_topn_rescore_skip_empty); a binding compares it
- * with the value it was written for right after loading the library. */
-#define SG_ABI_VERSION 13
+ * sg_matchlist_field_scores; 13 -- sg_topn_rescore_skip_empty; 14 -- sg_topn_rescore takes one sg_rescore_call, the two
+ * entries of 12 and 13 are gone); a binding compares it with the value it was written for right after loading the library. */
+#define SG_ABI_VERSION 14
 int sg_abi_version(void);
 int sg_device_count(int *count);
 /* hip_stream: a hipStream_t to launch on (e.g. torch.cuda.current_stream().cuda_stream), or NULL
@@ -477,7 +477,8 @@ int sg_topn_put_rows(sg_ctx *ctx, sg_topn *r, const int32_t *d_rows, int64_t n_r
  * field's multiply found (or several fields' multiplies, united by sg_topn_union below) -- cand: R rows, N columns, stride S,
  * counts -- scores every one of them on F further fields, weighs
  * the scores into one, and filters, orders and cuts every row anew.  Candidates never leave the device.  (The reference has no
- * analogue: it matches one column of strings, string_grouper.py:55-153; its users combine fields in pandas.)
+ * analogue: it matches one column of strings, string_grouper.py:55-153; its users combine fields in pandas.)  One call
+ * description, sg_rescore_call below, says all of it: the plain statement first, then what floors and empty fields change.
  *
  * A field f = 1 .. F is two matrices A_f (the left records' rows) and B_f (the right records'; the same handle for a
  * self-join), a weight, and per side an optional list of dead PHYSICAL rows (DEVICE memory, ascending and distinct -- the
@@ -495,56 +496,36 @@ int sg_topn_put_rows(sg_ctx *ctx, sg_topn *r, const int32_t *d_rows, int64_t n_r
  *                      j ascending, and the first min(top_n, S) of them stay; the bits written are c's own.
  * *out has R rows, N columns and the stride min(top_n, S); cand is only read.  The result feeds sg_matchlist_build like a
  * multiply's.
- * Refusals (SG_ERR_BADARG; nothing is returned, and the next call works):
- *   seen on the host     n_fields outside 1 .. 7; top_n < 1; S > 2048; a weight that is not finite (in T); a field whose
- *                        matrices differ from cand in value type, or from each other in columns; rows(A_f) - n_dead_a != R or
- *                        rows(B_f) - n_dead_b != N;
- *   seen on the device   a candidate column outside [0, N) -- nothing is read for it --, or a row of a field matrix that a
- *                        candidate reads whose columns are not strictly ascending, for matrices not known to be sorted (as
- *                        sg_csr_pairs_dot): one status word, a bit a cause, the call's only read-back. */
-typedef struct {
-    const sg_csr *A, *B;
-    double weight;
-    const int32_t *d_dead_a; /* NULL: none */
-    int32_t n_dead_a;
-    const int32_t *d_dead_b;
-    int32_t n_dead_b;
-} sg_rescore_field;
-int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
-                    double threshold, int32_t top_n, sg_topn **out);
-/* sg_topn_rescore_floors: sg_topn_rescore with a floor a FIELD.  "The city must agree" is a condition on one field, not on the
- * weighed sum: a pair with name 1.0, address 1.0 and city 0.0 reaches 0.8 at weights 0.5 / 0.3 / 0.2.  (The reference has no
- * analogue: it matches one column of strings, string_grouper.py:55-153; its users filter per-field frames in pandas.)
  *
- * floor0 is the floor m_0 of the score cand carries (s_0 = vals[i, e], as it is), floors[f - 1] the floor m_f of further field
- * f = 1 .. n_fields; a NaN means the field has no floor.  Everything is sg_topn_rescore's -- s_f, c, the order, the cut -- but
- * the filter:
+ * Floors (`floors` not NULL): a floor a FIELD.  "The city must agree" is a condition on one field, not on the weighed sum: a
+ * pair with name 1.0, address 1.0 and city 0.0 reaches 0.8 at weights 0.5 / 0.3 / 0.2.  (The reference has no analogue: it
+ * matches one column of strings, string_grouper.py:55-153; its users filter per-field frames in pandas.)
+ * floors[0] is the floor m_0 of the score cand carries (s_0 = vals[i, e], as it is), floors[f] the floor m_f of further field
+ * f = 1 .. n_fields; a NaN means the field has no floor.  Everything is the plain statement's -- s_f, c, the order, the cut --
+ * but the filter:
  *   filter             kept when c > (T)threshold AND s_f > (T)m_f for every field f with a floor.  Strict, as the threshold
  *                      is; a NaN score never passes a floor.  Floors act BEFORE the cut: the first min(top_n, S) of the
  *                      entries that passed stay.
  * A candidate that a floor refuses on field f is scored on no field f' > f: no row of B_f' is read for it.  So the column order
  * of a matrix not known to be sorted is looked at for the rows that are READ -- a row that only refused candidates name is not
- * looked at, and a call sg_topn_rescore would refuse for that row is served.  A NaN that the data produces (no floor on that
- * field) refuses nothing by itself: the candidate is scored on, its c is a NaN and the filter drops it, as in sg_topn_rescore.
- * With every floor a NaN the result is sg_topn_rescore's to the bit.
- * Refusals: those of sg_topn_rescore, and a floor that is infinite (SG_ERR_BADARG).  A candidate's column is range-checked
+ * looked at, and a call that the plain statement would refuse for that row is served.  A NaN that the data produces (no floor
+ * on that field) refuses nothing by itself: the candidate is scored on, its c is a NaN and the filter drops it, as without
+ * floors.  With every floor a NaN the result is the plain statement's to the bit.  A candidate's column is range-checked
  * before any floor is held against it: a column outside [0, N) refuses the call even where the primary's floor would have
- * refused the candidate. */
-int sg_topn_rescore_floors(sg_ctx *ctx, const sg_topn *cand, double w0, double floor0, const sg_rescore_field *fields,
-                           const double *floors, int32_t n_fields, double threshold, int32_t top_n, sg_topn **out);
-/* sg_topn_rescore_skip_empty: sg_topn_rescore_floors with a record's EMPTY fields left out of the score.  A blank address is an
- * empty row: its score is +0.0 and enters the weighed sum with its full weight, so two records with identical names and cities,
- * one of them without an address, reach 0.7 at weights 0.5 / 0.3 / 0.2; record linkage expects that a field unknown for a pair
- * takes no part in that pair and that its weight is shared among the fields that are known.  (The reference has no analogue: it
- * matches one column of strings, string_grouper.py:55-153; its users fill blanks with "" and combine fields in pandas.)
+ * refused the candidate.
  *
+ * Empty fields (`skip_empty` not 0): a record's EMPTY fields left out of the score.  A blank address is an empty row: its score
+ * is +0.0 and enters the weighed sum with its full weight, so two records with identical names and cities, one of them without
+ * an address, reach 0.7 at weights 0.5 / 0.3 / 0.2; record linkage expects that a field unknown for a pair takes no part in
+ * that pair and that its weight is shared among the fields that are known.  (The reference has no analogue: it matches one
+ * column of strings, string_grouper.py:55-153; its users fill blanks with "" and combine fields in pandas.)
  * Field f = 0 .. n_fields is EMPTY FOR THE PAIR (i, j) when physical row a of A_f or physical row b of B_f has no entries:
- * indptr[a + 1] == indptr[a], a and b from the live numbers i and j through the field's dead lists as in sg_topn_rescore.  A row
- * that holds entries is not empty whatever its values are (stored zeros included), and even if the product is 0.  Field 0 is the
- * field whose score cand carries: `primary` is its A, B and dead-row lists with the meaning they have in sg_topn_rescore (its
- * weight is ignored; only the row bounds are read: nothing is merged, so no column order is looked at and no status bit is
- * added).  primary NULL: field 0 is never empty.  floor0, floors: as in sg_topn_rescore_floors; floors NULL: no further field has
- * a floor.  Everything is sg_topn_rescore_floors' -- s_f, W_f = (T)w_f, the order, the cut -- but:
+ * indptr[a + 1] == indptr[a], a and b from the live numbers i and j through the field's dead lists as above.  A row that holds
+ * entries is not empty whatever its values are (stored zeros included), and even if the product is 0.  Field 0 is the field
+ * whose score cand carries: `primary` is its A, B and dead-row lists with the meaning they have in a further field (its weight
+ * is ignored; only the row bounds are read: nothing is merged, so no column order is looked at and no status bit is added).
+ * primary NULL: field 0 is never empty.  Floors as above; floors NULL: no field has a floor.  Everything is as above, floors
+ * included -- s_f, W_f = (T)w_f, the order, the cut -- but:
  *   combined score     c  = +0.0;  for f = 0 .. F, f not empty for the pair:  c  = rn(c  + rn(W_f * s_f))
  *                      wp = +0.0;  for f = 0 .. F, f not empty for the pair:  wp = rn(wp + W_f)
  *                      wt = +0.0;  for f = 0 .. F:                            wt = rn(wt + W_f)
@@ -561,11 +542,35 @@ int sg_topn_rescore_floors(sg_ctx *ctx, const sg_topn *cand, double w0, double f
  *                      then column, the first min(top_n, S).
  * Nothing of B_f is read for a pair whose left row is empty in field f: the whole row of candidates skips that field; a pair
  * whose right row alone is empty is not merged either.  So, as with floors, column order is looked at for the rows that are READ.
- * Refusals: those of sg_topn_rescore_floors, and a primary that check_pair_field refuses as an unweighed field (a null matrix,
- * another value type, matrices that differ in columns, rows(A) - n_dead_a != R or rows(B) - n_dead_b != N; SG_ERR_BADARG). */
-int sg_topn_rescore_skip_empty(sg_ctx *ctx, const sg_topn *cand, double w0, double floor0, const sg_rescore_field *primary,
-                               const sg_rescore_field *fields, const double *floors, int32_t n_fields, double threshold,
-                               int32_t top_n, sg_topn **out);
+ *
+ * Refusals (SG_ERR_BADARG; nothing is returned, and the next call works):
+ *   seen on the host     n_fields outside 1 .. 7; top_n < 1; S > 2048; a weight that is not finite (in T); a field whose
+ *                        matrices differ from cand in value type, or from each other in columns; rows(A_f) - n_dead_a != R or
+ *                        rows(B_f) - n_dead_b != N; a floor that is infinite; a primary without skip_empty; a primary that
+ *                        the same checks refuse as an unweighed field (a null matrix, another value type, matrices that
+ *                        differ in columns, rows(A) - n_dead_a != R or rows(B) - n_dead_b != N);
+ *   seen on the device   a candidate column outside [0, N) -- nothing is read for it --, or a row of a field matrix that a
+ *                        candidate reads whose columns are not strictly ascending, for matrices not known to be sorted (as
+ *                        sg_csr_pairs_dot): one status word, a bit a cause, the call's only read-back. */
+typedef struct {
+    const sg_csr *A, *B;
+    double weight;
+    const int32_t *d_dead_a; /* NULL: none */
+    int32_t n_dead_a;
+    const int32_t *d_dead_b;
+    int32_t n_dead_b;
+} sg_rescore_field;
+typedef struct {
+    double w0;                       /* weight of the score cand carries */
+    const sg_rescore_field *fields;  /* the further fields 1 .. n_fields */
+    int32_t n_fields;
+    const double *floors;            /* NULL: no floor; else n_fields + 1 of them, the carried score's first, NaN: none */
+    int32_t skip_empty;              /* not 0: a field empty for a pair takes no part in it */
+    const sg_rescore_field *primary; /* read with skip_empty only; NULL: field 0 is never empty; its weight is ignored */
+    double threshold;
+    int32_t top_n;
+} sg_rescore_call;
+int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, const sg_rescore_call *call, sg_topn **out);
 /* sg_topn_union: the candidates of SEVERAL fields' multiplies as one candidate result.  Two records that agree on address and
  * city but whose names fall below the candidate threshold are never compared when the names alone find the candidates; record
  * linkage takes the candidates from the union of several fields' matches instead.  (The reference has no analogue: it matches

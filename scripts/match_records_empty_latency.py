@@ -1,5 +1,5 @@
 """What leaving a record's empty fields out costs through Corpus.match_records(empty_fields="skip") (decided on the device:
-sg_topn_rescore_skip_empty) against the composed route it replaces, in one session.  The set-up is
+skip_empty of sg_topn_rescore) against the composed route it replaces, in one session.  The set-up is
 scripts/match_records_latency.py's: three SynthNames fields arranged by a seeded coin, fp32, candidates at 0.6 / top 50, final
 0.8 / top 20, weights 0.5 / 0.3 / 0.2, force_symmetries=False on every route -- and a fifth of the addresses set to "".
 

@@ -1,5 +1,5 @@
 """What a floor on ONE field costs through Corpus.match_records(field_min_similarity=...) (decided on the device:
-sg_topn_rescore_floors) against the composed route it replaces, and what the call WITHOUT the option costs on this build, in one
+the floors of sg_topn_rescore) against the composed route it replaces, and what the call WITHOUT the option costs on this build, in one
 session.  The set-up is scripts/match_records_latency.py's: three SynthNames fields arranged by a seeded coin, fp32, candidates at
 0.6 / top 50, final 0.8 / top 20, weights 0.5 / 0.3 / 0.2, force_symmetries=False on every route.
 

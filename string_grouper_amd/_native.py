@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("SG_HIP_LIB") or os.path.join(_HERE, "libsg_hip.so")
 
 SG_OK, SG_ERR_BADARG, SG_ERR_OOM, SG_ERR_OVERFLOW, SG_ERR_HIP, SG_ERR_NODEVICE, SG_ERR_UNSUPPORTED = range(7)
 SG_F32, SG_F64 = 0, 1
-ABI_VERSION = 13       # include/sg_hip.h: SG_ABI_VERSION
+ABI_VERSION = 14       # include/sg_hip.h: SG_ABI_VERSION
 SG_K_TOKENIZE, SG_K_WEIGHT, SG_K_POSTINGS, SG_K_SPGEMM, SG_K_ZIP, SG_K_VOCAB, SG_K_SPGEMM_KERNEL, SG_K_COUNT = range(8)
 KERNEL_NAMES = ("tokenize", "weight", "postings", "spgemm_topn", "zip", "vocab", "spgemm_kernel")
 
@@ -39,6 +39,13 @@ def _rescore_field(A, B, weight, dead_a, dead_b) -> SgRescoreField:
     a, b = (getattr(m.h, "value", m.h) for m in (A, B))                  # (a handle is a c_void_p or its integer)
     dead = [(None, 0) if d is None else (d.ptr, len(d)) for d in (dead_a, dead_b)]
     return SgRescoreField(a, b, float(weight), *dead[0], *dead[1])
+
+
+class SgRescoreCall(C.Structure):
+    """include/sg_hip.h: sg_rescore_call"""
+    _fields_ = [("w0", C.c_double), ("fields", C.POINTER(SgRescoreField)), ("n_fields", C.c_int32),
+                ("floors", C.POINTER(C.c_double)), ("skip_empty", C.c_int32), ("primary", C.POINTER(SgRescoreField)),
+                ("threshold", C.c_double), ("top_n", C.c_int32)]
 
 
 class SgStats(C.Structure):
@@ -130,11 +137,7 @@ ABI = {
     "sg_csr_take_rows": (C.c_int, [_P, _P, _P, C.c_int64, _PP]),
     "sg_csr_rowwise_dot": (C.c_int, [_P, _P, _P, _P]),
     "sg_csr_pairs_dot": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _P]),
-    "sg_topn_rescore": (C.c_int, [_P, _P, C.c_double, C.POINTER(SgRescoreField), C.c_int32, C.c_double, C.c_int32, _PP]),
-    "sg_topn_rescore_floors": (C.c_int, [_P, _P, C.c_double, C.c_double, C.POINTER(SgRescoreField), C.POINTER(C.c_double), C.c_int32,
-                                         C.c_double, C.c_int32, _PP]),
-    "sg_topn_rescore_skip_empty": (C.c_int, [_P, _P, C.c_double, C.c_double, C.POINTER(SgRescoreField), C.POINTER(SgRescoreField),
-                                             C.POINTER(C.c_double), C.c_int32, C.c_double, C.c_int32, _PP]),
+    "sg_topn_rescore": (C.c_int, [_P, _P, C.POINTER(SgRescoreCall), _PP]),
     "sg_topn_union": (C.c_int, [_P, C.POINTER(_P), C.c_int32, C.POINTER(SgRescoreField), _PP]),
     "sg_matchlist_field_scores": (C.c_int, [_P, _P, C.POINTER(SgRescoreField), C.c_int32, _P]),
     "sg_csr_row_norms": (C.c_int, [_P, _PP]),
@@ -888,42 +891,29 @@ class Context:
         most ``top_n`` a row.  ``cand`` is only read.  A refusal of the device (a column outside the result, an unsorted row
         that a candidate reads): ValueError.
 
-        ``floors``: None -- sg_topn_rescore -- or one entry a field, the candidates' own score first (``1 + len(fields)`` of
-        them), each None (no floor) or a number: a candidate is kept only when also ``s_f > floor_f`` on every field that has
-        one, before the cut (sg_topn_rescore_floors).  An infinite floor: ValueError.
+        ``floors``: None or one entry a field, the candidates' own score first (``1 + len(fields)`` of them), each None (no
+        floor) or a number: a candidate is kept only when also ``s_f > floor_f`` on every field that has one, before the cut.
+        An infinite floor: ValueError.
 
         ``skip_empty``: a field that is empty for a pair -- the physical row of either side has no entries -- is left out of
         that pair's sum, its weight is shared among the others (``c * wt / wp``, every step rounded on its own, one division),
-        its floor is not held against the pair, and a pair all of whose fields are empty is dropped
-        (sg_topn_rescore_skip_empty).  ``primary``: ``(A, B, dead_a, dead_b)`` of the field whose score ``cand`` carries, as
-        ``topn_union`` takes it -- only its row bounds are read; None: that field is never empty.  Without ``skip_empty`` a
-        ``primary`` is a ValueError."""
-        if primary is not None and not skip_empty:
-            raise ValueError("a primary field is read with skip_empty alone")
+        its floor is not held against the pair, and a pair all of whose fields are empty is dropped.  ``primary``: ``(A, B,
+        dead_a, dead_b)`` of the field whose score ``cand`` carries, as ``topn_union`` takes it -- only its row bounds are
+        read; None: that field is never empty.  Without ``skip_empty`` a ``primary`` is a ValueError (the library's)."""
         fields = list(fields)
-        arr = (SgRescoreField * max(len(fields), 1))()
-        for k, field in enumerate(fields):
-            arr[k] = _rescore_field(*field)
-        out = C.c_void_p()
-        if skip_empty:
-            floors = [None] * (len(fields) + 1) if floors is None else list(floors)
+        call = SgRescoreCall(w0=float(w0), n_fields=len(fields), skip_empty=bool(skip_empty), threshold=float(threshold),
+                             top_n=int(top_n))
+        call.fields = (SgRescoreField * max(len(fields), 1))(*[_rescore_field(*field) for field in fields])
         if floors is not None:
             floors = [float("nan") if m is None else float(m) for m in floors]
             if len(floors) != len(fields) + 1:
                 raise ValueError(f"{len(floors)} floors for {len(fields) + 1} fields: one a field is expected, the candidates' own first")
-            rest = (C.c_double * max(len(fields), 1))(*floors[1:])
-            if skip_empty:
-                first = None
-                if primary is not None:
-                    A, B, dead_a, dead_b = primary
-                    first = C.byref(_rescore_field(A, B, 1.0, dead_a, dead_b))
-                check(lib().sg_topn_rescore_skip_empty(self.h, cand.h, float(w0), floors[0], first, arr, rest, len(fields),
-                                                       float(threshold), int(top_n), C.byref(out)))
-                return TopN(self, out)
-            check(lib().sg_topn_rescore_floors(self.h, cand.h, float(w0), floors[0], arr, rest, len(fields), float(threshold),
-                                               int(top_n), C.byref(out)))
-            return TopN(self, out)
-        check(lib().sg_topn_rescore(self.h, cand.h, float(w0), arr, len(fields), float(threshold), int(top_n), C.byref(out)))
+            call.floors = (C.c_double * len(floors))(*floors)
+        if primary is not None:
+            A, B, dead_a, dead_b = primary
+            call.primary = C.pointer(_rescore_field(A, B, 1.0, dead_a, dead_b))
+        out = C.c_void_p()
+        check(lib().sg_topn_rescore(self.h, cand.h, C.byref(call), C.byref(out)))
         return TopN(self, out)
 
     def topn_union(self, parts, primary) -> TopN:

@@ -552,7 +552,7 @@ class CorpusEngine:
                 cand = before.own(self._record_candidates(states, rights, call, self_join, field))
                 fields = [field(k) for k in range(1, call.n_fields)]
                 weighed = [(rows, right, w, dead_a, dead_b) for (rows, right, dead_a, dead_b), w in zip(fields, call.weights[1:])]
-                # one call: its options choose the library's entry (no floors and no skip: sg_topn_rescore, as always)
+                # one call, the library's one entry: the floors and skip_empty go along in its call description
                 res = s.own(self.ctx.topn_rescore(cand, call.weights[0], weighed, threshold, top_n, floors=call.floors,
                                                   skip_empty=call.skip_empty, primary=field(0) if call.skip_empty else None))
             self._record_count(states, call)

@@ -13,11 +13,13 @@
 // reading the row's few scores from cache for a row of at most 64 candidates (rows of name lists hold about four), a block
 // with the row in LDS for the rows above that (up to 2 048 entries), which the first kernel lists on the device.
 //
-// sg_topn_rescore_floors: the same two launches with a floor a field in the filter (s_f > m_f, before the cut).  The scoring kernel
-// has a second instantiation for it (FLOORS, below); the select kernels are the same ones: a refused candidate's c is a NaN.
+// Floors (a call with a floor that is not a NaN): the same two launches with a floor a field in the filter (s_f > m_f, before the
+// cut).  The scoring kernel has a second instantiation for it (FLOORS, below); the select kernels are the same ones: a refused
+// candidate's c is a NaN.
 //
-// sg_topn_rescore_skip_empty: the same launches again, with a field that is EMPTY for a pair -- a row without entries on either
-// side -- left out of the pair's sum and its weight shared among the others (SKIP, below: a third instantiation).
+// skip_empty: the same launches again, with a field that is EMPTY for a pair -- a row without entries on either side -- left out
+// of the pair's sum and its weight shared among the others (SKIP, below: a third instantiation).  One entry, sg_topn_rescore,
+// chooses the instantiation by what its call description holds.
 #include "sg_pairs_device.h"
 
 #define SG_RESCORE_BLOCK 256
@@ -34,7 +36,7 @@ struct RescoreFields {
     PairField<T> f[SG_RESCORE_MAX_FIELDS];
 };
 
-// Floors (sg_topn_rescore_floors): a candidate must ALSO have s_f > m_f on every field f that has a floor, s_0 -- the score it
+// Floors (sg_rescore_call.floors): a candidate must ALSO have s_f > m_f on every field f that has a floor, s_0 -- the score it
 // carries -- included.  `has`: bit 0 the primary's floor, bit f that of further field f; without a bit the value is not read.
 template <typename T>
 struct RescoreFloors {
@@ -43,7 +45,7 @@ struct RescoreFloors {
 };
 struct NoFloors {};
 
-// Empty fields (sg_topn_rescore_skip_empty): field f is empty for the pair (i, j) when the physical row of A_f or of B_f has no
+// Empty fields (sg_rescore_call.skip_empty): field f is empty for the pair (i, j) when the physical row of A_f or of B_f has no
 // entries.  `floors`: as above (has == 0: none).  The primary's row bounds and dead lists say whether field 0 -- the score the
 // candidate carries -- is empty (a_indptr null: never); nothing else of the primary is read.  `empty`: a byte a candidate, the
 // candidates' shape: bit 0 field 0, bit f + 1 further field f, set where the RIGHT row is the empty one (a left row that is
@@ -299,76 +301,72 @@ __global__ void __launch_bounds__(SG_RESCORE_BLOCK) rescore_select_block_kernel(
 }
 
 template <typename T>
-static int rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
-                   double threshold, sg_topn *r, uint32_t *d_status, void *d_comb, int32_t *d_long_rows,
-                   const double *floors,   // floors: null (sg_topn_rescore), or n_fields + 1 of them, the primary's first
-                   bool skip, const sg_rescore_field *primary, uint8_t *d_empty) {   // skip: sg_topn_rescore_skip_empty
+static int rescore(sg_ctx *ctx, const sg_topn *cand, const sg_rescore_call &call, sg_topn *r, uint32_t *d_status, void *d_comb,
+                   int32_t *d_long_rows, uint8_t *d_empty) {
     RescoreFields<T> dev;
     memset(&dev, 0, sizeof(dev));
-    for (int f = 0; f < n_fields; ++f) dev.f[f] = make_pair_field<T>(fields[f]);
+    for (int f = 0; f < call.n_fields; ++f) dev.f[f] = make_pair_field<T>(call.fields[f]);
     constexpr int per_block = SG_RESCORE_BLOCK / SG_PAIR_LANES;
     const int32_t chunks = (cand->stride + SG_PAIR_ROW_CHUNK - 1) / SG_PAIR_ROW_CHUNK;
     const dim3 grid_score((unsigned)pair_blocks(cand->n_rows * chunks));
+    // the scoring kernel's one launch: the type of `extra` chooses the instantiation
+    auto score = [&](auto extra) {
+        constexpr bool skip = std::is_same_v<decltype(extra), RescoreSkip<T>>;
+        constexpr bool floors = skip || std::is_same_v<decltype(extra), RescoreFloors<T>>;
+        hipLaunchKernelGGL((rescore_score_kernel<T, floors, skip>), grid_score, dim3(SG_PAIR_BLOCK), 0, ctx->stream, cand->d_cols,
+                           (const T *)cand->d_vals, cand->d_counts, cand->n_rows, cand->n_cols, cand->stride, chunks, (T)call.w0,
+                           dev, call.n_fields, d_status, (T *)d_comb, extra);
+    };
     RescoreFloors<T> m;
     memset(&m, 0, sizeof(m));
-    for (int f = 0; floors && f <= n_fields; ++f)
-        if (!std::isnan(floors[f])) m.m[f] = (T)floors[f], m.has |= 1u << f;
-    if (skip) {
+    for (int f = 0; call.floors && f <= call.n_fields; ++f)
+        if (!std::isnan(call.floors[f])) m.m[f] = (T)call.floors[f], m.has |= 1u << f;
+    if (call.skip_empty) {
         RescoreSkip<T> x;
         memset(&x, 0, sizeof(x));
         x.floors = m, x.empty = d_empty;
-        if (primary) {
-            x.a_indptr = primary->A->d_indptr, x.b_indptr = primary->B->d_indptr;
-            x.dead_a = primary->d_dead_a, x.dead_b = primary->d_dead_b;
-            x.n_dead_a = primary->n_dead_a, x.n_dead_b = primary->n_dead_b;
+        if (const sg_rescore_field *p = call.primary) {
+            x.a_indptr = p->A->d_indptr, x.b_indptr = p->B->d_indptr;
+            x.dead_a = p->d_dead_a, x.dead_b = p->d_dead_b;
+            x.n_dead_a = p->n_dead_a, x.n_dead_b = p->n_dead_b;
         }
-        hipLaunchKernelGGL((rescore_score_kernel<T, true, true>), grid_score, dim3(SG_PAIR_BLOCK), 0, ctx->stream, cand->d_cols,
-                           (const T *)cand->d_vals, cand->d_counts, cand->n_rows, cand->n_cols, cand->stride, chunks, (T)w0, dev,
-                           n_fields, d_status, (T *)d_comb, x);
-    } else if (!floors) {
-        hipLaunchKernelGGL((rescore_score_kernel<T, false>), grid_score, dim3(SG_PAIR_BLOCK), 0, ctx->stream, cand->d_cols,
-                           (const T *)cand->d_vals, cand->d_counts, cand->n_rows, cand->n_cols, cand->stride, chunks, (T)w0, dev,
-                           n_fields, d_status, (T *)d_comb, NoFloors{});
+        score(x);
+    } else if (!m.has) {   // no floor, or every one a NaN: the plain statement's kernel, whose bits the floors' would give
+        score(NoFloors{});
     } else {
-        hipLaunchKernelGGL((rescore_score_kernel<T, true>), grid_score, dim3(SG_PAIR_BLOCK), 0, ctx->stream, cand->d_cols,
-                           (const T *)cand->d_vals, cand->d_counts, cand->n_rows, cand->n_cols, cand->stride, chunks, (T)w0, dev,
-                           n_fields, d_status, (T *)d_comb, m);
+        score(m);
     }
     SG_HIP_TRY(hipGetLastError());
     // the select kernel is chosen ROW BY ROW: eight lanes for a row of up to SG_RESCORE_SHORT candidates, whatever the stride;
     // the rows above it are listed on the device (no read-back) and taken by a fixed grid of blocks
     const int64_t blocks = (cand->n_rows + per_block - 1) / per_block;
     hipLaunchKernelGGL(rescore_select_short_kernel<T>, dim3((unsigned)blocks), dim3(SG_RESCORE_BLOCK), 0, ctx->stream,
-                       cand->d_cols, (const T *)d_comb, cand->d_counts, cand->n_rows, cand->stride, (T)threshold, r->stride,
+                       cand->d_cols, (const T *)d_comb, cand->d_counts, cand->n_rows, cand->stride, (T)call.threshold, r->stride,
                        r->d_cols, (T *)r->d_vals, r->d_counts, d_long_rows, d_status + 1);
     if (cand->stride > SG_RESCORE_SHORT) {
         SG_HIP_TRY(hipGetLastError());
         const int64_t grid = std::min<int64_t>(cand->n_rows, (int64_t)ctx->num_cu * 8);
         hipLaunchKernelGGL(rescore_select_block_kernel<T>, dim3((unsigned)grid), dim3(SG_RESCORE_BLOCK), 0, ctx->stream,
-                           cand->d_cols, (const T *)d_comb, cand->d_counts, cand->stride, (T)threshold, r->stride, r->d_cols,
+                           cand->d_cols, (const T *)d_comb, cand->d_counts, cand->stride, (T)call.threshold, r->stride, r->d_cols,
                            (T *)r->d_vals, r->d_counts, d_long_rows, d_status + 1);
     }
     SG_HIP_TRY(hipGetLastError());
     return SG_OK;
 }
 
-static int rescore_count_ok(int32_t n_fields) {
+// floors: null, or n_fields + 1 doubles -- the primary's first -- a NaN for a field without one; skip_empty with its primary
+// (null: field 0 is never empty)
+extern "C" int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, const sg_rescore_call *call, sg_topn **out) {
+    SG_REQUIRE(ctx && cand && call && out, "null argument");
+    const int32_t n_fields = call->n_fields;
+    const sg_rescore_field *const fields = call->fields, *const primary = call->primary;
     SG_REQUIRE(n_fields >= 1 && n_fields <= SG_RESCORE_MAX_FIELDS, "between 1 and 7 further fields are expected");
-    return SG_OK;
-}
-
-// the three entries; floors: null, or n_fields + 1 doubles -- the primary's first -- a NaN for a field without one; skip:
-// sg_topn_rescore_skip_empty, with its primary (null: field 0 is never empty)
-static int rescore_call(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
-                        double threshold, int32_t top_n, sg_topn **out, const double *floors, bool skip = false,
-                        const sg_rescore_field *primary = nullptr) {
-    SG_REQUIRE(ctx && cand && out, "null argument");
-    SG_TRY(rescore_count_ok(n_fields));
     SG_REQUIRE(fields != nullptr, "null argument");
-    SG_REQUIRE(top_n >= 1, "top_n must be at least 1");
+    SG_REQUIRE(!primary || call->skip_empty, "a primary field is read with skip_empty alone");
+    SG_REQUIRE(call->top_n >= 1, "top_n must be at least 1");
     SG_REQUIRE(cand->stride >= 1 && cand->stride <= SG_RESCORE_MAX_STRIDE, "the candidates' stride exceeds 2048: ask the multiply for fewer a row");
-    SG_REQUIRE(weight_ok(w0, cand->dtype), "a weight is not finite");
-    for (int f = 0; floors && f <= n_fields; ++f) SG_REQUIRE(!std::isinf(floors[f]), "a floor is infinite");
+    SG_REQUIRE(weight_ok(call->w0, cand->dtype), "a weight is not finite");
+    for (int f = 0; call->floors && f <= n_fields; ++f) SG_REQUIRE(!std::isinf(call->floors[f]), "a floor is infinite");
     for (int f = 0; f < n_fields; ++f)
         SG_TRY(check_pair_field(fields[f], cand->dtype, cand->n_rows, cand->n_cols, "a field's", "candidates", true));
     if (primary) SG_TRY(check_pair_field(*primary, cand->dtype, cand->n_rows, cand->n_cols, "the primary field's", "candidates", false));
@@ -378,7 +376,7 @@ static int rescore_call(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_re
     for (int f = 0; f < n_fields; ++f) SG_TRY(ensure_pair_rows(ctx, fields[f].A, fields[f].B));
     if (primary) SG_TRY(ensure_pair_rows(ctx, primary->A, primary->B));
     TopnPtr r;
-    SG_TRY(topn_alloc(ctx, cand->n_rows, cand->n_cols, std::min<int32_t>(top_n, cand->stride), cand->dtype, &r));
+    SG_TRY(topn_alloc(ctx, cand->n_rows, cand->n_cols, std::min<int32_t>(call->top_n, cand->stride), cand->dtype, &r));
     if (cand->n_rows == 0) {
         *out = r.release();
         return SG_OK;
@@ -389,12 +387,11 @@ static int rescore_call(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_re
     SG_TRY(tmp.alloc(head + (size_t)cand->n_rows * (size_t)cand->stride * s, &d_buf));
     int32_t *d_long_rows = nullptr;   // the rows of more than SG_RESCORE_SHORT candidates (word 1 of the head counts them)
     if (cand->stride > SG_RESCORE_SHORT) SG_TRY(tmp.alloc((size_t)cand->n_rows, &d_long_rows));
-    uint8_t *d_empty = nullptr;       // (skip) a byte a candidate: the fields whose right row is empty
-    if (skip) SG_TRY(tmp.alloc((size_t)cand->n_rows * (size_t)cand->stride, &d_empty));
+    uint8_t *d_empty = nullptr;       // (skip_empty) a byte a candidate: the fields whose right row is empty
+    if (call->skip_empty) SG_TRY(tmp.alloc((size_t)cand->n_rows * (size_t)cand->stride, &d_empty));
     SG_HIP_TRY(hipMemsetAsync(d_buf, 0, head, ctx->stream));
     SG_TRY(by_dtype(cand->dtype, [&](auto t) {
-        return rescore<decltype(t)>(ctx, cand, w0, fields, n_fields, threshold, r.get(), (uint32_t *)d_buf, d_buf + head, d_long_rows,
-                                    floors, skip, primary, d_empty);
+        return rescore<decltype(t)>(ctx, cand, *call, r.get(), (uint32_t *)d_buf, d_buf + head, d_long_rows, d_empty);
     }));
     uint32_t status = 0;
     SG_TRY(sg_fetch(ctx, &status, d_buf, 4));   // the one read-back
@@ -411,27 +408,4 @@ static int rescore_call(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_re
     }
     *out = r.release();
     return SG_OK;
-}
-
-extern "C" int sg_topn_rescore(sg_ctx *ctx, const sg_topn *cand, double w0, const sg_rescore_field *fields, int32_t n_fields,
-                               double threshold, int32_t top_n, sg_topn **out) {
-    return rescore_call(ctx, cand, w0, fields, n_fields, threshold, top_n, out, nullptr);
-}
-
-extern "C" int sg_topn_rescore_floors(sg_ctx *ctx, const sg_topn *cand, double w0, double floor0, const sg_rescore_field *fields,
-                                      const double *floors, int32_t n_fields, double threshold, int32_t top_n, sg_topn **out) {
-    SG_TRY(rescore_count_ok(n_fields));   // (before floors[] is copied: rescore_call holds the same check for both entries)
-    SG_REQUIRE(floors != nullptr, "null argument");
-    double all[SG_RESCORE_MAX_FIELDS + 1] = {floor0};
-    for (int f = 0; f < n_fields; ++f) all[f + 1] = floors[f];
-    return rescore_call(ctx, cand, w0, fields, n_fields, threshold, top_n, out, all);
-}
-
-extern "C" int sg_topn_rescore_skip_empty(sg_ctx *ctx, const sg_topn *cand, double w0, double floor0,
-                                          const sg_rescore_field *primary, const sg_rescore_field *fields, const double *floors,
-                                          int32_t n_fields, double threshold, int32_t top_n, sg_topn **out) {
-    SG_TRY(rescore_count_ok(n_fields));   // (before floors[] is copied)
-    double all[SG_RESCORE_MAX_FIELDS + 1];
-    for (int f = 0; f <= n_fields; ++f) all[f] = f == 0 ? floor0 : floors ? floors[f - 1] : NAN;
-    return rescore_call(ctx, cand, w0, fields, n_fields, threshold, top_n, out, all, true, primary);
 }

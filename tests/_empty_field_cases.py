@@ -1,4 +1,4 @@
-"""What sg_topn_rescore_skip_empty (csrc/sg_rescore.hip) is held to, for the CPU and the GPU tests alike.  TEST INFRASTRUCTURE ONLY.
+"""What sg_topn_rescore with skip_empty (csrc/sg_rescore.hip) is held to, for the CPU and the GPU tests alike.  TEST INFRASTRUCTURE ONLY.
 
 - ``ref_rescore_skip_empty``: the statement of include/sg_hip.h in numpy, built on ``candidate_scores`` / ``refused`` of
   tests/_floor_cases.py -- which fields are empty for a pair (``indptr[a + 1] == indptr[a]`` of the PHYSICAL rows of either
@@ -289,7 +289,7 @@ def cases(dtype):
         f1 = C.table_field(1, tab, dtype, 0.25)
         f2 = blank_field(1, np.ones(m), dtype, 0.25, right_blank=set(range(m)))
         out[f"ties_k{k}"] = (_frozen(C.Case(*C.make_cand([(cols, s0)], m, dtype, m), m, 0.5, [f1, f2], 0.0, k)), None, None)
-    # ---- no empty row anywhere: the bits of the entries without the option (2 048 entries a row and many long rows: one each)
+    # ---- no empty row anywhere: the bits of the call without the option (2 048 entries a row and many long rows: one each)
     base = C.cases(dtype)
     for name in ("counts_short", "counts_long", "weights_third_7", "dead_sides_and_fields_differ", "full_2048_top20",
                  "many_long_rows", "nan_inf", "zeros"):
@@ -311,9 +311,9 @@ def expected(dtype, name):
 
 @functools.lru_cache(maxsize=None)
 def expected_without(dtype, name):
-    """What the entries WITHOUT the option give on the case (``ref_rescore`` / ``ref_rescore_floors``), computed once."""
+    """What the call WITHOUT the option gives on the case (``ref_rescore`` / ``ref_rescore_floors``), computed once."""
     case, _, floors = cases(dtype)[name]
-    if name.startswith("no_blank:"):                        # (shared with the tests of those entries)
+    if name.startswith("no_blank:"):                        # (shared with the tests without the option)
         return C.expected(dtype, name.split(":", 1)[1]) if floors is None else FC.expected(dtype, name.split(":", 1)[1])
     want = C.ref_rescore(case) if floors is None else FC.ref_rescore_floors(case, floors)
     for a in want:

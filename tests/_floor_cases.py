@@ -1,4 +1,4 @@
-"""What sg_topn_rescore_floors (csrc/sg_rescore.hip) is held to, for the CPU and the GPU tests alike.  TEST INFRASTRUCTURE ONLY.
+"""What sg_topn_rescore with floors (csrc/sg_rescore.hip) is held to, for the CPU and the GPU tests alike.  TEST INFRASTRUCTURE ONLY.
 
 - ``ref_rescore_floors``: ``ref_rescore`` of tests/_rescore_cases.py with the floor mask -- ``s_f > (T)m_f`` on every field
   that has a floor, the score the candidate carries included -- applied to ``keep`` before the per-row selection;

@@ -1,6 +1,6 @@
-"""The inputs of the sg_topn_rescore_skip_empty tests, checked without a GPU: every edge the cases are built for is present
+"""The inputs of the skip_empty tests of sg_topn_rescore, checked without a GPU: every edge the cases are built for is present
 (``census``), every wrong turn of ``WRONG`` changes the answer on some case, and on the cases without an empty row the
-statement gives the bits of the references of the entries without the option."""
+statement gives the bits of the references of the call without the option."""
 import numpy as np
 import pytest
 

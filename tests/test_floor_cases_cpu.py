@@ -1,4 +1,4 @@
-"""CPU tests of the cases sg_topn_rescore_floors is held to (tests/_floor_cases.py): a census proves that every edge of the
+"""CPU tests of the cases sg_topn_rescore with floors is held to (tests/_floor_cases.py): a census proves that every edge of the
 floor mask is present, and every wrong turn the mask could take changes the answer on at least one case -- so the GPU test that
 holds the kernel to ``ref_rescore_floors`` bit for bit can tell them apart."""
 import numpy as np

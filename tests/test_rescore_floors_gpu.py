@@ -1,6 +1,6 @@
-"""GPU tests of sg_topn_rescore_floors through ``Context.topn_rescore(..., floors=...)``: every case of tests/_floor_cases.py
-held to ``ref_rescore_floors``' bits, the same call twice, the candidates untouched, floors that are all None against the old
-entry's bits, every refusal followed by a good call, and the order check that looks only at the rows that are read.  No
+"""GPU tests of sg_topn_rescore with floors through ``Context.topn_rescore(..., floors=...)``: every case of tests/_floor_cases.py
+held to ``ref_rescore_floors``' bits, the same call twice, the candidates untouched, floors that are all None against the
+plain call's bits, every refusal followed by a good call, and the order check that looks only at the rows that are read.  No
 tolerance anywhere."""
 import numpy as np
 import pytest

@@ -1,6 +1,6 @@
-"""GPU tests of sg_topn_rescore_skip_empty through ``Context.topn_rescore(..., skip_empty=True, primary=...)``: every case of
+"""GPU tests of sg_topn_rescore with skip_empty through ``Context.topn_rescore(..., skip_empty=True, primary=...)``: every case of
 tests/_empty_field_cases.py held to ``ref_rescore_skip_empty``'s bits in fp32 and fp64 -- columns, value bits and counts; the
-division is numpy's, one correctly rounded IEEE division --, the same call twice, the candidates untouched, the entries
+division is numpy's, one correctly rounded IEEE division --, the same call twice, the candidates untouched, the call
 without the option unchanged on the same inputs, and every refusal followed by a good call.  No tolerance anywhere."""
 import numpy as np
 import pytest
@@ -64,7 +64,7 @@ def test_every_case_equals_the_statement(ctx, dtype):
             cols, vals, counts = dev.cand.to_host()                             # the candidates are only read
             assert np.array_equal(cols, case.cols) and np.array_equal(C.bits(vals), C.bits(case.vals)), name
             assert np.array_equal(counts, case.counts), name
-            # the plain and the floors entry on the same inputs: what they were
+            # without the option, floors or none, on the same inputs: what it was
             assert C.same_result(dev.without(floors), EC.expected_without(dtype, name)), name
 
 
@@ -94,7 +94,7 @@ def test_refusals_and_a_good_call_after_each(ctx, dtype):
         refused("primary field's left matrix has not the candidates' rows", primary=(pB, pB, pda, pdb))
         wrong_type = s.own(ctx.csr_from_scipy(primary.B.astype(other)))
         refused("primary field's matrices differ from the candidates in value type", primary=(pA, wrong_type, pda, pdb))
-        # the refusals of sg_topn_rescore_floors hold here too
+        # the refusals without the option hold here too
         refused("between 1 and 7", fields=[], floors=[None])
         refused("top_n", top_n=0)
         refused("not finite", w0=np.nan)
