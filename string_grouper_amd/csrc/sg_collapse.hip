@@ -537,31 +537,11 @@ static bool worth_grouping(uint32_t n_groups, int64_t n, bool forced) {
 // `ptr`: its row pointers where they are filled already (null: allocated here, filled with the rows) -- this function's from
 // the moment it is called: the matrix's, or released.
 static int collapse_unique_matrix(sg_ctx *ctx, const sg_csr *B, SgCollapse *c, int64_t nnz_u, int64_t *ptr, bool defer_rows) {
-    const int64_t n_u = c->n_u;
-    int32_t *idx = nullptr;
-    void *val = nullptr;
-    const size_t vs = B->dtype == SG_F64 ? 8 : 4;
-    Scratch arrays(ctx);   // (the matrix's once the matrix exists)
-    if (ptr) arrays.adopt(ptr);
-    else SG_TRY(arrays.alloc((size_t)n_u + 2, &ptr));
-    SG_TRY(arrays.alloc((size_t)nnz_u + 64, &idx));
-    SG_TRY(arrays.alloc_bytes(((size_t)nnz_u + 64) * vs, &val));
-    sg_csr *m = new (std::nothrow) sg_csr();
-    if (!m) return SG_ERR_OOM;
-    m->ctx = ctx;
-    m->n_rows = n_u;
-    m->n_cols = B->n_cols;
-    m->nnz = nnz_u;
-    m->dtype = B->dtype;
-    m->d_indptr = arrays.keep(ptr);
-    m->d_indices = arrays.keep(idx);
-    m->d_data = arrays.keep(val);
-    m->owned = true;
-    m->props_state = B->props_state;          // a subset of B's rows: cosine-like if B is; the maxima are upper bounds
-    m->props_max_norm2 = B->props_max_norm2;
-    m->props_max_nnz = B->props_max_nnz;
+    CsrPtr m;
+    SG_TRY(csr_alloc(ctx, c->n_u, B->n_cols, nnz_u, B->dtype, CSR_SLACK_GATHER, &m, ptr));
+    csr_inherit(m.get(), B, CsrDerived::representatives);   // a subset of B's rows: cosine-like if B is; the maxima are upper bounds
     m->rows_of = c;
-    c->unique = m;
+    c->unique = m.release();
     c->pending_src = B;       // (written by sg_collapse_materialize: now, or when somebody asks sg_csr_ensure_rows)
     if (!defer_rows) return sg_collapse_materialize(ctx, c);
     return SG_OK;

@@ -297,16 +297,22 @@ __global__ void __launch_bounds__(CONCAT_BLOCK) gather_row_norms_kernel(const Co
     }
 }
 
-struct CsrDeleter {
-    void operator()(sg_csr *m) const { sg_csr_free(m); }
-};
+// ---- host drivers. Each entry point reads as its stages: describe the parts (describe_parts; the concatenation writes its
+// descriptors on the host), allocate the result and what it inherits (csr_alloc + csr_inherit, sg_csr.hip; rows_result for
+// select and take), copy (copy_rows / the concat kernel), the norms beside the kernels.
+
+// the copy kernels' grid: a thread a unit of four entries or a row, whichever are more; at most 32 workgroups a CU
+unsigned copy_grid(const sg_ctx *ctx, int64_t n_rows, int64_t nnz) {
+    const int64_t work = std::max<int64_t>(std::max<int64_t>((nnz + CONCAT_UNIT - 1) / CONCAT_UNIT, n_rows), 1);
+    const int64_t want = (work + CONCAT_BLOCK - 1) / CONCAT_BLOCK;
+    return (unsigned)std::min<int64_t>(want, (int64_t)ctx->num_cu * 32);
+}
 
 }   // namespace
 
 extern "C" int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_parts, sg_csr **out) {
     SG_REQUIRE(ctx && parts && out && n_parts >= 1, "null argument or no parts");
     int64_t n_rows = 0, nnz = 0;
-    bool all_vec = true, all_words = true, all_norms = true;
     for (int p = 0; p < n_parts; ++p) {
         SG_REQUIRE(parts[p] != nullptr, "a part is null");
         SG_REQUIRE(parts[p]->n_cols == parts[0]->n_cols && parts[p]->dtype == parts[0]->dtype,
@@ -315,36 +321,16 @@ extern "C" int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_
         if (parts[p]->rows_of) SG_TRY(sg_csr_ensure_rows(ctx, parts[p]));
         n_rows += parts[p]->n_rows;
         nnz += parts[p]->nnz;
-        all_vec = all_vec && parts[p]->from_vectoriser;
-        all_words = all_words && parts[p]->d_props_words != nullptr;
-        all_norms = all_norms && parts[p]->d_row_norm != nullptr;
     }
     if (n_rows > INT32_MAX) {
         sg_set_error("sg_csr_concat: %lld rows exceed int32 indices", (long long)n_rows);
         return SG_ERR_OVERFLOW;
     }
-    const int32_t dtype = parts[0]->dtype;
-    const size_t s = dtype == SG_F64 ? 8 : 4;
-    std::unique_ptr<sg_csr, CsrDeleter> m(new (std::nothrow) sg_csr());
-    if (!m) return SG_ERR_OOM;
-    m->ctx = ctx;
-    m->n_rows = n_rows;
-    m->n_cols = parts[0]->n_cols;
-    m->nnz = nnz;
-    m->dtype = dtype;
-    m->owned = true;
-    m->from_vectoriser = all_vec;
-    int64_t *dp = nullptr;
-    int32_t *di = nullptr;
-    void *dd = nullptr;
-    SG_TRY(sg_alloc(ctx, (size_t)n_rows + 1, &dp));
-    m->d_indptr = dp;
-    SG_TRY(sg_alloc(ctx, (size_t)nnz + 4, &di));
-    m->d_indices = di;
-    SG_TRY(ctx->alloc(((size_t)nnz + 4) * s, &dd));
-    m->d_data = dd;
-    if (all_vec && all_words) SG_TRY(sg_alloc(ctx, (size_t)4, &m->d_props_words));
-    if (all_norms) SG_TRY(sg_alloc(ctx, (size_t)n_rows + 1, &m->d_row_norm));
+    CsrPtr m;
+    SG_TRY(csr_alloc(ctx, n_rows, parts[0]->n_cols, nnz, parts[0]->dtype, CSR_SLACK_COPY, &m));
+    const CsrCarries carries = csr_inherit(m.get(), parts, n_parts, CsrDerived::stacked);
+    if (carries.words) SG_TRY(sg_alloc(ctx, (size_t)4, &m->d_props_words));
+    if (carries.norms) SG_TRY(sg_alloc(ctx, (size_t)n_rows + 1, &m->d_row_norm));
 
     std::vector<ConcatPart> desc((size_t)n_parts + 1);
     int64_t row_off = 0, nnz_off = 0;
@@ -360,18 +346,16 @@ extern "C" int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_
     SG_TRY(scratch.alloc(desc.size(), &d_desc));
     SG_HIP_TRY(hipMemcpyAsync(d_desc, desc.data(), desc.size() * sizeof(ConcatPart), hipMemcpyHostToDevice, ctx->stream));
     SG_HIP_TRY(hipStreamSynchronize(ctx->stream));      // desc is a local
-    const int64_t work = std::max<int64_t>(std::max<int64_t>((nnz + CONCAT_UNIT - 1) / CONCAT_UNIT, n_rows), 1);
-    const int64_t want = (work + CONCAT_BLOCK - 1) / CONCAT_BLOCK;
-    const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)ctx->num_cu * 32);
-    by_dtype(dtype, [&](auto t) {
+    const unsigned grid = copy_grid(ctx, n_rows, nnz);
+    by_dtype(m->dtype, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL(csr_concat_kernel<T>, dim3(grid), dim3(CONCAT_BLOCK), 0, ctx->stream, (const ConcatPart *)d_desc,
-                           (int)n_parts, dp, di, (T *)dd, m->d_props_words);
+                           (int)n_parts, (int64_t *)m->d_indptr, (int32_t *)m->d_indices, (T *)m->d_data, m->d_props_words);
         return SG_OK;
     });
     scratch.release(d_desc);       // (stream-ordered pool: a later taker of the block runs behind the kernel)
     SG_HIP_TRY(hipGetLastError());
-    if (all_norms) {               // the rows' norms, part by part (a view's pointer starts at its first row)
+    if (carries.norms) {           // the rows' norms, part by part (a view's pointer starts at its first row)
         int64_t at = 0;
         for (int p = 0; p < n_parts; ++p) {
             if (parts[p]->n_rows > 0)
@@ -386,26 +370,45 @@ extern "C" int sg_csr_concat(sg_ctx *ctx, const sg_csr *const *parts, int32_t n_
 
 namespace {
 
-template <typename T>
-int select_rows(sg_ctx *ctx, const sg_csr *m, const ConcatPart *d_desc, int64_t n_gaps, int64_t n_rows, int64_t nnz,
-                sg_csr *r) {
-    int64_t *dp = nullptr;
-    int32_t *di = nullptr;
-    T *dd = nullptr;
-    SG_TRY(sg_alloc(ctx, (size_t)n_rows + 1, &dp));
-    r->d_indptr = dp;
-    SG_TRY(sg_alloc(ctx, (size_t)nnz + 4, &di));
-    r->d_indices = di;
-    SG_TRY(sg_alloc(ctx, (size_t)nnz + 4, &dd));
-    r->d_data = dd;
-    if (m->from_vectoriser && m->d_props_words) SG_TRY(sg_alloc(ctx, (size_t)4, &r->d_props_words));
-    const int64_t work = std::max<int64_t>(std::max<int64_t>((nnz + CONCAT_UNIT - 1) / CONCAT_UNIT, n_rows), 1);
-    const int64_t want = (work + CONCAT_BLOCK - 1) / CONCAT_BLOCK;
-    const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)ctx->num_cu * 32);
-    hipLaunchKernelGGL(csr_select_kernel<T>, dim3(grid), dim3(CONCAT_BLOCK), 0, ctx->stream, d_desc, (int)n_gaps, dp, di, dd,
-                       (const uint32_t *)m->d_props_words, r->d_props_words);
+// A part-descriptor kernel (one workgroup) over a list of m's rows: n_parts descriptors and the sentinel into *d_desc, the
+// two totals into *d_info (both the scope's).  The totals are the one thing that comes back: they size the result (*nnz),
+// or refuse the list.
+using PartsKernel = void (*)(const int64_t *, const int32_t *, const void *, int64_t, const int32_t *, int64_t, ConcatPart *,
+                             int64_t *);
+int describe_parts(sg_ctx *ctx, Scratch &scratch, PartsKernel kernel, const sg_csr *m, const int32_t *d_list, int64_t n_list,
+                   int64_t n_parts, ConcatPart **d_desc, int64_t **d_info, int64_t *nnz, const char *refusal) {
+    SG_TRY(scratch.alloc((size_t)n_parts + 1, d_desc));
+    SG_TRY(scratch.alloc((size_t)2, d_info));
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(CONCAT_BLOCK), 0, ctx->stream, m->d_indptr, m->d_indices, m->d_data, m->n_rows,
+                       d_list, n_list, *d_desc, *d_info);
     SG_HIP_TRY(hipGetLastError());
+    int64_t info[2] = {0, 0};
+    SG_TRY(sg_fetch(ctx, ctx->h_fetch, *d_info, sizeof(info)));
+    memcpy(info, ctx->h_fetch, sizeof(info));
+    SG_REQUIRE(info[1] == 0, refusal);
+    *nnz = info[0];
     return SG_OK;
+}
+
+// n_rows of m's rows, nnz entries: the arrays, what such a result inherits, and the block of the words when it carries them
+int rows_result(sg_ctx *ctx, const sg_csr *m, int64_t n_rows, int64_t nnz, CsrDerived kind, CsrPtr *r, CsrCarries *carries) {
+    SG_TRY(csr_alloc(ctx, n_rows, m->n_cols, nnz, m->dtype, CSR_SLACK_COPY, r));
+    *carries = csr_inherit(r->get(), m, kind);
+    if (carries->words) SG_TRY(sg_alloc(ctx, (size_t)4, &(*r)->d_props_words));
+    return SG_OK;
+}
+
+// (a) and (b) of the header over the descriptors of m's rows; the words are the source's own
+int copy_rows(sg_ctx *ctx, const sg_csr *m, const ConcatPart *d_desc, int64_t n_parts, sg_csr *r) {
+    const unsigned grid = copy_grid(ctx, r->n_rows, r->nnz);
+    return by_dtype(m->dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        hipLaunchKernelGGL(csr_select_kernel<T>, dim3(grid), dim3(CONCAT_BLOCK), 0, ctx->stream, d_desc, (int)n_parts,
+                           (int64_t *)r->d_indptr, (int32_t *)r->d_indices, (T *)r->d_data, (const uint32_t *)m->d_props_words,
+                           r->d_props_words);
+        SG_HIP_TRY(hipGetLastError());
+        return SG_OK;
+    });
 }
 
 }   // namespace
@@ -416,38 +419,21 @@ extern "C" int sg_csr_select_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d
     SG_REQUIRE(n_drop == 0 || d_drop_sorted != nullptr, "the drop list is null");
     if (m->rows_of) SG_TRY(sg_csr_ensure_rows(ctx, m));
     const int64_t n_gaps = n_drop + 1;
-    std::unique_ptr<sg_csr, CsrDeleter> r(new (std::nothrow) sg_csr());
-    if (!r) return SG_ERR_OOM;
-    r->ctx = ctx;
-    r->n_rows = m->n_rows - n_drop;
-    r->n_cols = m->n_cols;
-    r->dtype = m->dtype;
-    r->owned = true;
-    r->from_vectoriser = m->from_vectoriser;
-    // the gaps' descriptors and the totals; the totals are the one thing that comes back: they size the result
+    CsrPtr r;
+    CsrCarries carries;
     Scratch scratch(ctx);
     ConcatPart *d_desc = nullptr;
     int64_t *d_info = nullptr;
-    SG_TRY(scratch.alloc((size_t)n_gaps + 1, &d_desc));
-    SG_TRY(scratch.alloc((size_t)2, &d_info));
-    hipLaunchKernelGGL(csr_select_gaps_kernel, dim3(1), dim3(CONCAT_BLOCK), 0, ctx->stream, m->d_indptr, m->d_indices, m->d_data,
-                       m->n_rows, d_drop_sorted, n_drop, d_desc, d_info);
-    SG_HIP_TRY(hipGetLastError());
-    int64_t info[2] = {0, 0};
-    SG_TRY(sg_fetch(ctx, ctx->h_fetch, d_info, sizeof(info)));
-    memcpy(info, ctx->h_fetch, sizeof(info));
-    SG_REQUIRE(info[1] == 0, "the rows to drop must be ascending, distinct and inside the matrix");
-    r->nnz = info[0];
-    SG_TRY(by_dtype(m->dtype, [&](auto t) {
-        return select_rows<decltype(t)>(ctx, m, d_desc, n_gaps, r->n_rows, r->nnz, r.get());
-    }));
-    if (m->d_row_norm) {           // the kept rows' norms, gathered past the dropped rows
+    int64_t nnz = 0;
+    SG_TRY(describe_parts(ctx, scratch, csr_select_gaps_kernel, m, d_drop_sorted, n_drop, n_gaps, &d_desc, &d_info, &nnz,
+                          "the rows to drop must be ascending, distinct and inside the matrix"));
+    SG_TRY(rows_result(ctx, m, m->n_rows - n_drop, nnz, CsrDerived::selected, &r, &carries));
+    SG_TRY(copy_rows(ctx, m, d_desc, n_gaps, r.get()));
+    if (carries.norms) {           // the kept rows' norms, gathered past the dropped rows
         SG_TRY(sg_alloc(ctx, (size_t)r->n_rows + 1, &r->d_row_norm));
         if (r->n_rows > 0) {
-            const int64_t want = (r->n_rows + CONCAT_BLOCK - 1) / CONCAT_BLOCK;
-            hipLaunchKernelGGL(gather_row_norms_kernel, dim3((unsigned)std::min<int64_t>(want, (int64_t)ctx->num_cu * 32)),
-                               dim3(CONCAT_BLOCK), 0, ctx->stream, (const ConcatPart *)d_desc, (int)n_gaps, m->d_indptr,
-                               (const double *)m->d_row_norm, r->d_row_norm);
+            hipLaunchKernelGGL(gather_row_norms_kernel, dim3(copy_grid(ctx, r->n_rows, 0)), dim3(CONCAT_BLOCK), 0, ctx->stream,
+                               (const ConcatPart *)d_desc, (int)n_gaps, m->d_indptr, (const double *)m->d_row_norm, r->d_row_norm);
             SG_HIP_TRY(hipGetLastError());
         }
     }
@@ -461,31 +447,16 @@ extern "C" int sg_csr_take_rows(sg_ctx *ctx, const sg_csr *m, const int32_t *d_r
     SG_REQUIRE(n_rows >= 0 && n_rows < INT32_MAX, "the number of rows to take is negative or exceeds int32");
     SG_REQUIRE(n_rows == 0 || d_rows != nullptr, "the list of rows is null");
     if (m->rows_of) SG_TRY(sg_csr_ensure_rows(ctx, m));
-    std::unique_ptr<sg_csr, CsrDeleter> r(new (std::nothrow) sg_csr());
-    if (!r) return SG_ERR_OOM;
-    r->ctx = ctx;
-    r->n_rows = n_rows;
-    r->n_cols = m->n_cols;
-    r->dtype = m->dtype;
-    r->owned = true;
-    r->from_vectoriser = m->from_vectoriser;
-    // a descriptor per taken row and the totals; the totals are the one thing that comes back: they size the result
-    Scratch scratch(ctx);
+    CsrPtr r;
+    CsrCarries carries;
+    Scratch scratch(ctx);          // (here the descriptors' block goes back first, then the totals': the order they were taken in)
     ConcatPart *d_desc = nullptr;
     int64_t *d_info = nullptr;
-    SG_TRY(scratch.alloc((size_t)n_rows + 1, &d_desc));
-    SG_TRY(scratch.alloc((size_t)2, &d_info));
-    hipLaunchKernelGGL(csr_take_parts_kernel, dim3(1), dim3(CONCAT_BLOCK), 0, ctx->stream, m->d_indptr, m->d_indices, m->d_data,
-                       m->n_rows, d_rows, n_rows, d_desc, d_info);
-    SG_HIP_TRY(hipGetLastError());
-    int64_t info[2] = {0, 0};
-    SG_HIP_TRY(hipMemcpyAsync(ctx->h_fetch, d_info, sizeof(info), hipMemcpyDeviceToHost, ctx->stream));
-    SG_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(info, ctx->h_fetch, sizeof(info));
-    SG_REQUIRE(info[1] == 0, "a row to take lies outside the matrix");
-    r->nnz = info[0];
-    SG_TRY(m->dtype == SG_F64 ? select_rows<double>(ctx, m, d_desc, n_rows, n_rows, r->nnz, r.get())
-                              : select_rows<float>(ctx, m, d_desc, n_rows, n_rows, r->nnz, r.get()));
+    int64_t nnz = 0;
+    SG_TRY(describe_parts(ctx, scratch, csr_take_parts_kernel, m, d_rows, n_rows, n_rows, &d_desc, &d_info, &nnz,
+                          "a row to take lies outside the matrix"));
+    SG_TRY(rows_result(ctx, m, n_rows, nnz, CsrDerived::taken, &r, &carries));
+    SG_TRY(copy_rows(ctx, m, d_desc, n_rows, r.get()));
     *out = r.release();
     return SG_OK;
 }

@@ -397,6 +397,91 @@ bool result_stride(int64_t n_rows, int64_t top_n, int64_t n_cols, int32_t *strid
 int result_overflow(int64_t n_rows, int32_t stride, const char *advice);
 int sort_rows_by_column(sg_ctx *ctx, sg_topn *r);   // every row of an unsorted result (sort == 0) by ascending column
 
+// sg_csr.hip: a matrix under construction (freed whole on every early return; the only owner type), the one maker, the
+// views and the rule of what a derived matrix carries over
+struct CsrFree {
+    void operator()(sg_csr *m) const { sg_csr_free(m); }
+};
+using CsrPtr = std::unique_ptr<sg_csr, CsrFree>;
+// The two size classes of a matrix's arrays: elements allocated beyond n_rows row pointers and beyond nnz entries.  The
+// sizes are the ones every site has always asked for, and the pool reuses blocks BY SIZE, so they stay.
+struct CsrSlack {
+    size_t rows, entries;
+};
+// n + 1 row pointers (none spare), nnz + 4 entries: what is uploaded, stacked, selected, taken or weighted (sg_csr_from_host,
+// sg_csr_ops.hip, the vectoriser).  copy_parts (sg_csr_ops.hip) WRITES in 16-byte units of four entries, but only whole units
+// that end at or before nnz, the tail goes entry by entry; K2, the reweigh kernel, the exact and the pruned multiply's row
+// set-up, the pair kernels and K9 all test a lane against the row's end before they load.  No kernel that reads or writes
+// the four spare entries was found.
+constexpr CsrSlack CSR_SLACK_COPY = {1, 4};
+// n + 2 row pointers, nnz + 64 entries: the matrices the index build gathers (the representatives' rows, sg_collapse.hip;
+// the rows in position order, sg_postings.hip).  gather_rows_kernel visits position n, the sentinel, and reads row pointer n
+// there, not n + 1; it and unique_rows_kernel guard every entry by the row's length, and the self-join's row set-up (64 lanes
+// a round) tests each lane.  No kernel that reads the second spare pointer or the 64 spare entries was found.
+constexpr CsrSlack CSR_SLACK_GATHER = {2, 64};
+// An owned matrix with its three arrays, nothing written.  `indptr`: row pointers that exist already (the vectoriser's
+// row_pointers, the sort-based grouping) -- the matrix's from the moment of the call: kept by it, or released with it when the
+// call fails.  nnz may be corrected by the caller where the arrays hold more than is used.
+int csr_alloc(sg_ctx *ctx, int64_t n_rows, int64_t n_cols, int64_t nnz, int32_t dtype, CsrSlack slack, CsrPtr *out,
+              int64_t *indptr = nullptr);
+// An unowned copy of the struct: the arrays stay the owner's, the owner's groups of identical rows (left_groups, left_state)
+// are NOT the copy's (reset in one place).  Two callers, one difference:
+//   csr_view      the copy an index keeps of the matrix it was built over (sg_postings.hip: built_from, src, caller_b_copy).  It
+//                 drops the vectoriser's words: "what it has cached stays the owner's" -- the copy is read for as long as the
+//                 index lives, sg_csr_props of it goes by the props_* fields it copied, and the words' block goes back to the
+//                 pool with the owner's handle.  (The norms' pointer and rows_of are kept, as the parent kept them.)
+//   csr_row_view  rows [r0, r1) of m as a handle of its own (sg_csr_row_block; nnz is the caller's to set, from the two row
+//                 pointers).  It keeps the words -- upper bounds over all rows hold for some of them, and the multiply reads
+//                 them through sg_csr_props -- and the norms, shifted to the first row.
+sg_csr csr_view(const sg_csr &m);
+sg_csr csr_row_view(const sg_csr &m, int64_t r0, int64_t r1);
+// What a derived matrix carries over from its source(s).  csr_inherit sets the fields below in dst (fresh from csr_alloc:
+// everything else stays at its default) and says which of the two optional arrays the result gets; the SITE allocates and
+// fills them, where and when it always did.  "-" = stays at the default (false / 0 / null).
+//
+//                     | same rows,    | a subset of rows                                     | sources    | rows
+//                     | other order   |                                                      | stacked    | reweighed
+//   field             | permuted      | representatives  | selected        | taken           | stacked    | reweighed
+//   ------------------+---------------+------------------+-----------------+-----------------+------------+-----------
+//   from_vectoriser   | - (1)         | - (1)            | source's        | source's        | all have   | true (6)
+//   d_props_words     | - (1)         | - (1)            | flag and words  | flag and words  | all flags, | yes (6)
+//                     |               |                  | (3)             | (3)             | all words  |
+//                     |               |                  |                 |                 | (5)        |
+//   d_row_norm        | - (1)         | - (1)            | source has them | never (4)       | all have   | yes (6)
+//   props_state,      | copied (2)    | copied (2)       | - (7)           | - (7)           | - (7)      | - (7)
+//   props_max_norm2,  |               |                  |                 |                 |            |
+//   props_max_nnz     |               |                  |                 |                 |            |
+//   props_repeated_   | copied (2)    | - (8)            | - (7)           | - (7)           | - (7)      | - (7)
+//   column            |               |                  |                 |                 |            |
+//   props_by_         | - (8)         | - (8)            | - (7)           | - (7)           | - (7)      | - (7)
+//   construction      |               |                  |                 |                 |            |
+//   left_groups,      | - (9)         | - (9)            | - (9)           | - (9)           | - (9)      | - (9)
+//   left_state        |               |                  |                 |                 |            |
+//   rows_of           | -             | the groups (10)  | -               | -               | -          | -
+//
+//   (1) internal to an index: nothing asks such a matrix for words or norms, and what the flag would say it learns from the
+//       copied props_state.
+//   (2) same rows, or some of them: cosine-like if the source is, the maxima hold as upper bounds; a row that names a column
+//       twice is still there after a permutation.
+//   (3) the words hold for any subset as upper bounds (csr_select_kernel copies them); without the flag nobody reads them.
+//       sg_csr_take_rows gets them through the same select_rows<T> as sg_csr_select_rows.
+//   (4) sg_csr_ops.hip's header: the one caller (the kept self-join's refill) multiplies what it took and frees it; only a
+//       matrix that may be weighted anew needs the norms.
+//   (5) csr_concat_kernel merges the words (sum, max, max), which needs every part's; a result carries norms only when every
+//       source row had one.
+//   (6) counts times positive weights, every row divided by its norm: the reweigh kernel writes both arrays.
+//   (7) a new matrix as far as sg_csr_props is concerned: measured, or known by the flag, on first use.
+//   (8) as the parent did; no reason found.  (The representatives are a subset of rows, so a repeated column among them
+//       implies one in the source, yet the flag is not copied; props_by_construction is copied by nobody.)
+//   (9) a matrix's groups are made on first use by the multiply, per handle.
+//  (10) set by collapse_unique_matrix itself: the rows may be pending (sg_csr_ensure_rows).
+enum class CsrDerived { permuted, representatives, selected, taken, stacked, reweighed };
+struct CsrCarries {
+    bool words = false, norms = false;
+};
+CsrCarries csr_inherit(sg_csr *dst, const sg_csr *const *src, int n_src, CsrDerived kind);
+static inline CsrCarries csr_inherit(sg_csr *dst, const sg_csr *src, CsrDerived kind) { return csr_inherit(dst, &src, 1, kind); }
+
 struct sg_vocab {
     sg_ctx *ctx = nullptr;
     sg_vec_params params;

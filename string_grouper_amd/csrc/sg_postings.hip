@@ -1102,15 +1102,6 @@ struct PostingsFree {
 };
 using PostingsPtr = std::unique_ptr<sg_postings, PostingsFree>;   // a half-built index goes back whole, whichever way a stage fails
 
-static sg_csr borrowed(const sg_csr &m) {   // the struct itself, copied: the arrays stay the owner's, and so does what it has cached
-    sg_csr c = m;
-    c.owned = false;
-    c.d_props_words = nullptr;
-    c.left_groups = nullptr;
-    c.left_state = 0;
-    return c;
-}
-
 static SgScoreCtx score_ctx_of(const sg_postings *p) {
     SgScoreCtx sc;
     if (!p->d_fwd_ptr) return sc;
@@ -1390,20 +1381,19 @@ static int build_permuted(sg_ctx *ctx, const sg_csr *B, int64_t tile_cols, sg_po
         }
         minv = (uint64_t)(t0 < 0 ? t0 + (long long)n : t0);
     }
-    Scratch scratch(ctx);   // (the five arrays are the index's and the copy's once the copy exists)
+    Scratch scratch(ctx);   // (the two tables are the index's once the copy exists)
     uint32_t *orig_of = nullptr, *pos_of = nullptr;
-    int64_t *ptr = nullptr;
-    int32_t *idx = nullptr;
-    void *val = nullptr;
-    const size_t vs = B->dtype == SG_F64 ? 8 : 4;
+    CsrPtr m;               // B's rows in position order: same rows, same properties
     // the rows of B itself, or -- B the representatives' matrix of `pending`, not written -- of the matrix they come from
     const bool from_groups = pending && pending->pending_src;
     const bool by_group = from_groups && pending->d_rep_len != nullptr;   // (table path: start and length per group; else B's row pointers are there)
     SG_TRY(scratch.alloc((size_t)n + 1, &orig_of));
     SG_TRY(scratch.alloc((size_t)n + 1, &pos_of));
-    SG_TRY(scratch.alloc((size_t)n + 2, &ptr));
-    SG_TRY(scratch.alloc((size_t)B->nnz + 64, &idx));
-    SG_TRY(scratch.alloc_bytes(((size_t)B->nnz + 64) * vs, &val));
+    SG_TRY(csr_alloc(ctx, B->n_rows, B->n_cols, B->nnz, B->dtype, CSR_SLACK_GATHER, &m));
+    csr_inherit(m.get(), B, CsrDerived::permuted);
+    int64_t *ptr = (int64_t *)m->d_indptr;
+    int32_t *idx = (int32_t *)m->d_indices;
+    void *val = (void *)m->d_data;
     SG_TRY(sg_scan_launch<int64_t>(ctx, PermutedLenLoad{n, minv, (uint64_t)(~0ull / n) + 1ull, by_group ? pending->d_rep_len : (const int32_t *)nullptr, B->d_indptr, pos_of, orig_of},
                                    SgScanStoreArray<int64_t>{ptr}, (int64_t)n, ptr + n));
     const unsigned grid = (unsigned)((((n + 1 + SG_GATHER_ROWS - 1) / SG_GATHER_ROWS) * 16 + 255) / 256);
@@ -1420,23 +1410,8 @@ static int build_permuted(sg_ctx *ctx, const sg_csr *B, int64_t tile_cols, sg_po
         return SG_OK;
     });
     if (hipGetLastError() != hipSuccess) return SG_ERR_HIP;
-    sg_csr *m = new (std::nothrow) sg_csr();
-    if (!m) return SG_ERR_OOM;
     rows->written = rows->fwd_ptr != nullptr;     // (the representatives' matrix in group order stays pending)
-    m->ctx = ctx;
-    m->n_rows = B->n_rows;
-    m->n_cols = B->n_cols;
-    m->nnz = B->nnz;
-    m->dtype = B->dtype;
-    m->d_indptr = scratch.keep(ptr);
-    m->d_indices = scratch.keep(idx);
-    m->d_data = scratch.keep(val);
-    m->owned = true;
-    m->props_state = B->props_state;         // same rows: same properties
-    m->props_max_norm2 = B->props_max_norm2;
-    m->props_max_nnz = B->props_max_nnz;
-    m->props_repeated_column = B->props_repeated_column;
-    p->permuted = m;
+    p->permuted = m.release();
     p->d_orig_of = scratch.keep(orig_of);
     p->d_pos_of = scratch.keep(pos_of);
     return SG_OK;
@@ -1474,7 +1449,7 @@ static int alloc_index(sg_ctx *ctx, sg_postings *p, const sg_csr *B_in, const sg
     p->dtype = B->dtype;
     p->tile_log2 = plan.tile_log2;
     p->tile_form = (flags & SG_POSTINGS_TILE_FORM) != 0;
-    p->built_from = borrowed(*B_in);
+    p->built_from = csr_view(*B_in);
     p->built_from_valid = true;
     p->n_tiles = (int32_t)plan.n_tiles;
     p->b_indptr = B_in->d_indptr;      // the caller's matrix: what "A is the matrix the postings were built from" compares
@@ -1482,7 +1457,7 @@ static int alloc_index(sg_ctx *ctx, sg_postings *p, const sg_csr *B_in, const sg
     p->b_data = B_in->d_data;
     p->cosine_like = plan.cosine_like;
     p->max_norm2 = plan.max_norm2;
-    p->src = borrowed(*B);
+    p->src = csr_view(*B);
     p->split = plan.split;
     const size_t vs = 8;   // f64 value, or packed {row, f32 value}
     SG_TRY(sg_alloc(ctx, (size_t)plan.n_bins + 1, &p->d_seg));
@@ -1758,7 +1733,7 @@ extern "C" int sg_postings_build_flags(sg_ctx *ctx, const sg_csr *B_in, int32_t 
     }
     if (col) {
         p->collapse = col;
-        p->caller_b_copy = borrowed(*B_in);
+        p->caller_b_copy = csr_view(*B_in);
         p->caller_b = &p->caller_b_copy;
         p->n_right_caller = B_in->n_rows;
     }

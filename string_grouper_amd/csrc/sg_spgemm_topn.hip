@@ -1256,8 +1256,7 @@ extern "C" int sg_sp_matmul_topn_host(sg_ctx *ctx, int64_t n_left, int64_t n_rig
                              std::memcmp(a_data, b_data, (dtype == SG_F64 ? 8 : 4) * nnz) == 0));
     }
     // the four handles, freed in reverse -- the result, the index, B (unless it is A), A -- whichever way the call ends
-    using CsrPtr = std::unique_ptr<sg_csr, int (*)(sg_csr *)>;
-    CsrPtr A(nullptr, sg_csr_free), B(nullptr, sg_csr_free);
+    CsrPtr A, B;
     std::unique_ptr<sg_postings, int (*)(sg_postings *)> P(nullptr, sg_postings_free);
     TopnPtr R;
     sg_csr *m = nullptr;

@@ -1091,7 +1091,6 @@ struct FreeWith {      // the deleter of a half-built handle: every failure path
     void operator()(H *h) const { (void)FREE(h); }
 };
 using VocabPtr = std::unique_ptr<sg_vocab, FreeWith<sg_vocab_free>>;
-using CsrPtr = std::unique_ptr<sg_csr, FreeWith<sg_csr_free>>;
 
 static TokParams make_tok_params(const sg_vocab *v, const VocabImpl *im, const sg_strings *s) {
     TokParams tp;
@@ -1809,14 +1808,6 @@ extern "C" int sg_vec_transform(sg_ctx *ctx, const sg_vocab *v, const sg_strings
     SG_REQUIRE(im != nullptr, "unknown vocab");
     SG_REQUIRE((strings->sym_width == 2) == im->symbols && (!im->symbols || strings->alphabet == im->alphabet),
                "the strings are not of the kind (bytes / symbols of this alphabet) the vocabulary was fitted on");
-    CsrPtr m(new (std::nothrow) sg_csr());
-    if (!m) return SG_ERR_OOM;
-    m->ctx = ctx;
-    m->n_rows = strings->n;
-    m->n_cols = v->n_terms;
-    m->dtype = v->params.dtype;
-    m->owned = true;
-    m->from_vectoriser = v->idf_trusted;
     // tokens: reuse the pass made by fit() when these strings were part of it
     OwnedTokens local(ctx);
     Scratch tmp(ctx);
@@ -1831,14 +1822,9 @@ extern "C" int sg_vec_transform(sg_ctx *ctx, const sg_vocab *v, const sg_strings
     SgTimer timer(ctx, SG_K_WEIGHT);
     RowPointers rp;
     SG_TRY(row_pointers(ctx, v, tc, fitted, tmp, &rp));
-    m->d_indptr = rp.indptr;
-    m->nnz = rp.nnz;
-    int32_t *idx = nullptr;
-    void *val = nullptr;
-    SG_TRY(sg_alloc(ctx, (size_t)m->nnz + 4, &idx));
-    m->d_indices = idx;
-    SG_TRY(ctx->alloc(((size_t)m->nnz + 4) * (m->dtype == SG_F64 ? 8 : 4), &val));
-    m->d_data = val;
+    CsrPtr m;   // (the row pointers are the matrix's from here)
+    SG_TRY(csr_alloc(ctx, strings->n, v->n_terms, rp.nnz, v->params.dtype, CSR_SLACK_COPY, &m, rp.indptr));
+    m->from_vectoriser = v->idf_trusted;
     // (K2 can leave the largest row norm and the longest row behind; nothing reads them unless the opt-in row blocks
     //  are built -- the matrix is cosine-like by construction, sg_csr_props)
     if (ctx->opt_is("SG_ROW_BLOCKS", '1')) {
@@ -1903,24 +1889,12 @@ extern "C" int sg_vec_reweigh(sg_ctx *ctx, sg_vocab *v, const sg_csr *m, const i
     SG_REQUIRE(n_docs >= 0, "negative number of documents");
     SG_REQUIRE(weights_positive_and_finite(idf_host, v->n_terms, dtype), "an idf that is not positive and finite");
     const size_t s = dtype == SG_F64 ? 8 : 4;
-    CsrPtr r(new (std::nothrow) sg_csr());
-    if (!r) return SG_ERR_OOM;
-    r->ctx = ctx;
-    r->n_rows = m->n_rows;
-    r->n_cols = m->n_cols;
-    r->nnz = m->nnz;
-    r->dtype = dtype;
-    r->owned = true;
-    r->from_vectoriser = true;               // (counts times positive weights, every row divided by its norm)
-    int64_t *dp = nullptr;
-    int32_t *di = nullptr;
-    void *dd = nullptr;
-    SG_TRY(sg_alloc(ctx, (size_t)r->n_rows + 1, &dp));
-    r->d_indptr = dp;
-    SG_TRY(sg_alloc(ctx, (size_t)r->nnz + 4, &di));
-    r->d_indices = di;
-    SG_TRY(ctx->alloc(((size_t)r->nnz + 4) * s, &dd));
-    r->d_data = dd;
+    CsrPtr r;
+    SG_TRY(csr_alloc(ctx, m->n_rows, m->n_cols, m->nnz, dtype, CSR_SLACK_COPY, &r));
+    csr_inherit(r.get(), m, CsrDerived::reweighed);   // (both arrays, always: the kernel writes them)
+    int64_t *dp = (int64_t *)r->d_indptr;
+    int32_t *di = (int32_t *)r->d_indices;
+    void *dd = (void *)r->d_data;
     SG_TRY(sg_alloc(ctx, (size_t)r->n_rows + 1, &r->d_row_norm));
     SG_TRY(sg_alloc(ctx, (size_t)4, &r->d_props_words));
     Scratch tmp(ctx);
