@@ -32,7 +32,7 @@ for width in (256, 4096, 16384, 65536):
             ctx.sync()
             k = ctx.stats()["ms_spgemm_kernel"]
             got[0].free()
-            ctx.device_free(got[1])
+            got[1].free()
             best = k if best is None or k < best else best
         out.append((frac, round(best, 3)))
     print(f"ranges of {width} rows ending at fraction f of the list: kernel ms {out}")

@@ -31,6 +31,6 @@ for bar in (None, "0", "200", "400", "800", "1600", "3200"):
             ctx.sync()
             best = min(best, ctx.stats()["ms_spgemm_kernel"])
             got[0].free()
-            ctx.device_free(got[1])
+            got[1].free()
         line.append(f"rank {rank}: {best:7.2f} ms")
     print(f"SG_HEAVY_ROUNDS={bar}: " + "   ".join(line), flush=True)

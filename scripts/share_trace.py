@@ -26,4 +26,4 @@ for rep in range(5):
     ctx.sync()
     print(rep, ctx.stats()["ms_spgemm_kernel"], flush=True)
     got[0].free()
-    ctx.device_free(got[1])
+    got[1].free()

@@ -103,20 +103,21 @@ def main():
                 return got
             warm = pass1()                      # (the first call allocates the pair list: not part of a steady step)
             warm[0].free()
-            ctx.device_free(warm[1])
+            warm[1].free()
             best = None
             for _ in range(2):
                 t_p1, k_p1, got = ms(pass1, reps=1)
                 if best is None or t_p1 < best[0]:
                     if best is not None:
                         best[2][0].free()
-                        ctx.device_free(best[2][1])
+                        best[2][1].free()
                     best = (t_p1, k_p1, got)
                 else:
                     got[0].free()
-                    ctx.device_free(got[1])
+                    got[1].free()
             t_p1, k_p1, got = best
-            res, ptr, n_pairs, words = got
+            part = D.SelfJoinPart(*got, post)
+            n_pairs = len(part.pairs) // part.words
             pair_counts.append(n_pairs)
             # the OTHER form of the step (distributed.sharded_topn without the self-join form): the rank's block of rows
             # against all columns, one-sided -- twice the pairs of the self-join form in all, but no pair exchange, no
@@ -138,31 +139,27 @@ def main():
                              "pass1_ms_wall": t_p1, "pass1_ms_kernel": k_p1.get("spgemm_topn", 0.0),
                              "pass1_ms_kernel_alone": k_p1.get("spgemm_kernel", 0.0), "pairs": int(n_pairs),
                              "row_block_form_ms_wall": t_rb,
-                             "_res": res, "_ptr": ptr, "_words": words})
+                             "_part": part})
         # the merge needs ALL ranks' pairs: concatenate them on the device (what the all-gather delivers)
         import torch
         all_pairs = []
         for pr in per_rank:
             if pr["pairs"]:
-                t = torch.as_tensor(D.DeviceTensorView(pr["_ptr"], pr["pairs"] * pr["_words"], "<i4"), device="cuda")
-                all_pairs.append(t.clone())
+                all_pairs.append(ops.selfjoin_pairs(pr["_part"]).clone())
         pairs_all = torch.cat(all_pairs) if all_pairs else torch.zeros(0, dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
         for pr in per_rank:
             plo, phi, pstep = pr["range"]
-            words = pr["_words"]
 
             def merge():
                 # the driver's call: merge of the pairs that point into the range + (index over groups) expansion of the
                 # range's groups into their member rows
-                return ops.selfjoin_merge({"res": pr["_res"], "ptr": pr["_ptr"], "n": pr["pairs"], "words": words, "post": post},
-                                          pairs_all, plo, phi, pstep)
+                return ops.selfjoin_merge(pr["_part"], pairs_all, plo, phi, pstep)
             t_m, k_m, blk = ms(merge, reps=1)
             pr["merge_ms_wall"] = t_m
             pr["rows_out"] = int(blk.dims()[0])
             blk.free()
-            for k in ("_res", "_ptr", "_words"):
-                pr.pop(k)
+            pr.pop("_part")
         # collectives (model): df table all-reduce (2 x table x (N-1)/N through the ring), CSR all-gather (a rank receives
         # the other ranks' blocks), pair all-gather
         table = 4 * (1 << 21)

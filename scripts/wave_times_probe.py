@@ -31,7 +31,7 @@ for rep in range(3):
     ctx.sync()
     ms = ctx.stats()["ms_spgemm_kernel"]
     got[0].free()
-    ctx.device_free(got[1])
+    got[1].free()
 lib.sg_debug_read_wave_times(buf.ctypes.data_as(ctypes.c_void_p), 0)
 w = buf.reshape(-1, 4)
 print(f"world {world} rank {rank}, {n} names: kernel {ms:.3f} ms")

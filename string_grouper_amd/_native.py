@@ -317,6 +317,12 @@ class Csr(_Handle):
         check(lib().sg_csr_dims(self.h, C.byref(r), C.byref(c), C.byref(z), C.byref(d)))
         return r.value, c.value, z.value, d.value
 
+    def device_ptrs(self):
+        """(indptr int64, indices int32, data) as device addresses (include/sg_hip.h: sg_csr_device_ptrs)."""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().sg_csr_device_ptrs(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value or 0, b.value or 0, c.value or 0
+
     def to_scipy(self):
         import scipy.sparse as sp
         r, c, nnz, d = self.dims()
@@ -365,6 +371,17 @@ class Csr(_Handle):
         return v
 
 
+def topn_arrays_to_scipy(cols: np.ndarray, vals: np.ndarray, cnt: np.ndarray, n_cols: int):
+    """CSR of a fixed-stride result on the host (``TopN.to_host``'s arrays, or rows taken from them): row i keeps its first
+    cnt[i] entries, in their order."""
+    import scipy.sparse as sp
+    indptr = np.zeros(len(cnt) + 1, np.int64)
+    np.cumsum(cnt, out=indptr[1:])
+    mask = np.arange(cols.shape[1], dtype=np.int32)[None, :] < cnt[:, None]
+    idx_dtype = np.int32 if indptr[-1] < 2 ** 31 else np.int64
+    return sp.csr_matrix((vals[mask], cols[mask], indptr.astype(idx_dtype)), shape=(len(cnt), n_cols))
+
+
 class TopN(_Handle):
     _free = "sg_topn_free"
 
@@ -372,6 +389,13 @@ class TopN(_Handle):
         r, s, d, c = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64()
         check(lib().sg_topn_dims(self.h, C.byref(r), C.byref(s), C.byref(d), C.byref(c)))
         return r.value, s.value, d.value, c.value
+
+    def device_ptrs(self):
+        """(cols int32 [rows, stride], vals [rows, stride], counts int32 [rows]) as device addresses (include/sg_hip.h:
+        sg_topn_device_ptrs)."""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().sg_topn_device_ptrs(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value or 0, b.value or 0, c.value or 0
 
     def to_host(self):
         r, s, d, c = self.dims()
@@ -389,14 +413,7 @@ class TopN(_Handle):
 
     def to_scipy(self):
         """CSR with the within-row order of the device result (score desc / col asc when sort=True)."""
-        import scipy.sparse as sp
-        r, s, d, c = self.dims()
-        cols, vals, cnt = self.to_host()
-        indptr = np.zeros(r + 1, np.int64)
-        np.cumsum(cnt, out=indptr[1:])
-        mask = np.arange(s, dtype=np.int32)[None, :] < cnt[:, None]
-        idx_dtype = np.int32 if indptr[-1] < 2 ** 31 else np.int64
-        return sp.csr_matrix((vals[mask], cols[mask], indptr.astype(idx_dtype)), shape=(r, c))
+        return topn_arrays_to_scipy(*self.to_host(), self.dims()[3])
 
 
 class MatchList(_Handle):
@@ -767,16 +784,16 @@ class Context:
 
     def selfjoin_range(self, A: Csr, Bt: Postings, top_n: int, threshold: float, row_lo: int, row_hi: int, row_step: int = 1):
         """The rows [row_lo, row_hi) -- with ``row_step`` s > 1: row_hi - 1, row_hi - 1 - s, ... >= row_lo -- of the
-        self-join form (include/sg_hip.h: sg_selfjoin_range).  Returns
-        (TopN over all rows, device pointer of the mirrored pairs, number of pairs, int32 words per pair), or None when
-        the form does not apply to this input."""
+        self-join form (include/sg_hip.h: sg_selfjoin_range).  Returns (TopN over all rows, the mirrored pairs, int32 words
+        per pair), or None when the form does not apply to this input.  The pairs are a ``DeviceInts`` without a host copy,
+        the caller's to free; ``len()`` of it is the number of int32 words, pairs x words."""
         out, pairs = C.c_void_p(), C.c_void_p()
         n_pairs, words, ok = C.c_int64(), C.c_int32(), C.c_int32()
         check(lib().sg_selfjoin_range(self.h, A.h, Bt.h, int(top_n), float(threshold), int(row_lo), int(row_hi),
                                       C.byref(out), C.byref(pairs), C.byref(n_pairs), C.byref(words), C.byref(ok), int(row_step)))
         if not ok.value:
             return None
-        return TopN(self, out), pairs.value, n_pairs.value, words.value
+        return TopN(self, out), DeviceInts.adopt(self, pairs.value, n_pairs.value * words.value), words.value
 
     def selfjoin_merge(self, res: TopN, Bt: Optional[Postings], d_pairs: int, n_pairs: int, pair_words: int, row_lo: int,
                        row_hi: int, row_step: int = 1) -> None:
@@ -810,16 +827,12 @@ class Context:
         return TopN(self, out)
 
     def topn_expand_range(self, Bt: Postings, groups: "TopN", pos_lo: int, pos_hi: int, pos_step: int = 1):
-        """(result rows, device pointer of their int32 row numbers -- ``device_free`` it --, how many) for the rows of the
-        groups at the positions [pos_lo, pos_hi) of the index (sg_topn_expand_range)."""
+        """(result rows, their int32 row numbers -- a ``DeviceInts`` without a host copy, the caller's to free) for the rows
+        of the groups at the positions [pos_lo, pos_hi) of the index (sg_topn_expand_range)."""
         out, rows, n = C.c_void_p(), C.c_void_p(), C.c_int64()
         check(lib().sg_topn_expand_range(self.h, Bt.h, groups.h, int(pos_lo), int(pos_hi), C.byref(out), C.byref(rows), C.byref(n),
                                          int(pos_step)))
-        return TopN(self, out), rows.value or 0, n.value
-
-    def device_free(self, d_ptr: int) -> None:
-        if d_ptr:
-            check(lib().sg_device_free(self.h, C.c_void_p(d_ptr)))
+        return TopN(self, out), DeviceInts.adopt(self, rows.value, n.value)
 
     def row_costs(self, A: Csr, Bt: Postings) -> np.ndarray:
         out = np.zeros(max(A.dims()[0], 1), np.int64)

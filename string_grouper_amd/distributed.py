@@ -25,6 +25,7 @@ concatenates is the same in both.  PyTorch is plumbing: tensors that alias libra
 """
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -299,7 +300,6 @@ def selfjoin_share(n_rows: int, rank: int, world: int):
     every cost -- equal shares without a cost model -- and its launch ends with its cheapest rows, as the whole pass on
     one GPU does; a contiguous range of high positions ends with rows as expensive as its first, which cost + 0.8 ms per
     range at 663 k (scripts/sim_scaling.py).  ``SG_DIST_INTERLEAVE=0``: the contiguous ranges of ``selfjoin_row_ranges``."""
-    import os
     if world <= 1:
         return 0, n_rows, 1
     if os.environ.get("SG_DIST_INTERLEAVE", "1") == "0":
@@ -318,7 +318,6 @@ def share_positions(lo: int, hi: int, step: int) -> np.ndarray:
 def selfjoin_form_wanted(n_rows: int, world: int) -> bool:
     """From this size on the self-join form (every pair scored once, mirrored pairs exchanged by one all-gather) beats
     the one-sided multiply of row blocks; ``SG_DIST_SYM=0|1`` forces it off / on."""
-    import os
     flag = os.environ.get("SG_DIST_SYM", "")
     if flag in ("0", "1"):
         return flag == "1"                     # (forced on even on one rank: the plumbing test)
@@ -339,7 +338,7 @@ def sharded_selfjoin_topn(ops, A_full, post, top_n: int, threshold: float, group
     # one exchange tells every rank the lengths of all pair lists AND whether every range was applicable (-1: not) -- and
     # that all ranks built the same index: ranges and merge are in the index's position space, so an index over the row
     # permutation on one rank and in row order on another (or over groups on one only) would give rows that look fine
-    permuted = int(bool(ops.index_is_permuted(post))) if hasattr(ops, "index_is_permuted") else 0
+    permuted = int(bool(ops.index_is_permuted(post)))
     heads = all_headers([pairs.numel() if pairs is not None else -1, n, permuted], ops.device, group)
     if len({(h[1], h[2]) for h in heads}) != 1:
         raise RuntimeError(f"ranks built different indexes (rows of the index, permuted): {[(h[1], h[2]) for h in heads]}")
@@ -359,12 +358,15 @@ def gather_topn(ops, res, group=None, on_device: bool = False):
     all-gather (the fused tail of fit(), K6-K8, runs on the device: no reason to cross PCIe twice)."""
     cols, vals, counts = ops.topn_tensors(res)
     stride = cols.shape[1] if cols.dim() == 2 else 1
-    row_ids = getattr(res, "row_ids", None)
-    if row_ids is not None and dist.get_world_size(group) > 1:
-        # the rank's block holds the rows row_ids (members of its groups of identical rows): their numbers travel along
-        sizes = [h[0] for h in all_headers([row_ids.numel()], counts.device, group)]
-        row_ids = torch.cat(all_gather_ragged(row_ids, group, sizes))
-    if dist.get_world_size(group) > 1:
+    world = dist.get_world_size(group)
+    # decided once: ``place`` is the caller's row of every row of the ranks' concatenation, or None when the concatenation is
+    # the result as it stands (row blocks -- a plain result --, contiguous ranges of an index in row order)
+    place, exchanged = None, False
+    if isinstance(res, RankBlock) and not res.in_order:
+        place, exchanged = res.whole, res.whole is None
+        if exchanged:      # (interleaved shares, members of the rank's groups: the blocks' row numbers travel along)
+            place = torch.cat(all_gather_ragged(res.wire_rows, group)) if world > 1 else res.wire_rows
+    if world > 1:
         head = all_headers([stride, counts.numel()], counts.device, group)
         strides, rows = [h[0] for h in head], [h[1] for h in head]
         if len(set(strides)) != 1:
@@ -373,22 +375,13 @@ def gather_topn(ops, res, group=None, on_device: bool = False):
         cols = torch.cat(all_gather_ragged(cols.reshape(-1), group, cells)).reshape(-1, stride)
         vals = torch.cat(all_gather_ragged(vals.reshape(-1), group, cells)).reshape(-1, stride)
         counts = torch.cat(all_gather_ragged(counts, group, rows))
-    orig_of = getattr(res, "orig_of", None)
-    if orig_of is not None:
-        # the ranks' ranges were ranges of positions of the library's row permutation: block p of the concatenation is
-        # row orig_of[p]
-        if counts.numel() != orig_of.numel():
-            raise RuntimeError(f"the ranks' ranges hold {counts.numel()} rows, the permutation {orig_of.numel()}")
-        cols = torch.empty_like(cols).index_copy_(0, orig_of, cols)
-        vals = torch.empty_like(vals).index_copy_(0, orig_of, vals)
-        counts = torch.empty_like(counts).index_copy_(0, orig_of, counts)
-    if row_ids is not None:
-        if counts.numel() != row_ids.numel() or (row_ids.numel() and int(row_ids.max()) >= row_ids.numel()):
-            raise RuntimeError(f"the ranks' blocks hold {counts.numel()} rows for {row_ids.numel()} row numbers")
-        row_ids = row_ids.to(torch.int64)
-        cols = torch.empty_like(cols).index_copy_(0, row_ids, cols)
-        vals = torch.empty_like(vals).index_copy_(0, row_ids, vals)
-        counts = torch.empty_like(counts).index_copy_(0, row_ids, counts)
+    if place is not None:
+        if counts.numel() != place.numel() or (exchanged and place.numel() and int(place.max()) >= place.numel()):
+            raise RuntimeError(f"the ranks' blocks hold {counts.numel()} rows for {place.numel()} row numbers (or one beyond them)")
+        place = place.to(torch.int64)
+        cols = torch.empty_like(cols).index_copy_(0, place, cols)
+        vals = torch.empty_like(vals).index_copy_(0, place, vals)
+        counts = torch.empty_like(counts).index_copy_(0, place, counts)
     if on_device:
         return cols.contiguous(), vals.contiguous(), counts.contiguous()
     return cols.cpu().numpy(), vals.cpu().numpy(), counts.cpu().numpy()
@@ -420,18 +413,22 @@ class DeviceTensorView:
         self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr, False), "version": 2}
 
 
+def device_view(ptr: int, n: int, typestr: str, device):
+    """Torch tensor of the ``n`` elements of library memory at ``ptr``, without a copy: valid while the library object
+    that owns the memory lives.  (A view cannot have no elements: one is made of one element and cut; no memory, no view.)"""
+    if not ptr:
+        return torch.from_numpy(np.empty(0, np.dtype(typestr))).to(device)
+    return torch.as_tensor(DeviceTensorView(ptr, max(n, 1), typestr), device=device)[:n]
+
+
 def csr_as_torch(csr) -> tuple:
     """(indptr, indices, data) torch tensors aliasing a device CSR of the HIP library."""
-    import ctypes as C
     from . import _native as N
     r, c, nnz, d = csr.dims()
-    p_ip, p_ix, p_d = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    N.check(N.lib().sg_csr_device_ptrs(csr.h, C.byref(p_ip), C.byref(p_ix), C.byref(p_d)))
+    p_ip, p_ix, p_d = csr.device_ptrs()
     dev = torch.device("cuda", csr.ctx.device)
-    indptr = torch.as_tensor(DeviceTensorView(p_ip.value, r + 1, "<i8"), device=dev)
-    indices = torch.as_tensor(DeviceTensorView(p_ix.value, max(nnz, 1), "<i4"), device=dev)[:nnz]
-    data = torch.as_tensor(DeviceTensorView(p_d.value, max(nnz, 1), "<f8" if d == N.SG_F64 else "<f4"), device=dev)[:nnz]
-    return indptr, indices, data
+    return (device_view(p_ip, r + 1, "<i8", dev), device_view(p_ix, nnz, "<i4", dev),
+            device_view(p_d, nnz, "<f8" if d == N.SG_F64 else "<f4", dev))
 
 
 def csr_from_torch(ctx, indptr, indices, data, shape):
@@ -443,43 +440,63 @@ def csr_from_torch(ctx, indptr, indices, data, shape):
                                data.data_ptr() if nnz else 0, dtype, keepalive=(indptr, indices, data))
 
 
-class TopNRows:
-    """The rows [lo, hi) of a device result (a rank's block of the self-join form over row ranges).  ``orig_of`` given:
-    the range is one of POSITIONS of the library's row permutation (int64 tensor, position -> row): the block's rows are
-    orig_of[lo:hi], in that order; the blocks of all ranks concatenated are the result in position order."""
+class SelfJoinPart:
+    """What ``ops.selfjoin_range`` returns: the result over all rows with the rank's own matches (``res``), the mirrored
+    pairs it publishes (``pairs``, ``words`` int32 words each) and the index they were scored on (``post``, kept alive).
+    ``free()`` releases what the part still owns; ``selfjoin_merge`` ends the part and may take the result out of it."""
 
-    def __init__(self, res, lo: int, hi: int, orig_of=None, row_ids=None, sel=None):
-        self.res, self.lo, self.hi, self.orig_of = res, lo, hi, orig_of
-        # ``row_ids`` given (int tensor): block row k is the caller's row row_ids[k] -- the rank's share was not a contiguous
-        # range of rows (interleaved shares; an index over GROUPS of identical rows, whose members are the block's rows);
-        # ``sel`` given (int64 tensor): the block is the rows sel of ``res`` (else the rows [lo, hi))
-        self.row_ids, self.sel = row_ids, sel
+    def __init__(self, res, pairs, words: int, post):
+        self.res, self.pairs, self.words, self.post = res, pairs, words, post
+
+    def take_res(self):
+        res, self.res = self.res, None
+        return res
+
+    def free(self):
+        for h in (self.pairs, self.res):
+            if hasattr(h, "free"):
+                h.free()
+        self.pairs = self.res = None
+
+
+class RankBlock:
+    """A rank's block of the self-join form: the rows ``sel`` -- ONE selector, a slice (a contiguous range: no copy) or an
+    int64 index tensor -- of the result ``res`` (a device result, or anything with its ``dims``, ``to_host`` and ``free``).
+    ``rows``: the caller's row number of every row of the block, in block order (int64), whatever the layout; ``wire_rows``:
+    the same numbers in the width they were made in (the library's lists are int32), as ``gather_topn`` exchanges them.
+    What ``gather_topn`` needs to place the ranks' concatenation:
+      ``in_order``  the ranks' blocks one after the other ARE the result (contiguous ranges of an index in row order);
+      ``whole``     else, the caller's row of every row of the concatenation when every rank knows it without asking
+                    (contiguous ranges of positions: the permutation's orig_of), or None: the ranks exchange ``rows``."""
+
+    def __init__(self, res, rows, sel=slice(None), in_order: bool = False, whole=None):
+        self.res, self.wire_rows, self.sel, self.in_order, self.whole = res, rows, sel, in_order, whole
         self._keep = None
+
+    @property
+    def rows(self):
+        return self.wire_rows.to(torch.int64)
 
     def free(self):
         self.res.free()
 
     def dims(self):
-        r, s, d, c = self.res.dims()
-        return (int(self.sel.numel()) if self.sel is not None else self.hi - self.lo), s, d, c
+        _, s, d, c = self.res.dims()
+        return int(self.wire_rows.numel()), s, d, c
+
+    def pick(self, *tensors):
+        """The block's rows of tensors that hold one entry per row of ``res``."""
+        if isinstance(self.sel, slice):
+            return tuple(t[self.sel] for t in tensors)
+        return tuple(t.index_select(0, self.sel) for t in tensors)
 
     def to_host(self):
-        cols, vals, cnt = self.res.to_host()
-        if self.sel is not None:
-            ids = self.sel.cpu().numpy()
-            return cols[ids], vals[ids], cnt[ids]
-        if self.orig_of is not None:
-            ids = self.orig_of[self.lo:self.hi].cpu().numpy()
-            return cols[ids], vals[ids], cnt[ids]
-        return cols[self.lo:self.hi], vals[self.lo:self.hi], cnt[self.lo:self.hi]
+        ids = self.sel if isinstance(self.sel, slice) else self.sel.cpu().numpy()
+        return tuple(a[ids] for a in self.res.to_host())
 
     def to_scipy(self):
-        import scipy.sparse as sp
-        cols, vals, cnt = self.to_host()
-        indptr = np.zeros(len(cnt) + 1, np.int64)
-        np.cumsum(cnt, out=indptr[1:])
-        mask = np.arange(cols.shape[1], dtype=np.int32)[None, :] < cnt[:, None]
-        return sp.csr_matrix((vals[mask], cols[mask], indptr), shape=(len(cnt), self.res.dims()[3]))
+        from ._native import topn_arrays_to_scipy
+        return topn_arrays_to_scipy(*self.to_host(), self.res.dims()[3])
 
 
 class HipOps:
@@ -507,10 +524,7 @@ class HipOps:
     def df_tensor(self, vec):
         ptr, n, _ = vec.df_table()
         self._sync()
-        return torch.as_tensor(DeviceTensorView(ptr, n, "<i4"), device=self.device)
-
-    def df_shareable(self, vec) -> bool:
-        return vec.df_table()[2]
+        return device_view(ptr, n, "<i4", self.device)
 
     def fit_info(self, vec):
         """(the table can be added to other ranks' tables, its entries) -- without touching the table (a sorted vocabulary
@@ -548,54 +562,46 @@ class HipOps:
     # ---- the self-join form over row ranges (sharded_selfjoin_topn)
     def selfjoin_range(self, A_full, post, top_n, threshold, lo, hi, step=1):
         got = self.ctx.selfjoin_range(A_full, post, top_n, threshold, lo, hi, step)
-        if got is None:
-            return None
-        res, ptr, n_pairs, words = got
-        return {"res": res, "ptr": ptr, "n": n_pairs, "words": words, "post": post}
+        return None if got is None else SelfJoinPart(*got, post)
 
     def selfjoin_pairs(self, part):
+        """The part's pair list as an int32 tensor: a view of the part's memory, valid only while the part lives (until
+        ``selfjoin_merge`` or ``selfjoin_discard``); ``clone()`` what has to outlast it."""
         self._sync()
-        n = part["n"] * part["words"]
-        if n == 0:
-            return torch.zeros(0, dtype=torch.int32, device=self.device)
-        return torch.as_tensor(DeviceTensorView(part["ptr"], n, "<i4"), device=self.device)[:n]
+        return device_view(part.pairs.ptr, len(part.pairs), "<i4", self.device)
 
     def selfjoin_discard(self, part):
-        self.ctx.device_free(part["ptr"])
-        part["res"].free()
+        part.free()
 
     def selfjoin_merge(self, part, pairs_all, lo, hi, step=1):
-        self._sync()                                  # the gathered list is torch's: ordered before the library reads it
-        words = part["words"]
-        pairs_all = pairs_all.contiguous()
-        post = part.get("post")
-        self.ctx.selfjoin_merge(part["res"], post, pairs_all.data_ptr(), pairs_all.numel() // words, words, lo, hi, step)
-        self.ctx.sync()                               # ... and the library is done with it before torch frees it
-        self.ctx.device_free(part["ptr"])
-        # the index is built over a permutation of the rows: the range [lo, hi) is one of POSITIONS, its rows are orig_of[lo:hi]
-        orig_of = None
-        if post is not None:
-            p_orig, _ = self.ctx.postings_permutation(post)
-            if p_orig:
-                n = part["res"].dims()[0]
-                orig_of = torch.as_tensor(DeviceTensorView(p_orig, n, "<i4"), device=self.device)[:n].to(torch.int64)
-        n_index, n_caller, p_gid = self.ctx.postings_rows(post) if post is not None else (0, 0, 0)
-        if not p_gid and step > 1:
-            # an interleaved share: the block's rows are the rows at the share's positions
-            pos = torch.from_numpy(share_positions(lo, hi, step)).to(self.device)
-            rows = orig_of.index_select(0, pos) if orig_of is not None else pos
-            return TopNRows(part["res"], 0, int(rows.numel()), None, row_ids=rows, sel=rows)
-        if not p_gid:
-            return TopNRows(part["res"], lo, hi, orig_of)
-        # an index over groups of identical rows: the range was one of groups; the rows of this rank are the members of
-        # its groups, expanded here from tables every rank holds (no exchange)
-        r, p_rows, n_mine = self.ctx.topn_expand_range(post, part["res"], lo, hi, step)
-        self.ctx.sync()
-        rows = torch.as_tensor(DeviceTensorView(p_rows, max(n_mine, 1), "<i4"), device=self.device)[:n_mine].clone()
-        torch.cuda.current_stream(self.device).synchronize()   # (copied before the library's list is released)
-        self.ctx.device_free(p_rows)
-        part["res"].free()
-        return TopNRows(r, 0, rows.numel(), None, row_ids=rows)
+        from ._native import Scope
+        ctx, post = self.ctx, part.post
+        with Scope() as s:
+            s.own(part)                               # whatever happens below, the part does not outlive this call
+            self._sync()                              # the gathered list is torch's: ordered before the library reads it
+            pairs_all = pairs_all.contiguous()
+            ctx.selfjoin_merge(part.res, post, pairs_all.data_ptr(), pairs_all.numel() // part.words, part.words, lo, hi, step)
+            ctx.sync()                                # ... and the library is done with it before torch frees it
+            part.pairs.free()
+            # the index is built over a permutation of the rows: the range [lo, hi) is one of POSITIONS, its rows are orig_of[lo:hi]
+            p_orig, _ = ctx.postings_permutation(post)
+            orig_of = device_view(p_orig, part.res.dims()[0], "<i4", self.device).to(torch.int64) if p_orig else None
+            if ctx.postings_rows(post)[2]:
+                # an index over groups of identical rows: the range was one of groups; the rows of this rank are the members
+                # of its groups, expanded here from tables every rank holds (no exchange)
+                r, d_rows = ctx.topn_expand_range(post, part.res, lo, hi, step)
+                s.own(r), s.own(d_rows)
+                ctx.sync()
+                rows = device_view(d_rows.ptr, len(d_rows), "<i4", self.device).clone()
+                torch.cuda.current_stream(self.device).synchronize()   # (copied before the library's list is released)
+                return RankBlock(s.keep(r), rows)
+            if step > 1:                              # an interleaved share: the rows at the share's positions
+                pos = torch.from_numpy(share_positions(lo, hi, step)).to(self.device)
+                rows = orig_of.index_select(0, pos) if orig_of is not None else pos
+                return RankBlock(part.take_res(), rows, rows)
+            if orig_of is not None:
+                return RankBlock(part.take_res(), orig_of[lo:hi], orig_of[lo:hi], whole=orig_of)
+            return RankBlock(part.take_res(), torch.arange(lo, hi), slice(lo, hi), in_order=True)   # (rows nobody sends: host)
 
     def selfjoin_rows(self, A_full, post):
         return self.ctx.postings_rows(post)[0]
@@ -613,25 +619,15 @@ class HipOps:
         return r
 
     def topn_tensors(self, res):
-        import ctypes as C
         from . import _native as N
-        if isinstance(res, TopNRows):
-            cols, vals, counts = self.topn_tensors(res.res)
-            if res.sel is not None:
-                return cols.index_select(0, res.sel), vals.index_select(0, res.sel), counts.index_select(0, res.sel)
-            if res.orig_of is not None:               # rows of the range in POSITION order
-                ids = res.orig_of[res.lo:res.hi]
-                return cols.index_select(0, ids), vals.index_select(0, ids), counts.index_select(0, ids)
-            return cols[res.lo:res.hi], vals[res.lo:res.hi], counts[res.lo:res.hi]
+        if isinstance(res, RankBlock):
+            return res.pick(*self.topn_tensors(res.res))
         r, s, d, _ = res.dims()
-        pc, pv, pn = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        N.check(N.lib().sg_topn_device_ptrs(res.h, C.byref(pc), C.byref(pv), C.byref(pn)))
+        pc, pv, pn = res.device_ptrs()
         self._sync()
-        cols = torch.as_tensor(DeviceTensorView(pc.value, max(r * s, 1), "<i4"), device=self.device)[:r * s].reshape(r, s)
-        vals = torch.as_tensor(DeviceTensorView(pv.value, max(r * s, 1), "<f8" if d == N.SG_F64 else "<f4"),
-                               device=self.device)[:r * s].reshape(r, s)
-        counts = torch.as_tensor(DeviceTensorView(pn.value, max(r, 1), "<i4"), device=self.device)[:r]
-        return cols, vals, counts
+        return (device_view(pc, r * s, "<i4", self.device).reshape(r, s),
+                device_view(pv, r * s, "<f8" if d == N.SG_F64 else "<f4", self.device).reshape(r, s),
+                device_view(pn, r, "<i4", self.device))
 
 
 # ---------------------------------------------------------------------------------------------- string exchange
@@ -691,7 +687,6 @@ def pruned_multiply_expected(top_n: int, threshold: float, ctx=None) -> bool:
     Its cost per left row is nearly uniform (the column-tile loop dominates), whereas the exact kernel's
     follows the row's intermediate products -- which decides how left rows are best cut across ranks.
     ``ctx``: the context whose switches apply (its frozen copy of SG_PRUNE / SG_PRUNE_MIN_THRESHOLD)."""
-    import os
     opts = ctx.options() if ctx is not None else os.environ
     if opts.get("SG_PRUNE", "1").startswith("0"):
         return False

@@ -53,15 +53,8 @@ def block_of(res, rank, world, n_rows):
     """(row numbers, CSR) of this rank's block of a result of ``distributed_self_join`` / ``distributed_match``."""
     import torch  # noqa: F401
     from string_grouper_amd import distributed as D
-    if isinstance(res, D.TopNRows):
-        C = res.to_scipy()
-        if res.row_ids is not None:
-            rows = res.row_ids.cpu().numpy().astype(np.int64)
-        elif res.orig_of is not None:
-            rows = res.orig_of[res.lo:res.hi].cpu().numpy().astype(np.int64)
-        else:
-            rows = np.arange(res.lo, res.hi)
-        return rows, C
+    if isinstance(res, D.RankBlock):
+        return res.rows.cpu().numpy(), res.to_scipy()
     lo, hi = D.row_block(rank, world, n_rows)
     return np.arange(lo, hi), res.to_scipy()
 
@@ -132,11 +125,12 @@ def _run(rank, world, workdir, jobs, out, device=0):
             res, _ = D.distributed_self_join(ops, block, top_n, thr)
             ctx.sync()
             st = ctx.stats()
-            form = "selfjoin" if isinstance(res, D.TopNRows) else "rowblock"
+            form = "selfjoin" if isinstance(res, D.RankBlock) else "rowblock"
             if job.get("form") and form != job["form"]:
                 out[tag + ":form"] = f"took the {form} form, the job expects {job['form']}"
             if job.get("grouped") is not None:
-                grouped = isinstance(res, D.TopNRows) and res.row_ids is not None and res.sel is None
+                # (asked of the index the block keeps alive: a row -> group table is present)
+                grouped = form == "selfjoin" and ctx.postings_rows(res._keep[0])[2] != 0
                 if form == "selfjoin" and grouped != job["grouped"]:
                     out[tag + ":grouped"] = f"index over groups: {grouped}, the job expects {job['grouped']}"
             rows, C = block_of(res, rank, world, len(names))

@@ -8,6 +8,7 @@ import torch
 
 from oracle import oracle as O
 from oracle import port as P
+from string_grouper_amd.distributed import RankBlock, SelfJoinPart, share_positions
 
 KEY_BITS = 7
 NGRAM = 3
@@ -54,9 +55,6 @@ class NumpyOps:
 
     def df_tensor(self, st):
         return st.df
-
-    def df_shareable(self, st):
-        return True
 
     # test hook: ranks for which fit_info reports a table that cannot be added to the others' (a block coded over the
     # alphabet of its own strings)
@@ -172,12 +170,11 @@ class NumpyOps:
     # ---- the self-join form over row ranges: the contract of sg_selfjoin_range / sg_selfjoin_merge restated with the
     #      oracle's multiply (rows of the range keep their matches j <= i; mirrored pairs (i, j < i, score) go out)
     def selfjoin_range(self, A_full, post, top_n, threshold, lo, hi, step=1):
-        from string_grouper_amd.distributed import share_positions
         if isinstance(post, GroupedIndex):
             # the result over GROUPS must hold what expansion needs: a row's top_n columns can come from top_n groups at
             # most, so top_n groups per group are enough (the library's argument, sg_collapse.hip)
             part = self.selfjoin_range(post.unique, post.unique, top_n, threshold, lo, hi, step)
-            part["groups_of"] = post
+            part.post = post
             return part
         n = A_full.shape[0]
         orig_of, pos_of = self.permutation(n) if self.permuted else (np.arange(n), np.arange(n))
@@ -204,18 +201,17 @@ class NumpyOps:
         for p, (i, jj, ss) in enumerate(pairs):
             flat[p, 0], flat[p, 1] = i, jj
             flat[p, 2:] = np.frombuffer(np.asarray([ss], self.dtype).tobytes(), np.int32)
-        return {"res": (cols, vals, cnt), "pairs": torch.from_numpy(flat.reshape(-1)), "words": words, "top_n": stride}
+        return SelfJoinPart(HostTopN(cols, vals, cnt, n), torch.from_numpy(flat.reshape(-1)), words, post)
 
     def selfjoin_pairs(self, part):
-        return part["pairs"]
+        return part.pairs
 
     def selfjoin_discard(self, part):
-        pass
+        part.free()
 
     def selfjoin_merge(self, part, pairs_all, lo, hi, step=1):
-        from string_grouper_amd.distributed import share_positions
-        cols, vals, cnt = part["res"]
-        words, stride = part["words"], part["top_n"]
+        cols, vals, cnt = part.res.to_host()
+        words, stride = part.words, cols.shape[1]
         rec = pairs_all.numpy().reshape(-1, words)
         scores = np.frombuffer(np.ascontiguousarray(rec[:, 2:]).tobytes(), self.dtype)
         n = cols.shape[0]
@@ -231,35 +227,41 @@ class NumpyOps:
             cnt[row] = len(order)
             cols[row, :len(order)] = c[order]
             vals[row, :len(order)] = v[order]
-        post = part.get("groups_of")
-        if post is not None:
+        my_rows = torch.from_numpy(my_rows)
+        post = part.post
+        if isinstance(post, GroupedIndex):
             # the range was one of groups: the rank's rows are the members of its groups, expanded from the tables of the
-            # index (which every rank holds)
+            # index (which every rank holds); their numbers are the library's, int32
             mine = set(int(g) for g in my_rows)
             rows = np.array([i for i in range(post.full.shape[0]) if int(post.gid[i]) in mine], np.int64)
-            return PermutedBlock(self.expand_rows(post, rows, cols, vals, cnt), None, torch.from_numpy(rows.astype(np.int32)))
+            expanded = HostTopN(*self.expand_rows(post, rows, cols, vals, cnt), post.full.shape[0])
+            return RankBlock(expanded, torch.from_numpy(rows.astype(np.int32)))
         if step > 1:     # an interleaved share: the block lists its rows
-            return PermutedBlock((cols[my_rows], vals[my_rows], cnt[my_rows]), None, torch.from_numpy(my_rows.astype(np.int64)))
+            return RankBlock(part.take_res(), my_rows, my_rows)
         if self.permuted:
-            ids = orig_of[lo:hi]
-            return PermutedBlock((cols[ids], vals[ids], cnt[ids]), torch.from_numpy(orig_of))
-        return cols[lo:hi], vals[lo:hi], cnt[lo:hi]
+            return RankBlock(part.take_res(), my_rows, my_rows, whole=torch.from_numpy(orig_of))
+        return RankBlock(part.take_res(), my_rows, slice(lo, hi), in_order=True)
 
     def topn_tensors(self, res):
-        if isinstance(res, PermutedBlock):
-            res = res.arrays
+        if isinstance(res, RankBlock):
+            return res.pick(*self.topn_tensors(res.res.to_host()))
         return torch.from_numpy(res[0]), torch.from_numpy(res[1]), torch.from_numpy(res[2])
 
 
-class PermutedBlock:
-    """A rank's block of the self-join form when the ranges are ranges of positions: rows orig_of[lo:hi] in that order
-    (what distributed.TopNRows is for the device library)."""
+class HostTopN:
+    """A fixed-stride result in host arrays with the face ``distributed.RankBlock`` asks of a result."""
 
-    def __init__(self, arrays, orig_of, row_ids=None):
-        self.arrays, self.orig_of, self.row_ids = arrays, orig_of, row_ids
+    def __init__(self, cols, vals, cnt, n_cols):
+        self.arrays, self.n_cols = (cols, vals, cnt), n_cols
 
-    def __getitem__(self, k):
-        return self.arrays[k]
+    def dims(self):
+        return (*self.arrays[0].shape, int(self.arrays[1].dtype == np.float64), self.n_cols)
+
+    def to_host(self):
+        return self.arrays
+
+    def free(self):
+        pass
 
 
 class GroupedIndex:

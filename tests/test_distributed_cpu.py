@@ -98,6 +98,19 @@ def _csr_of(cols, vals, counts, n_cols):
     return sp.csr_matrix((vals[mask], cols[mask], indptr), shape=(len(counts), n_cols))
 
 
+# What gather_topn moves per layout at world 2, {kind: (calls, bytes this rank received)}: 4 all-gathers where no row numbers
+# travel (one header, then cols, vals, counts), 6 where they do (one more header, the rows), nothing else.  The same on both
+# ranks (every gather is padded to the longer rank's).  Taken with this worker's inputs on commit 1cf0400, before the ranks'
+# blocks became one class: the layouts must go on costing what they cost there.
+_GATHER_TALLY = {
+    "rowblock": (4, 105436), "match": (4, 147616),
+    "ranges": (4, 156676), "positions": (4, 156676),
+    "groups": (6, 168280), "groups_permuted": (6, 165464),
+    "interleaved": (6, 118520), "interleaved_groups": (6, 113456),
+    "interleaved_permuted": (6, 118520), "interleaved_permuted_groups": (6, 116536),
+}
+
+
 def _sharded_worker(rank, world, port, ret):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -107,11 +120,19 @@ def _sharded_worker(rank, world, port, ret):
         from tests._numpy_ops import NumpyOps
         ops = NumpyOps(np.float32)
         ok = {}
+
+        def gather(tag, res):
+            D.reset_collective_tally()
+            out = D.gather_topn(ops, res)
+            want = {"all_gather": list(_GATHER_TALLY[tag]), "all_reduce": [0, 0], "broadcast": [0, 0]}
+            ok[tag + "_gather_collectives"] = D.COLLECTIVE_TALLY == want
+            return out
+
         # ---- self-join: every rank tokenises its block, df all-reduce, CSR all-gather, local multiply, result gather
         names = synth_names(2501, 42) + ["", "AB", "ACME HOLDINGS INC"] * 3          # odd size: uneven blocks
         lo, hi = D.row_block(rank, world, len(names))
         res, state = D.distributed_self_join(ops, names[lo:hi], 10, 0.8)
-        cols, vals, counts = D.gather_topn(ops, res)
+        cols, vals, counts = gather("rowblock", res)
         A, _, C = _expected(names, None, 10, 0.8, np.float32)
         got = _csr_of(cols, vals, counts, len(names))
         ok["selfjoin_counts"] = np.array_equal(np.diff(got.indptr), np.diff(C.indptr))
@@ -141,44 +162,50 @@ def _sharded_worker(rank, world, port, ret):
             finally:
                 os.environ["SG_DIST_SYM"] = "0"
                 ops.permuted = ops.grouped = False
-            cols, vals, counts = D.gather_topn(ops, res)
+            cols, vals, counts = gather(tag, res)
             got = _csr_of(cols, vals, counts, len(hubs))
             ok[tag + "_counts"] = np.array_equal(np.diff(got.indptr), np.diff(C.indptr))
             ok[tag + "_indices"] = np.array_equal(got.indices, C.indices)
             ok[tag + "_scores"] = np.array_equal(got.data, C.data)
+            # the block names the caller's row of each of its rows: the two ranks' together are every row once, and without
+            # groups they are the rows at the share's positions
+            ok[tag + "_block_lists_its_rows"] = res.rows.dtype == torch.int64 and res.dims()[0] == res.rows.numel()
+            both = D.all_gather_ragged(res.rows)
+            ok[tag + "_every_row_once"] = sorted(torch.cat(both).tolist()) == list(range(len(hubs)))
+            if not grouped:
+                orig_of = NumpyOps.permutation(len(hubs))[0] if permuted else np.arange(len(hubs))
+                mine = orig_of[D.share_positions(*D.selfjoin_share(len(hubs), rank, world))]
+                ok[tag + "_rows_of_my_positions"] = res.rows.tolist() == mine.tolist()
             return res
-
-        def every_row_once(tag, res):
-            ok[tag + "_block_lists_its_rows"] = res.row_ids is not None and len(res[2]) == res.row_ids.numel()
-            n_mine = torch.tensor([res.row_ids.numel()])
-            dist.all_reduce(n_mine)
-            ok[tag + "_every_row_once"] = int(n_mine) == len(hubs)
 
         # (a) contiguous ranges of rows / of positions of the library's row permutation (SG_DIST_INTERLEAVE=0): a rank's block
         #     holds the rows [lo, hi) / orig_of[lo:hi], gather_topn concatenates and puts the blocks back into row order
         os.environ["SG_DIST_INTERLEAVE"] = "0"
         res = run_form("ranges", False, False)
-        ok["range_block_is_mine"] = len(res[2]) == int(bounds[rank + 1] - bounds[rank])
+        ok["range_block_is_mine"] = res.dims()[0] == int(bounds[rank + 1] - bounds[rank]) and res.in_order
         res = run_form("positions", True, False)
-        ok["position_block_is_mine"] = len(res[2]) == int(bounds[rank + 1] - bounds[rank]) and res.orig_of is not None
+        ok["position_block_is_mine"] = (res.dims()[0] == int(bounds[rank + 1] - bounds[rank]) and not res.in_order
+                                        and res.whole.tolist() == NumpyOps.permutation(len(hubs))[0].tolist())
         # (b) ... over one representative per group of identical rows (what the library builds by default): ranges of GROUPS,
         #     a rank's block holds the rows that are members of its groups (expanded on the rank), gather_topn puts the
         #     gathered rows where their numbers say
         for permuted in (False, True):
-            every_row_once("groups_permuted" if permuted else "groups", run_form("groups_permuted" if permuted else "groups", permuted, True))
+            res = run_form("groups_permuted" if permuted else "groups", permuted, True)
+            ok["groups_exchange_their_rows"] = ok.get("groups_exchange_their_rows", True) and not res.in_order and res.whole is None
         # (c) the default: INTERLEAVED shares (rank r scores every world-th position from the top): blocks list their rows
         os.environ.pop("SG_DIST_INTERLEAVE")
         for permuted in (False, True):
             for grouped in (False, True):
                 tag = "interleaved" + ("_permuted" if permuted else "") + ("_groups" if grouped else "")
-                every_row_once(tag, run_form(tag, permuted, grouped))
+                res = run_form(tag, permuted, grouped)
+                ok[tag + "_exchanges_its_rows"] = not res.in_order and res.whole is None
         # ---- master x duplicates (configs[4]): both columns sharded, vocabulary from both, duplicates replicated
         master = synth_names(1800, 7)
         dups = synth_names(901, 8, perturb_of=master, perturb_frac=0.5)
         mlo, mhi = D.row_block(rank, world, len(master))
         dlo, dhi = D.row_block(rank, world, len(dups))
         res, _ = D.distributed_match(ops, master[mlo:mhi], dups[dlo:dhi], 20, 0.7)
-        cols, vals, counts = D.gather_topn(ops, res)
+        cols, vals, counts = gather("match", res)
         _, _, C = _expected(master, dups, 20, 0.7, np.float32)
         got = _csr_of(cols, vals, counts, len(dups))
         ok["match_counts"] = np.array_equal(np.diff(got.indptr), np.diff(C.indptr))

@@ -143,7 +143,7 @@ def test_row_ranges_of_the_selfjoin_form_on_mixed_norms(ctx, dtype):
                 parts = [ops.selfjoin_range(dA, post, top_n, thr, *sh) for sh in shares]
                 assert all(p is not None for p in parts), "the self-join form did not take the range"
                 assert ctx.stats()["prune_symmetric"] == 1 and ctx.stats()["prune_rows"] > 0
-                words = parts[0]["words"]
+                words = parts[0].words
                 pairs_all = torch.cat([ops.selfjoin_pairs(p).clone() for p in parts])
                 assert pairs_all.numel() > 0 and pairs_all.numel() % words == 0
                 if reverse:

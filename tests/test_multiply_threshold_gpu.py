@@ -128,19 +128,13 @@ def test_form_equals_the_port_at_the_threshold_and_the_cut(ctx, name, case, dtyp
 
 
 def _assemble(blocks, n, stride, dtype, n_cols):
-    """The ranks' blocks put together on the host: every block knows its rows (row numbers, positions of the library's
-    permutation, or a contiguous range)."""
+    """The ranks' blocks put together on the host: every block names the caller's row of each of its rows."""
     cols = np.zeros((n, stride), np.int32)
     vals = np.zeros((n, stride), dtype)
     cnt = np.full(n, -1, np.int32)
     for b in blocks:
         c, v, k = b.to_host()
-        if b.row_ids is not None:
-            ids = b.row_ids.cpu().numpy().astype(np.int64)
-        elif b.orig_of is not None:
-            ids = b.orig_of[b.lo:b.hi].cpu().numpy()
-        else:
-            ids = np.arange(b.lo, b.hi)
+        ids = b.rows.cpu().numpy()
         assert (cnt[ids] == -1).all(), "a row in two blocks"
         cols[ids], vals[ids], cnt[ids] = c, v, k
     assert (cnt >= 0).all(), "a row in no block"
@@ -177,7 +171,7 @@ def test_row_ranges_of_the_selfjoin_form_on_the_ladder(ctx, dtype):
                     parts = [ops.selfjoin_range(dA, post, top_n, thr, *sh) for sh in shares]
                     assert all(p is not None for p in parts), "the self-join form did not take the range"
                     assert ctx.stats()["prune_symmetric"] == 1 and ctx.stats()["prune_rows"] > 0
-                    words = parts[0]["words"]
+                    words = parts[0].words
                     pairs_all = torch.cat([ops.selfjoin_pairs(p).clone() for p in parts])
                     assert pairs_all.numel() > 0 and pairs_all.numel() % words == 0
                     if reverse:

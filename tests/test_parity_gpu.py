@@ -751,11 +751,9 @@ def test_device_resident_inputs_and_rccl_plumbing(ctx):
         os.environ["SG_DIST_SYM"] = "1"
         try:
             res5, _ = D.distributed_self_join(ops, block, 10, 0.8)
-            assert isinstance(res5, D.TopNRows) and ctx.stats()["prune_symmetric"] == 1
-            C5 = res5.to_scipy()              # the rank's block: rows in POSITION order when the index is permuted
-            if res5.orig_of is not None:
-                C5 = C5[np.argsort(res5.orig_of.cpu().numpy(), kind="stable")]
-            assert_csr_identical(C5, C_ref)
+            assert isinstance(res5, D.RankBlock) and ctx.stats()["prune_symmetric"] == 1
+            C5 = res5.to_scipy()              # the rank's block: block row k is the caller's row rows[k]
+            assert_csr_identical(C5[np.argsort(res5.rows.cpu().numpy(), kind="stable")], C_ref)
             c5, v5, n5 = D.gather_topn(ops, res5)
             assert n5.tolist() == np.diff(C_ref.indptr).tolist()
         finally:
@@ -1435,14 +1433,19 @@ def test_selfjoin_form_over_row_ranges_equals_the_whole(ctx, dtype):
     ops = D.HipOps(ctx, lambda: HipTfidfVectorizer(dtype=dtype, ctx=ctx))
     n = len(names)
 
-    def stacked(rows, blk_orig_of):
-        """the ranks' blocks put together; with the index over the library's row permutation the ranges are ranges of
-        POSITIONS and block row p is row orig_of[p]"""
-        C = sp.vstack(rows).tocsr()
-        if blk_orig_of is None:
-            return C
-        inverse = np.argsort(blk_orig_of.cpu().numpy(), kind="stable")
-        return C[inverse]
+    def stacked(blocks):
+        """the ranks' blocks put together (and freed): block row k is the caller's row rows[k], each row once"""
+        ids = torch.cat([b.rows for b in blocks]).cpu().numpy()
+        assert ids.dtype == np.int64 and np.array_equal(np.sort(ids), np.arange(len(ids)))
+        C = sp.vstack([b.to_scipy() for b in blocks]).tocsr()[np.argsort(ids, kind="stable")]
+        for b in blocks:
+            b.free()
+        return C
+
+    def orig_of_index(post, n_index):
+        """position -> row of the index, downloaded from the library (row order: the identity)"""
+        p_orig, _ = ctx.postings_permutation(post)
+        return _device_u32(p_orig, n_index) if p_orig else np.arange(n_index)
 
     ctx.set_option("SG_COLLAPSE", "0")            # (an index over every row first; over groups of identical rows below)
     for permute in (False, True):
@@ -1454,15 +1457,16 @@ def test_selfjoin_form_over_row_ranges_equals_the_whole(ctx, dtype):
             parts = [ops.selfjoin_range(dA, post, 10, 0.75, int(bounds[r]), int(bounds[r + 1])) for r in range(world)]
             assert all(p is not None for p in parts)
             pairs_all = torch.cat([ops.selfjoin_pairs(p).clone() for p in parts])
-            assert pairs_all.numel() % parts[0]["words"] == 0 and pairs_all.numel() > 0
-            rows, orig_of = [], None
+            assert pairs_all.numel() % parts[0].words == 0 and pairs_all.numel() > 0
+            orig_of = orig_of_index(post, n)
+            assert np.array_equal(orig_of, np.arange(n)) != permute
+            blocks = []
             for r in range(world):
                 blk = ops.selfjoin_merge(parts[r], pairs_all, int(bounds[r]), int(bounds[r + 1]))
-                assert (blk.orig_of is not None) == permute
-                orig_of = blk.orig_of
-                rows.append(blk.to_scipy())
-                blk.free()
-            assert_csr_identical(stacked(rows, orig_of), want, f"{world} ranges, permutation {permute}")
+                assert np.array_equal(blk.rows.cpu().numpy(), orig_of[int(bounds[r]):int(bounds[r + 1])])
+                assert blk.in_order == (not permute) and (blk.whole is not None) == permute
+                blocks.append(blk)
+            assert_csr_identical(stacked(blocks), want, f"{world} ranges, permutation {permute}")
         post.free()
     # ---- the index over one representative per group of identical rows (the default when enough rows repeat): the
     #      ranges are ranges of the groups' positions, a rank's block holds groups, the gathered blocks are expanded
@@ -1479,8 +1483,9 @@ def test_selfjoin_form_over_row_ranges_equals_the_whole(ctx, dtype):
             pairs_all = torch.cat([ops.selfjoin_pairs(p).clone() for p in parts])
             blocks = [ops.selfjoin_merge(parts[r], pairs_all, int(bounds[r]), int(bounds[r + 1])) for r in range(world)]
             # a rank's block: the rows that are members of its groups, expanded on the rank (sg_topn_expand_groups)
-            assert all(b.row_ids is not None and b.orig_of is None and b.dims()[0] == b.row_ids.numel() for b in blocks)
-            ids = torch.cat([b.row_ids for b in blocks]).to(torch.int64)
+            # ... whose numbers no other rank knows without an exchange
+            assert all(b.dims()[0] == b.rows.numel() and not b.in_order and b.whole is None for b in blocks)
+            ids = torch.cat([b.rows for b in blocks])
             assert ids.numel() == n and torch.equal(torch.sort(ids).values.cpu(), torch.arange(n))
             # what gather_topn does with the ranks' blocks: concatenate, put every row where its number says
             cols, vals, counts = (torch.cat(t) for t in zip(*[ops.topn_tensors(b) for b in blocks]))
@@ -1506,8 +1511,8 @@ def test_selfjoin_form_over_row_ranges_equals_the_whole(ctx, dtype):
                 assert all(p is not None for p in parts)
                 pairs_all = torch.cat([ops.selfjoin_pairs(p).clone() for p in parts])
                 blocks = [ops.selfjoin_merge(parts[r], pairs_all, *shares[r]) for r in range(world)]
-                assert all(b.row_ids is not None and b.dims()[0] == b.row_ids.numel() for b in blocks)
-                ids = torch.cat([b.row_ids for b in blocks]).to(torch.int64)
+                assert all(b.dims()[0] == b.rows.numel() and not b.in_order and b.whole is None for b in blocks)
+                ids = torch.cat([b.rows for b in blocks])
                 assert ids.numel() == n and torch.equal(torch.sort(ids).values.cpu(), torch.arange(n))
                 cols, vals, counts = (torch.cat(t) for t in zip(*[ops.topn_tensors(b) for b in blocks]))
                 cols, vals, counts = (torch.empty_like(t).index_copy_(0, ids, t).cpu().numpy() for t in (cols, vals, counts))
@@ -1531,14 +1536,9 @@ def test_selfjoin_form_over_row_ranges_equals_the_whole(ctx, dtype):
         parts = [ops.selfjoin_range(dL, postL, 10, 0.75, int(bounds[r]), int(bounds[r + 1])) for r in range(world)]
         assert all(p is not None for p in parts)
         pairs_all = torch.cat([ops.selfjoin_pairs(p).clone() for p in parts])
-        rows, orig_of = [], None
-        for r in range(world):
-            blk = ops.selfjoin_merge(parts[r], pairs_all, int(bounds[r]), int(bounds[r + 1]))
-            orig_of = blk.orig_of
-            rows.append(blk.to_scipy())
-            blk.free()
-        assert orig_of is not None
-        assert_csr_identical(stacked(rows, orig_of), wantL, f"{world} ranges with rows for the exact kernel")
+        blocks = [ops.selfjoin_merge(parts[r], pairs_all, int(bounds[r]), int(bounds[r + 1])) for r in range(world)]
+        assert all(b.whole is not None for b in blocks)
+        assert_csr_identical(stacked(blocks), wantL, f"{world} ranges with rows for the exact kernel")
     postL.free(); dL.free(); dA.free()
 
 
@@ -1571,14 +1571,12 @@ def test_rows_worked_off_in_parts_give_the_same_rows(ctx, dtype):
         parts = [ops.selfjoin_range(dA, post, 10, 0.8, int(bounds[r]), int(bounds[r + 1])) for r in range(3)]
         assert all(p is not None for p in parts)
         pairs_all = torch.cat([ops.selfjoin_pairs(p).clone() for p in parts])
-        rows, orig_of = [], None
-        for r in range(3):
-            blk = ops.selfjoin_merge(parts[r], pairs_all, int(bounds[r]), int(bounds[r + 1]))
-            orig_of = blk.orig_of
-            rows.append(blk.to_scipy())
-            blk.free()
-        C = sp.vstack(rows).tocsr()[np.argsort(orig_of.cpu().numpy(), kind="stable")]
+        blocks = [ops.selfjoin_merge(parts[r], pairs_all, int(bounds[r]), int(bounds[r + 1])) for r in range(3)]
+        ids = torch.cat([b.rows for b in blocks]).cpu().numpy()
+        C = sp.vstack([b.to_scipy() for b in blocks]).tocsr()[np.argsort(ids, kind="stable")]
         assert_csr_identical(C, want, f"three ranges, rows of >= {bar} rounds in parts")
+        for b in blocks:
+            b.free()
         post.free()
     dA.free()
 
