@@ -807,6 +807,11 @@ int sg_collapse_build(sg_ctx *ctx, const sg_csr *B, SgCollapse **out, bool left_
 // ------------------------------------------------------------------------------------------------ expansion
 // Thread per output row: the row's groups written out member by member; rows in which a group of several members ties
 // with another group are queued for the wave-per-row kernel.
+// The queueing rule (restated by the census of tests/_expand_cases.py): walking the row's groups while fewer than `stride`
+// columns are out, the row is queued at the first group of SEVERAL members whose score equals -- bit for bit, `==` -- the
+// previous or the next group's; runs of single-member groups and ties behind the cut queue nothing.
+// -0.0 is outside the contract: the multiply's sums start at +0.0 and cannot produce it, and `==` would take a group at -0.0
+// and one at +0.0 for a tie that the order (score descending) does not define.
 template <typename T>
 __global__ void __launch_bounds__(256) expand_simple_kernel(const int32_t *__restrict__ u_cols, const T *__restrict__ u_vals,
                                                             const int32_t *__restrict__ u_cnt, int32_t u_stride,
