@@ -367,7 +367,23 @@ int sg_row_costs(sg_ctx *ctx, const sg_csr *A, const sg_postings *Bt, int64_t *o
  *   sg_spgemm_topn on its rows.  All ranks must take the same branch.  (Rows the pruned kernel cannot take -- more
  *   than 128 non-zeros -- are scored by the exact kernel inside the same pass; they do not switch the form off.)
  * sg_selfjoin_merge: the pairs of ALL ranks, concatenated in any order, merged into the rows of the range of `res`:
- *   afterwards these rows equal the rows sg_spgemm_topn(A, Bt) would give, bit for bit.
+ *   afterwards these rows equal the rows sg_spgemm_topn(A, Bt) would give, bit for bit.  The contract, for any result
+ *   (sg_topn_from_host) and any record list (sg_device_upload), with no multiply in front of it:
+ *   - the rank's rows: row j with row_lo <= pos_of[j] < row_hi and (row_hi - 1 - pos_of[j]) % row_step == 0 (row_step < 1
+ *     counts as 1), pos_of being Bt's table row -> position.  Bt == NULL, or an index in row order: pos_of[j] = j;
+ *   - a rank's row j receives the column i of every record {i, j, ...}, with the score whose bits the record carries;
+ *   - repeats count once: a record that is in the list several times, and a record whose column i the row holds already;
+ *   - the row's entries and what it receives are ordered by score descending BY VALUE (-0.0 and +0.0 are equal), then
+ *     column ascending, whatever the order of the records; the first `stride` of the result stay, the row's count is
+ *     their number, and the bits stored are the entry's own (the sign of a zero included);
+ *   - every other row -- not the rank's, or named by no record -- keeps all its cells and its count;
+ *   - n_pairs == 0, or row_lo == row_hi: nothing changes (d_pairs may be null when n_pairs is 0).
+ *   Refused with SG_ERR_BADARG, nothing launched: null ctx or res, pair_words that do not match the result's value type
+ *   (3 for SG_F32, 4 for SG_F64), a range outside [0, rows of res], and a result whose stride exceeds 128 -- a row is
+ *   selected in at most two register lists of 64 (sg_selfjoin_range makes strides up to 64).
+ *   The caller's responsibility, not checked: every count of res within [0, stride]; every record's j within [0, rows of
+ *   res) (and a Bt over as many rows); the copies of a repeated record, and a record that repeats a stored column, carry
+ *   the same score bits as the first -- the contract defines no winner among different scores of one column; no NaN.
  * When the index is built over the row permutation (the default, sg_postings_build_flags) a range is a range of
  *   POSITIONS: the rows it covers are orig_of[row_lo .. row_hi) (sg_postings_permutation; null tables = row order).
  *   Pass the same Bt to sg_selfjoin_merge.

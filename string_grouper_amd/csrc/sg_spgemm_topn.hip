@@ -1100,6 +1100,9 @@ extern "C" int sg_selfjoin_merge(sg_ctx *ctx, sg_topn *res, const sg_postings *B
     SG_REQUIRE(n_pairs == 0 || d_pairs != nullptr, "pairs are null");
     SG_REQUIRE(pair_words == (res->dtype == SG_F64 ? 4 : 3), "pair records do not match the result's value type");
     SG_REQUIRE(row_lo >= 0 && row_lo <= row_hi && row_hi <= res->n_rows, "row range outside the result");
+    // (pairs_select_kernel keeps a row of more than 64 candidates in two register lists and reads its bar from lane
+    //  stride - 65 of the second: beyond 128 that is no lane, and no more than 128 entries could stay)
+    SG_REQUIRE(res->stride <= 2 * SG_TOPN_LANES, "the merge selects rows of at most 128 columns: the result's stride is larger");
     SgTimer timer(ctx, SG_K_ZIP);
     return sg_selfjoin_merge_pairs(ctx, res, d_pairs, n_pairs, row_lo, row_hi, Bt ? (const uint32_t *)Bt->d_pos_of : nullptr, row_step);
 }

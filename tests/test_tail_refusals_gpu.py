@@ -1,6 +1,6 @@
 """The refusals of the drivers behind the multiply -- K5 sg_topn_zip, K6 sg_matchlist_build, K8 sg_matchlist_group_reps, K9
 sg_csr_rowwise_dot, sg_row_costs and the result operations of a resident corpus (sg_topn_concat_rows, _put_rows, _drop_columns,
-_forget) -- and what the same context does right after one.  Every test (1) makes a call the host refuses by its arguments,
+_forget) and sg_selfjoin_merge -- and what the same context does right after one.  Every test (1) makes a call the host refuses by its arguments,
 before anything is allocated or launched, and holds the exception's type and a word of its sentence, (2) makes a good call of
 the same function on the same context, and (3) holds that call to a numpy expectation: the references of tests/_tail_cases.py
 where there is one, otherwise written out here.  Results of 4 - 8 rows and stride 2 - 3, both value types; no tolerance.
@@ -9,7 +9,9 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+from tests import _merge_cases as M
 from tests import _tail_cases as T
+from tests.test_selfjoin_merge_gpu import merge_and_compare
 from tests.test_tail_gpu import assert_list_equal, assert_topn_equal, upload
 
 pytestmark = pytest.mark.gpu
@@ -253,3 +255,22 @@ def test_forget_refuses_a_wide_result_and_then_forgets(ctx, dtype):
     assert n_short == len(short) and ctx.download_ints(d_short, n_short).tolist() == short
     assert short, "no row was cut short: the case shows nothing of the list of short rows"
     d_short.free()
+
+
+# ---------------------------------------------------------------------------------------------------- the self-join merge
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_selfjoin_merge_refuses_a_stride_beyond_128_and_then_merges(ctx, dtype):
+    """pairs_select_kernel holds a row in two register lists of 64: a result of 129 columns is refused on the host, whatever
+    its rows hold (these hold a few entries and are named by two records each), and stays as it was; 128 columns are taken."""
+    wide = small_result(dtype, 6, 300, 129, 19)
+    dwide = upload(ctx, wide)
+    records = M.make_records([250, 251] * 6, np.repeat(np.arange(6), 2), [0.5, 0.25] * 6, dtype)
+    d_records = ctx.upload_ints(records.reshape(-1))
+    with pytest.raises(ValueError, match="at most 128 columns"):
+        ctx.selfjoin_merge(dwide, None, d_records.ptr, len(records), records.shape[1], 0, 6, 1)
+    assert_topn_equal(dwide, wide)                            # (the refused call wrote nothing)
+    back = dwide.to_host()
+    assert np.array_equal(back[0], wide.cols) and back[1].tobytes() == wide.vals.tobytes()
+    d_records.free()
+    for name in ("boundaries-128", "batches-128"):
+        merge_and_compare(ctx, M.case(name, dtype), M.want(name, dtype), None, f"{name} after the refusal")
